@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py — train-step images/s (fwd+bwd) of the Gaussian-rasterizer hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3] [--no-cpu-baseline] [--no-secondary]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-secondary] [--no-extras] [--no-4k] [--train-loop ITERS]]
 
 A "step" is the reference's timed training window (train.py:79-108): render() through the drop-in
 rasterizer + L1/D-SSIM loss + backward into the leaf parameters, on BASELINE.json configs[2]'s scene
@@ -11,8 +12,12 @@ the timed region.  For N > 1 the image is split into tile-row slabs:
 rank renders its slab of the SAME image, so scaling is "strong".  `python bench.py --gpus N` without a launcher
 starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` itself (as a child process).
 
-Prints ONE JSON line on rank 0.  Besides the contract's keys:
-  roofline      dominant kernel of the step, timed live with hipEvents inside libgsrast.so; `valu` prices the blend
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`, ...), nothing else.  --dump-outputs DIR then writes what the last timed step computed (see _dump_outputs).
+Everything below is measured only with --full:
+  kernels, raster_ms_per_step, profiled_ms_per_step   the same K steps again with the library's per-kernel hipEvents
+  config.visible ...  workload statistics of the benchmark frame (one extra un-timed forward/backward)
+  roofline     dominant kernel of the step, timed live with hipEvents inside libgsrast.so; `valu` prices the blend
                 kernel's measured instruction mix (profiles/r03_valu_mix.json) with the issue rates measured by
                 profiles/valu_microbench on this chip
   cpu_baseline  the CPU oracle (a port, test infrastructure) on rank 0 at N = 1 only; .cfg1 = BASELINE configs[0]
@@ -21,6 +26,7 @@ Prints ONE JSON line on rank 0.  Besides the contract's keys:
   torch_getters the same step over a store whose getters are the reference's torch ops (gaussian_params.GaussianParams):
                 what a caller who keeps the reference's own GaussianModel class gets from the drop-in rasterizer alone
   reference_loss_composition   the step with the reference's own two-call loss (l1_loss + ssim: utils/loss_utils.py)
+  native_getters, fused_activations, getter_fusion, unchanged_caller, secondary_4k, train_loop   see their `what` / _train_loop
 """
 import argparse
 import gc
@@ -117,6 +123,9 @@ def main():
     ap.add_argument("--steps", type=int, default=200)   # 0.8 ms steps: a 20-step window (16 ms) measured the clock ramp, not the step
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="cfg3", choices=["cfg1", "cfg2", "cfg3", "cfg3n", "cfg3b", "cfg5", "cfg5n"])
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also measure everything besides the headline (per-kernel table, "
+                    "roofline, comparison passes, other scenes, training loop, CPU baseline); the --no-* options and --train-loop apply to it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the non-saturating scene and the second seed")
     ap.add_argument("--no-extras", action="store_true", help="skip the comparison passes (torch getters, fused activations, ...) "
@@ -169,8 +178,10 @@ def main():
 
     ctx = dict(dev=dev, dist=dist, world=world, rank=rank, sharded_on=(world > 1 or args.force_sharded))
     single = world == 1 and not args.force_sharded
-    m = measure(args.workload, args.steps, args.warmup, ctx, extras=single and not args.no_extras, traffic=(args.workload == "cfg3" and world == 1),
-                profile=not args.no_extras)
+    full = args.full
+    m = measure(args.workload, args.steps, args.warmup, ctx, extras=full and single and not args.no_extras,
+                traffic=(args.workload == "cfg3" and world == 1), profile=full and not args.no_extras, frame_stats=full,
+                dump_dir=args.dump_outputs if rank == 0 else None)
 
     if rank != 0:
         if dist is not None:
@@ -185,11 +196,16 @@ def main():
         "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {**m["config"], "parallelism": "single" if not ctx["sharded_on"] else f"tile-row slabs x{world}",
                    **({"collectives": collectives} if collectives else {})},
-        "raster_ms_per_step": m["raster_ms_per_step"], "profiled_ms_per_step": m["profiled_ms_per_step"],
         "gc_in_timed_window": m["gc_in_timed_window"],
         "host": {"bound_to_numa_node": bound[0] if bound else None, "cpus": len(os.sched_getaffinity(0))},
-        "kernels": m["kernels"], "roofline": m["roofline"], "cpu_baseline": None,
     }
+    if not full:
+        print(json.dumps(line))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+    line.update({"raster_ms_per_step": m["raster_ms_per_step"], "profiled_ms_per_step": m["profiled_ms_per_step"],
+                 "kernels": m["kernels"], "roofline": m["roofline"], "cpu_baseline": None})
     for k in ("native_getters", "torch_getters", "fused_activations", "getter_fusion", "reference_loss_composition", "unchanged_caller"):
         if m.get(k) is not None:
             line[k] = m[k]
@@ -227,8 +243,9 @@ def main():
         dist.destroy_process_group()
 
 
-def measure(workload, steps, warmup, ctx, extras, traffic, profile=True):
-    """Time `steps` steps of the training window on `workload`; returns the numbers of one bench object."""
+def measure(workload, steps, warmup, ctx, extras, traffic, profile=True, frame_stats=True, dump_dir=None):
+    """Time `steps` steps of the training window on `workload`; returns the numbers of one bench object.  Without `frame_stats`
+    only the timed region runs (no frame statistics, no roofline); `dump_dir`: see _dump_outputs."""
     import scene_synth as S
     from diff_gaussian_rasterization import _native as N
     from gaussian_params import GaussianParams, Pipe
@@ -257,6 +274,7 @@ def measure(workload, steps, warmup, ctx, extras, traffic, profile=True):
         from diff_gaussian_rasterization.sharded import ShardedRenderer
         sharded = ShardedRenderer(dist, world, rank)
     loss_fn = {"f": None}
+    last = {}
 
     def step():
         for p in params:
@@ -268,6 +286,7 @@ def measure(workload, steps, warmup, ctx, extras, traffic, profile=True):
         else:
             loss = training_loss(out["render"], gt) if sharded is None else sharded.training_loss(out["render"], gt)
         loss.backward()
+        last["loss"] = loss
         return out
 
     def sync():
@@ -300,6 +319,8 @@ def measure(workload, steps, warmup, ctx, extras, traffic, profile=True):
     # (1) the timed region: EXACTLY K steps, no instrumentation inside
     elapsed, out = timed(steps, warmup)
     gc_headline = dict(last_gc)
+    if dump_dir is not None:
+        _dump_outputs(dump_dir, out, last["loss"], model)
     # (2) the same K steps again with the library's per-kernel hipEvent pairs (roofline); the event packets
     # add ~10 us between kernels, so this pass is reported separately and never feeds `value`
     prof, elapsed_profiled = {}, 0.0
@@ -387,9 +408,22 @@ def measure(workload, steps, warmup, ctx, extras, traffic, profile=True):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    P = scene.P
+    res.update({
+        "value": round(steps / elapsed, 3), "ms_per_step": round(1e3 * elapsed / steps, 4),
+        "config": {"workload": f"{workload}: {P} Gaussians, {cfg['W']}x{cfg['H']}, SH degree {cfg['D']} "
+                               f"(SURVEY Appendix B generator, seed {cfg['seed']}"
+                               + (f", z >= {cfg['zmin']}, scales x{cfg['scale_mul']}" if "zmin" in cfg else "")
+                               + "); step = render() + L1/D-SSIM loss + backward (train.py:79-108 window)"},
+        "gc_in_timed_window": gc_headline,
+    })
+    if not frame_stats:
+        del model, params, scene, gt, out
+        torch.cuda.empty_cache()
+        return res
+
     # ---- workload statistics for the roofline (measured, not assumed)
     radii = out["radii"]
-    P = scene.P
     V = int((radii > 0).sum())
     Npix, Tn = cfg["W"] * cfg["H"], ((cfg["W"] + 15) // 16) * ((cfg["H"] + 15) // 16)
     K = M = (cfg["D"] + 1) ** 2
@@ -432,24 +466,51 @@ def measure(workload, steps, warmup, ctx, extras, traffic, profile=True):
                         pairs_per_s_G=round(pairs / 1e9 / (bwd_ms / 1e3), 1) if bwd_ms > 0 else None,
                         note="the blend kernels are VALU-issue-bound, not HBM-bound (SURVEY 8d caveat): `valu` is their "
                              "roofline; pairs_per_s_G = (pixel, splat) pairs per second in render_bwd")
+    res["config"].update({"visible": V, "num_rendered": R, "instances_emitted": Re, "chunks_run": stats["chunks_run"],
+                          "chunks_planned": stats["chunks_planned"], "binned_gaussians": Vb, "gaussians_with_gradient": Vlive,
+                          "instances_walked_bwd": stats["walked"], "bwd_work_units": stats["units"],
+                          "emitted_over_num_rendered": round(Re / max(R, 1), 4)})
     res.update({
-        "value": round(steps / elapsed, 3), "ms_per_step": round(1e3 * elapsed / steps, 4),
-        "config": {"workload": f"{workload}: {P} Gaussians, {cfg['W']}x{cfg['H']}, SH degree {cfg['D']} "
-                               f"(SURVEY Appendix B generator, seed {cfg['seed']}"
-                               + (f", z >= {cfg['zmin']}, scales x{cfg['scale_mul']}" if "zmin" in cfg else "")
-                               + "); step = render() + L1/D-SSIM loss + backward (train.py:79-108 window)",
-                   "visible": V, "num_rendered": R, "instances_emitted": Re, "chunks_run": stats["chunks_run"],
-                   "chunks_planned": stats["chunks_planned"], "binned_gaussians": Vb, "gaussians_with_gradient": Vlive,
-                   "instances_walked_bwd": stats["walked"], "bwd_work_units": stats["units"],
-                   "emitted_over_num_rendered": round(Re / max(R, 1), 4)},
         "raster_ms_per_step": round(raster_ms, 4), "profiled_ms_per_step": round(1e3 * elapsed_profiled / steps, 4),
-        "gc_in_timed_window": gc_headline,
         "kernels": {k: {kk: (round(vv, 4) if isinstance(vv, float) else vv) for kk, vv in v.items()} for k, v in per_kernel.items()},
         "roofline": roofline,
     })
     del model, params, scene, gt, out
     torch.cuda.empty_cache()
     return res
+
+
+DUMP_ROWS = 1 << 16          # Gaussians sampled from every per-Gaussian output
+DUMP_PIXELS = 1 << 21        # 1080p images are written whole; larger ones as a sample of their pixels
+DUMP_LIMIT = 64 << 20
+
+
+def _dump_outputs(dump_dir, out, loss, model):
+    """What a caller of the timed step receives from the LAST timed step, as float32 DIR/<name>.npy: the image (`render`), the
+    loss, and per Gaussian the radii and the gradients of the screen-space points and of every parameter leaf (`grad_<leaf>`).
+    Per-Gaussian arrays hold the rows of a fixed, seeded sample of DUMP_ROWS Gaussians in index order (all rows when P is
+    smaller); an image of more than DUMP_PIXELS pixels is a fixed, seeded sample of its pixels as [n, 3].  The inputs are seeded
+    too, so two builds run with the same arguments can be compared file by file."""
+    import numpy as np
+
+    def sample(n, k, seed):
+        idx = np.sort(np.random.default_rng(seed).choice(n, k, replace=False)) if n > k else np.arange(n)
+        return torch.as_tensor(idx, device=out["render"].device)
+
+    rows = sample(model._t["xyz"].shape[0], DUMP_ROWS, 0)
+    img = out["render"].detach()
+    if img[0].numel() > DUMP_PIXELS:
+        img = img.reshape(img.shape[0], -1).t()[sample(img[0].numel(), DUMP_PIXELS, 1)]
+    arrays = {"render": img, "loss": loss.detach(), "radii": out["radii"][rows],
+              "viewspace_points_grad": out["viewspace_points"].grad[rows]}
+    arrays.update({f"grad_{k}": t.grad[rows] for k, t in model._t.items()})
+    arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT}-byte limit")
+    os.makedirs(dump_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dump_dir, k + ".npy"), a)
 
 
 def _self_launch(n: int) -> int:

@@ -4,8 +4,8 @@ MI355X_MICROARCH.md "HBM" prescribes) into profiles/traffic.json = HBM bytes per
 the number bench.py reports as roofline.traffic.
 
     cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline
     python3 profiles/pmc_to_traffic.py <fetch counter_collection.csv> <write counter_collection.csv> profiles
 
 Units and corrections (guide, "HBM [CDNA4]"): both counters are in KiB-like units of 1024 B as rocprofv3

@@ -34,7 +34,7 @@ def main():
     out = {}
     reduce(sys.argv[1], out)
     reduce(sys.argv[2], out)
-    json.dump({"source": "rocprofv3 --pmc <8 SQ counters per pass> -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline "
+    json.dump({"source": "rocprofv3 --pmc <8 SQ counters per pass> -- python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline "
                          "--no-secondary (two passes: profiles/collect.sh); first 3 launches of every kernel dropped",
                "kernels": dict(sorted(out.items()))}, open(sys.argv[3], "w"), indent=1)
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Profiling aid: N iterations of the full training loop at cfg3 (what `bench.py --train-loop` times), nothing else,
+"""Profiling aid: N iterations of the full training loop at cfg3 (what `bench.py --full --train-loop` times), nothing else,
 so that `rocprofv3 --kernel-trace --stats -- python3 profiles/train_loop_probe.py 100 1` shows its kernels only.
 argv: iterations, fused_activations (0/1)."""
 import os

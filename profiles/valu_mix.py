@@ -74,7 +74,7 @@ def mix(pmc_csv, isa_path, out_path):
                     per[key][row["Counter_Name"]].append(float(row["Counter_Value"]))
     isa = isa_counts(isa_path)
     out = {"workload": WORKLOAD, "source": "rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_ADD_F32 "
-           "SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_CVT SQ_INSTS_SALU -- python3 bench.py --steps 6 --warmup 2 "
+           "SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_CVT SQ_INSTS_SALU -- python3 bench.py --full --steps 6 --warmup 2 "
            "--no-cpu-baseline --no-secondary", "kernels": {}}
     for key, ctr in per.items():
         avg = {c: sum(v[SKIP_FIRST:]) / max(len(v[SKIP_FIRST:]), 1) for c, v in ctr.items()}

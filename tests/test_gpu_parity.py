@@ -1184,7 +1184,7 @@ def test_randomised_configurations_against_oracle():
 
 
 def test_bench_line_contract():
-    """bench.py on the small workload, in a child process: exactly one JSON line on stdout with the fields the driver and
+    """bench.py --full on the small workload, in a child process: exactly one JSON line on stdout with the fields the driver and
     the judge read (metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling /
     vs_baseline / dtype / data / config.workload + roofline{bound, achieved, peak, unit, frac, traffic} +
     cpu_baseline), and self-consistent numbers."""
@@ -1193,7 +1193,7 @@ def test_bench_line_contract():
     import sys
     root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cfg2", "--steps", "4", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -1211,6 +1211,41 @@ def test_bench_line_contract():
     assert r["traffic"] is None                      # PMC traffic is only attached to the run it was measured on (cfg3)
     assert r["kernels_over_hbm_peak"] == []          # the per-kernel algorithmic-byte table charges nothing twice
     assert d["cpu_baseline"] is None                 # --no-cpu-baseline
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """bench.py without --full, twice with the same arguments: one JSON line holding the headline and nothing that needs a run
+    of its own, and --dump-outputs writes the last timed step's image, loss, radii and gradients as float32 .npy files within
+    64 MB, identical from run to run (seeded inputs, gradients in an order the program fixes)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cfg2", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True
+        assert d["unit"] == "images/s" and d["dtype"] == "f32" and d["metric"].startswith("train-step images/sec")
+        assert abs(d["value"] - 1000.0 / d["ms_per_step"]) <= 1e-2 * d["value"]
+        for k in ("kernels", "roofline", "cpu_baseline", "secondary", "train_loop", "torch_getters"):
+            assert k not in d, k
+        dumps.append({f.stem: np.load(f) for f in sorted(out.glob("*.npy"))})
+    a, b = dumps
+    cfg = S.CONFIGS["cfg2"]
+    assert set(a) == {"render", "loss", "radii", "viewspace_points_grad", "grad_xyz", "grad_features", "grad_opacity",
+                      "grad_scaling", "grad_rotation"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["render"].shape == (3, cfg["H"], cfg["W"]) and a["grad_features"].shape == (1 << 16, 16, 3)
+    assert (a["radii"] > 0).any() and np.abs(a["grad_xyz"]).max() > 0
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
 
 
 def test_getter_fusion_is_transparent():
