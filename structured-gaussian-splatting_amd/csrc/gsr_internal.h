@@ -133,14 +133,11 @@ struct GeomWS {                 // O(P): the reference's geomBuffer
 // work units: (tile, chunk, segment).  kSeg list entries are ~25 us of one wave; a 400-entry tile as ONE unit was 100 us and the
 // launch ended with a third of its time draining (two rounds of 4096 resident waves, tail = the last-started tiles).
 // The forward's wave of a (tile, chunk) appends the pair's units itself when it is done — one returning atomic on one of
-// kUnitShards counters (shard = tile % 8), so that the list costs no kernel and no block of its own — and the backward reads
-// every shard's list BACKWARDS: the tiles that finish the forward last are the long ones, and the launch should start with them.
-#ifndef GSR_BWD_SEG
-#define GSR_BWD_SEG 128
-#endif
-constexpr int kSeg = GSR_BWD_SEG;
+// kUnitShards counters (shard = tile % 8), so that the list costs no kernel and no block of its own — and the backward walks every
+// shard's lists in order, longest first: the full segments, then the partial ones by length class (below).
+constexpr int kSeg = 128;
 static_assert(kSeg % kWave == 0, "segments are whole 64-entry batches");
-constexpr int kCkptFloats = 16 * kWave;   // one checkpoint = (T, r, g, b) of the tile's 256 pixels: [quadrant][field][lane], 4 KB
+constexpr int kCkptFloats = 16 * kWave;   // one checkpoint = (T, r, g, b) of the tile's 256 pixels, 4 KB (layout: gsr_render.hip ckpt_word)
 constexpr int kUnitTileBits = 24;         // BwdUnit.x = tile | chunk << 24; .y = segment
 constexpr int kUnitShards = 8;
 // ... in kUnitClasses lists per shard, longest first: full segments, then the pairs' last, partial segments in 16 length classes of

@@ -6,7 +6,8 @@
 //     (l & 7, l >> 3) of each of the tile's four 8x8 QUADRANTS, so "can this splat reach quadrant k at all" is wave-uniform and
 //     clear quadrants are skipped with scalar branches (sub-tile culling); early termination is a wave ballot per quadrant.
 //     Chunks of small splats (k_render_fwd_groups): the backward's mapping, one 16-lane group per quadrant, each walking its own
-//     entries.  The two render the same bits.  No workgroup barrier exists anywhere in the blend loops.
+//     entries.  Both kernels are one body (render_fwd) over the pixel mapping (QuadrantLanes, GroupLanes), so they render the same
+//     bits and leave the checkpoints in one layout (ckpt_word).  No workgroup barrier exists anywhere in the blend loops.
 //   * splat records (48 B: xy, conic, opacity, rgb) are gathered 64 at a time, one per lane, staged in
 //     LDS and read back as broadcasts (ds_read_b128).
 //   * backward: FRONT TO BACK, in independent work units of kSeg list entries (gsr_internal.h: kSeg, UnitLists) that start from the
@@ -61,22 +62,9 @@ __device__ __forceinline__ int wave_max_uniform(int v)
     return __builtin_amdgcn_readfirstlane(v);
 }
 
-#ifndef GSR_FWD_WAVES
-#define GSR_FWD_WAVES 5        // resident waves per SIMD the register allocation of k_render_fwd aims for
-#endif
-#ifndef GSR_BWD_WAVES
-#define GSR_BWD_WAVES 4        // ... and of k_render_bwd
-#endif
+constexpr int kFwdWaves = 5;       // resident waves per SIMD the register allocation of the forward kernels aims for
+constexpr int kBwdWaves = 4;       // ... and of k_render_bwd
 typedef float v2f __attribute__((ext_vector_type(2)));      // packed-fp32 operand: the lane's two pixels of a pair
-
-// Pixel mapping of k_render_fwd ("one wave, one tile", QUADRANT-major; the group kernels have their own, see k_render_bwd): lane l owns
-// the pixel (l & 7, l >> 3) of each of the tile's four 8x8 quadrants.  Whether a splat can reach a quadrant at all (quadrant_mask_q: the
-// exact alpha >= 1/255 bound on the 8x8 pixel rectangle) is then WAVE-UNIFORM: the 4-bit mask travels with the tile list's entry, and the
-// blend loop skips clear quadrants with scalar branches.  A 2-3 px splat reaches one or two quadrants of a tile, not four.
-// The two quadrants of a pair share dy and differ by 8 in dx: they run as packed fp32 (v_pk_fma_f32 issues two FMAs in the cycles
-// of 1.2 plain ones on gfx950: profiles/valu_microbench).
-__device__ __forceinline__ int lane_px(int lane) { return lane & 7; }
-__device__ __forceinline__ int lane_py(int lane) { return lane >> 3; }
 
 // lp = log2(opacity exp(power)) of a pair of pixels from the pre-scaled record (qA, qB, qC = a.z, a.w, b.x; log2 opacity = b.y):
 //     lp = qA dx^2 + qB dx dy + qC dy^2 + lop = ((qC dy + qB dx) dy) + (qA dx) dx + lop
@@ -131,7 +119,7 @@ constexpr float kLog2AlphaMin = -7.99435343685886f;      // log2(1 / 255)
 
 // Per pixel: T (signed, see FwdPair), colour, last contributor.  A rejected splat runs the same arithmetic with alpha = 0, which leaves
 // everything unchanged, so the only selects are on alpha, on the stop decision and on the contributor index.
-struct FwdPair {             // state of a lane's two pixels in one pair of quadrants (left, right)
+struct FwdPair {             // state of a lane's two pixels in one pair (elements 0, 1 or 2, 3)
     v2f T, Cr, Cg, Cb;       // T > 0: live transmittance; T < 0: the pixel has taken the cut-off (or lies outside the image), |T| = the
     int last0, last1;        // transmittance to report (frozen in front of the stopping splat): exactly what T_state holds
 };
@@ -159,16 +147,89 @@ __device__ __forceinline__ void fwd_pair(bool active, v2f lp, float lop, float c
     P.last1 = (keep1 && !stop1) ? contributor : P.last1;
 }
 
-// wave-uniform 4-bit mask: quadrant k still has a live pixel
-__device__ __forceinline__ unsigned live_quadrants(const FwdPair &A, const FwdPair &B)
-{
-    unsigned m = 0;
-    if (__ballot(A.T[0] > 0.f) != 0ull) m |= 1u;
-    if (__ballot(A.T[1] > 0.f) != 0ull) m |= 2u;
-    if (__ballot(B.T[0] > 0.f) != 0ull) m |= 4u;
-    if (__ballot(B.T[1] > 0.f) != 0ull) m |= 8u;
-    return m;
-}
+// ---- Which four pixels of a tile a lane owns, and where their state sits in a checkpoint.  A lane owns two PAIRS of pixels (elements
+// e = 0, 1 and 2, 3): the two pixels of a pair share dy and lie kPair apart in x, and run as packed fp32 (v_pk_fma_f32 issues two FMAs
+// in the cycles of 1.2 plain ones on gfx950: profiles/valu_microbench); the second pair lies kPair below the first.
+//
+// The checkpoint (kCkptFloats: the pixels' state in front of a list position, which the forward writes and the backward reads) holds
+// the tile's 256 pixels as [quadrant][T, r, g, b][y << 3 | x inside the 8x8 quadrant]; this is its one definition.  The parts of a
+// word take disjoint bits, so a word is also the sum of the words of its parts (a lane's base plus a constant per element and field).
+__device__ __forceinline__ int ckpt_word(int quadrant, int field, int qx, int qy) { return (4 * quadrant + field) * kWave + (qy << 3 | qx); }
+template <int P> struct LanePairs {
+    static constexpr int kPair = P;
+    __device__ static int ex(int e) { return (e & 1) * kPair; }      // element e's pixel, from the lane's first (element 0)
+    __device__ static int ey(int e) { return (e >> 1) * kPair; }
+};
+
+// k_render_fwd ("one wave, one tile", QUADRANT-major): lane l owns the pixel (l & 7, l >> 3) of each of the tile's four 8x8 quadrants
+// (element e = quadrant e).  Whether a splat can reach a quadrant at all (quadrant_mask_q: the exact alpha >= 1/255 bound on the 8x8
+// pixel rectangle) is then WAVE-UNIFORM: the 4-bit mask travels with the tile list's entry, and the blend loop skips clear quadrants
+// with scalar branches.  A 2-3 px splat reaches one or two quadrants of a tile, not four.
+struct QuadrantLanes : LanePairs<8> {
+    static constexpr bool kLockStep = true;
+    int lx, ly;                                          // the lane's pixel inside each quadrant
+    __device__ explicit QuadrantLanes(int lane) : lx(lane & 7), ly(lane >> 3) {}
+    __device__ int x0(int tx) const { return tx * GSR_TILE + lx; }      // the lane's first pixel (element 0) in the tile (tx, ty)
+    __device__ int y0(int ty) const { return ty * GSR_TILE + ly; }
+    __device__ int ckpt(int e, int field) const { return ckpt_word(0, 0, lx, ly) + ckpt_word(e, field, 0, 0); }
+    // wave-uniform 4-bit mask: quadrant k still has a live pixel
+    __device__ unsigned live(const FwdPair &A, const FwdPair &B) const
+    {
+        unsigned m = 0;
+        if (__ballot(A.T[0] > 0.f) != 0ull) m |= 1u;
+        if (__ballot(A.T[1] > 0.f) != 0ull) m |= 2u;
+        if (__ballot(B.T[0] > 0.f) != 0ull) m |= 4u;
+        if (__ballot(B.T[1] > 0.f) != 0ull) m |= 8u;
+        return m;
+    }
+};
+
+// k_render_bwd and k_render_fwd_groups: the wave is four GROUPS of 16 lanes, one per quadrant; lane l belongs to quadrant g = l >> 4
+// and owns the pixels (i & 3 [+ 4], i >> 2 [+ 4]), i = l & 15, of it.  Each group walks its own entries (GroupWalk).
+struct GroupLanes : LanePairs<4> {
+    static constexpr bool kLockStep = false;
+    int grp, lx, ly;                                     // the lane's quadrant, and its first pixel inside it
+    __device__ explicit GroupLanes(int lane) : grp(lane >> 4), lx(lane & 3), ly((lane & 15) >> 2) {}
+    __device__ int x0(int tx) const { return tx * GSR_TILE + (grp & 1) * 8 + lx; }
+    __device__ int y0(int ty) const { return ty * GSR_TILE + (grp >> 1) * 8 + ly; }
+    __device__ int ckpt(int e, int field) const { return ckpt_word(grp, 0, lx, ly) + ckpt_word(0, field, ex(e), ey(e)); }
+    // bit g: group (= quadrant) g still has a live pixel.  One ballot
+    __device__ unsigned live(const FwdPair &A, const FwdPair &B) const
+    {
+        const unsigned long long bal = __ballot(A.T[0] > 0.f || A.T[1] > 0.f || B.T[0] > 0.f || B.T[1] > 0.f);
+        return ((bal & 0xFFFFull) ? 1u : 0u) | ((bal & 0xFFFF0000ull) ? 2u : 0u) | ((bal & 0xFFFF00000000ull) ? 4u : 0u) |
+               ((bal & 0xFFFF000000000000ull) ? 8u : 0u);
+    }
+};
+
+// The four groups' walk of a batch: per group, the batch's entries it still has to walk (wave-uniform bit sets: scalar registers).
+struct GroupWalk {
+    unsigned long long act0, act1, act2, act3;
+    // the entries whose quadrant mask has the group's bit, for the groups whose bit is set in `live`
+    __device__ GroupWalk(unsigned mymask, unsigned live)
+        : act0((live & 1u) ? __ballot((mymask & 1u) != 0u) : 0ull), act1((live & 2u) ? __ballot((mymask & 2u) != 0u) : 0ull),
+          act2((live & 4u) ? __ballot((mymask & 4u) != 0u) : 0ull), act3((live & 8u) ? __ballot((mymask & 8u) != 0u) : 0ull) {}
+    __device__ bool more() const { return (act0 | act1 | act2 | act3) != 0ull; }
+    // each group's next entry (255: it is through with the batch), one byte per group in a scalar register; returns the lane's group's,
+    // and in jj the entry to read: an idle group reads the batch's first record, staged for sure, where the slots behind a short
+    // batch's end hold whatever LDS held
+    __device__ unsigned next(unsigned grp_shift, unsigned &jj)
+    {
+        const unsigned j0 = act0 ? (unsigned)__ffsll((long long)act0) - 1u : 255u, j1 = act1 ? (unsigned)__ffsll((long long)act1) - 1u : 255u,
+                       j2 = act2 ? (unsigned)__ffsll((long long)act2) - 1u : 255u, j3 = act3 ? (unsigned)__ffsll((long long)act3) - 1u : 255u;
+        act0 &= act0 - 1ull; act1 &= act1 - 1ull; act2 &= act2 - 1ull; act3 &= act3 - 1ull;      // (0 & anything = 0)
+        const unsigned j = __builtin_amdgcn_ubfe(j0 | j1 << 8 | j2 << 16 | j3 << 24, grp_shift, 8u);
+        jj = j < (unsigned)kWave ? j : 0u;
+        return j;
+    }
+    __device__ void keep(unsigned live)      // groups whose quadrant is done stop
+    {
+        if (!(live & 1u)) act0 = 0ull;
+        if (!(live & 2u)) act1 = 0ull;
+        if (!(live & 4u)) act2 = 0ull;
+        if (!(live & 8u)) act3 = 0ull;
+    }
+};
 
 #if defined(GSR_BWD_TRACE) || defined(GSR_FWD_TRACE)
 // debug builds only (tools/bwd_trace.sh): per block {start, end (100 MHz clock), HW_ID, XCC_ID} of the last launch of the
@@ -218,14 +279,19 @@ __device__ __forceinline__ void fwd_tile_epilogue(int t, int tile, int c, int la
     }
 }
 
-__global__ __launch_bounds__(kWave, GSR_FWD_WAVES) void k_render_fwd(FrameK f, int n_tiles, int c, int finalize_all,
-                                                      const uint2 *__restrict__ ranges_c, uint32_t *__restrict__ open,
-                                                      const uint32_t *__restrict__ sorted_gid,
-                                                      const float4 *__restrict__ records, const float *__restrict__ bg,
-                                                      float *__restrict__ out_color, float *__restrict__ T_state,
-                                                      int32_t *__restrict__ last_enc, uint32_t *__restrict__ tile_walk_c,
-                                                      float *__restrict__ ckpt, float *__restrict__ ckpt_start_c,
-                                                      UnitLists units, uint32_t *__restrict__ unit_count)
+// One blend forward of a (tile, chunk) for both pixel mappings; only the batch walk differs.  Lock step (QuadrantLanes): the wave walks
+// the batch's splats that reach a live quadrant together.  Groups (GroupLanes): each group walks the entries that reach ITS quadrant -
+// the mapping and the walk of k_render_bwd - for chunks of SMALL splats (launch_render_fwd's `groups`: fewer than 4.5 tiles per
+// Gaussian).  A splat that reaches one or two quadrants costs the lock-step walk a pass of the whole wave; with groups up to four
+// different splats share a pass.  Where splats reach most quadrants lock step is faster (wave-uniform records, whole pairs skipped):
+// cfg3n 258 -> 230 us with groups, but cfg3 105 -> 116, cfg5n 696 -> 706 - hence two kernels.  The checkpoints and every per-pixel
+// array are the same either way, and so are the bits.
+template <class Map>
+__device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, const uint2 *__restrict__ ranges_c, uint32_t *__restrict__ open,
+                                           const uint32_t *__restrict__ sorted_gid, const float4 *__restrict__ records,
+                                           const float *__restrict__ bg, float *__restrict__ out_color, float *__restrict__ T_state,
+                                           int32_t *__restrict__ last_enc, uint32_t *__restrict__ tile_walk_c, float *__restrict__ ckpt,
+                                           float *__restrict__ ckpt_start_c, const UnitLists &units, uint32_t *__restrict__ unit_count)
 {
     __shared__ float4 sh_rec[kWave * 3];
 #ifdef GSR_FWD_TRACE
@@ -239,14 +305,15 @@ __global__ __launch_bounds__(kWave, GSR_FWD_WAVES) void k_render_fwd(FrameK f, i
     if (open[tile] == 0u) return;                       // closed by an earlier chunk: pixels are final
     const uint2 rng = ranges_c[tile];
     const int lane = threadIdx.x;
-    const int px0 = tx * GSR_TILE + lane_px(lane), py0 = ty * GSR_TILE + lane_py(lane);       // the lane's pixel in quadrant 0
-    const float fy0 = (float)py0, fy1 = fy0 + 8.f;
-    const v2f fxv = {(float)px0, (float)(px0 + 8)};
+    const Map map(lane);
+    const int px0 = map.x0(tx), py0 = map.y0(ty);
+    const float fy0 = (float)py0, fy1 = fy0 + (float)Map::kPair;
+    const v2f fxv = {(float)px0, (float)(px0 + Map::kPair)};
     const size_t N = (size_t)f.W * f.H;
 
     FwdPair P0, P1;
-    auto load_px = [&](int k, float &t_, float &r_, float &g_, float &b_, int &last) {
-        const int px = px0 + (k & 1) * 8, py = py0 + (k >> 1) * 8;
+    auto load_px = [&](int e, float &t_, float &r_, float &g_, float &b_, int &last) {
+        const int px = px0 + map.ex(e), py = py0 + map.ey(e);
         const bool inside = px < f.W && py < f.H;
         t_ = inside ? 1.f : -1.f; r_ = g_ = b_ = 0.f; last = 0;
         if (c > 0 && inside) {
@@ -268,53 +335,72 @@ __global__ __launch_bounds__(kWave, GSR_FWD_WAVES) void k_render_fwd(FrameK f, i
     const int enc_base = (c + 1) << kLastShift;
     // The blend backward walks this list front to back in independent segments of kSeg entries (gsr_internal.h): it starts a
     // segment from the pixels' state (live transmittance, colour so far) in front of the segment's first entry, kept here.
-    auto checkpoint = [&](float *dst) {                 // [quadrant][T, r, g, b][lane]: sixteen coalesced 256-byte stores
-        dst[0 * kWave + lane] = P0.T[0]; dst[1 * kWave + lane] = P0.Cr[0]; dst[2 * kWave + lane] = P0.Cg[0]; dst[3 * kWave + lane] = P0.Cb[0];
-        dst[4 * kWave + lane] = P0.T[1]; dst[5 * kWave + lane] = P0.Cr[1]; dst[6 * kWave + lane] = P0.Cg[1]; dst[7 * kWave + lane] = P0.Cb[1];
-        dst[8 * kWave + lane] = P1.T[0]; dst[9 * kWave + lane] = P1.Cr[0]; dst[10 * kWave + lane] = P1.Cg[0]; dst[11 * kWave + lane] = P1.Cb[0];
-        dst[12 * kWave + lane] = P1.T[1]; dst[13 * kWave + lane] = P1.Cr[1]; dst[14 * kWave + lane] = P1.Cg[1]; dst[15 * kWave + lane] = P1.Cb[1];
+    auto checkpoint = [&](float *dst) {
+        auto put = [&](int e, const FwdPair &P, int h) {
+            dst[map.ckpt(e, 0)] = P.T[h]; dst[map.ckpt(e, 1)] = P.Cr[h]; dst[map.ckpt(e, 2)] = P.Cg[h]; dst[map.ckpt(e, 3)] = P.Cb[h];
+        };
+        put(0, P0, 0); put(1, P0, 1); put(2, P1, 0); put(3, P1, 1);
+    };
+    // blend entry j of the batch into the pairs m names (bits 0-1: P0, 2-3: P1; active: the lane's group has an entry in this pass)
+    auto blend = [&](int base, unsigned j, bool active, unsigned m) {
+        const float4 a = sh_rec[3u * j], b = sh_rec[3u * j + 1u];
+        const float cbl = sh_rec[3u * j + 2u].x;
+        const int contributor = enc_base | (int)((unsigned)base + j + 1u);
+        const v2f dx = a.x - fxv;                                 // one subtraction from the pixel's x (all three blend kernels)
+        const LpTerms lt = lp_terms(a.z, a.w, b.y, dx);
+        if (m & 3u) {
+            const float dy = a.y - fy0;
+            fwd_pair(active, lp_at(lt, b.x, dy), b.y, b.z, b.w, cbl, contributor, P0);
+        }
+        if (m & 12u) {
+            const float dy = a.y - fy1;
+            fwd_pair(active, lp_at(lt, b.x, dy), b.y, b.z, b.w, cbl, contributor, P1);
+        }
     };
     if (c > 0 && n_total > 0) checkpoint(ckpt_start_c + (size_t)tile * kCkptFloats);
     for (int base = 0; base < n_total; base += kWave) {
-        unsigned live = live_quadrants(P0, P1);
+        unsigned live = map.live(P0, P1);
         if (live == 0u) break;
         if (base > 0 && base % kSeg == 0) checkpoint(ckpt + (size_t)((rng.x + (uint32_t)base) / kSeg) * kCkptFloats);
         const int n = min(kWave, n_total - base);
         __syncthreads();
         const unsigned mymask = stage_batch(sh_rec, lane, n, sorted_gid, rng.x + base, records);
         __syncthreads();
-        // splats of the batch that can reach a live quadrant, front to back (bit j = splat j): the others cost nothing
-        unsigned long long act = __ballot((mymask & live) != 0u);
+        // every 8 blended splats (passes, with groups) the live mask is refreshed: quadrants (and tiles) that saturate mid-batch stop there
         int since_refresh = 0;
-        while (act != 0ull) {
-            const int j = __ffsll((long long)act) - 1;
-            act &= act - 1ull;
-            const unsigned m = (unsigned)__builtin_amdgcn_readlane((int)mymask, j) & live;
-            const float4 a = sh_rec[3 * j], b = sh_rec[3 * j + 1];
-            const float cbl = sh_rec[3 * j + 2].x;
-            const int contributor = enc_base | (base + j + 1);
-            const v2f dx = a.x - fxv;                                 // one subtraction from the pixel's x (all three blend kernels)
-            const LpTerms lt = lp_terms(a.z, a.w, b.y, dx);
-            if (m & 3u) {
-                const float dy = a.y - fy0;
-                fwd_pair(true, lp_at(lt, b.x, dy), b.y, b.z, b.w, cbl, contributor, P0);
+        if constexpr (Map::kLockStep) {
+            // splats of the batch that can reach a live quadrant, front to back (bit j = splat j): the others cost nothing
+            unsigned long long act = __ballot((mymask & live) != 0u);
+            while (act != 0ull) {
+                const int j = __ffsll((long long)act) - 1;
+                act &= act - 1ull;
+                blend(base, (unsigned)j, true, (unsigned)__builtin_amdgcn_readlane((int)mymask, j) & live);
+                if (++since_refresh == 8) {
+                    since_refresh = 0;
+                    live = map.live(P0, P1);
+                    act &= __ballot((mymask & live) != 0u);
+                }
             }
-            if (m & 12u) {
-                const float dy = a.y - fy1;
-                fwd_pair(true, lp_at(lt, b.x, dy), b.y, b.z, b.w, cbl, contributor, P1);
-            }
-            if (++since_refresh == 8) {       // every 8 blended splats: quadrants (and tiles) that saturate mid-batch stop there
-                since_refresh = 0;
-                live = live_quadrants(P0, P1);
-                act &= __ballot((mymask & live) != 0u);
+        } else {
+            // each group walks the batch's entries that reach ITS quadrant, front to back, while the quadrant holds a live pixel
+            GroupWalk walk(mymask, live);
+            while (walk.more()) {
+                unsigned jj;
+                const unsigned j = walk.next(8u * (unsigned)map.grp, jj);
+                blend(base, jj, j < (unsigned)kWave, 15u);
+                if (++since_refresh == 8) {
+                    since_refresh = 0;
+                    live = map.live(P0, P1);
+                    walk.keep(live);
+                }
             }
         }
     }
-    const bool closing = live_quadrants(P0, P1) == 0u;
+    const bool closing = map.live(P0, P1) == 0u;
     const bool finalize = closing || finalize_all != 0;
     const float bg0 = finalize ? bg[0] : 0.f, bg1 = finalize ? bg[1] : 0.f, bg2 = finalize ? bg[2] : 0.f;
-    auto store_px = [&](int k, float t_, float r_, float g_, float b_, int last) {
-        const int px = px0 + (k & 1) * 8, py = py0 + (k >> 1) * 8;
+    auto store_px = [&](int e, float t_, float r_, float g_, float b_, int last) {
+        const int px = px0 + map.ex(e), py = py0 + map.ey(e);
         if (px < f.W && py < f.H) {
             const size_t pix = (size_t)py * f.W + px;
             const float tf = fabsf(t_);
@@ -331,7 +417,7 @@ __global__ __launch_bounds__(kWave, GSR_FWD_WAVES) void k_render_fwd(FrameK f, i
     store_px(3, P1.T[1], P1.Cr[1], P1.Cg[1], P1.Cb[1], P1.last1);
     // 2 = open AND some pixel is still more than half transparent after everything so far: a tile no splat has covered yet
     // (the chunk plan merges the remaining chunks when such tiles exist: the frame is not going to close, gsr_api.hip)
-    auto clear_px = [&](int k, float t_) { return px0 + (k & 1) * 8 < f.W && py0 + (k >> 1) * 8 < f.H && t_ > 0.5f; };
+    auto clear_px = [&](int e, float t_) { return px0 + map.ex(e) < f.W && py0 + map.ey(e) < f.H && t_ > 0.5f; };
     const bool stuck = __ballot(clear_px(0, P0.T[0]) || clear_px(1, P0.T[1]) || clear_px(2, P1.T[0]) || clear_px(3, P1.T[1])) != 0ull;
     // what the backward's wave will walk of this chunk's range: up to the tile's deepest contributor (launch order of K7)
     auto depth_here = [&](int last) { return (last >> kLastShift) == c + 1 ? (last & ((1 << kLastShift) - 1)) : 0; };
@@ -339,139 +425,28 @@ __global__ __launch_bounds__(kWave, GSR_FWD_WAVES) void k_render_fwd(FrameK f, i
     fwd_tile_epilogue(t, tile, c, lane, closing, stuck, walked, open, tile_walk_c, units, unit_count);
 }
 
-// ---- The same blend with the wave split into four GROUPS of 16 lanes, one per quadrant (the mapping and the walk of k_render_bwd):
-// for chunks of SMALL splats (launch_render_fwd's `groups`: fewer than 4.5 tiles per Gaussian).  A splat that reaches one or two
-// quadrants costs the lock-step kernel a pass of the whole wave; here up to four different splats share a pass.  Where splats reach
-// most quadrants the lock-step kernel is faster (wave-uniform records, whole pairs skipped): cfg3n 258 -> 230 us with groups, but
-// cfg3 105 -> 116, cfg5n 696 -> 706 - hence two kernels.  The checkpoints and every per-pixel array are the same either way.
-// per 16-lane group (= quadrant): does it still hold a live pixel?  One ballot; bit g of the result = group g
-__device__ __forceinline__ unsigned live_groups(const FwdPair &A, const FwdPair &B)
+__global__ __launch_bounds__(kWave, kFwdWaves) void k_render_fwd(FrameK f, int n_tiles, int c, int finalize_all,
+                                                   const uint2 *__restrict__ ranges_c, uint32_t *__restrict__ open,
+                                                   const uint32_t *__restrict__ sorted_gid,
+                                                   const float4 *__restrict__ records, const float *__restrict__ bg,
+                                                   float *__restrict__ out_color, float *__restrict__ T_state,
+                                                   int32_t *__restrict__ last_enc, uint32_t *__restrict__ tile_walk_c,
+                                                   float *__restrict__ ckpt, float *__restrict__ ckpt_start_c,
+                                                   UnitLists units, uint32_t *__restrict__ unit_count)
 {
-    const unsigned long long bal = __ballot(A.T[0] > 0.f || A.T[1] > 0.f || B.T[0] > 0.f || B.T[1] > 0.f);
-    return ((bal & 0xFFFFull) ? 1u : 0u) | ((bal & 0xFFFF0000ull) ? 2u : 0u) | ((bal & 0xFFFF00000000ull) ? 4u : 0u) |
-           ((bal & 0xFFFF000000000000ull) ? 8u : 0u);
+    render_fwd<QuadrantLanes>(f, c, finalize_all, ranges_c, open, sorted_gid, records, bg, out_color, T_state, last_enc, tile_walk_c, ckpt, ckpt_start_c, units, unit_count);
 }
 
-__global__ __launch_bounds__(kWave, GSR_FWD_WAVES) void k_render_fwd_groups(FrameK f, int n_tiles, int c, int finalize_all,
-                                                      const uint2 *__restrict__ ranges_c, uint32_t *__restrict__ open,
-                                                      const uint32_t *__restrict__ sorted_gid,
-                                                      const float4 *__restrict__ records, const float *__restrict__ bg,
-                                                      float *__restrict__ out_color, float *__restrict__ T_state,
-                                                      int32_t *__restrict__ last_enc, uint32_t *__restrict__ tile_walk_c,
-                                                      float *__restrict__ ckpt, float *__restrict__ ckpt_start_c,
-                                                      UnitLists units, uint32_t *__restrict__ unit_count)
+__global__ __launch_bounds__(kWave, kFwdWaves) void k_render_fwd_groups(FrameK f, int n_tiles, int c, int finalize_all,
+                                                          const uint2 *__restrict__ ranges_c, uint32_t *__restrict__ open,
+                                                          const uint32_t *__restrict__ sorted_gid,
+                                                          const float4 *__restrict__ records, const float *__restrict__ bg,
+                                                          float *__restrict__ out_color, float *__restrict__ T_state,
+                                                          int32_t *__restrict__ last_enc, uint32_t *__restrict__ tile_walk_c,
+                                                          float *__restrict__ ckpt, float *__restrict__ ckpt_start_c,
+                                                          UnitLists units, uint32_t *__restrict__ unit_count)
 {
-    __shared__ float4 sh_rec[kWave * 3];
-    const int t = (int)blockIdx.x;
-    const int tx = t % f.Gx, ty = f.ty0 + t / f.Gx;
-    const int tile = ty * f.Gx + tx;
-    if (open[tile] == 0u) return;                       // closed by an earlier chunk: pixels are final
-    const uint2 rng = ranges_c[tile];
-    const int lane = threadIdx.x, grp = lane >> 4, gi = lane & 15;
-    const int lx = gi & 3, ly = gi >> 2;                                                  // inside the quadrant; the other pixels are 4 further
-    const int px0 = tx * GSR_TILE + (grp & 1) * 8 + lx, py0 = ty * GSR_TILE + (grp >> 1) * 8 + ly;
-    const v2f fxv = {(float)px0, (float)(px0 + 4)};
-    const float fy0 = (float)py0, fy1 = fy0 + 4.f;
-    const size_t N = (size_t)f.W * f.H;
-    const unsigned grp_shift = 8u * (unsigned)grp;
-
-    FwdPair P0, P1;
-    auto load_px = [&](int e, float &t_, float &r_, float &g_, float &b_, int &last) {
-        const int px = px0 + (e & 1) * 4, py = py0 + (e >> 1) * 4;
-        const bool inside = px < f.W && py < f.H;
-        t_ = inside ? 1.f : -1.f; r_ = g_ = b_ = 0.f; last = 0;
-        if (c > 0 && inside) {
-            const size_t pix = (size_t)py * f.W + px;
-            t_ = T_state[pix];
-            r_ = out_color[pix]; g_ = out_color[N + pix]; b_ = out_color[2 * N + pix];
-            last = last_enc[pix];
-        }
-    };
-    {
-        float t0, r0, g0, b0, t1, r1, g1, b1;
-        load_px(0, t0, r0, g0, b0, P0.last0); load_px(1, t1, r1, g1, b1, P0.last1);
-        P0.T = v2f{t0, t1}; P0.Cr = v2f{r0, r1}; P0.Cg = v2f{g0, g1}; P0.Cb = v2f{b0, b1};
-        load_px(2, t0, r0, g0, b0, P1.last0); load_px(3, t1, r1, g1, b1, P1.last1);
-        P1.T = v2f{t0, t1}; P1.Cr = v2f{r0, r1}; P1.Cg = v2f{g0, g1}; P1.Cb = v2f{b0, b1};
-    }
-
-    const int n_total = (int)(rng.y - rng.x);
-    const int enc_base = (c + 1) << kLastShift;
-    // checkpoints in the layout k_render_fwd writes: [quadrant][T, r, g, b][y << 3 | x inside the quadrant]
-    auto checkpoint = [&](float *dst) {
-        float *q = dst + 4 * grp * kWave + (ly << 3 | lx);
-        q[0] = P0.T[0]; q[kWave] = P0.Cr[0]; q[2 * kWave] = P0.Cg[0]; q[3 * kWave] = P0.Cb[0];
-        q[4] = P0.T[1]; q[kWave + 4] = P0.Cr[1]; q[2 * kWave + 4] = P0.Cg[1]; q[3 * kWave + 4] = P0.Cb[1];
-        q[32] = P1.T[0]; q[kWave + 32] = P1.Cr[0]; q[2 * kWave + 32] = P1.Cg[0]; q[3 * kWave + 32] = P1.Cb[0];
-        q[36] = P1.T[1]; q[kWave + 36] = P1.Cr[1]; q[2 * kWave + 36] = P1.Cg[1]; q[3 * kWave + 36] = P1.Cb[1];
-    };
-    if (c > 0 && n_total > 0) checkpoint(ckpt_start_c + (size_t)tile * kCkptFloats);
-    for (int base = 0; base < n_total; base += kWave) {
-        unsigned live = live_groups(P0, P1);
-        if (live == 0u) break;
-        if (base > 0 && base % kSeg == 0) checkpoint(ckpt + (size_t)((rng.x + (uint32_t)base) / kSeg) * kCkptFloats);
-        const int n = min(kWave, n_total - base);
-        __syncthreads();
-        const unsigned mymask = stage_batch(sh_rec, lane, n, sorted_gid, rng.x + base, records);
-        __syncthreads();
-        // each group walks the batch's entries that reach ITS quadrant, front to back, while the quadrant holds a live pixel
-        unsigned long long act0 = (live & 1u) ? __ballot((mymask & 1u) != 0u) : 0ull, act1 = (live & 2u) ? __ballot((mymask & 2u) != 0u) : 0ull,
-                           act2 = (live & 4u) ? __ballot((mymask & 4u) != 0u) : 0ull, act3 = (live & 8u) ? __ballot((mymask & 8u) != 0u) : 0ull;
-        int since_refresh = 0;
-        while ((act0 | act1 | act2 | act3) != 0ull) {
-            const unsigned j0 = act0 ? (unsigned)__ffsll((long long)act0) - 1u : 255u, j1 = act1 ? (unsigned)__ffsll((long long)act1) - 1u : 255u,
-                           j2 = act2 ? (unsigned)__ffsll((long long)act2) - 1u : 255u, j3 = act3 ? (unsigned)__ffsll((long long)act3) - 1u : 255u;
-            act0 &= act0 - 1ull; act1 &= act1 - 1ull; act2 &= act2 - 1ull; act3 &= act3 - 1ull;
-            const unsigned j = __builtin_amdgcn_ubfe(j0 | j1 << 8 | j2 << 16 | j3 << 24, grp_shift, 8u);      // 255: the group idles
-            const bool active = j < (unsigned)kWave;
-            const unsigned jj = active ? j : 0u;                       // (an idle group reads the batch's first record: staged for sure)
-            const float4 a = sh_rec[3u * jj], b = sh_rec[3u * jj + 1u];
-            const float cbl = sh_rec[3u * jj + 2u].x;
-            const int contributor = enc_base | (int)((unsigned)base + jj + 1u);
-            const v2f dx = a.x - fxv;
-            const LpTerms lt = lp_terms(a.z, a.w, b.y, dx);
-            {
-                const float dy = a.y - fy0;
-                fwd_pair(active, lp_at(lt, b.x, dy), b.y, b.z, b.w, cbl, contributor, P0);
-            }
-            {
-                const float dy = a.y - fy1;
-                fwd_pair(active, lp_at(lt, b.x, dy), b.y, b.z, b.w, cbl, contributor, P1);
-            }
-            if (++since_refresh == 8) {       // every 8 passes: quadrants (and tiles) that saturate mid-batch stop there
-                since_refresh = 0;
-                live = live_groups(P0, P1);
-                if (!(live & 1u)) act0 = 0ull;
-                if (!(live & 2u)) act1 = 0ull;
-                if (!(live & 4u)) act2 = 0ull;
-                if (!(live & 8u)) act3 = 0ull;
-            }
-        }
-    }
-    const bool closing = live_groups(P0, P1) == 0u;
-    const bool finalize = closing || finalize_all != 0;
-    const float bg0 = finalize ? bg[0] : 0.f, bg1 = finalize ? bg[1] : 0.f, bg2 = finalize ? bg[2] : 0.f;
-    auto store_px = [&](int e, float t_, float r_, float g_, float b_, int last) {
-        const int px = px0 + (e & 1) * 4, py = py0 + (e >> 1) * 4;
-        if (px < f.W && py < f.H) {
-            const size_t pix = (size_t)py * f.W + px;
-            const float tf = fabsf(t_);
-            out_color[pix] = r_ + tf * bg0;
-            out_color[N + pix] = g_ + tf * bg1;
-            out_color[2 * N + pix] = b_ + tf * bg2;
-            T_state[pix] = t_;
-            last_enc[pix] = last;
-        }
-    };
-    store_px(0, P0.T[0], P0.Cr[0], P0.Cg[0], P0.Cb[0], P0.last0);
-    store_px(1, P0.T[1], P0.Cr[1], P0.Cg[1], P0.Cb[1], P0.last1);
-    store_px(2, P1.T[0], P1.Cr[0], P1.Cg[0], P1.Cb[0], P1.last0);
-    store_px(3, P1.T[1], P1.Cr[1], P1.Cg[1], P1.Cb[1], P1.last1);
-    auto clear_px = [&](int e, float t_) { return px0 + (e & 1) * 4 < f.W && py0 + (e >> 1) * 4 < f.H && t_ > 0.5f; };
-    const bool stuck = __ballot(clear_px(0, P0.T[0]) || clear_px(1, P0.T[1]) || clear_px(2, P1.T[0]) || clear_px(3, P1.T[1])) != 0ull;
-    auto depth_here = [&](int last) { return (last >> kLastShift) == c + 1 ? (last & ((1 << kLastShift) - 1)) : 0; };
-    const int walked = wave_max_uniform(max(max(depth_here(P0.last0), depth_here(P0.last1)), max(depth_here(P1.last0), depth_here(P1.last1))));
-    fwd_tile_epilogue(t, tile, c, lane, closing, stuck, walked, open, tile_walk_c, units, unit_count);
+    render_fwd<GroupLanes>(f, c, finalize_all, ranges_c, open, sorted_gid, records, bg, out_color, T_state, last_enc, tile_walk_c, ckpt, ckpt_start_c, units, unit_count);
 }
 
 int launch_render_fwd(const FrameK &f, const gsr_camera &cam, int c, bool last_chunk, int sort_result, const GeomWS &gw, const BinningWS &bw,
@@ -563,19 +538,15 @@ __device__ __forceinline__ void bwd_pair(const BwdSplat sp, v2f lp, v2f dx, floa
     }
 }
 
-#ifndef GSR_BWD_ORDERED_ADDS
-#define GSR_BWD_ORDERED_ADDS 1     // groups that meet on an entry in one pass add to its LDS sums one group after the other: the order of
-#endif                             // every floating-point sum is fixed by the program (0: one LDS instruction for all four, 2 % faster)
 // The kernel: one wave per work unit, front to back from the forward's checkpoint, with the wave split into four GROUPS of 16 lanes,
-// one per 8x8 quadrant of the tile.  A small splat reaches
-// one or two quadrants; walked in lock step the whole wave spends a pass (and a wave-wide reduction) on it.  Here lane l belongs
-// to quadrant g = l >> 4 and owns the pixels (i & 3 [+ 4], i >> 2 [+ 4]), i = l & 15, of it (two packed pairs), and each group walks
+// one per 8x8 quadrant of the tile (GroupLanes).  A small splat reaches one or two quadrants; walked in lock step the whole wave spends
+// a pass (and a wave-wide reduction) on it.  Here each group walks (GroupWalk)
 // only the batch's entries whose mask has ITS bit: in one pass the wave works on up to four different splats, and one transposing
 // butterfly over the rows of 16 lanes (row_sum9_transpose) reduces all four.  The order inside a quadrant is the list's, which is
 // all the blend needs.  A group's totals are added to the entry's nine sums in LDS; when the batch is through, lane j forms entry
 // j's gradient row and stores it whole (48 B) - rows are written for every entry some group attempted (row_valid).
 // A batch ends when its slowest group does (measured imbalance over a frame: 1.01 .. 1.14, tools/quad_stats.py).
-__global__ __launch_bounds__(kWave, GSR_BWD_WAVES) void k_render_bwd(FrameK f, const uint2 *__restrict__ ranges,
+__global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const uint2 *__restrict__ ranges,
                                                       const uint32_t *__restrict__ tile_walk,
                                                       const uint32_t *__restrict__ sorted_gid, const uint32_t *__restrict__ sorted_slot,
                                                       const float4 *__restrict__ records, const float *__restrict__ out_color,
@@ -599,13 +570,14 @@ __global__ __launch_bounds__(kWave, GSR_BWD_WAVES) void k_render_bwd(FrameK f, c
     }
     const uint32_t n_units = list_end[kUnitClasses - 1];
     const size_t Tn = (size_t)f.Gx * f.Gy;
-    const int lane = threadIdx.x, grp = lane >> 4, gi = lane & 15;
+    const int lane = threadIdx.x;
+    const GroupLanes map(lane);
     const size_t N = (size_t)f.W * f.H;
     const float half_w = 0.5f * (float)f.W, half_h = 0.5f * (float)f.H;
     // where the butterfly leaves this lane's share of a group's totals: which value (of which register), if any
     const int quad = (lane >> 2) & 3, in_quad = lane & 3;
     const unsigned acc_idx = (unsigned)(in_quad == 0 ? (quad < 2 ? quad : quad + 2) : in_quad == 1 ? (quad < 2 ? quad + 2 : quad + 4) : 8);
-    const unsigned grp_shift = 8u * (unsigned)grp;
+    const unsigned grp_shift = 8u * (unsigned)map.grp;
     const bool acc_on = in_quad < 2 || (in_quad == 2 && quad == 0);
 #pragma unroll
     for (int k = 0; k < 9; ++k) sh_acc[lane * 9 + k] = 0.f;
@@ -616,12 +588,11 @@ __global__ __launch_bounds__(kWave, GSR_BWD_WAVES) void k_render_bwd(FrameK f, c
         const int tile = (int)(unit.x & ((1u << kUnitTileBits) - 1u)), c = (int)(unit.x >> kUnitTileBits);
         const int sgm = (int)unit.y;
         const int ty = tile / f.Gx, tx = tile - ty * f.Gx;
-        const int lx = gi & 3, ly = gi >> 2;                                    // inside the quadrant; the other pixels are 4 further
-        const int px0 = tx * GSR_TILE + (grp & 1) * 8 + lx, py0 = ty * GSR_TILE + (grp >> 1) * 8 + ly;
+        const int px0 = map.x0(tx), py0 = map.y0(ty);
         // dx and dy are one subtraction from the pixel's coordinate, as in the forward kernels: every pixel's lp, alpha and transmittance
         // are the forward's, bit for bit
-        const v2f fxv = {(float)px0, (float)(px0 + 4)};
-        const float fy0 = (float)py0, fy1 = fy0 + 4.f;
+        const v2f fxv = {(float)px0, (float)(px0 + GroupLanes::kPair)};
+        const float fy0 = (float)py0, fy1 = fy0 + (float)GroupLanes::kPair;
         const uint2 rng = ranges[(size_t)c * Tn + tile];
         const int n_total = (int)(rng.y - rng.x);
         const int seg_begin = sgm * kSeg, seg_end = min(n_total, seg_begin + kSeg);
@@ -631,8 +602,7 @@ __global__ __launch_bounds__(kWave, GSR_BWD_WAVES) void k_render_bwd(FrameK f, c
         const float *chk = (sgm > 0) ? ckpt + (size_t)((rng.x + (uint32_t)seg_begin) / kSeg) * kCkptFloats
                                      : (c > 0 ? ckpt_start + ((size_t)(c - 1) * Tn + tile) * kCkptFloats : nullptr);
         auto load_px = [&](int e, float &Tk, float &Ek, float &r_, float &g_, float &b_, int &limit) {
-            const int ox = (e & 1) * 4, oy = (e >> 1) * 4;
-            const int px = px0 + ox, py = py0 + oy;
+            const int px = px0 + map.ex(e), py = py0 + map.ey(e);
             const bool inside = px < f.W && py < f.H;
             const size_t pix = inside ? (size_t)py * f.W + px : 0;
             const int enc = inside ? last_enc[pix] : 0;
@@ -642,10 +612,11 @@ __global__ __launch_bounds__(kWave, GSR_BWD_WAVES) void k_render_bwd(FrameK f, c
             float er = inside ? out_color[pix] : 0.f, eg = inside ? out_color[N + pix] : 0.f, eb = inside ? out_color[2 * N + pix] : 0.f;
             Tk = 1.f;
             if (chk) {
-                // the forward's checkpoint layout: [quadrant][T, r, g, b][its lane = (y << 3 | x) inside the quadrant]
-                const float *q = chk + 4 * grp * kWave + ((ly + oy) << 3 | (lx + ox));
+                // read from one pointer per element: with -ffp-contract=fast the shape of these loads has decided which product of E's
+                // sum below the compiler contracts, i.e. its rounding
+                const float *q = chk + map.ckpt(e, 0);
                 Tk = q[0];
-                er -= q[kWave]; eg -= q[2 * kWave]; eb -= q[3 * kWave];
+                er -= q[ckpt_word(0, 1, 0, 0)]; eg -= q[ckpt_word(0, 2, 0, 0)]; eb -= q[ckpt_word(0, 3, 0, 0)];
             }
             Ek = er * r_ + eg * g_ + eb * b_;
         };
@@ -673,22 +644,14 @@ __global__ __launch_bounds__(kWave, GSR_BWD_WAVES) void k_render_bwd(FrameK f, c
             __syncthreads();
             const int mypos = base + lane;
             mymask &= (mypos < qmax0 ? 1u : 0u) | (mypos < qmax1 ? 2u : 0u) | (mypos < qmax2 ? 4u : 0u) | (mypos < qmax3 ? 8u : 0u);
-            // the entries each group has to walk (wave-uniform bit sets: scalar registers)
-            unsigned long long act0 = __ballot((mymask & 1u) != 0u), act1 = __ballot((mymask & 2u) != 0u),
-                               act2 = __ballot((mymask & 4u) != 0u), act3 = __ballot((mymask & 8u) != 0u);
+            GroupWalk walk(mymask, 15u);
             // a pixel's limit relative to the batch, clamped to [0, 64]: an idle group's entry number (255) fails it by itself
             const int L00 = P0.limit0, L01 = P0.limit1, L10 = P1.limit0, L11 = P1.limit1;
             P0.limit0 = min(max(L00 - base, 0), kWave); P0.limit1 = min(max(L01 - base, 0), kWave);
             P1.limit0 = min(max(L10 - base, 0), kWave); P1.limit1 = min(max(L11 - base, 0), kWave);
-            while ((act0 | act1 | act2 | act3) != 0ull) {
-                // each group's next entry (255: it is through with the batch), one byte per group in a scalar register
-                const unsigned j0 = act0 ? (unsigned)__ffsll((long long)act0) - 1u : 255u, j1 = act1 ? (unsigned)__ffsll((long long)act1) - 1u : 255u,
-                               j2 = act2 ? (unsigned)__ffsll((long long)act2) - 1u : 255u, j3 = act3 ? (unsigned)__ffsll((long long)act3) - 1u : 255u;
-                act0 &= act0 - 1ull; act1 &= act1 - 1ull; act2 &= act2 - 1ull; act3 &= act3 - 1ull;      // (0 & anything = 0)
-                const unsigned jw = j0 | j1 << 8 | j2 << 16 | j3 << 24;
-                const unsigned j = __builtin_amdgcn_ubfe(jw, grp_shift, 8u);
-                const unsigned jj = j < (unsigned)kWave ? j : 0u;       // (an idle group reads the batch's first record: staged for sure,
-                                                                         // where the slots behind a short batch's end hold whatever LDS held)
+            while (walk.more()) {
+                unsigned jj;
+                const unsigned j = walk.next(grp_shift, jj);
                 const float4 a = sh_rec[3u * jj], b = sh_rec[3u * jj + 1u];
                 const BwdSplat sp{b.y, b.z, b.w, sh_rec[3u * jj + 2u].x};
                 const v2f dx = a.x - fxv;
@@ -706,15 +669,11 @@ __global__ __launch_bounds__(kWave, GSR_BWD_WAVES) void k_render_bwd(FrameK f, c
                               add_halves(A.S6), add_halves(A.S7), add_halves(A.S8)};
                 row_sum9_transpose(s);
                 const float mine = in_quad == 0 ? s[0] : in_quad == 1 ? s[2] : s[8];
-#if GSR_BWD_ORDERED_ADDS
-                // groups that meet on an entry in the same pass add in group order: one LDS instruction per group
+                // groups that meet on an entry in the same pass add in group order, one LDS instruction per group: the order of every
+                // floating-point sum is fixed by the program
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    if (acc_on && j < (unsigned)kWave && grp == k) atomicAdd(&sh_acc[jj * 9u + acc_idx], mine);
-#else
-                // (one instruction: the order in which the LDS serves lanes of different groups that meet on an entry is the hardware's)
-                if (acc_on && j < (unsigned)kWave) atomicAdd(&sh_acc[jj * 9u + acc_idx], mine);
-#endif
+                    if (acc_on && j < (unsigned)kWave && map.grp == k) atomicAdd(&sh_acc[jj * 9u + acc_idx], mine);
             }
             P0.limit0 = L00; P0.limit1 = L01; P1.limit0 = L10; P1.limit1 = L11;
             __syncthreads();
@@ -827,12 +786,8 @@ int launch_reduce_rows(const FrameK &f, const gsr_frame_plan &plan, const GeomWS
         // (two lanes per Gaussian for small splats, measured: 89 us against 81 at cfg3n, 352 against 374 at cfg5n — not kept)
         const long long threads = (long long)(r1 - r0) * (wide ? 64 : 8);
         const dim3 grid((unsigned)((threads + kRedBlock - 1) / kRedBlock));
-        if (wide)
-            hipLaunchKernelGGL(k_reduce_rows<64>, grid, dim3(kRedBlock), 0, s, r0, r1, gw.order, gw.cnt_open, gw.row_begin,
-                               bw.row_valid, reinterpret_cast<const float4 *>(bw.grad_rows), reinterpret_cast<float4 *>(screen_grads), write_empty);
-        else
-            hipLaunchKernelGGL(k_reduce_rows<8>, grid, dim3(kRedBlock), 0, s, r0, r1, gw.order, gw.cnt_open, gw.row_begin,
-                               bw.row_valid, reinterpret_cast<const float4 *>(bw.grad_rows), reinterpret_cast<float4 *>(screen_grads), write_empty);
+        hipLaunchKernelGGL(wide ? k_reduce_rows<64> : k_reduce_rows<8>, grid, dim3(kRedBlock), 0, s, r0, r1, gw.order, gw.cnt_open, gw.row_begin,
+                           bw.row_valid, reinterpret_cast<const float4 *>(bw.grad_rows), reinterpret_cast<float4 *>(screen_grads), write_empty);
     }
     GSR_LAUNCH_CHECK("reduce_rows", debug, s);
     return GSR_OK;
