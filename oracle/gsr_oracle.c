@@ -28,6 +28,17 @@
 
 #include "../include/gsr_constants.h"
 
+/* fragile_px: one bit per band a blend decision fell into (gsr_oracle.py FRAGILE_BITS names them) */
+#define GSO_FRAG_POWER 1u   /* sign of the power */
+#define GSO_FRAG_ALPHA 2u   /* alpha against 1/255 */
+#define GSO_FRAG_DEPTH 4u   /* depth order of two list neighbours that both reach the pixel */
+#define GSO_FRAG_TCUT  8u   /* transmittance against the cut-off */
+#define GSO_FRAG_TILE  16u  /* tile membership of a splat that reaches the pixel */
+
+/* backward_screen's front-to-back order restarts from the forward's state every GSO_SEG list entries, as the HIP backward
+ * restarts from its checkpoints (csrc/gsr_internal.h kSeg) */
+#define GSO_SEG 128
+
 #define GSO_CAT_(a, b) a##b
 #define GSO_CAT(a, b) GSO_CAT_(a, b)
 

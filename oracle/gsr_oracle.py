@@ -13,6 +13,14 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 FRAGILE_POS_ULPS = 2.0
+# fragile_px is a bit mask: which band(s) a pixel's blend decisions fell into (oracle/gsr_oracle.c GSO_FRAG_*).  Zero = strict.
+FRAGILE_POWER = 1        # sign of a splat's power (reaches the pixel at all)
+FRAGILE_ALPHA = 2        # alpha against 1/255
+FRAGILE_DEPTH = 4        # depth order of two list neighbours that both reach the pixel
+FRAGILE_TCUT = 8         # transmittance against the 1e-4 cut-off
+FRAGILE_TILE = 16        # tile membership of a splat that reaches the pixel
+FRAGILE_BITS = {"power": FRAGILE_POWER, "alpha": FRAGILE_ALPHA, "depth": FRAGILE_DEPTH, "T_cut": FRAGILE_TCUT, "tile": FRAGILE_TILE}
+SEG = 128                # backward_screen(order="front_to_back") restarts from the forward's state every SEG list entries
 _LIB = None
 
 
@@ -91,6 +99,30 @@ class OracleFrame:
         getattr(lib, f"gso_get_binning_{suf}")(C.c_void_p(handle), _ptr(self.keys), _ptr(self.point_list),
                                                 _ptr(self.ranges))
         self.keys, self.point_list = self.keys[:R], self.point_list[:R]
+        # per list instance: the largest transmittance in front of it over the pixels it is composited at (0: composited nowhere)
+        self.inst_T = np.zeros(max(R, 1), dtype)
+        self.stopped = np.zeros((H, W), np.uint8)        # the blend ended at the transmittance cut-off
+        getattr(lib, f"gso_get_inst_T_{suf}")(C.c_void_p(handle), _ptr(self.inst_T), _ptr(self.stopped))
+        self.inst_T = self.inst_T[:R]
+
+    def T_max(self) -> np.ndarray:
+        """[P]: per Gaussian, the largest transmittance in front of it over every pixel it is composited at (0: nowhere)."""
+        out = np.zeros(self.P, np.float64)
+        if self.num_rendered:
+            np.maximum.at(out, self.point_list.astype(np.int64), self.inst_T.astype(np.float64))
+        return out
+
+    def inst_position(self) -> np.ndarray:
+        """[R]: each list instance's 0-based position in its tile's list."""
+        R = self.num_rendered
+        tile = (self.keys >> np.uint64(32)).astype(np.int64)
+        return np.arange(R, dtype=np.int64) - self.ranges[tile, 0]
+
+    def fragile_counts(self) -> dict:
+        """Fragile pixels by cause (a pixel may count under several) and in all."""
+        out = {name: int((self.fragile_px & bit != 0).sum()) for name, bit in FRAGILE_BITS.items()}
+        out["any"] = int((self.fragile_px != 0).sum())
+        return out
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -98,14 +130,17 @@ class OracleFrame:
             self._h = None
 
     # ---- backward (A.9 then A.10) -------------------------------------------------------------
-    def backward_screen(self, dL_dcolor: np.ndarray, parallel: bool = False) -> np.ndarray:
+    def backward_screen(self, dL_dcolor: np.ndarray, parallel: bool = False, order: str = "back_to_front") -> np.ndarray:
         """Per-Gaussian screen-space gradients [P, 9]:
-        (dmean2D.x, dmean2D.y, gA, gB, gC, dopacity, drgb[3])."""
+        (dmean2D.x, dmean2D.y, gA, gB, gC, dopacity, drgb[3]).  order="back_to_front": A.9 as published;
+        "front_to_back": the HIP backward's algebra (E rebuilt from the forward's state every SEG entries, then
+        E -= w <c, dL/dpix>, dL/dalpha = T <c, dL/dpix> - E / (1 - alpha)), the yardstick of what it reaches in this dtype."""
+        f2b = {"back_to_front": 0, "front_to_back": 1}[order]
         g = np.ascontiguousarray(dL_dcolor, self.dtype)
         assert g.shape == (3, self.H, self.W)
         screen = np.zeros((max(self.P, 1), 9), self.dtype)
-        getattr(_lib(), f"gso_backward_screen_{self._suf}")(C.c_void_p(self._h), _ptr(g), C.c_int(int(parallel)),
-                                                             _ptr(screen))
+        getattr(_lib(), f"gso_backward_screen_order_{self._suf}")(C.c_void_p(self._h), _ptr(g), C.c_int(int(parallel)),
+                                                             C.c_int(f2b), _ptr(screen))
         return screen[:self.P]
 
     def backward_geom(self, screen: np.ndarray, g0: int = 0, g1: Optional[int] = None) -> dict:
@@ -126,8 +161,8 @@ class OracleFrame:
         out["shs"] = out["shs"][:, :M]
         return out
 
-    def backward(self, dL_dcolor: np.ndarray, parallel: bool = False) -> dict:
-        screen = self.backward_screen(dL_dcolor, parallel)
+    def backward(self, dL_dcolor: np.ndarray, parallel: bool = False, order: str = "back_to_front") -> dict:
+        screen = self.backward_screen(dL_dcolor, parallel, order)
         out = self.backward_geom(screen)
         out["screen"] = screen
         return out
@@ -199,11 +234,11 @@ class OracleRawFrame:
         self.frame = frame
         self._scales, self._rot, self._op, self._raw_rot, self._norm = scales, rotations, opacities, raw_rotations, norm
 
-    def __getattr__(self, name):                     # color, radii, fragile_px, xy, Gx, ... : the activated frame's
+    def __getattr__(self, name):                     # color, radii, fragile_px, inst_T, T_max(), xy, Gx, ... : the activated frame's
         return getattr(self.frame, name)
 
-    def backward(self, dL_dcolor: np.ndarray, parallel: bool = False) -> dict:
-        act = self.frame.backward(dL_dcolor, parallel=parallel)
+    def backward(self, dL_dcolor: np.ndarray, parallel: bool = False, order: str = "back_to_front") -> dict:
+        act = self.frame.backward(dL_dcolor, parallel=parallel, order=order)
         P = self.frame.P
         # get_scaling = exp(_scaling)                      (scene/gaussian_model.py:101-104)
         d_scaling = act["scales"] * self._scales

@@ -29,12 +29,14 @@ typedef struct FN(ctx) {
     uint64_t *keys;
     uint32_t *vals;
     int64_t *ranges;             /* 2 * Tn : [start, end) */
+    REAL *inst_T;                /* [R]: largest transmittance in front of the list instance over the pixels it is composited at (0: none) */
     /* per-pixel forward state (A.8) */
     REAL *color;                 /* [3, H, W] */
     REAL *final_T;               /* [H*W] */
     int32_t *n_contrib;          /* [H*W] */
-    uint8_t *fragile_px;         /* [H*W]: a skip/stop decision fell within fragile_eps of its threshold */
+    uint8_t *fragile_px;         /* [H*W]: a skip/stop decision fell within fragile_eps of its threshold; one GSO_FRAG_* bit per band */
     uint8_t *fragile_g;          /* [P]: Gaussian contributes to (or was decided at) a fragile pixel */
+    uint8_t *stopped;            /* [H*W]: the blend ended at the transmittance cut-off (not at the end of the list) */
     int64_t n_pairs;             /* (pixel, splat) pairs evaluated by the forward blend */
 } FN(ctx);
 
@@ -54,7 +56,8 @@ void FN(free)(FN(ctx) *c)
     free(c->radii); free(c->xy); free(c->depth); free(c->cov3D); free(c->conic_op);
     free(c->rgb); free(c->kappa); free(c->depth_lo); free(c->depth_hi); free(c->clamped); free(c->rect); free(c->tiles_touched);
     free(c->keys); free(c->vals); free(c->ranges);
-    free(c->color); free(c->final_T); free(c->n_contrib); free(c->fragile_px); free(c->fragile_g);
+    free(c->inst_T);
+    free(c->color); free(c->final_T); free(c->n_contrib); free(c->fragile_px); free(c->fragile_g); free(c->stopped);
     free(c);
 }
 
@@ -317,7 +320,8 @@ static void FN(binning)(FN(ctx) *c)
     }
 }
 
-/* ---- A.8: forward blend of one tile (all its pixels), front to back. */
+/* ---- A.8: forward blend of one tile (all its pixels), front to back.  Also records, per list instance of the tile (its own
+ * range of inst_T: no other tile writes there), the largest transmittance in front of it over the pixels it is composited at. */
 static void FN(render_tile)(FN(ctx) *c, int tx, int ty, int64_t *pairs_out)
 {
     const int W = c->W, H = c->H;
@@ -344,11 +348,11 @@ static void FN(render_tile)(FN(ctx) *c, int tx, int ty, int64_t *pairs_out)
                  * through its determinant (kappa), and the splat's pixel position -- xy ~ W/2 carries an absolute error of a
                  * few ulps of the image size, which dx = xy - pix inherits in full -- times d power / d xy */
                 const REAL band = eps * c->kappa[g], pband = c->fragile_pos * (R_FABS(co[0] * dx + co[1] * dy) + R_FABS(co[2] * dy + co[1] * dx));
-                if (R_FABS(power) <= band * mag + pband && mag > 0) fragile = 1;   /* sign of power uncertain */
+                if (R_FABS(power) <= band * mag + pband && mag > 0) fragile |= GSO_FRAG_POWER;   /* sign of power uncertain */
                 if (power > 0) continue;
                 REAL alpha = co[3] * R_EXP(power);
                 if (alpha > (REAL)GSR_ALPHA_MAX) alpha = (REAL)GSR_ALPHA_MAX;
-                if (R_FABS(alpha * 255 - 1) <= band * (1 + mag) + pband) fragile = 1;
+                if (R_FABS(alpha * 255 - 1) <= band * (1 + mag) + pband) fragile |= GSO_FRAG_ALPHA;
                 /* the sort key is the BINARY32 view depth: two list neighbours whose depths sit within a few ulps of each other
                  * may come in either order in a binary32 evaluation; the blend of two splats does not commute (the colour moves
                  * by alpha_1 alpha_2 (c_1 - c_2) T, n_contrib by one) when both reach this pixel */
@@ -356,7 +360,7 @@ static void FN(render_tile)(FN(ctx) *c, int tx, int ty, int64_t *pairs_out)
                     const float dlo = c->depth_lo[g], dhi = c->depth_hi[g];
                     const int reaches = alpha * 255 - 1 >= -(band * (1 + mag) + pband);
                     /* (depths that every evaluation finds bit-identical are ordered by index everywhere: A.7's sort is stable) */
-                    if (reaches && prev_reaches && prev_hi >= dlo && !(prev_lo == prev_hi && dlo == dhi && prev_lo == dlo)) fragile = 1;
+                    if (reaches && prev_reaches && prev_hi >= dlo && !(prev_lo == prev_hi && dlo == dhi && prev_lo == dlo)) fragile |= GSO_FRAG_DEPTH;
                     /* a neighbour that does not reach the pixel hides nothing: keep the last one that does */
                     if (reaches) { prev_lo = dlo; prev_hi = dhi > prev_hi || !prev_reaches ? dhi : prev_hi; prev_reaches = 1; }
                 }
@@ -367,11 +371,12 @@ static void FN(render_tile)(FN(ctx) *c, int tx, int ty, int64_t *pairs_out)
                 /* (an alpha that sits on its 0.99 clamp with room to spare does not move with its inputs) */
                 const REAL rho = band * (1 + mag) + pband;
                 const REAL da = co[3] * R_EXP(power) * (1 - rho) > (REAL)GSR_ALPHA_MAX ? 0 : rho * alpha / (1 - alpha);
-                if (R_FABS(test_T - (REAL)GSR_T_CUTOFF) <= (64 * eps + terr + da) * (REAL)GSR_T_CUTOFF) fragile = 1;
-                if (test_T < (REAL)GSR_T_CUTOFF) break;
+                if (R_FABS(test_T - (REAL)GSR_T_CUTOFF) <= (64 * eps + terr + da) * (REAL)GSR_T_CUTOFF) fragile |= GSO_FRAG_TCUT;
+                if (test_T < (REAL)GSR_T_CUTOFF) { c->stopped[(size_t)py * W + px] = 1; break; }
                 terr += da;
                 const REAL *col = c->rgb + 3 * g;
                 C[0] += col[0] * alpha * T; C[1] += col[1] * alpha * T; C[2] += col[2] * alpha * T;
+                if (T > c->inst_T[j]) c->inst_T[j] = T;
                 T = test_T;
                 last = contributor;
             }
@@ -444,7 +449,7 @@ static void FN(mark_rect_fragile)(FN(ctx) *c)
                         if (power > band * mag + pband) continue;
                         REAL alpha = co[3] * R_EXP(power > 0 ? 0 : power);
                         if (alpha * 255 - 1 < -(band * (1 + mag) + pband)) continue;
-                        c->fragile_px[(size_t)y * c->W + x] = 1;
+                        c->fragile_px[(size_t)y * c->W + x] |= GSO_FRAG_TILE;
                         c->fragile_g[i] = 1;
                     }
             }
@@ -486,10 +491,11 @@ FN(ctx) *FN(forward)(int P, int D, int M, int W, int H, double tanfovx, double t
     c->ranges = (int64_t *)calloc((size_t)2 * c->Gx * c->Gy, sizeof(int64_t));
     c->color = (REAL *)calloc(3 * N, sizeof(REAL)); c->final_T = (REAL *)calloc(N, sizeof(REAL));
     c->n_contrib = (int32_t *)calloc(N, 4); c->fragile_px = (uint8_t *)calloc(N, 1);
-    c->fragile_g = (uint8_t *)calloc(Pn, 1);
+    c->fragile_g = (uint8_t *)calloc(Pn, 1); c->stopped = (uint8_t *)calloc(N, 1);
 
     FN(preprocess)(c);
     FN(binning)(c);
+    c->inst_T = (REAL *)calloc((size_t)(c->R ? c->R : 1), sizeof(REAL));
     FN(mark_rect_fragile)(c);
     int64_t total_pairs = 0;
     const int Tn_slab = (c->ty1 - c->ty0) * c->Gx;
@@ -543,6 +549,55 @@ static void FN(render_tile_bwd)(const FN(ctx) *c, int tx, int ty, const REAL *dL
                 dL_dalpha *= T;
                 last_alpha = alpha;
                 dL_dalpha += (-T_final / (1 - alpha)) * bg_dot;
+                REAL dL_dG = co[3] * dL_dalpha;
+                REAL gdx = G * dx, gdy = G * dy;
+                REAL dG_ddelx = -gdx * co[0] - gdy * co[1];
+                REAL dG_ddely = -gdy * co[2] - gdx * co[1];
+                a[0] += dL_dG * dG_ddelx * ddelx_dx;
+                a[1] += dL_dG * dG_ddely * ddely_dy;
+                a[2] += -(REAL)0.5 * gdx * dx * dL_dG;
+                a[3] += -(REAL)0.5 * gdx * dy * dL_dG;
+                a[4] += -(REAL)0.5 * gdy * dy * dL_dG;
+                a[5] += G * dL_dalpha;
+            }
+        }
+}
+
+/* ---- A.9 FRONT TO BACK, in the HIP backward's algebra (csrc/gsr_render.hip bwd_pair): with Q = <out_color, dL/dpix> and D the
+ * forward's colour so far dotted with dL/dpix, the state E = Q - D is rebuilt from the forward's (T, colour) every GSO_SEG entries
+ * of the list, then E -= w <c, dL/dpix> and dL/dalpha = T <c, dL/dpix> - E / (1 - alpha); T is the forward's product.  A yardstick
+ * for what this algorithm reaches in REAL (E cancels: its relative error grows like eps / T), not a bit-exact twin of the kernel. */
+static void FN(render_tile_bwd_f2b)(const FN(ctx) *c, int tx, int ty, const REAL *dL_dpix, REAL *acc)
+{
+    const int W = c->W, H = c->H;
+    const int64_t start = c->ranges[2 * (ty * c->Gx + tx)];
+    const REAL ddelx_dx = (REAL)0.5 * W, ddely_dy = (REAL)0.5 * H;
+    for (int py = ty * GSR_TILE; py < (ty + 1) * GSR_TILE && py < H; ++py)
+        for (int px = tx * GSR_TILE; px < (tx + 1) * GSR_TILE && px < W; ++px) {
+            size_t pix = (size_t)py * W + px;
+            const int32_t last = c->n_contrib[pix];
+            REAL dpix[3], out[3], C[3] = {0, 0, 0}, T = 1, E = 0;
+            for (int ch = 0; ch < 3; ++ch) { dpix[ch] = dL_dpix[(size_t)ch * H * W + pix]; out[ch] = c->color[(size_t)ch * H * W + pix]; }
+            for (int64_t j = start; j < start + last; ++j) {
+                if ((j - start) % GSO_SEG == 0)        /* a checkpoint: the forward's state in front of entry j */
+                    E = (out[0] - C[0]) * dpix[0] + (out[1] - C[1]) * dpix[1] + (out[2] - C[2]) * dpix[2];
+                uint32_t g = c->vals[j];
+                REAL dx = c->xy[2 * g] - (REAL)px, dy = c->xy[2 * g + 1] - (REAL)py;
+                const REAL *co = c->conic_op + 4 * g;
+                REAL power = -(REAL)0.5 * (co[0] * dx * dx + co[2] * dy * dy) - co[1] * dx * dy;
+                if (power > 0) continue;
+                REAL G = R_EXP(power);
+                REAL alpha = co[3] * G;
+                if (alpha > (REAL)GSR_ALPHA_MAX) alpha = (REAL)GSR_ALPHA_MAX;
+                if (alpha < (REAL)GSR_ALPHA_MIN) continue;
+                const REAL *col = c->rgb + 3 * g;
+                REAL *a = acc + 9 * (j - start);
+                const REAL cdp = col[0] * dpix[0] + col[1] * dpix[1] + col[2] * dpix[2];
+                const REAL w = alpha * T, one_m = 1 - alpha;
+                E -= w * cdp;
+                const REAL dL_dalpha = T * cdp - E / one_m;
+                for (int ch = 0; ch < 3; ++ch) { a[6 + ch] += w * dpix[ch]; C[ch] += col[ch] * alpha * T; }
+                T = T * one_m;
                 REAL dL_dG = co[3] * dL_dalpha;
                 REAL gdx = G * dx, gdy = G * dy;
                 REAL dG_ddelx = -gdx * co[0] - gdy * co[1];
@@ -703,8 +758,9 @@ static void FN(geom_bwd)(const FN(ctx) *c, const REAL *screen, int g0, int g1,
     }
 }
 
-/* Screen-space stage of the backward (A.9): screen[9*P], zero for Gaussians that touch no tile. */
-void FN(backward_screen)(const FN(ctx) *c, const REAL *dL_dpix, int parallel, REAL *screen)
+/* Screen-space stage of the backward (A.9): screen[9*P], zero for Gaussians that touch no tile.  front_to_back: the HIP
+ * backward's order and algebra (render_tile_bwd_f2b) instead of A.9's back-to-front walk. */
+void FN(backward_screen_order)(const FN(ctx) *c, const REAL *dL_dpix, int parallel, int front_to_back, REAL *screen)
 {
     memset(screen, 0, (size_t)9 * (c->P ? c->P : 1) * sizeof(REAL));
     const int Tn_slab = (c->ty1 - c->ty0) * c->Gx;
@@ -714,7 +770,8 @@ void FN(backward_screen)(const FN(ctx) *c, const REAL *dL_dpix, int parallel, RE
         int64_t start = c->ranges[2 * (ty * c->Gx + tx)], end = c->ranges[2 * (ty * c->Gx + tx) + 1];
         if (end <= start) continue;
         REAL *acc = (REAL *)calloc((size_t)9 * (end - start), sizeof(REAL));
-        FN(render_tile_bwd)(c, tx, ty, dL_dpix, acc);
+        if (front_to_back) FN(render_tile_bwd_f2b)(c, tx, ty, dL_dpix, acc);
+        else FN(render_tile_bwd)(c, tx, ty, dL_dpix, acc);
 #pragma omp critical
         for (int64_t j = start; j < end; ++j) {
             REAL *dst = screen + 9 * (size_t)c->vals[j];
@@ -722,6 +779,12 @@ void FN(backward_screen)(const FN(ctx) *c, const REAL *dL_dpix, int parallel, RE
         }
         free(acc);
     }
+}
+
+/* A.9's order (the entry point's signature is unchanged since the oracle's first version) */
+void FN(backward_screen)(const FN(ctx) *c, const REAL *dL_dpix, int parallel, REAL *screen)
+{
+    FN(backward_screen_order)(c, dL_dpix, parallel, 0, screen);
 }
 
 /* Geometry stage of the backward (A.10) on Gaussians [g0, g1); outputs must be zero-initialised. */
@@ -757,6 +820,11 @@ void FN(get_geom)(const FN(ctx) *c, int32_t *radii, REAL *xy, REAL *depth, REAL 
     if (rect) memcpy(rect, c->rect, 4 * P * 4);
     if (tiles_touched) memcpy(tiles_touched, c->tiles_touched, P * 4);
     if (fragile_g) memcpy(fragile_g, c->fragile_g, P);
+}
+void FN(get_inst_T)(const FN(ctx) *c, REAL *inst_T, uint8_t *stopped)
+{
+    if (inst_T) memcpy(inst_T, c->inst_T, (size_t)c->R * sizeof(REAL));
+    if (stopped) memcpy(stopped, c->stopped, (size_t)c->W * c->H);
 }
 void FN(get_binning)(const FN(ctx) *c, uint64_t *keys, uint32_t *vals, int64_t *ranges)
 {

@@ -101,16 +101,27 @@ def _strict_pixels(fr64, radii, exact_radii=True):
     return strict
 
 
-def _check_forward(kw, fr64, color, radii, exact_radii=True, fr32=None):
+FRAGILE_CAP = 0.03            # no frame may have more fragile pixels than this
+
+
+def fragile_cap(measured):
+    """The cap on a workload's fragile (non-strict) pixel fraction: its measured fraction x 1.25, clipped to FRAGILE_CAP."""
+    return min(FRAGILE_CAP, 1.25 * measured)
+
+
+def _check_forward(kw, fr64, color, radii, exact_radii=True, fr32=None, frag_cap=FRAGILE_CAP):
     """Pixels at 1e-5 on the strict (non-fragile) pixels.  `fr32` (the oracle's binary32 instantiation of the same frame) switches
     to the bound for DEEP lists: with hundreds of composited splats per pixel (cfg3n: 400) a binary32 blend — the reference's own
     arithmetic restated in binary32 included — sits more than 1e-5 from the exact result on a fraction of a percent of the pixels
     (every alpha inherits ~1e-4 of relative error from its splat's binary32 screen position at 1080p; measured: 0.41 % of cfg3n's
     pixels for the binary32 oracle, 5e-5 at most).  There the HIP image must be at least as close to the binary64 result as the
-    binary32 oracle is: no strict pixel beyond 1e-4, and no more pixels beyond 1e-5 than the binary32 oracle has (x1.25 + 1e-4 N)."""
+    binary32 oracle is: no strict pixel beyond 1e-4, and no more pixels beyond 1e-5 than the binary32 oracle has (x1.25 + 1e-4 N).
+    `frag_cap`: the workload's cap on the non-strict fraction (fragile_cap of its measured fraction; FRAGILE_CAP where unmeasured).
+    Prints the oracle's fragile pixels by cause (oracle.FRAGILE_BITS)."""
     strict = _strict_pixels(fr64, radii, exact_radii)
     err = np.abs(color.astype(np.float64) - fr64.color).max(0)
-    assert strict.mean() > 0.97, f"too many fragile pixels: {1 - strict.mean():.4f}"
+    print(f"fragile pixels by cause {fr64.fragile_counts()} of {strict.size}; non-strict {1 - strict.mean():.5f} (cap {frag_cap:.5f})")
+    assert 1 - strict.mean() <= frag_cap and 1 - strict.mean() < FRAGILE_CAP, f"too many fragile pixels: {1 - strict.mean():.5f} (cap {frag_cap:.5f})"
     if fr32 is None:
         assert err[strict].max() <= 1e-5, f"pixel error {err[strict].max():.3e} on non-fragile pixels"
     else:
@@ -153,10 +164,19 @@ def _check_grads(fr64, want, got, names, masked=False):
     return int(live.sum()), int((live & ~frag).sum())
 
 
+def check_deep_per_gaussian(fr64, fr32, want, grads, gm, names, label, parallel=True):
+    """Deep lists (fr32 given): next to the tensor-wide bound, every Gaussian's gradient against its own scale, by T_max stratum
+    (tests/gradcheck.py; the yardstick: both binary32 oracles, A.9's order and the HIP backward's)."""
+    import gradcheck as GC
+    b2f = fr32.backward(gm.astype(np.float32), parallel=parallel)
+    f2b = fr32.backward(gm.astype(np.float32), parallel=parallel, order="front_to_back")
+    GC.check_grads_per_gaussian(want, GC.yardstick(want, b2f, f2b, names), grads, GC.t_max_strata(fr64.T_max()), names, label=label)
+
+
 GRAD_NAMES = ("means3D", "means2D", "opacities", "shs", "colors_precomp", "scales", "rotations", "cov3D_precomp")
 
 
-def _forward_backward_strict(kw, fr64, gimg, exact_radii=True, label="", parallel=False, fr32=None):
+def _forward_backward_strict(kw, fr64, gimg, exact_radii=True, label="", parallel=False, fr32=None, frag_cap=FRAGILE_CAP):
     """The parity check proper: forward at 1e-5 on strict pixels, then the backward of a dL/dcolor that is ZERO on every
     non-strict pixel — identically for the HIP run and the oracle — with EVERY Gaussian held to the strict bound."""
     state = {}
@@ -165,27 +185,29 @@ def _forward_backward_strict(kw, fr64, gimg, exact_radii=True, label="", paralle
         state["strict"] = _strict_pixels(fr64, radii, exact_radii)
         return np.where(state["strict"][None], gimg, 0.0).astype(np.float32)
     color, radii, grads = _run_gpu(kw, masked)
-    _check_forward(kw, fr64, color, radii, exact_radii, fr32=fr32)
+    _check_forward(kw, fr64, color, radii, exact_radii, fr32=fr32, frag_cap=frag_cap)
     gm = np.where(state["strict"][None], gimg, 0.0).astype(np.float64)
     want = fr64.backward(gm, parallel=parallel)
     names = [n for n in GRAD_NAMES if n in grads]
     live, strict_live = _check_grads(fr64, want, grads, names, masked=True)
     assert strict_live == live
+    if fr32 is not None:
+        check_deep_per_gaussian(fr64, fr32, want, grads, gm, names, label, parallel)
     print(f"{label}: {live} Gaussians with a non-zero gradient, {strict_live} held to {GRAD_ATOL_REL:g}*scale + "
           f"{GRAD_RTOL:g}*|w|; {int((~state['strict']).sum())} of {state['strict'].size} pixels masked")
     return color, radii, grads, want, live
 
 
 FIXTURES = [
-    dict(P=1, W=32, H=32, D=0, seed=101),
-    dict(P=2, W=32, H=32, D=1, seed=102),
-    dict(P=64, W=48, H=80, D=2, seed=103),
-    dict(P=64, W=80, H=48, D=3, seed=104, bg=(1.0, 1.0, 1.0)),
-    dict(P=2048, W=128, H=128, D=3, seed=105),
-    dict(P=2048, W=128, H=128, D=0, seed=106, mode="color"),
-    dict(P=2048, W=100, H=60, D=3, seed=107, mode="cov", bg=(0.2, 0.4, 0.6)),
-    dict(P=2048, W=128, H=128, D=1, seed=108, mode="color+cov"),
-    dict(P=5000, W=256, H=192, D=3, seed=109, scale_modifier=1.7),
+    dict(P=1, W=32, H=32, D=0, seed=101, frag=0.0),
+    dict(P=2, W=32, H=32, D=1, seed=102, frag=0.0),
+    dict(P=64, W=48, H=80, D=2, seed=103, frag=0.00026),
+    dict(P=64, W=80, H=48, D=3, seed=104, bg=(1.0, 1.0, 1.0), frag=0.00026),
+    dict(P=2048, W=128, H=128, D=3, seed=105, frag=0.00073),
+    dict(P=2048, W=128, H=128, D=0, seed=106, mode="color", frag=0.00079),
+    dict(P=2048, W=100, H=60, D=3, seed=107, mode="cov", bg=(0.2, 0.4, 0.6), frag=0.00117),
+    dict(P=2048, W=128, H=128, D=1, seed=108, mode="color+cov", frag=0.00092),
+    dict(P=5000, W=256, H=192, D=3, seed=109, scale_modifier=1.7, frag=0.00997),
 ]
 
 
@@ -210,7 +232,7 @@ def test_forward_backward_match_oracle(c):
     kw = _fixture_kwargs(c)
     fr64 = oracle.rasterize(dtype=np.float64, **kw)
     gimg = S.make_grad_image(c["W"], c["H"], c["seed"]).numpy()
-    _forward_backward_strict(kw, fr64, gimg, label=f"fixture P={c['P']} {c['W']}x{c['H']}")
+    _forward_backward_strict(kw, fr64, gimg, label=f"fixture P={c['P']} {c['W']}x{c['H']}", frag_cap=fragile_cap(c["frag"]))
     # and the un-masked gradient image: Gaussians that reach a fragile pixel may differ by one flipped splat
     color, radii, grads = _run_gpu(kw, gimg)
     want = fr64.backward(gimg.astype(np.float64))
@@ -561,7 +583,7 @@ def test_chunk_sort_paths_agree_and_equal_depths_keep_index_order():
     kw["means3D"][:4000, 2] = 1.5                              # S.make_camera looks down +z from the origin: view depth = z
     fr64 = oracle.rasterize(dtype=np.float64, **kw)
     assert np.unique(fr64.depth[:4000][fr64.radii[:4000] > 0].astype(np.float32)).size == 1
-    *_, live = _forward_backward_strict(kw, fr64, gimg, label="equal depths")
+    *_, live = _forward_backward_strict(kw, fr64, gimg, label="equal depths", frag_cap=fragile_cap(0.00124))
     assert live > 100
 
 
@@ -625,7 +647,7 @@ def test_cfg1_vs_oracle():
     fr64 = oracle.rasterize(dtype=np.float64, **kw)
     assert fr64.M == 1 and fr64.D == 0 and fr64.W == fr64.H == 256 and fr64.P == 10_000
     gimg = S.make_grad_image(256, 256, 1).numpy()
-    *_, live = _forward_backward_strict(kw, fr64, gimg, label="cfg1")
+    *_, live = _forward_backward_strict(kw, fr64, gimg, label="cfg1", frag_cap=fragile_cap(0.00137))
     assert live > 100
 
 
@@ -635,7 +657,7 @@ def test_cfg2_full_size_vs_oracle():
     kw = raster_kwargs(scene, cam)
     fr64 = oracle.rasterize(dtype=np.float64, parallel=True, **kw)
     gimg = S.make_grad_image(800, 800, 2).numpy()
-    *_, live = _forward_backward_strict(kw, fr64, gimg, label="cfg2", parallel=True)
+    *_, live = _forward_backward_strict(kw, fr64, gimg, label="cfg2", parallel=True, frag_cap=fragile_cap(0.0076))
     assert live > 1000
 
 
@@ -835,7 +857,7 @@ def test_cfg3_full_size_vs_oracle():
     kw = raster_kwargs(scene, cam)
     fr64 = oracle.rasterize(dtype=np.float64, parallel=True, **kw)
     gimg = S.make_grad_image(1920, 1080, 3).numpy()
-    *_, live = _forward_backward_strict(kw, fr64, gimg, exact_radii=False, label="cfg3", parallel=True)
+    *_, live = _forward_backward_strict(kw, fr64, gimg, exact_radii=False, label="cfg3", parallel=True, frag_cap=fragile_cap(0.009))
     assert live > 1000
 
 
@@ -848,7 +870,8 @@ def test_cfg3n_full_size_vs_oracle():
     fr64 = oracle.rasterize(dtype=np.float64, parallel=True, **kw)
     fr32 = oracle.rasterize(dtype=np.float32, parallel=True, **kw)
     gimg = S.make_grad_image(1920, 1080, 3).numpy()
-    *_, live = _forward_backward_strict(kw, fr64, gimg, exact_radii=False, label="cfg3n", parallel=True, fr32=fr32)
+    *_, live = _forward_backward_strict(kw, fr64, gimg, exact_radii=False, label="cfg3n", parallel=True, fr32=fr32,
+                                        frag_cap=fragile_cap(0.015))
     assert live > 800_000
 
 
@@ -1328,7 +1351,7 @@ def test_frame_with_an_uncovered_region_runs_the_live_filter_and_matches_the_ora
             assert bool((d[1:] >= d[:-1]).all())                                          # ... in depth order
     fr64 = oracle.rasterize(dtype=np.float64, parallel=True, **kw)
     gimg = S.make_grad_image(W, H, 4).numpy()
-    *_, live = _forward_backward_strict(kw, fr64, gimg, label="uncovered half", parallel=True)
+    *_, live = _forward_backward_strict(kw, fr64, gimg, label="uncovered half", parallel=True, frag_cap=fragile_cap(0.0098))
     assert live > 1000
 
 
