@@ -352,6 +352,13 @@ int gsr_densify_stats(int32_t P, const int32_t *radii, const float *viewspace_gr
 int gsr_debug_sort_temp_bytes(size_t *bytes);
 int gsr_debug_sort_pairs(uint32_t *keys0, uint32_t *keys1, uint32_t *vals0, uint32_t *vals1, int64_t n, int32_t end_bit,
                          int32_t count_on_device, void *temp, int32_t *result_buffer, void *stream);
+/* The same sort as the per-chunk tile sort calls it: the count n and the base offset are read from the device; n_max (>= n)
+ * sizes the grid and picks the scatter variant (>= 4 Mi: the LDS-reordering one); pairs live at [base, base + n) of each
+ * buffer; vals2_0 / vals2_1 (both or neither) is a second payload that travels with vals; even_passes != 0 returns the result
+ * in buffer 0 whatever the pass count.  temp: gsr_debug_sort_temp_bytes. */
+int gsr_debug_sort_pairs_ex(uint32_t *keys0, uint32_t *keys1, uint32_t *vals0, uint32_t *vals1, uint32_t *vals2_0, uint32_t *vals2_1,
+                            int64_t n, int64_t n_max, int64_t base, int32_t end_bit, int32_t even_passes, void *temp,
+                            int32_t *result_buffer, void *stream);
 
 /* Per-kernel device timing (hipEvent pairs recorded on the caller's stream around every kernel this
  * library launches, from any thread).  Off by default; the only process-wide state of the library,

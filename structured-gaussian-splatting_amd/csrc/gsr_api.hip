@@ -707,6 +707,28 @@ int gsr_debug_sort_pairs(uint32_t *keys0, uint32_t *keys1, uint32_t *vals0, uint
     return rc;
 }
 
+int gsr_debug_sort_pairs_ex(uint32_t *keys0, uint32_t *keys1, uint32_t *vals0, uint32_t *vals1, uint32_t *vals2_0, uint32_t *vals2_1,
+                            int64_t n, int64_t n_max, int64_t base, int32_t end_bit, int32_t even_passes, void *temp,
+                            int32_t *result_buffer, void *stream)
+{
+    if (!keys0 || !keys1 || !vals0 || !vals1 || !temp || !result_buffer || (!vals2_0 != !vals2_1) || n < 0 || n > n_max ||
+        n_max > 0xFFFFFFFFll || base < 0 || base + n_max > 0xFFFFFFFFll || end_bit < 1 || end_bit > 32) {
+        set_error("gsr_debug_sort_pairs_ex: bad argument");
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    uint32_t *keys[2] = {keys0, keys1}, *vals[2] = {vals0, vals1}, *vals2[2] = {vals2_0, vals2_1};
+    uint32_t *dev = reinterpret_cast<uint32_t *>((char *)temp + radix_temp_bytes());
+    const uint32_t words[2] = {(uint32_t)n, (uint32_t)base};         // count and base on the device, as the tile sort reads them
+    GSR_HIP_CHECK(hipMemcpyAsync(dev, words, sizeof words, hipMemcpyHostToDevice, s));
+    int result = 0;
+    int rc = launch_radix_sort<uint32_t>(keys, vals, dev, 0, (uint64_t)n_max, dev + 1, 0, end_bit, temp, &result, "debug_sort", false, s,
+                                         even_passes != 0, vals2_0 ? vals2 : nullptr);
+    *result_buffer = result;
+    GSR_HIP_CHECK(hipStreamSynchronize(s));                           // words lives on this stack frame
+    return rc;
+}
+
 int gsr_profile_enable(int enable)
 {
     std::lock_guard<std::mutex> lk(g_prof_mu);

@@ -494,13 +494,15 @@ template <typename K>
 __global__ __launch_bounds__(kRadixBlock) void k_radix_copy_back(const K *__restrict__ keys_in, const uint32_t *__restrict__ vals_in,
                                                                  K *__restrict__ keys_out, uint32_t *__restrict__ vals_out,
                                                                  const uint32_t *__restrict__ n_ptr, uint32_t n_host,
-                                                                 const uint32_t *__restrict__ base_ptr)
+                                                                 const uint32_t *__restrict__ base_ptr,
+                                                                 const uint32_t *__restrict__ vals2_in, uint32_t *__restrict__ vals2_out)
 {
     const uint32_t n = n_ptr ? *n_ptr : n_host;
     const uint32_t bo = base_ptr ? *base_ptr : 0u;
     for (uint32_t i = blockIdx.x * kRadixBlock + threadIdx.x; i < n; i += gridDim.x * kRadixBlock) {
         keys_out[bo + i] = keys_in[bo + i];
         vals_out[bo + i] = vals_in[bo + i];
+        if (vals2_in) vals2_out[bo + i] = vals2_in[bo + i];          // the second payload comes back with its pairs
     }
 }
 
@@ -561,7 +563,7 @@ int launch_radix_sort(K *const keys[2], uint32_t *const vals[2], const uint32_t 
         uint64_t blocks = (n_max + 4 * kRadixBlock - 1) / (4 * kRadixBlock);
         if (blocks > 2048) blocks = 2048;
         hipLaunchKernelGGL(k_radix_copy_back<K>, dim3((unsigned)(blocks ? blocks : 1)), dim3(kRadixBlock), 0, s, keys[cur], vals[cur], keys[cur ^ 1],
-                           vals[cur ^ 1], n_ptr, n_host, base_ptr);
+                           vals[cur ^ 1], n_ptr, n_host, base_ptr, vals2 ? vals2[cur] : nullptr, vals2 ? vals2[cur ^ 1] : nullptr);
         cur ^= 1;
     }
     *result = cur;

@@ -66,7 +66,7 @@ class DebugViews(C.Structure):
 EXPORTS = ("gsr_version", "gsr_last_error", "gsr_workspace_sizes", "gsr_binning_size", "gsr_binning_first_chunk_capacity", "gsr_forward_preprocess", "gsr_forward",
            "gsr_forward_render", "gsr_bwd_segment_entries", "gsr_backward_rows_size", "gsr_backward_prepare", "gsr_backward_render", "gsr_backward_geom", "gsr_backward_geom_rows", "gsr_frame_arrays", "gsr_exchange_rows_gather", "gsr_exchange_rows_scatter", "gsr_mark_visible", "gsr_debug_get_views", "gsr_profile_enable",
            "gsr_profile_read", "gsr_loss_workspace_size", "gsr_loss_l1_ssim_forward", "gsr_loss_l1_ssim_backward", "gsr_loss_l1_ssim_forward_rows", "gsr_loss_l1_ssim_backward_rows", "gsr_loss_l1_backward",
-           "gsr_debug_sort_temp_bytes", "gsr_debug_sort_pairs", "gsr_dist2_workspace_size", "gsr_dist2_knn3", "gsr_adam_step", "gsr_adam_step_split", "gsr_adam_step_multi", "gsr_densify_stats",
+           "gsr_debug_sort_temp_bytes", "gsr_debug_sort_pairs", "gsr_debug_sort_pairs_ex", "gsr_dist2_workspace_size", "gsr_dist2_knn3", "gsr_adam_step", "gsr_adam_step_split", "gsr_adam_step_multi", "gsr_densify_stats",
            "gsr_activations_forward", "gsr_activations_backward")
 
 _lib = None
@@ -366,6 +366,36 @@ def debug_sort_pairs(keys: torch.Tensor, vals: torch.Tensor, end_bit: int, count
                                            C.c_int64(n), C.c_int32(end_bit), C.c_int32(int(count_on_device)), _ptr(temp),
                                            C.byref(res), _stream(keys.device)), "gsr_debug_sort_pairs")
     return k[res.value], v[res.value]
+
+
+def debug_sort_pairs_ex(keys: torch.Tensor, vals: torch.Tensor, end_bit: int, n_max: int, base: int = 0,
+                        vals2: Optional[torch.Tensor] = None, even_passes: bool = False):
+    """The library's stable radix sort as the per-chunk tile sort calls it (test hook): the n = keys.numel() pairs sit at
+    [base, base + n) of buffers of base + n_max words, the count and the base are device words, n_max sizes the launch and
+    picks the scatter variant, vals2 (optional) travels with vals.  Returns (keys, vals, vals2 or None, result buffer) of the
+    pairs' range."""
+    n = keys.numel()
+    if n > n_max:
+        raise ValueError("n > n_max")
+    size = base + max(n_max, 1)
+
+    def pair(t):
+        a = torch.full((size,), -1, dtype=torch.int32, device=keys.device)
+        a[base:base + n] = t.reshape(-1).to(torch.int32)
+        return [a, torch.full_like(a, -1)]
+    k, v = pair(keys), pair(vals)
+    v2 = pair(vals2) if vals2 is not None else [None, None]
+    b = C.c_size_t(0)
+    _check(load().gsr_debug_sort_temp_bytes(C.byref(b)), "gsr_debug_sort_temp_bytes")
+    temp = torch.empty(b.value, dtype=torch.uint8, device=keys.device)
+    res = C.c_int32(0)
+    with torch.cuda.device(keys.device):
+        _check(load().gsr_debug_sort_pairs_ex(_ptr(k[0]), _ptr(k[1]), _ptr(v[0]), _ptr(v[1]), _ptr(v2[0]), _ptr(v2[1]), C.c_int64(n),
+                                              C.c_int64(n_max), C.c_int64(base), C.c_int32(end_bit), C.c_int32(int(even_passes)),
+                                              _ptr(temp), C.byref(res), _stream(keys.device)), "gsr_debug_sort_pairs_ex")
+    r = res.value
+    out = lambda bufs: None if bufs[r] is None else bufs[r][base:base + n]
+    return out(k), out(v), out(v2), r
 
 
 def dist2_knn3(xyz: torch.Tensor) -> torch.Tensor:
