@@ -25,6 +25,13 @@ constexpr float kC1 = 0.01f * 0.01f, kC2 = 0.03f * 0.03f;
 struct Win { float g[11]; };
 typedef float v2f __attribute__((ext_vector_type(2)));     // packed-fp32 operand: two moments of one pixel per VALU issue
 
+// The five moments and the three covariances are accumulated with explicit fused multiply-adds, one rounding per tap, so
+// that E[ab] and s12 round exactly as E[a^2], E[b^2], s1 and s2 do.  Left to -ffp-contract=fast, the scalar E[ab] chain
+// was SLP-vectorised into a packed multiply and separate adds (two roundings per tap) and s12 into a rounded product and
+// a subtraction: at a = b, s12 != s1 and A2 != B2, and SSIM's gradient, zero there, kept a residue of a few hundred ulps
+// of its C2-sized terms.
+__device__ __forceinline__ v2f pk_fma(float g, v2f x, v2f acc) { return __builtin_elementwise_fma(v2f{g, g}, x, acc); }
+
 // 1-D grid, XCD-aware: workgroups are dealt round-robin over the 8 XCDs, so XCD x gets the contiguous run of
 // (channel, tile row, tile column) items [start(x), start(x) + count(x)): neighbouring tiles, whose 5-px halos
 // overlap, then share one L2 instead of fetching the halo from HBM once per XCD.
@@ -181,9 +188,9 @@ __global__ __launch_bounds__(kLBlock) void k_loss_fwd(int C, int H, int W, LossR
 #pragma unroll
             for (int i = 0; i < 11; ++i) {
                 const float g = win.g[i];
-                s01 += g * ab[o + i];
-                s23 += g * sq[o + i];
-                s4 += g * pr[o + i];
+                s01 = pk_fma(g, ab[o + i], s01);
+                s23 = pk_fma(g, sq[o + i], s23);
+                s4 = fmaf(g, pr[o + i], s4);
             }
             m[0][o] = s01[0]; m[1][o] = s01[1]; m[2][o] = s23[0]; m[3][o] = s23[1]; m[4][o] = s4;
         }
@@ -212,7 +219,12 @@ __global__ __launch_bounds__(kLBlock) void k_loss_fwd(int C, int H, int W, LossR
             v2f t01 = {0.f, 0.f}, t23 = {0.f, 0.f};
             float t4 = 0.f;
 #pragma unroll
-            for (int i = 0; i < 11; ++i) { const float g = win.g[i]; t01 += g * v01[k + i]; t23 += g * v23[k + i]; t4 += g * v4[k + i]; }
+            for (int i = 0; i < 11; ++i) {
+                const float g = win.g[i];
+                t01 = pk_fma(g, v01[k + i], t01);
+                t23 = pk_fma(g, v23[k + i], t23);
+                t4 = fmaf(g, v4[k + i], t4);
+            }
             acc[0][k] = t01[0]; acc[1][k] = t01[1]; acc[2][k] = t23[0]; acc[3][k] = t23[1]; acc[4][k] = t4;
         }
     }
@@ -222,7 +234,7 @@ __global__ __launch_bounds__(kLBlock) void k_loss_fwd(int C, int H, int W, LossR
         const int y = y0 + rr0 + k, x = x0 + cc;
         const float mu1 = acc[0][k], mu2 = acc[1][k], eaa = acc[2][k], ebb = acc[3][k], eab = acc[4][k];
         if (y < H && x < W && y >= rows.map_b && y < rows.map_e) {
-            const float s1 = eaa - mu1 * mu1, s2 = ebb - mu2 * mu2, s12 = eab - mu1 * mu2;
+            const float s1 = fmaf(-mu1, mu1, eaa), s2 = fmaf(-mu2, mu2, ebb), s12 = fmaf(-mu1, mu2, eab);
             const float A1 = 2.f * mu1 * mu2 + kC1, A2 = 2.f * s12 + kC2;
             const float B1 = mu1 * mu1 + mu2 * mu2 + kC1, B2 = s1 + s2 + kC2;
             const float inv = 1.f / (B1 * B2);
