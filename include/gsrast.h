@@ -29,7 +29,8 @@ extern "C" {
 
 #define GSR_VERSION 12
 #define GSR_SCREEN_GRAD_STRIDE 12   /* floats per Gaussian in `screen_grads`: (dmean2D.x, dmean2D.y,
-                                       dconic A, B, C, dopacity, drgb[3], 3 pad) */
+                                       dconic A, B, C, dopacity, drgb[3], dz (gsr_backward_render_aux;
+                                       0 otherwise), 2 pad) */
 
 typedef enum gsr_status {
     GSR_OK = 0,
@@ -219,6 +220,43 @@ int gsr_backward_geom(const gsr_frame_desc *desc, const gsr_camera *cam, const g
 int gsr_backward_geom_rows(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, const int32_t *radii,
                            const void *geom_ws, const float *screen_grads, const int32_t *rows, int32_t n_rows, const gsr_grads *out,
                            void *stream);
+
+/* ---- Depth and alpha maps beside the colour image (the "aux" outputs; additive: every call above keeps its meaning).
+ * For one pixel, over the splats the colour composites (same alpha >= 1/255 test, 0.99 clamp and stop rule), w_i = alpha_i T_i:
+ *   depth = sum_i w_i z_i   z_i = the Gaussian's view-space z, (means3D . viewmatrix)_z; no background term, not normalised
+ *                           (mean depth = depth / alpha)
+ *   alpha = 1 - T_final     T_final = |final_T| of gsr_debug_views (frozen in front of the stopping splat)
+ * Both are differentiable: gsr_backward_render_aux takes their upstream gradients, gsr_backward_geom_aux adds the depth's chain
+ * to means3D.  The means2D gradient then carries the depth and alpha loss terms too (it feeds the densification statistics).
+ * ckpt_ws: the depth so far at every checkpoint of the blend backward, gsr_aux_workspace_size bytes for a binning workspace of
+ * `binning_capacity` instances (0 = num_rendered): 1 KB per 128 instances plus (GSR_MAX_CHUNKS - 1) KB per 16x16 tile.  It may
+ * be NULL when the frame binned nothing (num_rendered == 0).  Whole images only (tile_row_begin = tile_row_end = 0). */
+typedef struct gsr_aux_outputs {
+    float *depth;          /* [H,W] */
+    float *alpha;          /* [H,W] */
+    void *ckpt_ws;
+} gsr_aux_outputs;
+int gsr_aux_workspace_size(const gsr_frame_desc *desc, int64_t binning_capacity, size_t *bytes);
+/* gsr_forward_render / gsr_forward that also write aux->depth and aux->alpha (aux NULL: exactly the plain call).  The colour, the
+ * radii and the plan are those of the plain call, bit for bit. */
+int gsr_forward_render_aux(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws,
+                           void *binning_ws, void *image_ws, gsr_frame_plan *plan_host, float *out_color,
+                           const gsr_aux_outputs *aux, void *stream);
+int gsr_forward_aux(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *image_ws,
+                    int32_t *radii, gsr_frame_plan *plan_host, void *binning_ws, int64_t binning_capacity, float *out_color,
+                    gsr_grads *early_fill, const gsr_aux_outputs *aux, void *stream);
+/* gsr_backward_render of an aux frame: aux = what its forward was given (depth and ckpt_ws are read, alpha is not);
+ * dL_dcolor [3,H,W], dL_ddepth [H,W], dL_dalpha [H,W]: any may be NULL (zero).  screen_grads slot 9 receives dL/dz, the
+ * gradient of the Gaussian's view depth.  aux NULL: exactly gsr_backward_render (dL_dcolor required, the other two ignored). */
+int gsr_backward_render_aux(const gsr_frame_desc *desc, const gsr_camera *cam, const void *geom_ws, void *binning_ws,
+                            const void *image_ws, void *rows_ws, const gsr_frame_plan *plan_host, const float *out_color,
+                            const gsr_aux_outputs *aux, const float *dL_dcolor, const float *dL_ddepth, const float *dL_dalpha,
+                            float *screen_grads, void *stream);
+/* gsr_backward_geom plus the depth's chain: out->means3D (when not NULL) gains dL/dz (V[0][2], V[1][2], V[2][2]), dL/dz from
+ * screen_grads slot 9 (gsr_backward_render_aux), V = viewmatrix as passed. */
+int gsr_backward_geom_aux(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g,
+                          const int32_t *radii, const void *geom_ws, const float *screen_grads, int32_t g_begin,
+                          int32_t g_end, int32_t binned_ranks, const gsr_frame_plan *own_plan, const gsr_grads *out, void *stream);
 
 /* Device pointers into a frame's geometry workspace (valid after gsr_forward_preprocess):
  *   depth_keys [P]  by Gaussian: the bits of its view depth (a positive binary32: ordered as an integer), 0xFFFFFFFF = not

@@ -357,8 +357,10 @@ int gsr_forward_preprocess(const gsr_frame_desc *desc, const gsr_camera *cam, co
 
 // fill (optional): a zero fill to enqueue behind the FIRST chunk's blend and readback kernels, ahead of the wait for that readback
 // (gsr_forward's early fill); *fill_done reports whether it was enqueued
+// aux (optional): the depth / alpha outputs (gsr_forward_render_aux)
 static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *binning_ws,
-                               void *image_ws, gsr_frame_plan *plan, float *out_color, void *stream, const ZeroSegs *fill, bool *fill_done)
+                               void *image_ws, gsr_frame_plan *plan, float *out_color, void *stream, const ZeroSegs *fill, bool *fill_done,
+                               const gsr_aux_outputs *aux_out = nullptr)
 {
     int rc = validate(desc);
     if (rc) return rc;
@@ -373,6 +375,10 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
     const bool dbg = desc->debug != 0;
     const FrameK f = make_frame(*desc);
     ImageWS iw = carve_image(image_ws, f);
+    if (aux_out && (!aux_out->depth || !aux_out->alpha || (plan->num_rendered > 0 && !aux_out->ckpt_ws) || f.ty0 != 0 || f.ty1 != f.Gy)) {
+        set_error("gsr_forward_render_aux: depth, alpha and (for a frame that bins anything) ckpt_ws are required; whole images only");
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
     plan->chunks_run = 0; plan->instances_emitted = 0; plan->sort_result = 0; plan->tile_order_ready = 0;
     if (f.P == 0 || plan->num_rendered == 0) {
         // nothing to bin: one blend pass over empty ranges writes the background
@@ -380,7 +386,9 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
         BinningWS bw0 = carve_binning(binning_ws, 0, f);
         if (f.P == 0 || !geom_ws) gw0.ctrl = iw.ctrl_scratch;   // no geometry workspace at all
         if ((rc = launch_binning_init(f, gw0, iw, dbg, s))) return rc;
-        if ((rc = launch_render_fwd(f, *cam, 0, true, 0, gw0, bw0, iw, out_color, dbg, s))) return rc;
+        AuxWS ax0 = carve_aux(nullptr, 0, f);          // (no list entries: the checkpoints are never touched)
+        if (aux_out) { ax0.depth = aux_out->depth; ax0.alpha = aux_out->alpha; ax0.ckpt = ax0.ckpt_start = nullptr; }
+        if ((rc = launch_render_fwd(f, *cam, 0, true, 0, gw0, bw0, iw, out_color, dbg, s, false, aux_out ? &ax0 : nullptr))) return rc;
         plan->chunks_run = 1;
         return GSR_OK;
     }
@@ -391,6 +399,8 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
     // GSR_ERR_WORKSPACE before anything of that chunk is written (re-run this stage with a workspace for R instances).
     const int64_t capacity = plan->binning_capacity > 0 ? plan->binning_capacity : plan->num_rendered;
     BinningWS bw = carve_binning(binning_ws, capacity, f);
+    AuxWS ax = carve_aux(aux_out ? aux_out->ckpt_ws : nullptr, capacity, f);
+    if (aux_out) { ax.depth = aux_out->depth; ax.alpha = aux_out->alpha; }
     if (!plan->binning_initialised && (rc = launch_binning_init(f, gw, iw, dbg, s))) return rc;
     plan->binning_initialised = 0;                  // a re-run of this stage must reset the tile ranges / open flags itself
     int sort_result = 0;
@@ -463,7 +473,7 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
         // small splats (fewer than 4.5 tiles per Gaussian on average; filtered chunks bin a small, unknown part of their bound):
         // the blend forward with one 16-lane group per quadrant
         const bool small_splats = kFwdGroups >= 0 ? kFwdGroups != 0 : (!((plan->chunks_filtered >> c) & 1) && chunk_n > 0 && chunk_max * 2 < chunk_n * 9);
-        if ((rc = launch_render_fwd(f, *cam, c, last, sort_result, gw, bw, iw, out_color, dbg, s, small_splats))) return rc;
+        if ((rc = launch_render_fwd(f, *cam, c, last, sort_result, gw, bw, iw, out_color, dbg, s, small_splats, aux_out ? &ax : nullptr))) return rc;
         plan->chunks_run = c + 1;
         plan->instances_emitted = -1;                 // the last chunk's count stays on the device
         if (last) break;
@@ -494,8 +504,9 @@ int gsr_forward_render(const gsr_frame_desc *desc, const gsr_camera *cam, const 
     return forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, nullptr, &unused);
 }
 
-int gsr_forward(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *image_ws, int32_t *radii,
-                gsr_frame_plan *plan, void *binning_ws, int64_t binning_capacity, float *out_color, gsr_grads *early_fill, void *stream)
+static int forward_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *image_ws, int32_t *radii,
+                        gsr_frame_plan *plan, void *binning_ws, int64_t binning_capacity, float *out_color, gsr_grads *early_fill, void *stream,
+                        const gsr_aux_outputs *aux)
 {
     int rc = gsr_forward_preprocess(desc, cam, g, geom_ws, image_ws, radii, plan, stream);
     if (rc) return rc;
@@ -526,7 +537,8 @@ int gsr_forward(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gau
         const BinningWS bw = carve_binning(binning_ws, cap, f);
         fill = zero_segments(f, *g, nullptr, *early_fill, bw.row_valid, ((size_t)(cap < 1 ? 1 : cap) + 15) & ~(size_t)15);
     }
-    if ((rc = forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, fill.n > 0 ? &fill : nullptr, &filled)))
+    if ((rc = forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, fill.n > 0 ? &fill : nullptr, &filled,
+                                  aux)))
         return rc;
     if (fill_wanted && plan->chunks_run > 0 && effective_binned_ranks(*plan) * 4 < (long long)desc->P) {
         if (!filled) {
@@ -537,6 +549,35 @@ int gsr_forward(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gau
         early_fill->prezeroed = 1;
         plan->tile_order_ready = 1;                      // the fill also cleared the blend backward's row flags
     }
+    return GSR_OK;
+}
+
+int gsr_forward(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *image_ws, int32_t *radii,
+                gsr_frame_plan *plan, void *binning_ws, int64_t binning_capacity, float *out_color, gsr_grads *early_fill, void *stream)
+{
+    return forward_impl(desc, cam, g, geom_ws, image_ws, radii, plan, binning_ws, binning_capacity, out_color, early_fill, stream, nullptr);
+}
+
+int gsr_forward_aux(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *image_ws, int32_t *radii,
+                    gsr_frame_plan *plan, void *binning_ws, int64_t binning_capacity, float *out_color, gsr_grads *early_fill,
+                    const gsr_aux_outputs *aux, void *stream)
+{
+    return forward_impl(desc, cam, g, geom_ws, image_ws, radii, plan, binning_ws, binning_capacity, out_color, early_fill, stream, aux);
+}
+
+int gsr_forward_render_aux(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *binning_ws,
+                           void *image_ws, gsr_frame_plan *plan, float *out_color, const gsr_aux_outputs *aux, void *stream)
+{
+    bool unused = false;
+    return forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, nullptr, &unused, aux);
+}
+
+int gsr_aux_workspace_size(const gsr_frame_desc *desc, int64_t binning_capacity, size_t *bytes)
+{
+    int rc = validate(desc);
+    if (rc) return rc;
+    if (binning_capacity < 0 || !bytes) { set_error("gsr_aux_workspace_size: bad binning_capacity / NULL out"); return GSR_ERR_INVALID_ARGUMENT; }
+    *bytes = carve_aux(nullptr, binning_capacity, make_frame(*desc)).total;
     return GSR_OK;
 }
 
@@ -566,13 +607,18 @@ int gsr_backward_prepare(const gsr_frame_desc *desc, const gsr_gaussians *g, gsr
 
 int gsr_bwd_segment_entries(void) { return kSeg; }
 
-int gsr_backward_render(const gsr_frame_desc *desc, const gsr_camera *cam, const void *geom_ws, void *binning_ws,
-                        const void *image_ws, void *rows_ws, const gsr_frame_plan *plan, const float *out_color, const float *dL_dcolor,
-                        float *screen_grads, void *stream)
+static int backward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const void *geom_ws, void *binning_ws,
+                                const void *image_ws, void *rows_ws, const gsr_frame_plan *plan, const float *out_color,
+                                const gsr_aux_outputs *aux_out, const float *dL_dcolor, const float *dL_ddepth, const float *dL_dalpha,
+                                float *screen_grads, void *stream)
 {
     int rc = validate(desc);
     if (rc) return rc;
-    if (!cam || !cam->bg || !dL_dcolor || !out_color || !plan || (desc->P > 0 && (!screen_grads || !geom_ws)) || !image_ws ||
+    if (aux_out && (!aux_out->depth || (plan && plan->num_rendered > 0 && !aux_out->ckpt_ws))) {
+        set_error("gsr_backward_render_aux: aux->depth and (for a frame that binned anything) aux->ckpt_ws are required");
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if (!cam || !cam->bg || (!dL_dcolor && !aux_out) || !out_color || !plan || (desc->P > 0 && (!screen_grads || !geom_ws)) || !image_ws ||
         (plan->num_rendered > 0 && (!binning_ws || !rows_ws))) {
         set_error("gsr_backward_render: NULL argument");
         return GSR_ERR_INVALID_ARGUMENT;
@@ -589,18 +635,38 @@ int gsr_backward_render(const gsr_frame_desc *desc, const gsr_camera *cam, const
     for (int c = 0; c < plan->chunks_run && c < GSR_MAX_CHUNKS; ++c) rows_upper += plan->chunk_instances_max[c];
     if (plan->num_rendered > 0) {
         if (!plan->tile_order_ready) GSR_HIP_CHECK(hipMemsetAsync(bw.row_valid, 0, valid_bytes(plan), s));
-        if ((rc = launch_render_bwd(f, plan->chunks_run, plan->sort_result, plan->instances_emitted >= 0 ? (long long)plan->instances_emitted : rows_upper,
-                                    gw, bw, iw, out_color, dL_dcolor, dbg, s)))
+        const long long rows_n = plan->instances_emitted >= 0 ? (long long)plan->instances_emitted : rows_upper;
+        AuxWS ax = carve_aux(aux_out ? aux_out->ckpt_ws : nullptr, plan->binning_capacity > 0 ? plan->binning_capacity : plan->num_rendered, f);
+        if (aux_out) { ax.depth = aux_out->depth; ax.alpha = aux_out->alpha; }
+        if ((rc = launch_render_bwd(f, plan->chunks_run, plan->sort_result, rows_n, gw, bw, iw, out_color, dL_dcolor, dbg, s,
+                                    aux_out ? &ax : nullptr, dL_ddepth, dL_dalpha)))
             return rc;
     }
     // only the depth ranks of chunks that ran can own gradient rows
-    if ((rc = launch_reduce_rows(f, *plan, gw, bw, screen_grads, plan->screen_prezeroed, dbg, s))) return rc;
+    if ((rc = launch_reduce_rows(f, *plan, gw, bw, screen_grads, plan->screen_prezeroed, dbg, s, aux_out != nullptr))) return rc;
     return GSR_OK;
 }
 
-int gsr_backward_geom(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, const int32_t *radii,
-                      const void *geom_ws, const float *screen_grads, int32_t g_begin, int32_t g_end, int32_t binned_ranks,
-                      const gsr_frame_plan *own_plan, const gsr_grads *out, void *stream)
+int gsr_backward_render(const gsr_frame_desc *desc, const gsr_camera *cam, const void *geom_ws, void *binning_ws,
+                        const void *image_ws, void *rows_ws, const gsr_frame_plan *plan, const float *out_color, const float *dL_dcolor,
+                        float *screen_grads, void *stream)
+{
+    return backward_render_impl(desc, cam, geom_ws, binning_ws, image_ws, rows_ws, plan, out_color, nullptr, dL_dcolor, nullptr, nullptr,
+                                screen_grads, stream);
+}
+
+int gsr_backward_render_aux(const gsr_frame_desc *desc, const gsr_camera *cam, const void *geom_ws, void *binning_ws,
+                            const void *image_ws, void *rows_ws, const gsr_frame_plan *plan, const float *out_color,
+                            const gsr_aux_outputs *aux, const float *dL_dcolor, const float *dL_ddepth, const float *dL_dalpha,
+                            float *screen_grads, void *stream)
+{
+    return backward_render_impl(desc, cam, geom_ws, binning_ws, image_ws, rows_ws, plan, out_color, aux, dL_dcolor, aux ? dL_ddepth : nullptr,
+                                aux ? dL_dalpha : nullptr, screen_grads, stream);
+}
+
+static int backward_geom_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, const int32_t *radii,
+                              const void *geom_ws, const float *screen_grads, int32_t g_begin, int32_t g_end, int32_t binned_ranks,
+                              const gsr_frame_plan *own_plan, const gsr_grads *out, void *stream, bool depth_chain)
 {
     int rc = validate(desc);
     if (rc) return rc;
@@ -618,8 +684,26 @@ int gsr_backward_geom(const gsr_frame_desc *desc, const gsr_camera *cam, const g
         binned_ranks = own_plan->chunk_rank_begin[own_plan->chunks_run];
         own_sparse = effective_binned_ranks(*own_plan) * 4 < (long long)desc->P;
     }
-    return launch_geom_bwd(f, *cam, *g, radii, gw, screen_grads, g_begin, g_end, binned_ranks, *out, desc->debug != 0,
-                           (hipStream_t)stream, nullptr, own_sparse);
+    if ((rc = launch_geom_bwd(f, *cam, *g, radii, gw, screen_grads, g_begin, g_end, binned_ranks, *out, desc->debug != 0,
+                              (hipStream_t)stream, nullptr, own_sparse)))
+        return rc;
+    if (!depth_chain) return GSR_OK;
+    return launch_geom_bwd_depth(f, *cam, radii, screen_grads, g_begin, g_end, binned_ranks, gw.order, own_sparse ? gw.cnt_open : nullptr,
+                                 geom_bwd_sparse(f, g_begin, g_end, binned_ranks, own_sparse), out->means3D, desc->debug != 0, (hipStream_t)stream);
+}
+
+int gsr_backward_geom(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, const int32_t *radii,
+                      const void *geom_ws, const float *screen_grads, int32_t g_begin, int32_t g_end, int32_t binned_ranks,
+                      const gsr_frame_plan *own_plan, const gsr_grads *out, void *stream)
+{
+    return backward_geom_impl(desc, cam, g, radii, geom_ws, screen_grads, g_begin, g_end, binned_ranks, own_plan, out, stream, false);
+}
+
+int gsr_backward_geom_aux(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, const int32_t *radii,
+                          const void *geom_ws, const float *screen_grads, int32_t g_begin, int32_t g_end, int32_t binned_ranks,
+                          const gsr_frame_plan *own_plan, const gsr_grads *out, void *stream)
+{
+    return backward_geom_impl(desc, cam, g, radii, geom_ws, screen_grads, g_begin, g_end, binned_ranks, own_plan, out, stream, true);
 }
 
 int gsr_backward_geom_rows(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, const int32_t *radii,

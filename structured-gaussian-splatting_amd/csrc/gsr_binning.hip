@@ -107,6 +107,19 @@ BinningWS carve_binning(void *base, int64_t R, const FrameK &f)
     return w;
 }
 
+AuxWS carve_aux(void *base, int64_t R, const FrameK &f)
+{
+    AuxWS w;
+    size_t o = 0;
+    char *b = (char *)base;
+    const size_t Rn = (size_t)(R > 0 ? R : 1), Tn = (size_t)f.Gx * f.Gy;
+    w.depth = w.alpha = nullptr;                    // the caller's maps (gsr_aux_outputs)
+    w.ckpt = (float *)(b + o); o += align_up((Rn / kSeg + 2) * (size_t)kAuxCkptFloats * sizeof(float));
+    w.ckpt_start = (float *)(b + o); o += align_up((Tn ? Tn : 1) * (size_t)(GSR_MAX_CHUNKS - 1) * kAuxCkptFloats * sizeof(float));
+    w.total = o;
+    return w;
+}
+
 // i / w and i % w for tile counts (both < 2^24: gsr_forward_preprocess rejects frames with more tiles): the float quotient with the
 // precomputed reciprocal is off by at most one; ~10 instructions instead of the ~45 of the 32-bit division sequence, per candidate
 __device__ __forceinline__ void divmod_tiles(uint32_t i, uint32_t w, float inv_w, int &q, int &r)

@@ -586,6 +586,31 @@ __global__ __launch_bounds__(kGeomBlock) void k_geom_bwd_sparse(FrameK f, int n_
     }
 }
 
+// ---- the aux backward's z chain: z = (means3D . viewmatrix)_z in the header's row-vector convention, so dL/dmeans3D gains
+// dL/dz (V[0][2], V[1][2], V[2][2]) = dL/dz (view[2], view[6], view[10]); dL/dz is screen_grads slot 9.  Runs behind the geometry
+// backward over the same rows (SPARSE: the ranks it visited; otherwise [g0, g0 + n)) and adds to the means3D rows it wrote.
+template <bool SPARSE>
+__global__ __launch_bounds__(kGeomBlock) void k_geom_bwd_depth(int g0, int n, int P, const uint32_t *__restrict__ order,
+                                                               const uint32_t *__restrict__ cnt_open, const float *__restrict__ view,
+                                                               const int32_t *__restrict__ radii, const float4 *__restrict__ screen,
+                                                               float *__restrict__ dmeans)
+{
+    const int t = blockIdx.x * kGeomBlock + threadIdx.x;
+    if (t >= n) return;
+    int i = g0 + t;
+    if constexpr (SPARSE) {
+        if (cnt_open && cnt_open[t] == 0u) return;
+        i = (int)order[t];
+        if (i < 0 || i >= P) return;
+    }
+    if (radii[i] <= 0) return;                       // (an invisible Gaussian's screen row may be undefined)
+    const float dz = screen[3 * (size_t)i + 2].y;
+    if (dz == 0.f) return;
+    dmeans[3 * (size_t)i] += dz * view[2];
+    dmeans[3 * (size_t)i + 1] += dz * view[6];
+    dmeans[3 * (size_t)i + 2] += dz * view[10];
+}
+
 // ---- one launch that zero-fills up to nine output tensors (the sparse path's "memset"): the segments are laid end to
 // end in a virtual float index space; each thread clears a float4 where the 16 bytes lie inside one segment.
 __global__ __launch_bounds__(kGeomBlock) void k_zero_segments(ZeroSegs z)
@@ -645,13 +670,31 @@ int launch_zero_segments(const ZeroSegs &z, hipStream_t s)
     return GSR_OK;
 }
 
+// the aux backward's z chain (k_geom_bwd_depth), behind launch_geom_bwd of the same arguments: over the rows it visited
+int launch_geom_bwd_depth(const FrameK &f, const gsr_camera &cam, const int32_t *radii, const float *screen_grads, int g0, int g1,
+                          int n_ranks, const uint32_t *rows, const uint32_t *cnt_open, bool sparse, float *dmeans, bool debug, hipStream_t s)
+{
+    const int n = sparse ? n_ranks : g1 - g0;
+    if (!dmeans || n <= 0) return GSR_OK;
+    ProfileScope prof("geom_bwd_depth", s);
+    const dim3 grid((unsigned)((n + kGeomBlock - 1) / kGeomBlock));
+    const float4 *screen = reinterpret_cast<const float4 *>(screen_grads);
+    if (sparse)
+        hipLaunchKernelGGL(k_geom_bwd_depth<true>, grid, dim3(kGeomBlock), 0, s, 0, n, f.P, rows, cnt_open, cam.viewmatrix, radii, screen, dmeans);
+    else
+        hipLaunchKernelGGL(k_geom_bwd_depth<false>, grid, dim3(kGeomBlock), 0, s, g0, n, f.P, nullptr, nullptr, cam.viewmatrix, radii, screen,
+                           dmeans);
+    GSR_LAUNCH_CHECK("geom_bwd_depth", debug, s);
+    return GSR_OK;
+}
+
 int launch_geom_bwd(const FrameK &f, const gsr_camera &cam, const gsr_gaussians &g, const int32_t *radii, const GeomWS &gw,
                     const float *screen_grads, int g0, int g1, int n_ranks, const gsr_grads &out, bool debug, hipStream_t s,
                     const uint32_t *rows, bool own_frame_sparse)
 {
     if (g1 <= g0) return GSR_OK;
     if (!rows) rows = gw.order;                  // the frame's own binned prefix
-    if (n_ranks >= 0 && g0 == 0 && g1 == f.P && (own_frame_sparse || (long long)n_ranks * 4 < (long long)f.P)) {
+    if (geom_bwd_sparse(f, g0, g1, n_ranks, own_frame_sparse)) {
         // depth-complex frame: almost every gradient row is zero -> memset the outputs, then visit the binned prefix only
         ProfileScope prof("geom_bwd", s);
         int rc0;

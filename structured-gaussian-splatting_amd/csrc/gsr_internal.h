@@ -12,7 +12,7 @@
 namespace gsr {
 
 constexpr int kWave = 64;                 // CDNA wavefront
-constexpr int kRowFloats = 12;            // per-instance gradient row (48 B, 3 x float4; 9 used)
+constexpr int kRowFloats = 12;            // per-instance gradient row (48 B, 3 x float4; 9 used, 10 by the aux backward)
 constexpr size_t kAlign = 256;
 
 void set_error(const char *fmt, ...);     // thread-local message behind gsr_last_error()
@@ -188,6 +188,17 @@ struct BinningWS {              // O(R): the reference's binningBuffer
                                 // backward-time allocation (gsr_backward_rows_size), not part of the carved block
     size_t total;
 };
+// The depth + alpha maps of an aux frame (gsr_forward_render_aux) and their checkpoints: the depth so far in front of every checkpoint
+// of BinningWS::ckpt (same slot) and ImageWS::ckpt_start (same chunk and tile), one 1 KB plane each.  Carved from the caller's
+// gsr_aux_outputs.ckpt_ws, allocated only for aux frames; the colour checkpoints keep their layout.
+constexpr int kAuxCkptFloats = 4 * kWave;
+struct AuxWS {
+    float *depth, *alpha;       // [H, W] the caller's maps
+    float *ckpt;                // [R / kSeg + 2][kAuxCkptFloats]
+    float *ckpt_start;          // [GSR_MAX_CHUNKS - 1][Tn][kAuxCkptFloats]
+    size_t total;
+};
+AuxWS carve_aux(void *base, int64_t R, const FrameK &f);
 constexpr int kLastShift = 26;  // last_enc = (chunk + 1) << kLastShift | position
 constexpr int kQuadMaskShift = 28;                // BinningWS::gids = quadrant mask << 28 | Gaussian (P < 2^28)
 constexpr uint32_t kGidMask = (1u << kQuadMaskShift) - 1u;
@@ -247,17 +258,22 @@ struct ZeroSegs {
 ZeroSegs zero_segments(const FrameK &f, const gsr_gaussians &g, float *screen, const gsr_grads &out, uint8_t *row_valid = nullptr,
                        size_t valid_bytes = 0);
 // groups: the chunk's splats are small (fewer than 4.5 tiles per Gaussian): the quadrant-group kernel (gsr_render.hip)
+// aux (optional): also render the depth and alpha maps (the aux kernels)
 int launch_render_fwd(const FrameK &f, const gsr_camera &cam, int c, bool last_chunk, int sort_result, const GeomWS &gw, const BinningWS &bw,
-                      ImageWS &iw, float *out_color, bool debug, hipStream_t s, bool groups = false);
+                      ImageWS &iw, float *out_color, bool debug, hipStream_t s, bool groups = false, const AuxWS *aux = nullptr);
 // rows_upper: bound of the instances the chunks that ran emitted (sizes the launch: the unit count lives on the device)
+// aux (optional): the aux backward - dL_dcolor, dL_ddepth, dL_dalpha may each be NULL (zero); rows get slot 9 = sum of w dL/ddepth
+// (dL/dz of the splat)
 int launch_render_bwd(const FrameK &f, int chunks_run, int sort_result, long long rows_upper, const GeomWS &gw, BinningWS &bw,
-                      const ImageWS &iw, const float *out_color, const float *dL_dcolor, bool debug, hipStream_t s);
+                      const ImageWS &iw, const float *out_color, const float *dL_dcolor, bool debug, hipStream_t s, const AuxWS *aux = nullptr,
+                      const float *dL_ddepth = nullptr, const float *dL_dalpha = nullptr);
 // row_valid / valid_bytes: also clear that many bytes of the blend backward's row-valid flags
 int launch_zero_segments(const ZeroSegs &z, hipStream_t s);
 int launch_zero_outputs(const FrameK &f, const gsr_gaussians &g, float *screen, const gsr_grads &out, hipStream_t s,
                         uint8_t *row_valid = nullptr, size_t valid_bytes = 0);
+// aux: the rows come from the aux backward - slot 9 (dL/dz) is carried into screen_grads too
 int launch_reduce_rows(const FrameK &f, const gsr_frame_plan &plan, const GeomWS &gw, const BinningWS &bw, float *screen_grads,
-                       int prezeroed, bool debug, hipStream_t s);
+                       int prezeroed, bool debug, hipStream_t s, bool aux = false);
 // Depth ranks that can own a gradient, as far as the host knows: the chunks that ran, a chunk that went through the live filter
 // counted as nothing (only the Gaussians that still reached an open tile were binned: few, and how few is the device's knowledge).
 // Decides "sparse geometry backward + zero fill" against "dense geometry backward" (sparse below P / 4).
@@ -274,6 +290,15 @@ inline long long effective_binned_ranks(const gsr_frame_plan &plan)
 int launch_geom_bwd(const FrameK &f, const gsr_camera &cam, const gsr_gaussians &g, const int32_t *radii, const GeomWS &gw,
                     const float *screen_grads, int g0, int g1, int n_ranks, const gsr_grads &out, bool debug, hipStream_t s,
                     const uint32_t *rows = nullptr, bool own_frame_sparse = false);
+// launch_geom_bwd visits the ranks [0, n_ranks) of `rows` (sparse) instead of the Gaussians [g0, g1)
+inline bool geom_bwd_sparse(const FrameK &f, int g0, int g1, int n_ranks, bool own_frame_sparse)
+{
+    return n_ranks >= 0 && g0 == 0 && g1 == f.P && (own_frame_sparse || (long long)n_ranks * 4 < (long long)f.P);
+}
+// The aux backward's z chain behind launch_geom_bwd (same rows, same sparse choice): dmeans3D += dL/dz (view[2], view[6], view[10]),
+// dL/dz = screen_grads slot 9.  cnt_open: as launch_geom_bwd's own_frame_sparse (ranks that emitted nothing are skipped), else NULL.
+int launch_geom_bwd_depth(const FrameK &f, const gsr_camera &cam, const int32_t *radii, const float *screen_grads, int g0, int g1,
+                          int n_ranks, const uint32_t *rows, const uint32_t *cnt_open, bool sparse, float *dmeans, bool debug, hipStream_t s);
 int launch_mark_visible(int P, const float *means3D, const float *view, uint8_t *present, hipStream_t s);
 
 }  // namespace gsr

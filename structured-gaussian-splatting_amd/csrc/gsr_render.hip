@@ -54,6 +54,31 @@ __device__ __forceinline__ void row_sum9_transpose(float (&a)[9])
                  : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]), "+v"(a[8]));
 #undef GSR_DPP
 }
+// The same butterfly with a tenth value (the aux backward's sum of w dL/ddepth), reduced over the row like value 8 - four more DPP
+// adds, each placed right behind value 8's, so the wait states above cover it:   a[9]: value 9 in every lane of the row
+__device__ __forceinline__ void row_sum10_transpose(float (&a)[10])
+{
+#define GSR_DPP(d, s_, ctrl, bank) "v_add_f32_dpp %" #d ", %" #s_ ", %" #s_ " " ctrl " row_mask:0xf bank_mask:" bank "\n\t"
+    asm volatile("s_nop 1\n\t"
+                 GSR_DPP(0, 0, "row_ror:8", "0x3") GSR_DPP(1, 1, "row_ror:8", "0x3") GSR_DPP(2, 2, "row_ror:8", "0x3")
+                 GSR_DPP(3, 3, "row_ror:8", "0x3") GSR_DPP(8, 8, "row_ror:8", "0xf") GSR_DPP(9, 9, "row_ror:8", "0xf")
+                 GSR_DPP(0, 4, "row_ror:8", "0xc") GSR_DPP(1, 5, "row_ror:8", "0xc") GSR_DPP(2, 6, "row_ror:8", "0xc")
+                 GSR_DPP(3, 7, "row_ror:8", "0xc")
+                 "s_nop 1\n\t"
+                 GSR_DPP(0, 0, "row_half_mirror", "0x5") GSR_DPP(2, 2, "row_half_mirror", "0x5") GSR_DPP(8, 8, "row_half_mirror", "0xf")
+                 GSR_DPP(9, 9, "row_half_mirror", "0xf")
+                 GSR_DPP(0, 1, "row_half_mirror", "0xa") GSR_DPP(2, 3, "row_half_mirror", "0xa")
+                 "s_nop 1\n\t"
+                 GSR_DPP(0, 0, "quad_perm:[1,0,3,2]", "0xf") GSR_DPP(2, 2, "quad_perm:[1,0,3,2]", "0xf")
+                 GSR_DPP(8, 8, "quad_perm:[1,0,3,2]", "0xf") GSR_DPP(9, 9, "quad_perm:[1,0,3,2]", "0xf")
+                 "s_nop 0\n\t"
+                 GSR_DPP(0, 0, "quad_perm:[2,3,0,1]", "0xf") GSR_DPP(2, 2, "quad_perm:[2,3,0,1]", "0xf")
+                 GSR_DPP(8, 8, "quad_perm:[2,3,0,1]", "0xf") GSR_DPP(9, 9, "quad_perm:[2,3,0,1]", "0xf")
+                 "s_nop 1"
+                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]), "+v"(a[8]),
+                   "+v"(a[9]));
+#undef GSR_DPP
+}
 
 __device__ __forceinline__ int wave_max_uniform(int v)
 {
@@ -127,7 +152,8 @@ struct FwdPair {             // state of a lane's two pixels in one pair (elemen
 // One register per pixel carries both "live transmittance" and "final transmittance of a done pixel": for a done pixel
 // test_T = T (1 - alpha) is negative, so the stop test fires by itself, nothing is composited and T keeps its value.
 // ONE definition for both forward kernels (active: the lane's group has a splat in this pass - always, in the lock-step kernel).
-__device__ __forceinline__ void fwd_pair(bool active, v2f lp, float lop, float cr, float cg, float cb, int contributor, FwdPair &P)
+// Returns the pair's blend weights w = alpha T (0 where nothing was composited): the aux kernels blend the depth with them.
+__device__ __forceinline__ v2f fwd_pair(bool active, v2f lp, float lop, float cr, float cg, float cb, int contributor, FwdPair &P)
 {
     const bool keep0 = active && !(lp[0] > lop) && !(lp[0] < kLog2AlphaMin);      // power > 0  <=>  lp > lop;  alpha < 1/255  <=>  lp < log2(1/255)
     const bool keep1 = active && !(lp[1] > lop) && !(lp[1] < kLog2AlphaMin);
@@ -145,6 +171,7 @@ __device__ __forceinline__ void fwd_pair(bool active, v2f lp, float lop, float c
     P.T = v2f{stop0 ? -fabsf(P.T[0]) : test_T[0], stop1 ? -fabsf(P.T[1]) : test_T[1]};
     P.last0 = (keep0 && !stop0) ? contributor : P.last0;
     P.last1 = (keep1 && !stop1) ? contributor : P.last1;
+    return w;
 }
 
 // ---- Which four pixels of a tile a lane owns, and where their state sits in a checkpoint.  A lane owns two PAIRS of pixels (elements
@@ -155,6 +182,9 @@ __device__ __forceinline__ void fwd_pair(bool active, v2f lp, float lop, float c
 // the tile's 256 pixels as [quadrant][T, r, g, b][y << 3 | x inside the 8x8 quadrant]; this is its one definition.  The parts of a
 // word take disjoint bits, so a word is also the sum of the words of its parts (a lane's base plus a constant per element and field).
 __device__ __forceinline__ int ckpt_word(int quadrant, int field, int qx, int qy) { return (4 * quadrant + field) * kWave + (qy << 3 | qx); }
+// The aux checkpoint (kAuxCkptFloats: the depth so far in front of the same list positions) is one plane of the tile's 256 pixels,
+// [quadrant][y << 3 | x]: ckpt_word's layout with one field.
+__device__ __forceinline__ int aux_word(int quadrant, int qx, int qy) { return quadrant * kWave + (qy << 3 | qx); }
 template <int P> struct LanePairs {
     static constexpr int kPair = P;
     __device__ static int ex(int e) { return (e & 1) * kPair; }      // element e's pixel, from the lane's first (element 0)
@@ -172,6 +202,7 @@ struct QuadrantLanes : LanePairs<8> {
     __device__ int x0(int tx) const { return tx * GSR_TILE + lx; }      // the lane's first pixel (element 0) in the tile (tx, ty)
     __device__ int y0(int ty) const { return ty * GSR_TILE + ly; }
     __device__ int ckpt(int e, int field) const { return ckpt_word(0, 0, lx, ly) + ckpt_word(e, field, 0, 0); }
+    __device__ int aux(int e) const { return aux_word(0, lx, ly) + aux_word(e, 0, 0); }
     // wave-uniform 4-bit mask: quadrant k still has a live pixel
     __device__ unsigned live(const FwdPair &A, const FwdPair &B) const
     {
@@ -193,6 +224,7 @@ struct GroupLanes : LanePairs<4> {
     __device__ int x0(int tx) const { return tx * GSR_TILE + (grp & 1) * 8 + lx; }
     __device__ int y0(int ty) const { return ty * GSR_TILE + (grp >> 1) * 8 + ly; }
     __device__ int ckpt(int e, int field) const { return ckpt_word(grp, 0, lx, ly) + ckpt_word(0, field, ex(e), ey(e)); }
+    __device__ int aux(int e) const { return aux_word(grp, lx, ly) + aux_word(0, ex(e), ey(e)); }
     // bit g: group (= quadrant) g still has a live pixel.  One ballot
     __device__ unsigned live(const FwdPair &A, const FwdPair &B) const
     {
@@ -286,12 +318,23 @@ __device__ __forceinline__ void fwd_tile_epilogue(int t, int tile, int c, int la
 // different splats share a pass.  Where splats reach most quadrants lock step is faster (wave-uniform records, whole pairs skipped):
 // cfg3n 258 -> 230 us with groups, but cfg3 105 -> 116, cfg5n 696 -> 706 - hence two kernels.  The checkpoints and every per-pixel
 // array are the same either way, and so are the bits.
-template <class Map>
+//
+// kAux (gsr_forward_render_aux): the same blend also renders the expected depth, one more packed accumulator per pair,
+// Z = fma(z, w, Z) with the record's view depth z - the colour channels' own operation, so depth is bit for bit a colour channel fed
+// z - and alpha = 1 - |T| when the tile stores its pixels.  Between chunks Z lives in the depth map (as the unfinished colour lives in
+// out_color); in front of every checkpoint it goes into the aux checkpoint plane of the same slot (AuxFwdK).
+struct AuxFwdK {
+    float *depth, *alpha;              // [H, W]
+    float *ckpt;                       // [R / kSeg + 2][kAuxCkptFloats]: Z in front of the checkpoint of the same slot (BinningWS::ckpt)
+    float *ckpt_start_c;               // [Tn][kAuxCkptFloats]: Z when this chunk (>= 1) starts on a tile (ImageWS::ckpt_start)
+};
+template <class Map, bool kAux>
 __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, const uint2 *__restrict__ ranges_c, uint32_t *__restrict__ open,
                                            const uint32_t *__restrict__ sorted_gid, const float4 *__restrict__ records,
                                            const float *__restrict__ bg, float *__restrict__ out_color, float *__restrict__ T_state,
                                            int32_t *__restrict__ last_enc, uint32_t *__restrict__ tile_walk_c, float *__restrict__ ckpt,
-                                           float *__restrict__ ckpt_start_c, const UnitLists &units, uint32_t *__restrict__ unit_count)
+                                           float *__restrict__ ckpt_start_c, const UnitLists &units, uint32_t *__restrict__ unit_count,
+                                           const AuxFwdK &ax)
 {
     __shared__ float4 sh_rec[kWave * 3];
 #ifdef GSR_FWD_TRACE
@@ -330,16 +373,27 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
         load_px(2, t0, r0, g0, b0, P1.last0); load_px(3, t1, r1, g1, b1, P1.last1);
         P1.T = v2f{t0, t1}; P1.Cr = v2f{r0, r1}; P1.Cg = v2f{g0, g1}; P1.Cb = v2f{b0, b1};
     }
+    v2f Z0 = {0.f, 0.f}, Z1 = {0.f, 0.f};                  // kAux: the depth so far of the two pairs
+    if constexpr (kAux) {
+        auto load_z = [&](int e) {
+            const int px = px0 + map.ex(e), py = py0 + map.ey(e);
+            return (c > 0 && px < f.W && py < f.H) ? ax.depth[(size_t)py * f.W + px] : 0.f;
+        };
+        Z0 = v2f{load_z(0), load_z(1)}; Z1 = v2f{load_z(2), load_z(3)};
+    }
 
     const int n_total = (int)(rng.y - rng.x);
     const int enc_base = (c + 1) << kLastShift;
     // The blend backward walks this list front to back in independent segments of kSeg entries (gsr_internal.h): it starts a
     // segment from the pixels' state (live transmittance, colour so far) in front of the segment's first entry, kept here.
-    auto checkpoint = [&](float *dst) {
+    auto checkpoint = [&](float *dst, float *zdst) {
         auto put = [&](int e, const FwdPair &P, int h) {
             dst[map.ckpt(e, 0)] = P.T[h]; dst[map.ckpt(e, 1)] = P.Cr[h]; dst[map.ckpt(e, 2)] = P.Cg[h]; dst[map.ckpt(e, 3)] = P.Cb[h];
         };
         put(0, P0, 0); put(1, P0, 1); put(2, P1, 0); put(3, P1, 1);
+        if constexpr (kAux) {
+            zdst[map.aux(0)] = Z0[0]; zdst[map.aux(1)] = Z0[1]; zdst[map.aux(2)] = Z1[0]; zdst[map.aux(3)] = Z1[1];
+        }
     };
     // blend entry j of the batch into the pairs m names (bits 0-1: P0, 2-3: P1; active: the lane's group has an entry in this pass)
     auto blend = [&](int base, unsigned j, bool active, unsigned m) {
@@ -350,18 +404,24 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
         const LpTerms lt = lp_terms(a.z, a.w, b.y, dx);
         if (m & 3u) {
             const float dy = a.y - fy0;
-            fwd_pair(active, lp_at(lt, b.x, dy), b.y, b.z, b.w, cbl, contributor, P0);
+            const v2f w = fwd_pair(active, lp_at(lt, b.x, dy), b.y, b.z, b.w, cbl, contributor, P0);
+            if constexpr (kAux) { const float z = sh_rec[3u * j + 2u].y; Z0 = __builtin_elementwise_fma(v2f{z, z}, w, Z0); }
         }
         if (m & 12u) {
             const float dy = a.y - fy1;
-            fwd_pair(active, lp_at(lt, b.x, dy), b.y, b.z, b.w, cbl, contributor, P1);
+            const v2f w = fwd_pair(active, lp_at(lt, b.x, dy), b.y, b.z, b.w, cbl, contributor, P1);
+            if constexpr (kAux) { const float z = sh_rec[3u * j + 2u].y; Z1 = __builtin_elementwise_fma(v2f{z, z}, w, Z1); }
         }
     };
-    if (c > 0 && n_total > 0) checkpoint(ckpt_start_c + (size_t)tile * kCkptFloats);
+    if (c > 0 && n_total > 0)
+        checkpoint(ckpt_start_c + (size_t)tile * kCkptFloats, kAux ? ax.ckpt_start_c + (size_t)tile * kAuxCkptFloats : nullptr);
     for (int base = 0; base < n_total; base += kWave) {
         unsigned live = map.live(P0, P1);
         if (live == 0u) break;
-        if (base > 0 && base % kSeg == 0) checkpoint(ckpt + (size_t)((rng.x + (uint32_t)base) / kSeg) * kCkptFloats);
+        if (base > 0 && base % kSeg == 0) {
+            const size_t slot = (rng.x + (uint32_t)base) / kSeg;
+            checkpoint(ckpt + slot * kCkptFloats, kAux ? ax.ckpt + slot * kAuxCkptFloats : nullptr);
+        }
         const int n = min(kWave, n_total - base);
         __syncthreads();
         const unsigned mymask = stage_batch(sh_rec, lane, n, sorted_gid, rng.x + base, records);
@@ -415,6 +475,17 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
     store_px(1, P0.T[1], P0.Cr[1], P0.Cg[1], P0.Cb[1], P0.last1);
     store_px(2, P1.T[0], P1.Cr[0], P1.Cg[0], P1.Cb[0], P1.last0);
     store_px(3, P1.T[1], P1.Cr[1], P1.Cg[1], P1.Cb[1], P1.last1);
+    if constexpr (kAux) {
+        auto store_aux = [&](int e, float t_, float z_) {
+            const int px = px0 + map.ex(e), py = py0 + map.ey(e);
+            if (px < f.W && py < f.H) {
+                const size_t pix = (size_t)py * f.W + px;
+                ax.depth[pix] = z_;                             // no background term
+                ax.alpha[pix] = 1.f - fabsf(t_);
+            }
+        };
+        store_aux(0, P0.T[0], Z0[0]); store_aux(1, P0.T[1], Z0[1]); store_aux(2, P1.T[0], Z1[0]); store_aux(3, P1.T[1], Z1[1]);
+    }
     // 2 = open AND some pixel is still more than half transparent after everything so far: a tile no splat has covered yet
     // (the chunk plan merges the remaining chunks when such tiles exist: the frame is not going to close, gsr_api.hip)
     auto clear_px = [&](int e, float t_) { return px0 + map.ex(e) < f.W && py0 + map.ey(e) < f.H && t_ > 0.5f; };
@@ -434,7 +505,8 @@ __global__ __launch_bounds__(kWave, kFwdWaves) void k_render_fwd(FrameK f, int n
                                                    float *__restrict__ ckpt, float *__restrict__ ckpt_start_c,
                                                    UnitLists units, uint32_t *__restrict__ unit_count)
 {
-    render_fwd<QuadrantLanes>(f, c, finalize_all, ranges_c, open, sorted_gid, records, bg, out_color, T_state, last_enc, tile_walk_c, ckpt, ckpt_start_c, units, unit_count);
+    render_fwd<QuadrantLanes, false>(f, c, finalize_all, ranges_c, open, sorted_gid, records, bg, out_color, T_state, last_enc, tile_walk_c, ckpt, ckpt_start_c, units, unit_count,
+                                     AuxFwdK{});
 }
 
 __global__ __launch_bounds__(kWave, kFwdWaves) void k_render_fwd_groups(FrameK f, int n_tiles, int c, int finalize_all,
@@ -446,16 +518,41 @@ __global__ __launch_bounds__(kWave, kFwdWaves) void k_render_fwd_groups(FrameK f
                                                           float *__restrict__ ckpt, float *__restrict__ ckpt_start_c,
                                                           UnitLists units, uint32_t *__restrict__ unit_count)
 {
-    render_fwd<GroupLanes>(f, c, finalize_all, ranges_c, open, sorted_gid, records, bg, out_color, T_state, last_enc, tile_walk_c, ckpt, ckpt_start_c, units, unit_count);
+    render_fwd<GroupLanes, false>(f, c, finalize_all, ranges_c, open, sorted_gid, records, bg, out_color, T_state, last_enc, tile_walk_c, ckpt, ckpt_start_c, units, unit_count,
+                                  AuxFwdK{});
+}
+
+// the aux instantiations of both pixel mappings: colour, radii and every array above as the plain kernels, plus depth and alpha
+template <class Map>
+__global__ __launch_bounds__(kWave, 4) void k_render_fwd_aux(FrameK f, int n_tiles, int c, int finalize_all,
+                                                             const uint2 *__restrict__ ranges_c, uint32_t *__restrict__ open,
+                                                             const uint32_t *__restrict__ sorted_gid,
+                                                             const float4 *__restrict__ records, const float *__restrict__ bg,
+                                                             float *__restrict__ out_color, float *__restrict__ T_state,
+                                                             int32_t *__restrict__ last_enc, uint32_t *__restrict__ tile_walk_c,
+                                                             float *__restrict__ ckpt, float *__restrict__ ckpt_start_c,
+                                                             UnitLists units, uint32_t *__restrict__ unit_count, AuxFwdK ax)
+{
+    render_fwd<Map, true>(f, c, finalize_all, ranges_c, open, sorted_gid, records, bg, out_color, T_state, last_enc, tile_walk_c, ckpt, ckpt_start_c, units, unit_count, ax);
 }
 
 int launch_render_fwd(const FrameK &f, const gsr_camera &cam, int c, bool last_chunk, int sort_result, const GeomWS &gw, const BinningWS &bw,
-                      ImageWS &iw, float *out_color, bool debug, hipStream_t s, bool groups)
+                      ImageWS &iw, float *out_color, bool debug, hipStream_t s, bool groups, const AuxWS *aux)
 {
     const int n_tiles = (f.ty1 - f.ty0) * f.Gx;
     if (n_tiles <= 0) return GSR_OK;
-    ProfileScope prof("render_fwd", s);
     const size_t Tn = (size_t)f.Gx * f.Gy;
+    if (aux) {
+        ProfileScope prof("render_fwd_aux", s);
+        const AuxFwdK ax{aux->depth, aux->alpha, aux->ckpt, c > 0 ? aux->ckpt_start + (size_t)(c - 1) * Tn * kAuxCkptFloats : nullptr};
+        hipLaunchKernelGGL(groups ? k_render_fwd_aux<GroupLanes> : k_render_fwd_aux<QuadrantLanes>, dim3(n_tiles), dim3(kWave), 0, s, f, n_tiles, c,
+                           last_chunk ? 1 : 0, iw.ranges + (size_t)c * Tn, iw.open, bw.gids[1], gw.records, cam.bg, out_color, iw.T_state,
+                           iw.last_enc, iw.tile_walk + (size_t)c * Tn, bw.ckpt,
+                           c > 0 ? iw.ckpt_start + (size_t)(c - 1) * Tn * kCkptFloats : nullptr, bw.units, iw.unit_count, ax);
+        GSR_LAUNCH_CHECK("render_fwd_aux", debug, s);
+        return GSR_OK;
+    }
+    ProfileScope prof("render_fwd", s);
     hipLaunchKernelGGL(groups ? k_render_fwd_groups : k_render_fwd, dim3(n_tiles), dim3(kWave), 0, s, f, n_tiles, c, last_chunk ? 1 : 0,
                        iw.ranges + (size_t)c * Tn, iw.open, bw.gids[1], gw.records, cam.bg, out_color, iw.T_state,
                        iw.last_enc, iw.tile_walk + (size_t)c * Tn, bw.ckpt,
@@ -486,16 +583,26 @@ int launch_render_fwd(const FrameK &f, const gsr_camera &cam, int c, bool last_c
 // per pixel (dL/dopacity = sum(G dL/dalpha) = sum(ga dL/dalpha) / opacity: one division per splat, after the reduction), and
 // the conic enters through the pre-scaled record fields directly: cA = -2 ln2 qA, cB = -ln2 qB, cC = -2 ln2 qC, so
 // -(tx cA + ty cB) = ln2 (2 qA tx + qB ty): the factor ln2 goes into the row store.
+//
+// The aux backward (k_render_bwd<true>) adds the depth and alpha maps' upstream gradients g_z, g_a.  Depth is one more linear channel
+// (colour z_i, no background): <c_i, dL/dpix> gains z_i g_z, E's starting value g_z (depth_final - Z at the checkpoint), and
+// dL/dz_i = sum w_i g_z is a tenth per-splat sum.  alpha = 1 - T_final adds g_a T_final / (1 - alpha_i) to dL/dalpha_i: a constant
+// per pixel (GA = g_a T_final) times the 1 / (1 - alpha) the colour term already has, one FMA - not through E, where it would be a
+// difference of near-equal numbers once T is small.
 struct BwdSplat {            // per-splat values (uniform over a 16-lane group)
     float lop, cr, cg, cb;
+    float z;                           // aux: the view depth
 };
 struct BwdPair {             // state of a lane's pair of pixels (4 apart in x, the same row)
     v2f T, E, dpr, dpg, dpb;           // transmittance in front of the current splat; E = Q - D: what everything behind the current
                                        // splat (and the background) still adds to <pixel, dL/dpix>; dL/dpix
     int limit0, limit1;                // contributors of the current chunk each pixel takes part in
 };
+struct BwdPairAux {          // aux: the same pair's dL/ddepth and dL/dalpha T_final
+    v2f dpz, GA;
+};
 // the lane's partial sums of one splat, per pair element: X = sum tA dx, Y = sum tA dy (dL/dmean2D = ln2 (2 qA X + qB Y, 2 qC Y + qB X):
-// formed once per splat by the lane that stores the row), S2..S4 the conic's, S5 the opacity's, S6..S8 the colour's
+// formed once per splat by the lane that stores the row), S2..S4 the conic's, S5 the opacity's, S6..S8 the colour's, S9 (aux) the depth's
 struct BwdAcc { v2f X, Y, S2, S3, S4, S5, S6, S7, S8; };
 __device__ __forceinline__ float add_halves(v2f v)
 {
@@ -504,8 +611,9 @@ __device__ __forceinline__ float add_halves(v2f v)
     return r;
 }
 
-template <bool INIT>         // INIT: the splat's first pair, the sums start here (A comes in undefined)
-__device__ __forceinline__ void bwd_pair(const BwdSplat sp, v2f lp, v2f dx, float dy, int pos, BwdPair &P, BwdAcc &A)
+template <bool INIT, bool kAux = false>         // INIT: the splat's first pair, the sums start here (A comes in undefined)
+__device__ __forceinline__ void bwd_pair(const BwdSplat sp, v2f lp, v2f dx, float dy, int pos, BwdPair &P, BwdAcc &A,
+                                         const BwdPairAux &PA = BwdPairAux{}, v2f *S9 = nullptr)
 {
     const bool valid0 = (pos < P.limit0) && !(lp[0] > sp.lop) && !(lp[0] < kLog2AlphaMin);      // power > 0 <=> lp > lop
     const bool valid1 = (pos < P.limit1) && !(lp[1] > sp.lop) && !(lp[1] < kLog2AlphaMin);
@@ -514,10 +622,12 @@ __device__ __forceinline__ void bwd_pair(const BwdSplat sp, v2f lp, v2f dx, floa
     const v2f ae = {fminf((float)GSR_ALPHA_MAX, ga[0]), fminf((float)GSR_ALPHA_MAX, ga[1])};
     const v2f one_m = 1.f - ae;
     const v2f inv1ma = {fast_rcp(one_m[0]), fast_rcp(one_m[1])};
-    const v2f cdp = sp.cr * P.dpr + sp.cg * P.dpg + sp.cb * P.dpb;      // <c_i, dL/dpix>
+    v2f cdp = sp.cr * P.dpr + sp.cg * P.dpg + sp.cb * P.dpb;            // <c_i, dL/dpix>
+    if constexpr (kAux) cdp = __builtin_elementwise_fma(v2f{sp.z, sp.z}, PA.dpz, cdp);      // + z_i dL/ddepth
     const v2f w = ae * P.T;                                              // d colour / d rgb
     P.E -= w * cdp;                                                      // this splat's own share leaves the remainder
-    const v2f dL_dalpha = P.T * cdp - P.E * inv1ma;
+    v2f dL_dalpha = P.T * cdp - P.E * inv1ma;
+    if constexpr (kAux) dL_dalpha = __builtin_elementwise_fma(PA.GA, inv1ma, dL_dalpha);      // + dL/dalpha T_final / (1 - alpha_i)
     P.T = P.T * one_m;                                                   // exactly the forward's update
     const v2f tA = dL_dalpha * ga;
     const v2f tx = tA * dx, ty = tA * dy;
@@ -528,6 +638,7 @@ __device__ __forceinline__ void bwd_pair(const BwdSplat sp, v2f lp, v2f dx, floa
         A.S4 = ty * dy;
         A.S5 = tA;
         A.S6 = w * P.dpr; A.S7 = w * P.dpg; A.S8 = w * P.dpb;
+        if constexpr (kAux) *S9 = w * PA.dpz;
     } else {
         A.X += tx; A.Y += ty;
         A.S2 += tx * dx;
@@ -535,6 +646,7 @@ __device__ __forceinline__ void bwd_pair(const BwdSplat sp, v2f lp, v2f dx, floa
         A.S4 += ty * dy;
         A.S5 += tA;
         A.S6 += w * P.dpr; A.S7 += w * P.dpg; A.S8 += w * P.dpb;
+        if constexpr (kAux) *S9 += w * PA.dpz;
     }
 }
 
@@ -546,6 +658,13 @@ __device__ __forceinline__ void bwd_pair(const BwdSplat sp, v2f lp, v2f dx, floa
 // all the blend needs.  A group's totals are added to the entry's nine sums in LDS; when the batch is through, lane j forms entry
 // j's gradient row and stores it whole (48 B) - rows are written for every entry some group attempted (row_valid).
 // A batch ends when its slowest group does (measured imbalance over a frame: 1.01 .. 1.14, tools/quad_stats.py).
+// kAux (k_render_bwd<true>): a tenth sum per entry (dL/dz, row slot 9); the LDS stride goes to 11 words, odd, still conflict-free.
+struct AuxBwdK {
+    const float *depth;                // [H, W] the forward's depth map (final)
+    const float *dL_ddepth, *dL_dalpha;      // [H, W] each, NULL = zero
+    const float *ckpt, *ckpt_start;    // the aux checkpoints (AuxWS)
+};
+template <bool kAux>
 __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const uint2 *__restrict__ ranges,
                                                       const uint32_t *__restrict__ tile_walk,
                                                       const uint32_t *__restrict__ sorted_gid, const uint32_t *__restrict__ sorted_slot,
@@ -554,10 +673,12 @@ __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const
                                                       const float *__restrict__ dL_dpix, const float *__restrict__ ckpt,
                                                       const float *__restrict__ ckpt_start, float4 *__restrict__ grad_rows,
                                                       uint8_t *__restrict__ row_valid, UnitLists units,
-                                                      const uint32_t *__restrict__ unit_count)
+                                                      const uint32_t *__restrict__ unit_count, AuxBwdK ax)
 {
+    constexpr int kSums = kAux ? 10 : 9;         // per-entry sums
+    constexpr int kAccStride = kAux ? 11 : 9;
     __shared__ float4 sh_rec[kWave * 3];
-    __shared__ float sh_acc[kWave * 9];          // the batch's sums, [entry][value]: stride 9 words, conflict-free by lane
+    __shared__ float sh_acc[kWave * kAccStride];      // the batch's sums, [entry][value]: stride 9 (11) words, conflict-free by lane
 #ifdef GSR_BWD_TRACE
     TraceEnd trace_end{(unsigned long long)wall_clock64(), (int)blockIdx.x};
 #endif
@@ -576,11 +697,11 @@ __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const
     const float half_w = 0.5f * (float)f.W, half_h = 0.5f * (float)f.H;
     // where the butterfly leaves this lane's share of a group's totals: which value (of which register), if any
     const int quad = (lane >> 2) & 3, in_quad = lane & 3;
-    const unsigned acc_idx = (unsigned)(in_quad == 0 ? (quad < 2 ? quad : quad + 2) : in_quad == 1 ? (quad < 2 ? quad + 2 : quad + 4) : 8);
+    const unsigned acc_idx = (unsigned)(in_quad == 0 ? (quad < 2 ? quad : quad + 2) : in_quad == 1 ? (quad < 2 ? quad + 2 : quad + 4) : (kAux ? 8 + quad : 8));
     const unsigned grp_shift = 8u * (unsigned)map.grp;
-    const bool acc_on = in_quad < 2 || (in_quad == 2 && quad == 0);
+    const bool acc_on = in_quad < 2 || (in_quad == 2 && (kAux ? quad < 2 : quad == 0));
 #pragma unroll
-    for (int k = 0; k < 9; ++k) sh_acc[lane * 9 + k] = 0.f;
+    for (int k = 0; k < kSums; ++k) sh_acc[lane * kAccStride + k] = 0.f;
     for (uint32_t u = blockIdx.x / kUnitShards; u < n_units; u += gridDim.x / kUnitShards) {
         int cls = 0;
         for (int k = 0; k < kUnitClasses - 1; ++k) cls += u >= list_end[k] ? 1 : 0;
@@ -608,7 +729,8 @@ __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const
             const int enc = inside ? last_enc[pix] : 0;
             const int c_last = (enc >> kLastShift) - 1;
             limit = c < c_last ? n_total : (c == c_last ? (enc & ((1 << kLastShift) - 1)) : 0);
-            r_ = inside ? dL_dpix[pix] : 0.f; g_ = inside ? dL_dpix[N + pix] : 0.f; b_ = inside ? dL_dpix[2 * N + pix] : 0.f;
+            const bool has_c = !kAux || dL_dpix != nullptr;      // (the aux kernel takes a NULL colour gradient)
+            r_ = inside && has_c ? dL_dpix[pix] : 0.f; g_ = inside && has_c ? dL_dpix[N + pix] : 0.f; b_ = inside && has_c ? dL_dpix[2 * N + pix] : 0.f;
             float er = inside ? out_color[pix] : 0.f, eg = inside ? out_color[N + pix] : 0.f, eb = inside ? out_color[2 * N + pix] : 0.f;
             Tk = 1.f;
             if (chk) {
@@ -626,6 +748,25 @@ __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const
             P0.T = v2f{Ta, Tb}; P0.E = v2f{Ea, Eb}; P0.dpr = v2f{ra, rb}; P0.dpg = v2f{ga, gb}; P0.dpb = v2f{bla, blb};
             load_px(2, Ta, Ea, ra, ga, bla, P1.limit0); load_px(3, Tb, Eb, rb, gb, blb, P1.limit1);
             P1.T = v2f{Ta, Tb}; P1.E = v2f{Ea, Eb}; P1.dpr = v2f{ra, rb}; P1.dpg = v2f{ga, gb}; P1.dpb = v2f{bla, blb};
+        }
+        BwdPairAux PA0, PA1;
+        if constexpr (kAux) {
+            // E gains g_z (depth_final - Z in front of the segment); GA = g_a T_final, T_final = |T_state| (frozen at the stop)
+            const float *zchk = (sgm > 0) ? ax.ckpt + (size_t)((rng.x + (uint32_t)seg_begin) / kSeg) * kAuxCkptFloats
+                                          : (c > 0 ? ax.ckpt_start + ((size_t)(c - 1) * Tn + tile) * kAuxCkptFloats : nullptr);
+            auto load_aux = [&](int e, float &E, float &gz, float &gaT) {
+                const int px = px0 + map.ex(e), py = py0 + map.ey(e);
+                const bool inside = px < f.W && py < f.H;
+                const size_t pix = inside ? (size_t)py * f.W + px : 0;
+                gz = inside && ax.dL_ddepth ? ax.dL_ddepth[pix] : 0.f;
+                gaT = inside && ax.dL_dalpha ? ax.dL_dalpha[pix] * fabsf(T_state[pix]) : 0.f;
+                const float zf = inside ? ax.depth[pix] : 0.f, zc = zchk ? zchk[map.aux(e)] : 0.f;
+                E += gz * (zf - zc);
+            };
+            float E0 = P0.E[0], E1 = P0.E[1], E2 = P1.E[0], E3 = P1.E[1], z0, z1, z2, z3, a0, a1, a2, a3;
+            load_aux(0, E0, z0, a0); load_aux(1, E1, z1, a1); load_aux(2, E2, z2, a2); load_aux(3, E3, z3, a3);
+            P0.E = v2f{E0, E1}; PA0.dpz = v2f{z0, z1}; PA0.GA = v2f{a0, a1};
+            P1.E = v2f{E2, E3}; PA1.dpz = v2f{z2, z3}; PA1.GA = v2f{a2, a3};
         }
         // per quadrant (= per group): its last participating contributor
         int gmax = max(max(P0.limit0, P0.limit1), max(P1.limit0, P1.limit1));
@@ -653,41 +794,52 @@ __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const
                 unsigned jj;
                 const unsigned j = walk.next(grp_shift, jj);
                 const float4 a = sh_rec[3u * jj], b = sh_rec[3u * jj + 1u];
-                const BwdSplat sp{b.y, b.z, b.w, sh_rec[3u * jj + 2u].x};
+                const BwdSplat sp{b.y, b.z, b.w, sh_rec[3u * jj + 2u].x, kAux ? sh_rec[3u * jj + 2u].y : 0.f};
                 const v2f dx = a.x - fxv;
                 const LpTerms lt = lp_terms(a.z, a.w, b.y, dx);
                 BwdAcc A;
+                v2f S9;                                  // aux: the lane's sum of w dL/ddepth
                 {
                     const float dy = a.y - fy0;
-                    bwd_pair<true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P0, A);
+                    if constexpr (kAux) bwd_pair<true, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P0, A, PA0, &S9);
+                    else bwd_pair<true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P0, A);
                 }
                 {
                     const float dy = a.y - fy1;
-                    bwd_pair<false>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P1, A);
+                    if constexpr (kAux) bwd_pair<false, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P1, A, PA1, &S9);
+                    else bwd_pair<false>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P1, A);
                 }
-                float s[9] = {add_halves(A.X), add_halves(A.Y), add_halves(A.S2), add_halves(A.S3), add_halves(A.S4), add_halves(A.S5),
-                              add_halves(A.S6), add_halves(A.S7), add_halves(A.S8)};
-                row_sum9_transpose(s);
-                const float mine = in_quad == 0 ? s[0] : in_quad == 1 ? s[2] : s[8];
+                float mine;
+                if constexpr (kAux) {
+                    float s[10] = {add_halves(A.X), add_halves(A.Y), add_halves(A.S2), add_halves(A.S3), add_halves(A.S4), add_halves(A.S5),
+                                   add_halves(A.S6), add_halves(A.S7), add_halves(A.S8), add_halves(S9)};
+                    row_sum10_transpose(s);
+                    mine = in_quad == 0 ? s[0] : in_quad == 1 ? s[2] : (quad == 0 ? s[8] : s[9]);
+                } else {
+                    float s[9] = {add_halves(A.X), add_halves(A.Y), add_halves(A.S2), add_halves(A.S3), add_halves(A.S4), add_halves(A.S5),
+                                  add_halves(A.S6), add_halves(A.S7), add_halves(A.S8)};
+                    row_sum9_transpose(s);
+                    mine = in_quad == 0 ? s[0] : in_quad == 1 ? s[2] : s[8];
+                }
                 // groups that meet on an entry in the same pass add in group order, one LDS instruction per group: the order of every
                 // floating-point sum is fixed by the program
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    if (acc_on && j < (unsigned)kWave && map.grp == k) atomicAdd(&sh_acc[jj * 9u + acc_idx], mine);
+                    if (acc_on && j < (unsigned)kWave && map.grp == k) atomicAdd(&sh_acc[jj * (unsigned)kAccStride + acc_idx], mine);
             }
             P0.limit0 = L00; P0.limit1 = L01; P1.limit0 = L10; P1.limit1 = L11;
             __syncthreads();
             if (mymask != 0u) {
-                float v[9];
+                float v[kSums];
 #pragma unroll
-                for (int k = 0; k < 9; ++k) { v[k] = sh_acc[lane * 9 + k]; sh_acc[lane * 9 + k] = 0.f; }
+                for (int k = 0; k < kSums; ++k) { v[k] = sh_acc[lane * kAccStride + k]; sh_acc[lane * kAccStride + k] = 0.f; }
                 const float4 a = sh_rec[3 * lane], b = sh_rec[3 * lane + 1];
                 // -(X cA + Y cB) = ln2 (2 qA X + qB Y), likewise for y; gA, gB, gC carry the -1/2 of A.9; dL/dopacity = sum / opacity
                 const float gx = 2.f * a.z * v[0] + a.w * v[1], gy = 2.f * b.x * v[1] + a.w * v[0];
                 float4 *row = grad_rows + 3 * (size_t)slot;
                 row[0] = make_float4(gx * (0.69314718f * half_w), gy * (0.69314718f * half_h), v[2] * -0.5f, v[3] * -0.5f);
                 row[1] = make_float4(v[4] * -0.5f, v[5] * __builtin_amdgcn_exp2f(-b.y), v[6], v[7]);
-                row[2] = make_float4(v[8], 0.f, 0.f, 0.f);
+                row[2] = make_float4(v[8], kAux ? v[kSums - 1] : 0.f, 0.f, 0.f);
                 row_valid[slot] = 1;
             }
         }
@@ -695,7 +847,8 @@ __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const
 }
 
 int launch_render_bwd(const FrameK &f, int chunks_run, int sort_result, long long rows_upper, const GeomWS &gw, BinningWS &bw,
-                      const ImageWS &iw, const float *out_color, const float *dL_dcolor, bool debug, hipStream_t s)
+                      const ImageWS &iw, const float *out_color, const float *dL_dcolor, bool debug, hipStream_t s, const AuxWS *aux,
+                      const float *dL_ddepth, const float *dL_dalpha)
 {
     const int n_tiles = (f.ty1 - f.ty0) * f.Gx;
     if (n_tiles <= 0 || chunks_run <= 0) return GSR_OK;
@@ -704,11 +857,14 @@ int launch_render_bwd(const FrameK &f, int chunks_run, int sort_result, long lon
     long long per_shard = (rows_upper / kSeg + (long long)n_tiles * chunks_run) / kUnitShards + 1;
     if (per_shard > (long long)bw.units.shard_stride()) per_shard = (long long)bw.units.shard_stride();
     if (per_shard > (1 << 13)) per_shard = 1 << 13;
-    ProfileScope prof("render_bwd", s);
-    hipLaunchKernelGGL(k_render_bwd, dim3((unsigned)(per_shard * kUnitShards)), dim3(kWave), 0, s, f, iw.ranges, iw.tile_walk, bw.gids[1],
-                       bw.vals[sort_result], gw.records, out_color, iw.T_state, iw.last_enc, dL_dcolor, bw.ckpt, iw.ckpt_start,
-                       reinterpret_cast<float4 *>(bw.grad_rows), bw.row_valid, bw.units, iw.unit_count);
-    GSR_LAUNCH_CHECK("render_bwd", debug, s);
+    // the two instantiations take the same arguments; the colour-only one ignores the aux block
+    const char *name = aux ? "render_bwd_aux" : "render_bwd";
+    const AuxBwdK ax = aux ? AuxBwdK{aux->depth, dL_ddepth, dL_dalpha, aux->ckpt, aux->ckpt_start} : AuxBwdK{};
+    ProfileScope prof(name, s);
+    hipLaunchKernelGGL(aux ? k_render_bwd<true> : k_render_bwd<false>, dim3((unsigned)(per_shard * kUnitShards)), dim3(kWave), 0, s, f,
+                       iw.ranges, iw.tile_walk, bw.gids[1], bw.vals[sort_result], gw.records, out_color, iw.T_state, iw.last_enc, dL_dcolor,
+                       bw.ckpt, iw.ckpt_start, reinterpret_cast<float4 *>(bw.grad_rows), bw.row_valid, bw.units, iw.unit_count, ax);
+    GSR_LAUNCH_CHECK(name, debug, s);
     return GSR_OK;
 }
 
@@ -717,8 +873,9 @@ int launch_render_bwd(const FrameK &f, int chunks_run, int sort_result, long lon
 // i, i+8, ... and three xor-shuffles combine the group.  The near, screen-filling Gaussians own hundreds of
 // rows each; one thread per Gaussian left a tail of a few thousand threads walking them serially.
 // Only ranks of chunks that actually ran can own rows; every other Gaussian's gradient row is zero (memset).
+// kAux: rows of the aux backward - slot 9 (dL/dz) is summed too, in the same order as the others.
 constexpr int kRedBlock = 256;
-template <int kRedGroup>
+template <int kRedGroup, bool kAux = false>
 __global__ __launch_bounds__(kRedBlock) void k_reduce_rows(int r_begin, int n_ranks, const uint32_t *__restrict__ order,
                                                            const uint32_t *__restrict__ cnt_open,
                                                            const uint32_t *__restrict__ row_begin,
@@ -732,25 +889,28 @@ __global__ __launch_bounds__(kRedBlock) void k_reduce_rows(int r_begin, int n_ra
     // the rank's three words in one round trip (the chain was count -> first row -> rows -> Gaussian: four)
     const uint32_t cnt = live ? cnt_open[r] : 0u, begin = live ? row_begin[r] : 0u, g = live ? order[r] : 0u;
     float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
-    float a8 = 0.f;
+    float a8 = 0.f, a9 = 0.f;
     if (cnt) {
         for (uint32_t sl = begin + sub; sl < begin + cnt; sl += kRedGroup) {
             // a clear valid byte: nobody walked that far into the tile's list, or no pixel accepted the splat — the row was never
             // written.  Wide groups (big splats: most rows of a saturating frame are invalid) test the byte first; narrow ones (small
             // splats, nearly every row valid) load the row beside its byte — one memory round trip instead of two — and drop it after
             float4 r0, r1;
-            float r2;
+            float r2, r9 = 0.f;
             if constexpr (kRedGroup >= 64) {
                 if (!row_valid[sl]) continue;
                 r0 = grad_rows[3 * (size_t)sl]; r1 = grad_rows[3 * (size_t)sl + 1]; r2 = grad_rows[3 * (size_t)sl + 2].x;
+                if constexpr (kAux) r9 = grad_rows[3 * (size_t)sl + 2].y;
             } else {
                 const uint8_t ok = row_valid[sl];
                 r0 = grad_rows[3 * (size_t)sl]; r1 = grad_rows[3 * (size_t)sl + 1]; r2 = grad_rows[3 * (size_t)sl + 2].x;
+                if constexpr (kAux) r9 = grad_rows[3 * (size_t)sl + 2].y;
                 if (!ok) continue;                      // (whatever the unwritten row holds — NaN patterns included — is never added)
             }
             a0.x += r0.x; a0.y += r0.y; a0.z += r0.z; a0.w += r0.w;
             a1.x += r1.x; a1.y += r1.y; a1.z += r1.z; a1.w += r1.w;
             a8 += r2;
+            if constexpr (kAux) a9 += r9;
         }
     }
 #pragma unroll
@@ -758,9 +918,10 @@ __global__ __launch_bounds__(kRedBlock) void k_reduce_rows(int r_begin, int n_ra
         a0.x += __shfl_xor(a0.x, off); a0.y += __shfl_xor(a0.y, off); a0.z += __shfl_xor(a0.z, off); a0.w += __shfl_xor(a0.w, off);
         a1.x += __shfl_xor(a1.x, off); a1.y += __shfl_xor(a1.y, off); a1.z += __shfl_xor(a1.z, off); a1.w += __shfl_xor(a1.w, off);
         a8 += __shfl_xor(a8, off);
+        if constexpr (kAux) a9 += __shfl_xor(a9, off);
     }
     if (live && (cnt || write_empty) && sub < 3)
-        screen[3 * (size_t)g + sub] = sub == 0 ? a0 : (sub == 1 ? a1 : make_float4(a8, 0.f, 0.f, 0.f));
+        screen[3 * (size_t)g + sub] = sub == 0 ? a0 : (sub == 1 ? a1 : make_float4(a8, a9, 0.f, 0.f));
 }
 
 // One launch per depth chunk that ran, each with its own lanes-per-Gaussian: a whole wave where the chunk's Gaussians own many
@@ -768,12 +929,12 @@ __global__ __launch_bounds__(kRedBlock) void k_reduce_rows(int r_begin, int n_ra
 // through the live filter, whose instance bound says nothing about what it emitted (a training frame's last chunk is most of the
 // scene with a bound of tens of millions: 64 lanes for each of its 1e6 ranks was 100 us of idle threads).
 int launch_reduce_rows(const FrameK &f, const gsr_frame_plan &plan, const GeomWS &gw, const BinningWS &bw, float *screen_grads,
-                       int prezeroed, bool debug, hipStream_t s)
+                       int prezeroed, bool debug, hipStream_t s, bool aux)
 {
     // prezeroed: 0 = clear the whole tensor first; 1 = the caller already has; 2 = only the rows of the binned prefix will ever
     // be read (the sparse geometry backward of the same frame): every prefix row is written, zeros included, nothing else
     if (f.P == 0) return GSR_OK;
-    ProfileScope prof("reduce_rows", s);
+    ProfileScope prof(aux ? "reduce_rows_aux" : "reduce_rows", s);
     if (prezeroed == 0) GSR_HIP_CHECK(hipMemsetAsync(screen_grads, 0, (size_t)f.P * kRowFloats * sizeof(float), s));
     const int write_empty = prezeroed == 2 ? 1 : 0;
     const int chunks = (plan.num_rendered > 0 && plan.chunks_run > 0) ? plan.chunks_run : 0;
@@ -786,7 +947,7 @@ int launch_reduce_rows(const FrameK &f, const gsr_frame_plan &plan, const GeomWS
         // (two lanes per Gaussian for small splats, measured: 89 us against 81 at cfg3n, 352 against 374 at cfg5n — not kept)
         const long long threads = (long long)(r1 - r0) * (wide ? 64 : 8);
         const dim3 grid((unsigned)((threads + kRedBlock - 1) / kRedBlock));
-        hipLaunchKernelGGL(wide ? k_reduce_rows<64> : k_reduce_rows<8>, grid, dim3(kRedBlock), 0, s, r0, r1, gw.order, gw.cnt_open, gw.row_begin,
+        hipLaunchKernelGGL(aux ? (wide ? k_reduce_rows<64, true> : k_reduce_rows<8, true>) : (wide ? k_reduce_rows<64> : k_reduce_rows<8>), grid, dim3(kRedBlock), 0, s, r0, r1, gw.order, gw.cnt_open, gw.row_begin,
                            bw.row_valid, reinterpret_cast<const float4 *>(bw.grad_rows), reinterpret_cast<float4 *>(screen_grads), write_empty);
     }
     GSR_LAUNCH_CHECK("reduce_rows", debug, s);

@@ -9,6 +9,11 @@ Public surface = what the reference imports and calls (gaussian_renderer/__init_
         -> (color[3,H,W] float32, radii[P] int32)
     GaussianRasterizer.markVisible(positions) -> bool[P]
 
+Extension: GaussianRasterizer(raster_settings, depth_alpha=True) returns (color[3,H,W], radii[P], depth[1,H,W], alpha[1,H,W]) from
+the same blend: depth = sum_i w_i z_i (w_i = alpha_i T_i over the splats the colour composites, z_i the view-space depth; no
+background term, not normalised: the mean depth is depth / alpha) and alpha = 1 - T_final.  Both are differentiable; a loss on
+them reaches means3D (through z too) and means2D - so the densification statistics, which read means2D.grad, see it as well.
+
 Autograd contract (train.py:106, scene/gaussian_model.py:415-417): gradients for
 (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, None) in that order;
 `means2D.grad[:, :2]` is dL/d(NDC position) with the W/2, H/2 pixel scale folded in, `[:, 2] = 0`.
@@ -76,7 +81,8 @@ _binning_guess = {}        # (P, W, H, slab, device) -> instances the binning wo
 
 class _Frame:
     """Native handles of one forward pass, kept alive by autograd's ctx for the backward."""
-    __slots__ = ("desc", "cam", "keep", "plan", "geom_ws", "binning_ws", "image_ws", "radii", "color", "gauss", "M", "device", "raw", "pre")
+    __slots__ = ("desc", "cam", "keep", "plan", "geom_ws", "binning_ws", "image_ws", "radii", "color", "gauss", "M", "device", "raw", "pre",
+                 "depth", "alpha", "aux_ws", "aux")
 
     @property
     def R(self):
@@ -112,14 +118,24 @@ def caller_grad_enabled() -> bool:
     return torch.is_grad_enabled() if g is None else g
 
 
+def _aux_outputs(fr: "_Frame", capacity: int):
+    """gsr_aux_outputs of an aux frame, with a depth-checkpoint workspace for a binning workspace of `capacity` instances."""
+    fr.aux_ws = _workspace(N.aux_workspace_size(fr.desc, capacity), fr.device)
+    fr.aux = N.AuxOutputs(N._ptr(fr.depth), N._ptr(fr.alpha), N._ptr(fr.aux_ws))
+    return fr.aux
+
+
 def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                       rs: GaussianRasterizationSettings, tile_rows=None, out_color=None, sh_rest=None, raw=False,
-                      prepare_needs=None):
+                      prepare_needs=None, aux=False):
     """Stage 1 + stage 2 of the native forward.  Returns (color, radii, frame).
+    aux=True: the same blend also renders frame.depth and frame.alpha ([1,H,W] each; whole images only).
     raw=True: the tensors are the parameter store's RAW values (sh = _features_dc, sh_rest = _features_rest,
     opacities = logits, scales = log-scales, rotations = unnormalised) and the activations run in the kernels.
     prepare_needs: which gradients a backward will want (as rasterize_backward_geom's `needs`), when one will follow: the
     backward's output tensors are then allocated up front, while the host waits for the plan anyway."""
+    if aux and tile_rows is not None:
+        raise ValueError("depth / alpha maps are rendered for whole images only: no tile_rows (sharded slabs) with aux=True")
     device = means3D.device
     if device.type != "cuda":
         raise RuntimeError("diff_gaussian_rasterization (MI355X build) needs tensors on a HIP device; "
@@ -152,6 +168,10 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
     fr.keep = (cam_keep, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, sh_rest)
     fr.raw = raw
     fr.pre = None
+    fr.depth = fr.alpha = fr.aux_ws = fr.aux = None
+    if aux:                # every pixel is written by the first chunk's blend
+        fr.depth = torch.empty(1, H, W, dtype=torch.float32, device=device)
+        fr.alpha = torch.empty(1, H, W, dtype=torch.float32, device=device)
     geom_bytes, image_bytes = N.workspace_sizes(fr.desc)
     fr.geom_ws = _workspace(geom_bytes, device)
     fr.image_ws = _workspace(image_bytes, device)
@@ -178,7 +198,8 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
         done = False
         if binning is not None:
             plan, done = N.forward_both(fr.desc, fr.cam, fr.gauss, fr.geom_ws, fr.image_ws, fr.radii, binning, guess, color, device,
-                                        early_fill=early[2] if early is not None else None)
+                                        early_fill=early[2] if early is not None else None,
+                                        aux=_aux_outputs(fr, guess) if aux else None)
         else:
             plan = N.forward_preprocess(fr.desc, fr.cam, fr.gauss, fr.geom_ws, fr.radii, device, image_ws=fr.image_ws)
         fr.plan = plan
@@ -207,7 +228,8 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
             plan.binning_capacity = capacity
             fr.binning_ws = binning
             try:
-                N.forward_render(fr.desc, fr.cam, fr.gauss, fr.geom_ws, binning, fr.image_ws, plan, color, device)
+                N.forward_render(fr.desc, fr.cam, fr.gauss, fr.geom_ws, binning, fr.image_ws, plan, color, device,
+                                 aux=_aux_outputs(fr, capacity) if aux else None)
                 break
             except N.GsrError as e:
                 if e.status != N.ERR_WORKSPACE or capacity >= R:
@@ -220,25 +242,34 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
     return color, fr.radii, fr
 
 
-def rasterize_backward_screen(fr: "_Frame", grad_color: torch.Tensor, only_for_own_geom: bool = False) -> torch.Tensor:
+def rasterize_backward_screen(fr: "_Frame", grad_color: torch.Tensor, only_for_own_geom: bool = False, grad_depth=None,
+                              grad_alpha=None) -> torch.Tensor:
     """K7 + deterministic per-Gaussian reduction -> screen-space gradients [P, 12].
+    grad_depth / grad_alpha ([1,H,W] or [H,W], an aux frame only; None = zero): when either is given the aux backward runs and slot 9
+    holds dL/dz; otherwise the colour-only kernels (the plain frame's bits).
     only_for_own_geom: the tensor goes straight into this frame's geometry backward and nowhere else (the autograd path): rows it
     never reads may stay undefined.  The dense geometry backward reads the rows of VISIBLE Gaussians; when every planned chunk ran,
     all of them sit in the binned prefix, whose rows the reduction writes (zeros included): no 48 P-byte memset."""
     P = fr.desc.P
     grad_color = _f32c(grad_color, fr.device)
+    grad_depth, grad_alpha = _f32c(grad_depth, fr.device), _f32c(grad_alpha, fr.device)
+    with_aux = fr.aux is not None and (grad_depth is not None or grad_alpha is not None)
     screen = fr.pre.pop("screen", None) if fr.pre is not None else None        # allocated (and, on sparse frames, zero-filled) by the forward
     if screen is None:
         screen = torch.empty(max(P, 1), N.SCREEN_GRAD_STRIDE, dtype=torch.float32, device=fr.device)
         covered = fr.plan.num_rendered > 0 and fr.plan.chunks_run == fr.plan.num_chunks
         fr.plan.screen_prezeroed = 2 if (only_for_own_geom and covered) else 0            # (1: set only by prepare_backward(), for the very tensor it filled)
-    if grad_color is None:
+    if grad_color is None and not with_aux:
         return screen.zero_()[:P]
     with torch.cuda.device(fr.device):
         # one 48-B gradient row per EMITTED instance: backward-only scratch, returned to the allocator on exit
         rows = _workspace(N.backward_rows_size(fr.desc, fr.plan), fr.device)
-        N.backward_render(fr.desc, fr.cam, fr.geom_ws, fr.binning_ws, fr.image_ws, rows, fr.plan, fr.color, grad_color, screen,
-                          fr.device)
+        if with_aux:
+            N.backward_render_aux(fr.desc, fr.cam, fr.geom_ws, fr.binning_ws, fr.image_ws, rows, fr.plan, fr.color, fr.aux, grad_color,
+                                  grad_depth, grad_alpha, screen, fr.device)
+        else:
+            N.backward_render(fr.desc, fr.cam, fr.geom_ws, fr.binning_ws, fr.image_ws, rows, fr.plan, fr.color, grad_color, screen,
+                              fr.device)
         fr.plan.screen_prezeroed = 0
     return screen[:P]
 
@@ -290,12 +321,13 @@ def prepare_backward(fr: "_Frame", needs, screen_prefix_only: bool = False) -> N
 
 
 def rasterize_backward_geom(fr: "_Frame", screen: torch.Tensor, needs, g0: int = 0, g1: Optional[int] = None,
-                            binned_ranks: Optional[int] = None, rows: Optional[torch.Tensor] = None):
+                            binned_ranks: Optional[int] = None, rows: Optional[torch.Tensor] = None, depth_chain: bool = False):
     """K8 + K9 on Gaussians [g0, g1).  `needs` = (means3D, means2D, sh, colors, opacities, scales, rotations,
     cov3D[, sh_rest]) booleans.  Returns the 8 gradient tensors (None where not needed / not applicable); for a
     raw-mode frame 9: sh is then d/d_features_dc [P,1,3] and the ninth d/d_features_rest [P,M-1,3].
     rows (int32 device tensor, whole range only): the Gaussians that can have a non-zero screen gradient, when that is not
-    the frame's own binned prefix (a sharded render: the union over the ranks)."""
+    the frame's own binned prefix (a sharded render: the union over the ranks).
+    depth_chain: `screen` came from the aux backward (slot 9 = dL/dz): its chain to means3D is added."""
     P, dev = fr.desc.P, fr.device
     g1 = P if g1 is None else g1
     partial = (g0, g1) != (0, P)
@@ -316,7 +348,7 @@ def rasterize_backward_geom(fr: "_Frame", screen: torch.Tensor, needs, g0: int =
                 binned_ranks = int(plan.chunk_rank_begin[plan.chunks_run]) if plan.num_rendered > 0 and plan.chunks_run > 0 else 0
             if binned_ranks != -2:
                 N.backward_geom(fr.desc, fr.cam, fr.gauss, fr.radii, fr.geom_ws, screen, g0, g1, grads, dev, binned_ranks,
-                                own_plan=None if partial else own)
+                                own_plan=None if partial else own, depth_chain=depth_chain)
     if fr.raw:
         return g_means3D, g_means2D, g_sh, g_col, g_op, g_sc, g_rot, g_cov, g_rest
     return g_means3D, g_means2D, g_sh, g_col, g_op, g_sc, g_rot, g_cov
@@ -338,11 +370,14 @@ def _stash_frame(ctx, frame):
     like the upstream extension's saved buffers they are released right after backward() — or kept, and a second
     backward() allowed, under retain_graph=True; a second backward() without it raises autograd's usual error."""
     keep = [t for t in frame.keep[1:] if t is not None]
-    ctx.save_for_backward(*(getattr(frame, n) for n in _FRAME_TENSORS), *frame.keep[0], *keep)
+    aux = (frame.depth, frame.aux_ws) if frame.aux is not None else ()          # an aux frame: its depth map and checkpoints, last
+    ctx.save_for_backward(*(getattr(frame, n) for n in _FRAME_TENSORS), *frame.keep[0], *keep, *aux)
     ctx.frame_keep_mask = tuple(t is not None for t in frame.keep[1:])
+    ctx.frame_aux = bool(aux)
     for n in _FRAME_TENSORS:
         setattr(frame, n, None)
     frame.keep = None
+    frame.depth = frame.alpha = frame.aux_ws = None
     ctx.frame = frame
 
 
@@ -353,6 +388,9 @@ def _unstash_frame(ctx):
         setattr(fr, n, t)
     it = iter(saved[9:])
     fr.keep = (tuple(saved[5:9]),) + tuple(next(it) if m else None for m in ctx.frame_keep_mask)
+    if ctx.frame_aux:
+        fr.depth, fr.aux_ws = saved[-2], saved[-1]
+        fr.aux = N.AuxOutputs(N._ptr(fr.depth), None, N._ptr(fr.aux_ws))      # (the backward does not read alpha)
     return fr
 
 
@@ -360,51 +398,55 @@ def _restash_frame(fr):
     for n in _FRAME_TENSORS:
         setattr(fr, n, None)
     fr.keep = None
+    fr.depth = fr.aux_ws = None
     fr.plan.screen_prezeroed = 0
 
 
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings):
+                raster_settings, aux=False):
         rs = raster_settings
         args = (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
         if rs.debug:
             cpu_args = tuple(a.detach().cpu().clone() for a in args)      # README.md:147-150 semantics
             try:
-                color, radii, frame = rasterize_forward(*args, rs)
+                color, radii, frame = rasterize_forward(*args, rs, aux=aux)
                 torch.cuda.synchronize(means3D.device)
             except Exception:
                 _dump("snapshot_fw.dump", (cpu_args, tuple(rs)))
                 print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
                 raise
         else:
-            color, radii, frame = rasterize_forward(*args, rs, prepare_needs=tuple(ctx.needs_input_grad[:8]))
+            color, radii, frame = rasterize_forward(*args, rs, prepare_needs=tuple(ctx.needs_input_grad[:8]), aux=aux)
             prepare_backward(frame, tuple(ctx.needs_input_grad[:8]), screen_prefix_only=True)
+        maps = (frame.depth, frame.alpha)
         _stash_frame(ctx, frame)
         ctx.raster_settings = rs
         ctx.shapes = (means2D.shape, opacities.shape)
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)         # radii's "gradient" would arrive as a zero-filled int32 [P] tensor: one launch per step
-        return color, radii
+        return (color, radii) + (maps if aux else ())
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii):
+    def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None):
         fr, rs = _unstash_frame(ctx), ctx.raster_settings
         needs = tuple(ctx.needs_input_grad[:8])
         # input order: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp
         order = (needs[0], needs[1], needs[2], needs[3], needs[4], needs[5], needs[6], needs[7])
+        # no depth / alpha gradient: the colour-only kernels, bit for bit the plain frame's gradients
+        with_aux = grad_depth is not None or grad_alpha is not None
 
         def run():
-            screen = rasterize_backward_screen(fr, grad_out_color, only_for_own_geom=True)
-            return rasterize_backward_geom(fr, screen, order)
+            screen = rasterize_backward_screen(fr, grad_out_color, only_for_own_geom=True, grad_depth=grad_depth, grad_alpha=grad_alpha)
+            return rasterize_backward_geom(fr, screen, order, depth_chain=with_aux)
         if rs.debug:
             try:
                 out = run()
                 torch.cuda.synchronize(fr.device)
             except Exception:
                 _dump("snapshot_bw.dump", (tuple(None if k is None else k.detach().cpu() for k in fr.keep[1:]),
-                                           grad_out_color.detach().cpu(), tuple(rs)))
+                                           None if grad_out_color is None else grad_out_color.detach().cpu(), tuple(rs)))
                 print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
                 raise
         else:
@@ -415,7 +457,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         if g_means2D is not None:
             g_means2D = g_means2D.view(ctx.shapes[0])
         _restash_frame(fr)
-        return g_means3D, g_means2D, g_sh, g_col, g_op, g_sc, g_rot, g_cov, None
+        return g_means3D, g_means2D, g_sh, g_col, g_op, g_sc, g_rot, g_cov, None, None
 
 
 class _RasterizeGaussiansRaw(torch.autograd.Function):
@@ -424,42 +466,44 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
     the preprocess kernel, their chain rule inside the geometry backward: gradients arrive on the raw parameters."""
 
     @staticmethod
-    def forward(ctx, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations, raster_settings):
+    def forward(ctx, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations, raster_settings, aux=False):
         rs = raster_settings
         n = ctx.needs_input_grad       # xyz, means2D, f_dc, f_rest, opacity, scales, rotations
         needs = (n[0], n[1], n[2], False, n[4], n[5], n[6], False, n[3])
         # features_rest None: features_dc is the whole interleaved table [P,M,3] (scene.GaussianModel's packed leaf)
         color, radii, frame = rasterize_forward(xyz, features_dc, None, opacity_logits, log_scales, raw_rotations, None, rs,
                                                 sh_rest=features_rest, raw=2 if features_rest is None else 1,
-                                                prepare_needs=None if rs.debug else needs)
+                                                prepare_needs=None if rs.debug else needs, aux=aux)
         if rs.debug:
             torch.cuda.synchronize(xyz.device)
         prepare_backward(frame, needs, screen_prefix_only=True)
+        maps = (frame.depth, frame.alpha)
         _stash_frame(ctx, frame)
         ctx.shapes = (means2D.shape, opacity_logits.shape)
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)         # radii's "gradient" would arrive as a zero-filled int32 [P] tensor: one launch per step
-        return color, radii
+        return (color, radii) + (maps if aux else ())
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii):
+    def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None):
         fr = _unstash_frame(ctx)
         n = ctx.needs_input_grad       # xyz, means2D, f_dc, f_rest, opacity, scales, rotations
         needs = (n[0], n[1], n[2], False, n[4], n[5], n[6], False, n[3])
-        screen = rasterize_backward_screen(fr, grad_out_color, only_for_own_geom=True)
-        g_xyz, g_means2D, g_dc, _, g_op, g_sc, g_rot, _, g_rest = rasterize_backward_geom(fr, screen, needs)
+        with_aux = grad_depth is not None or grad_alpha is not None
+        screen = rasterize_backward_screen(fr, grad_out_color, only_for_own_geom=True, grad_depth=grad_depth, grad_alpha=grad_alpha)
+        g_xyz, g_means2D, g_dc, _, g_op, g_sc, g_rot, _, g_rest = rasterize_backward_geom(fr, screen, needs, depth_chain=with_aux)
         if g_op is not None:
             g_op = g_op.view(ctx.shapes[1])
         if g_means2D is not None:
             g_means2D = g_means2D.view(ctx.shapes[0])
         _restash_frame(fr)
-        return g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None
+        return g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None, None
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings):
+                        raster_settings, depth_alpha=False):
     return _apply(_RasterizeGaussians, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                  cov3Ds_precomp, raster_settings)
+                  cov3Ds_precomp, raster_settings, bool(depth_alpha))
 
 
 # ---- opt-in: fuse the reference's getters without touching the caller -------------------------------------------
@@ -537,9 +581,11 @@ def _match_getters(means3D, opacities, shs, scales, rotations):
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings: GaussianRasterizationSettings):
+    def __init__(self, raster_settings: GaussianRasterizationSettings, depth_alpha: bool = False):
+        """depth_alpha=True (extension): forward / forward_raw also return the depth and alpha maps [1,H,W] (module docstring)."""
         super().__init__()
         self.raster_settings = raster_settings
+        self.depth_alpha = bool(depth_alpha)
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         """Frustum test per point (the reference's `_C.mark_visible`; unused in-tree, kept for API parity)."""
@@ -573,9 +619,9 @@ class GaussianRasterizer(nn.Module):
             leaves = _match_getters(means3D, opacities, shs, scales, rotations)
             if leaves is not None:
                 xyz, dc, rest, op, sc, rot = leaves
-                return _apply(_RasterizeGaussiansRaw, xyz, means2D, dc, rest, op, sc, rot, rs)
+                return _apply(_RasterizeGaussiansRaw, xyz, means2D, dc, rest, op, sc, rot, rs, self.depth_alpha)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, rs)
+                                   cov3D_precomp, rs, self.depth_alpha)
 
     def forward_raw(self, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations):
         """Extension (not in the reference API): render straight from the reference GaussianModel's raw parameters
@@ -587,4 +633,5 @@ class GaussianRasterizer(nn.Module):
         packed = features_rest is None and features_dc.dim() == 3 and features_dc.shape[1] > 1      # one [P,M,3] table
         if not packed and (features_rest is None or features_rest.numel() == 0):
             features_rest = torch.empty(0, dtype=torch.float32, device=xyz.device)
-        return _apply(_RasterizeGaussiansRaw, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations, rs)
+        return _apply(_RasterizeGaussiansRaw, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations, rs,
+                      self.depth_alpha)

@@ -43,6 +43,11 @@ class Grads(C.Structure):
                 ("shs_rest", _f32p), ("prezeroed", C.c_int32)]
 
 
+class AuxOutputs(C.Structure):
+    """gsr_aux_outputs: the depth and alpha maps [H,W] and their checkpoint workspace (gsr_aux_workspace_size)."""
+    _fields_ = [("depth", _f32p), ("alpha", _f32p), ("ckpt_ws", C.c_void_p)]
+
+
 MAX_CHUNKS = 8
 LAST_SHIFT = 26
 
@@ -67,7 +72,8 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_workspace_sizes", "gsr_binning_
            "gsr_forward_render", "gsr_bwd_segment_entries", "gsr_backward_rows_size", "gsr_backward_prepare", "gsr_backward_render", "gsr_backward_geom", "gsr_backward_geom_rows", "gsr_frame_arrays", "gsr_exchange_rows_gather", "gsr_exchange_rows_scatter", "gsr_mark_visible", "gsr_debug_get_views", "gsr_profile_enable",
            "gsr_profile_read", "gsr_loss_workspace_size", "gsr_loss_l1_ssim_forward", "gsr_loss_l1_ssim_backward", "gsr_loss_l1_ssim_forward_rows", "gsr_loss_l1_ssim_backward_rows", "gsr_loss_l1_backward",
            "gsr_debug_sort_temp_bytes", "gsr_debug_sort_pairs", "gsr_debug_sort_pairs_ex", "gsr_dist2_workspace_size", "gsr_dist2_knn3", "gsr_adam_step", "gsr_adam_step_split", "gsr_adam_step_multi", "gsr_densify_stats",
-           "gsr_activations_forward", "gsr_activations_backward")
+           "gsr_activations_forward", "gsr_activations_backward",
+           "gsr_aux_workspace_size", "gsr_forward_aux", "gsr_forward_render_aux", "gsr_backward_render_aux", "gsr_backward_geom_aux")
 
 _lib = None
 
@@ -158,22 +164,36 @@ def forward_preprocess(desc, cam: Camera, g: Gaussians, geom_ws, radii, device, 
 
 
 def forward_both(desc, cam: Camera, g: Gaussians, geom_ws, image_ws, radii, binning_ws, binning_capacity, out_color, device,
-                 early_fill: Optional[Grads] = None):
-    """gsr_forward: both stages in one call.  Returns (plan, done): done = False when the binning workspace was too small for the
-    first chunk (nothing of stage 2 ran: allocate and call forward_render)."""
+                 early_fill: Optional[Grads] = None, aux: Optional[AuxOutputs] = None):
+    """gsr_forward (gsr_forward_aux with `aux`): both stages in one call.  Returns (plan, done): done = False when the binning workspace
+    was too small for the first chunk (nothing of stage 2 ran: allocate and call forward_render)."""
     plan = FramePlan()
-    rc = load().gsr_forward(C.byref(desc), C.byref(cam), C.byref(g), _ptr(geom_ws), _ptr(image_ws), _ptr(radii), C.byref(plan),
-                            _ptr(binning_ws), C.c_int64(int(binning_capacity)), _ptr(out_color),
-                            None if early_fill is None else C.byref(early_fill), _stream(device))
+    args = (C.byref(desc), C.byref(cam), C.byref(g), _ptr(geom_ws), _ptr(image_ws), _ptr(radii), C.byref(plan),
+            _ptr(binning_ws), C.c_int64(int(binning_capacity)), _ptr(out_color), None if early_fill is None else C.byref(early_fill))
+    if aux is None:
+        rc = load().gsr_forward(*args, _stream(device))
+    else:
+        rc = load().gsr_forward_aux(*args, C.byref(aux), _stream(device))
     if rc == ERR_WORKSPACE:           # the guessed workspace did not do (for the first chunk, or for a later one)
         return plan, False
     _check(rc, "gsr_forward")
     return plan, True
 
 
-def forward_render(desc, cam: Camera, g: Gaussians, geom_ws, binning_ws, image_ws, plan: FramePlan, out_color, device):
-    _check(load().gsr_forward_render(C.byref(desc), C.byref(cam), C.byref(g), _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws),
-                                     C.byref(plan), _ptr(out_color), _stream(device)), "gsr_forward_render")
+def forward_render(desc, cam: Camera, g: Gaussians, geom_ws, binning_ws, image_ws, plan: FramePlan, out_color, device,
+                   aux: Optional[AuxOutputs] = None):
+    args = (C.byref(desc), C.byref(cam), C.byref(g), _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws), C.byref(plan), _ptr(out_color))
+    if aux is None:
+        _check(load().gsr_forward_render(*args, _stream(device)), "gsr_forward_render")
+    else:
+        _check(load().gsr_forward_render_aux(*args, C.byref(aux), _stream(device)), "gsr_forward_render_aux")
+
+
+def aux_workspace_size(desc: FrameDesc, binning_capacity: int) -> int:
+    """gsr_aux_workspace_size: bytes of the depth checkpoints of an aux frame whose binning workspace holds that many instances."""
+    b = C.c_size_t(0)
+    _check(load().gsr_aux_workspace_size(C.byref(desc), C.c_int64(int(binning_capacity)), C.byref(b)), "gsr_aux_workspace_size")
+    return b.value
 
 
 def backward_rows_size(desc: FrameDesc, plan: FramePlan) -> int:
@@ -194,6 +214,14 @@ def backward_render(desc, cam: Camera, geom_ws, binning_ws, image_ws, rows_ws, p
            "gsr_backward_render")
 
 
+def backward_render_aux(desc, cam: Camera, geom_ws, binning_ws, image_ws, rows_ws, plan: FramePlan, out_color, aux: AuxOutputs,
+                        dL_dcolor, dL_ddepth, dL_dalpha, screen_grads, device):
+    """gsr_backward_render_aux: any of the three upstream gradients may be None (zero); screen_grads slot 9 receives dL/dz."""
+    _check(load().gsr_backward_render_aux(C.byref(desc), C.byref(cam), _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws), _ptr(rows_ws),
+                                          C.byref(plan), _ptr(out_color), C.byref(aux), _ptr(dL_dcolor), _ptr(dL_ddepth), _ptr(dL_dalpha),
+                                          _ptr(screen_grads), _stream(device)), "gsr_backward_render_aux")
+
+
 _SEG = [0]
 
 
@@ -205,11 +233,14 @@ def bwd_segment_entries() -> int:
 
 
 def backward_geom(desc, cam: Camera, g: Gaussians, radii, geom_ws, screen_grads, g0, g1, grads: Grads, device,
-                  binned_ranks: int = -1, own_plan: Optional[FramePlan] = None):
-    """own_plan: the frame's plan when screen_grads are this very frame's (gsr_backward_render of the same plan), else None."""
-    _check(load().gsr_backward_geom(C.byref(desc), C.byref(cam), C.byref(g), _ptr(radii), _ptr(geom_ws),
-                                    _ptr(screen_grads), C.c_int32(g0), C.c_int32(g1), C.c_int32(binned_ranks),
-                                    None if own_plan is None else C.byref(own_plan), C.byref(grads), _stream(device)), "gsr_backward_geom")
+                  binned_ranks: int = -1, own_plan: Optional[FramePlan] = None, depth_chain: bool = False):
+    """own_plan: the frame's plan when screen_grads are this very frame's (gsr_backward_render of the same plan), else None.
+    depth_chain: screen_grads slot 9 holds dL/dz (gsr_backward_render_aux): gsr_backward_geom_aux adds its chain to means3D."""
+    fn = load().gsr_backward_geom_aux if depth_chain else load().gsr_backward_geom
+    _check(fn(C.byref(desc), C.byref(cam), C.byref(g), _ptr(radii), _ptr(geom_ws),
+              _ptr(screen_grads), C.c_int32(g0), C.c_int32(g1), C.c_int32(binned_ranks),
+              None if own_plan is None else C.byref(own_plan), C.byref(grads), _stream(device)),
+           "gsr_backward_geom_aux" if depth_chain else "gsr_backward_geom")
 
 
 def effective_binned_ranks(plan: FramePlan) -> int:

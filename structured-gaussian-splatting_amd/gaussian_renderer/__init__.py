@@ -55,8 +55,9 @@ def _zero_points(like: torch.Tensor) -> torch.Tensor:
     return z
 
 
-def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None):
-    """Render the scene.  Background tensor (bg_color) must be on the GPU."""
+def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, depth_alpha=False):
+    """Render the scene.  Background tensor (bg_color) must be on the GPU.
+    depth_alpha=True (extension): the dict also holds "depth" and "alpha" [1,H,W], differentiable (diff_gaussian_rasterization)."""
     xyz = pc.get_xyz
     # (the reference builds this as zeros_like(...) + 0 and retain_grad()s the non-leaf result; a leaf with requires_grad keeps
     # its .grad by itself.  Its VALUES are never read, by the rasterizer or by the training loop, only its .grad: every frame
@@ -69,7 +70,13 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         bg=bg_color, scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_view_transform,
         projmatrix=viewpoint_camera.full_proj_transform, sh_degree=pc.active_sh_degree,
         campos=viewpoint_camera.camera_center, prefiltered=False, debug=pipe.debug)
-    rasterizer = GaussianRasterizer(raster_settings=raster_settings)
+    rasterizer = GaussianRasterizer(raster_settings=raster_settings, depth_alpha=depth_alpha)
+
+    def result(out):
+        d = {"render": out[0], "viewspace_points": screenspace_points, "visibility_filter": out[1] > 0, "radii": out[1]}
+        if depth_alpha:
+            d["depth"], d["alpha"] = out[2], out[3]
+        return d
 
     # the fused path hands the RAW parameters to the kernels and so bypasses the getters — and with them the reference's
     # freeze flags (scene/gaussian_model.py:104-125 detach() the getter's result): a model with any of them set takes the
@@ -82,13 +89,10 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     if (fused and override_color is None and not pipe.compute_cov3D_python and not pipe.convert_SHs_python and not frozen
             and (packed or hasattr(pc, "_features_rest"))):
         if packed:               # exp / normalize / sigmoid inside the kernels, the SH table as it is: no getter runs at all
-            rendered_image, radii = rasterizer.forward_raw(pc._xyz, screenspace_points, pc._features, None,
-                                                           pc._opacity, pc._scaling, pc._rotation)
-        else:
-            rendered_image, radii = rasterizer.forward_raw(pc._xyz, screenspace_points, pc._features_dc, pc._features_rest,
-                                                           pc._opacity, pc._scaling, pc._rotation)
-        return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-                "radii": radii}
+            return result(rasterizer.forward_raw(pc._xyz, screenspace_points, pc._features, None,
+                                                 pc._opacity, pc._scaling, pc._rotation))
+        return result(rasterizer.forward_raw(pc._xyz, screenspace_points, pc._features_dc, pc._features_rest,
+                                             pc._opacity, pc._scaling, pc._rotation))
 
     scales = rotations = cov3D_precomp = None
     if pipe.compute_cov3D_python:
@@ -109,8 +113,5 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     else:
         colors_precomp = override_color
 
-    rendered_image, radii = rasterizer(means3D=xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp,
-                                       opacities=pc.get_opacity, scales=scales, rotations=rotations,
-                                       cov3D_precomp=cov3D_precomp)
-    return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-            "radii": radii}
+    return result(rasterizer(means3D=xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp,
+                             opacities=pc.get_opacity, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp))
