@@ -42,13 +42,17 @@
 #define GSO_CAT_(a, b) a##b
 #define GSO_CAT(a, b) GSO_CAT_(a, b)
 
-/* ---- binary32 instantiation: gso_*_f32 */
+/* ---- binary32 instantiation: gso_*_f32
+ * R_VIEW: component k of p_view.  The one fused operation of the binary32 build: the reference's compiler contracts the
+ * left-to-right sum of transformPoint4x3 into fma(p2, ., fma(p1, ., p0 * .)) + . (the depth band's "dB"), and the product's
+ * csrc/gsr_math.h view_coord() evaluates exactly that.  At the identity camera it is the plain sum's result. */
 #define REAL float
 #define FN(name) GSO_CAT(GSO_CAT(gso_, name), _f32)
 #define R_SQRT sqrtf
 #define R_EXP expf
 #define R_CEIL ceilf
 #define R_FABS fabsf
+#define R_VIEW(p, V, k) (fmaf((p)[2], (V)[8 + (k)], fmaf((p)[1], (V)[4 + (k)], (p)[0] * (V)[k])) + (V)[12 + (k)])
 #include "gsr_oracle_impl.h"
 #undef REAL
 #undef FN
@@ -56,6 +60,7 @@
 #undef R_EXP
 #undef R_CEIL
 #undef R_FABS
+#undef R_VIEW
 
 /* ---- binary64 instantiation: gso_*_f64 */
 #define REAL double
@@ -64,6 +69,7 @@
 #define R_EXP exp
 #define R_CEIL ceil
 #define R_FABS fabs
+#define R_VIEW(p, V, k) ((p)[0] * (V)[k] + (p)[1] * (V)[4 + (k)] + (p)[2] * (V)[8 + (k)] + (V)[12 + (k)])
 #include "gsr_oracle_impl.h"
 #undef REAL
 #undef FN

@@ -152,9 +152,9 @@ static void FN(preprocess)(FN(ctx) *c)
         c->tiles_touched[i] = 0;
         const REAL *p = c->means3D + 3 * i;
         /* A.0 row-vector convention; twin utils/graphics_utils.py:22-29 */
-        REAL tvx = p[0] * V[0] + p[1] * V[4] + p[2] * V[8] + V[12];
-        REAL tvy = p[0] * V[1] + p[1] * V[5] + p[2] * V[9] + V[13];
-        REAL tvz = p[0] * V[2] + p[1] * V[6] + p[2] * V[10] + V[14];
+        REAL tvx = R_VIEW(p, V, 0);
+        REAL tvy = R_VIEW(p, V, 1);
+        REAL tvz = R_VIEW(p, V, 2);
         if (tvz <= (REAL)GSR_NEAR_CUT) continue;                                    /* A.1 */
         REAL hx = p[0] * PV[0] + p[1] * PV[4] + p[2] * PV[8] + PV[12];
         REAL hy = p[0] * PV[1] + p[1] * PV[5] + p[2] * PV[9] + PV[13];
@@ -630,9 +630,9 @@ static void FN(geom_bwd)(const FN(ctx) *c, const REAL *screen, int g0, int g1,
         REAL dmean[3] = {0, 0, 0};
 
         /* ---- conic -> cov2D -> (cov3D, t) */
-        REAL tvx = p[0] * V[0] + p[1] * V[4] + p[2] * V[8] + V[12];
-        REAL tvy = p[0] * V[1] + p[1] * V[5] + p[2] * V[9] + V[13];
-        REAL tvz = p[0] * V[2] + p[1] * V[6] + p[2] * V[10] + V[14];
+        REAL tvx = R_VIEW(p, V, 0);
+        REAL tvy = R_VIEW(p, V, 1);
+        REAL tvz = R_VIEW(p, V, 2);
         REAL limx = (REAL)GSR_FOV_CLAMP * c->tanfovx, limy = (REAL)GSR_FOV_CLAMP * c->tanfovy;
         REAL txtz = tvx / tvz, tytz = tvy / tvz;
         REAL tx = (txtz < -limx ? -limx : (txtz > limx ? limx : txtz)) * tvz;

@@ -241,6 +241,17 @@ GSR_HD void cov3d_from_scale_rot(const float s[3], float mod, const float q[4], 
     cov[5] = R[6] * R[6] * v0 + R[7] * R[7] * v1 + R[8] * R[8] * v2;
 }
 
+// p_view component k of a world point (transformPoint4x3 with the transposed view matrix V): evaluated as ONE fixed binary32
+// expression, fma(p2, V[8+k], fma(p1, V[4+k], p0 * V[k])) + V[12+k] -- the reference compiler's contraction of the left-to-right
+// sum, and one of the evaluations the oracle's depth band holds (oracle/gsr_oracle_impl.h "dB").  Left to the compiler, the device
+// contracted the first multiply instead (fma(p2, ., fma(p0, ., p1 * .))): at a posed camera the terms cancel (|p_view.z| ~ 0.2 from
+// terms ~ 0.5) and that evaluation is a few ulps away, so two splats an ulp apart swapped depth order outside the oracle's band.
+// z is the depth sort key and the near cut (A.1), so preprocess, geometry backward and markVisible all use this one function.
+GSR_HD float view_coord(const float p[3], const float *V, int k)
+{
+    return fmaf(p[2], V[8 + k], fmaf(p[1], V[4 + k], p[0] * V[k])) + V[12 + k];
+}
+
 // Shared by forward and backward: everything the EWA projection (A.4) derives from p_view and Sigma.
 struct Ewa {
     float tx, ty, tz;            // clamped view-space point
@@ -389,9 +400,9 @@ GSR_HD void preprocess_one(const FrameK &f, const float *V, const float *PV, con
     o.radius = 0; o.tiles = 0; o.clamped = 0; o.mass = 0.f;
     o.s = Splat{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float pv[3];
-    pv[0] = p[0] * V[0] + p[1] * V[4] + p[2] * V[8] + V[12];
-    pv[1] = p[0] * V[1] + p[1] * V[5] + p[2] * V[9] + V[13];
-    pv[2] = p[0] * V[2] + p[1] * V[6] + p[2] * V[10] + V[14];
+    pv[0] = view_coord(p, V, 0);
+    pv[1] = view_coord(p, V, 1);
+    pv[2] = view_coord(p, V, 2);
     if (pv[2] <= (float)GSR_NEAR_CUT) return;                                   // A.1
     const float hx = p[0] * PV[0] + p[1] * PV[4] + p[2] * PV[8] + PV[12];
     const float hy = p[0] * PV[1] + p[1] * PV[5] + p[2] * PV[9] + PV[13];
@@ -451,9 +462,9 @@ GSR_HD void geom_backward_one(const FrameK &f, const float *V, const float *PV, 
                               GeomGrad &g, float *dsh, bool want_dsh = true)
 {
     float pv[3];
-    pv[0] = p[0] * V[0] + p[1] * V[4] + p[2] * V[8] + V[12];
-    pv[1] = p[0] * V[1] + p[1] * V[5] + p[2] * V[9] + V[13];
-    pv[2] = p[0] * V[2] + p[1] * V[6] + p[2] * V[10] + V[14];
+    pv[0] = view_coord(p, V, 0);
+    pv[1] = view_coord(p, V, 1);
+    pv[2] = view_coord(p, V, 2);
     float cov[6];
     if (covpre) { for (int k = 0; k < 6; ++k) cov[k] = covpre[k]; }
     else cov3d_from_scale_rot(scale, f.scale_modifier, quat, cov);
@@ -595,7 +606,7 @@ GSR_HD void activate_raw_backward(const RawAct &a, GeomGrad &g)
 // ---- A.1 alone (markVisible).
 GSR_HD bool in_frustum(const float p[3], const float *V)
 {
-    return (p[0] * V[2] + p[1] * V[6] + p[2] * V[10] + V[14]) > (float)GSR_NEAR_CUT;
+    return view_coord(p, V, 2) > (float)GSR_NEAR_CUT;
 }
 
 }  // namespace gsr

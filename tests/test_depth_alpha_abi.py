@@ -132,7 +132,22 @@ def _view_z_column(kw):
 
 @pytest.mark.parametrize("P,W,H,seed", [(40, 48, 32, 31), (32, 40, 56, 32)])
 def test_oracle_depth_alpha_frame_matches_torch_autograd(P, W, H, seed):
-    scene, cam = S.make_scene(P, W, H, 1, seed, scale_lo=0.02, scale_hi=0.25), S.make_camera(W, H)
+    _depth_alpha_vs_autograd(P, W, H, seed)
+
+
+def test_oracle_depth_alpha_frame_matches_torch_autograd_at_a_posed_camera():
+    """The z chain dz (view[2], view[6], view[10]) with every view-matrix entry non-zero (tests/posed.py)."""
+    _depth_alpha_vs_autograd(40, 48, 40, 33, pose="b")
+
+
+def _depth_alpha_vs_autograd(P, W, H, seed, pose=None):
+    scene = S.make_scene(P, W, H, 1, seed, scale_lo=0.02, scale_hi=0.25)
+    if pose is None:
+        cam = S.make_camera(W, H)
+    else:
+        import posed as PO
+        cam = PO.posed_camera(W, H, pose)
+        scene = PO.to_world(scene, cam)
     kw = raster_kwargs(scene, cam)
     V = np.asarray(kw["viewmatrix"], np.float64)
     m3 = np.asarray(kw["means3D"], np.float64)

@@ -67,13 +67,17 @@ def _frame(name):
         return _faint_scene(3_500_000, 256, 240, 11, 2.0, 0.012), S.make_camera(256, 240), None
     if name == "carry_3pass":           # 272 x 257 tiles (3 passes), one chunk of >= 4 Mi instances
         return _faint_scene(3_000_000, 4352, 4112, 12, 2.0, 0.012), S.make_camera(4352, 4112), None
+    if name == "posed_edge":            # tests/posed.py: splats with far off-screen centres (clamped), near-plane giants, needles
+        import posed as PO
+        cam = PO.posed_camera(640, 360, "c", tanfovx=1.2 * 0.5 * 640 / 360)
+        return PO.edge_scene(640, 360, cam, 122, 12000)[0], cam, None
     if name == "cfg5n":
         sc, cam = S.make_config("cfg5n")
         return sc, cam, None
     raise KeyError(name)
 
 
-FRAMES = ["p20k_320x200", "team16", "team4", "wide_faint", "uncovered", "slab", "carry_1pass", "carry_3pass", "cfg5n"]
+FRAMES = ["p20k_320x200", "team16", "team4", "wide_faint", "uncovered", "slab", "carry_1pass", "carry_3pass", "cfg5n", "posed_edge"]
 # the frames whose paths an experiment switch changes
 SWITCHED = {"GSR_NO_GATHER": ["team16", "team4", "wide_faint"], "GSR_NO_LIVE_FILTER": ["uncovered"],
             "GSR_NO_CHUNK_MERGE": ["uncovered"]}

@@ -25,6 +25,7 @@ import pytest
 import torch
 
 import oracle
+import posed as PO
 import scene_synth as S
 from util import cov3d_from, raster_kwargs, unscale_records
 
@@ -140,23 +141,36 @@ GRAD_ATOL_REL = 1e-4        # x max|want| of the tensor
 GRAD_RTOL = 1e-4            # x |want| of the element        (north_star: "1e-4 on grads")
 
 
-def _check_grads(fr64, want, got, names, masked=False):
+def _check_grads(fr64, want, got, names, masked=False, groups=None):
     """masked=True: dL/dcolor was zero on every fragile pixel for both sides -> EVERY Gaussian is strict.
     masked=False: Gaussians that reach a fragile pixel (fr64.fragile_g) may differ by one flipped splat.
+    groups: {label: bool mask [P]} covering every Gaussian once: each group's max|want| is the scale of its own Gaussians (so one
+    near-plane splat does not loosen the bound on the rest of the frame); None: the tensor's max|want| for all.
     Returns (Gaussians with a non-zero gradient, how many of them were held to the strict bound)."""
     frag = np.zeros_like(fr64.fragile_g, dtype=bool) if masked else fr64.fragile_g.astype(bool)
     live = np.zeros(frag.shape[0], bool)
+    if groups is not None:
+        assert (np.sum([m.astype(int) for m in groups.values()], 0) == 1).all(), "groups must cover every Gaussian once"
     for n in names:
         w = want[n].reshape(got[n].shape).astype(np.float64)
         g = got[n].astype(np.float64)
         live |= (np.abs(w).reshape(w.shape[0], -1).max(1) > 0) if w.size else False
-        scale = max(np.abs(w).max(initial=0.0), 1e-30)
         err = np.abs(g - w)
+        if groups is None:
+            scale = max(np.abs(w).max(initial=0.0), 1e-30)
+        else:
+            scale = np.zeros((w.shape[0],) + (1,) * (w.ndim - 1))
+            for lab, m in groups.items():
+                s_g = max(np.abs(w[m]).max(initial=0.0), 1e-30)
+                scale[m] = s_g
+                e_g = err[m].max(initial=0.0)
+                print(f"  {n:10s} {lab:12s} n={int(m.sum()):6d} live={int((np.abs(w[m]).reshape(int(m.sum()), -1).max(1, initial=0.0) > 0).sum()):6d}"
+                      f"  max err {e_g:.3e}  scale {s_g:.3e}  err/scale {e_g / s_g:.2e}")
         bound = GRAD_ATOL_REL * scale + GRAD_RTOL * np.abs(w)
         mask = ~frag.reshape((-1,) + (1,) * (w.ndim - 1)) & np.ones_like(w, bool)
         bad = (err > bound) & mask
         assert not bad.any(), (f"{n}: {bad.sum()} elements of {np.unique(np.nonzero(bad)[0]).size} Gaussians off; "
-                               f"max err {err[mask].max():.3e} scale {scale:.3e} "
+                               f"max err {err[mask].max():.3e} scale {np.max(scale):.3e} "
                                f"worst ratio {(err / bound)[mask].max():.2f}")
         if frag.any():
             loose = 2e-2 * scale + 5e-2 * np.abs(w)
@@ -208,15 +222,46 @@ FIXTURES = [
     dict(P=2048, W=100, H=60, D=3, seed=107, mode="cov", bg=(0.2, 0.4, 0.6), frag=0.00117),
     dict(P=2048, W=128, H=128, D=1, seed=108, mode="color+cov", frag=0.00092),
     dict(P=5000, W=256, H=192, D=3, seed=109, scale_modifier=1.7, frag=0.00997),
+    # posed cameras (tests/posed.py): the same view-space scenes in front of a camera whose view matrix has no zero entry
+    dict(P=2048, W=128, H=128, D=3, seed=105, pose="a", frag=0.00104),
+    dict(P=2048, W=128, H=128, D=0, seed=106, mode="color", pose="b", frag=0.00128),
+    dict(P=2048, W=100, H=60, D=3, seed=107, mode="cov", bg=(0.2, 0.4, 0.6), pose="c", frag=0.00033),
+    dict(P=2048, W=128, H=128, D=1, seed=108, mode="color+cov", pose="a", frag=0.0011),
+    # the edge frames (posed.edge_scene: `edge` ordinary Gaussians next to the clamp / near / culled / needle / opaque / SH-clamp
+    # populations), the second with non-square pixels
+    dict(P=3512, W=256, H=192, D=3, seed=121, edge=3000, pose="b", frag=0.00071),
+    dict(P=12512, W=640, H=360, D=3, seed=122, edge=12000, pose="c", tanfovx=1.2 * 0.5 * 640 / 360, frag=0.00216),
 ]
+EDGE_FIXTURES = [c for c in FIXTURES if "edge" in c]
+POSED_FIXTURES = [c for c in FIXTURES if "pose" in c and "edge" not in c]
 
 
-def _fixture_kwargs(c):
+def _fixture_id(c):
+    return (f"P{c['P']}_{c['W']}x{c['H']}_D{c['D']}_{c.get('mode', 'sh')}" + (f"_pose{c['pose']}" if "pose" in c else "")
+            + ("_edge" if "edge" in c else ""))
+
+
+def _fixture_scene(c):
+    """(scene, camera, population labels or None) of a fixture; `pose` places the view-space scene in front of posed.posed_camera,
+    `edge` builds posed.edge_scene with that many ordinary Gaussians."""
     W, H = c["W"], c["H"]
+    cam = PO.posed_camera(W, H, c["pose"], tanfovx=c.get("tanfovx")) if "pose" in c else S.make_camera(W, H)
+    if "edge" in c:
+        scene, labels = PO.edge_scene(W, H, cam, c["seed"], c["edge"])
+        assert scene.P == c["P"] and c["D"] == 3
+        return scene, cam, labels
     lo, hi = (0.01, 0.2) if c["P"] <= 64 else (0.005, 0.06)
-    scene, cam = S.make_scene(c["P"], W, H, c["D"], c["seed"], scale_lo=lo, scale_hi=hi), S.make_camera(W, H)
+    scene = S.make_scene(c["P"], W, H, c["D"], c["seed"], scale_lo=lo, scale_hi=hi)
     if c["P"] <= 2:     # make sure the tiny cases are actually on screen
         scene.means3D[:] = torch.tensor([[0.05, -0.03, 2.0], [-0.2, 0.1, 3.0]])[:c["P"]]
+    if "pose" in c:
+        scene = PO.to_world(scene, cam)
+    return scene, cam, None
+
+
+def _fixture_kwargs(c, scene_cam=None):
+    """scene_cam: the fixture's (scene, camera) when the caller built it already (_fixture_scene)."""
+    scene, cam = scene_cam if scene_cam is not None else _fixture_scene(c)[:2]
     a = scene.activated()
     extra = {}
     mode = c.get("mode", "")
@@ -227,7 +272,7 @@ def _fixture_kwargs(c):
     return raster_kwargs(scene, cam, bg=c.get("bg", (0, 0, 0)), scale_modifier=c.get("scale_modifier", 1.0), **extra)
 
 
-@pytest.mark.parametrize("c", FIXTURES, ids=lambda c: f"P{c['P']}_{c['W']}x{c['H']}_D{c['D']}_{c.get('mode', 'sh')}")
+@pytest.mark.parametrize("c", FIXTURES, ids=_fixture_id)
 def test_forward_backward_match_oracle(c):
     kw = _fixture_kwargs(c)
     fr64 = oracle.rasterize(dtype=np.float64, **kw)
@@ -237,6 +282,130 @@ def test_forward_backward_match_oracle(c):
     color, radii, grads = _run_gpu(kw, gimg)
     want = fr64.backward(gimg.astype(np.float64))
     _check_grads(fr64, want, grads, [n for n in GRAD_NAMES if n in grads])
+
+
+@pytest.mark.parametrize("c", EDGE_FIXTURES, ids=_fixture_id)
+def test_edge_frame_every_population_against_the_oracle(c):
+    """The edge frames by population (tests/posed.py): radii exact, pixels 1e-5 on strict pixels, every Gaussian's gradient at 1e-4
+    of ITS POPULATION's max|want| (a near-plane splat's gradient is ~100x an ordinary one's), every Gaussian against its own scale
+    by population (gradcheck, >= 16 Gaussians with a gradient each), and the culled population with radius 0 and no gradient.
+    (Measured: the binary32 oracle meets the population bound on every population, worst 0.55 of it: DESIGN.md section 2.)"""
+    import gradcheck as GC
+    scene, cam, labels = _fixture_scene(c)
+    kw = _fixture_kwargs(c, (scene, cam))
+    pops = PO.population_masks(labels)
+    fr64 = oracle.rasterize(dtype=np.float64, parallel=True, **kw)
+    fr32 = oracle.rasterize(dtype=np.float32, parallel=True, **kw)
+    gimg = S.make_grad_image(c["W"], c["H"], c["seed"]).numpy()
+    color, radii, grads, want, live = _forward_backward_strict(kw, fr64, gimg, label=_fixture_id(c), parallel=True,
+                                                               frag_cap=fragile_cap(c["frag"]))
+    names = [n for n in GRAD_NAMES if n in grads]
+    _check_grads(fr64, want, grads, names, masked=True, groups=pops)
+    culled = pops["culled"]
+    assert np.all(radii[culled] == 0) and np.all(fr64.radii[culled] == 0)
+    for n in names:
+        assert not np.any(grads[n][culled]), f"{n}: a culled Gaussian got a gradient"
+    gm = np.where(_strict_pixels(fr64, radii)[None], gimg, 0.0)
+    b2f = fr32.backward(gm.astype(np.float32), parallel=True)
+    f2b = fr32.backward(gm.astype(np.float32), parallel=True, order="front_to_back")
+    strata = {p: (m, 16) for p, m in pops.items() if p != "culled"}
+    GC.check_grads_per_gaussian(want, GC.yardstick(want, b2f, f2b, names), grads, strata, names, label=_fixture_id(c))
+
+
+def _geom_variants(plan, P, has_shs):
+    """Mirror of the library's dispatch for a frame's own backward (csrc/gsr_geom.hip launch_chunk_colors, csrc/gsr_internal.h
+    geom_bwd_sparse with gsr_api.hip backward_geom_impl's own-plan arguments): the colour kernels the chunks that ran launch, and
+    whether the geometry backward (and its depth chain) takes the sparse or the dense kernel."""
+    from diff_gaussian_rasterization import _native as N
+    out = set()
+    runs = plan.num_rendered > 0 and plan.chunks_run > 0
+    if has_shs:
+        for c in range(int(plan.chunks_run)):
+            r0, r1 = int(plan.chunk_rank_begin[c]), int(plan.chunk_rank_begin[c + 1])
+            if r1 > r0:
+                full = r0 == 0 and r1 >= plan.num_visible and 2 * int(plan.num_visible) >= P
+                out.add("k_chunk_colors_all" if full else "k_chunk_colors")
+    binned = int(plan.chunk_rank_begin[plan.chunks_run]) if runs else 0
+    own_sparse = runs and N.effective_binned_ranks(plan) * 4 < P
+    out.add("sparse" if own_sparse or binned * 4 < P else "dense")
+    return out
+
+
+def _uncovered_half_posed():
+    """The frame of test_frame_with_an_uncovered_region..., its view-space scene placed in front of a posed camera (to_world)."""
+    scene = S.make_scene(260_000, 480, 320, 1, 91, scale_lo=0.01, scale_hi=0.07)
+    scene.means3D[:, 1] = -scene.means3D[:, 1].abs() - 0.02 * scene.means3D[:, 2]
+    cam = PO.posed_camera(480, 320, "a")
+    return PO.to_world(scene, cam), cam
+
+
+def test_posed_frames_reach_every_geometry_kernel_variant():
+    """The posed frames of this suite (the posed and edge fixtures; the posed uncovered half, whose values test_gpu_depth_alpha G1
+    and test_gpu_timed_path check) through the three routes: the standard API (raw mode 0), render() with fused activations (raw
+    mode 1, split SH tables) and bench.py's raw leaves (raw mode 2), and the aux backward.  Which variant ran is the mirror's
+    (_geom_variants) reading of the frame's plan from the standard-API run: the library's launch counts only show that the
+    colour, geometry-backward and depth-chain launchers ran (each scope covers both of its kernels), and for raw modes 1 and 2
+    the plan is that of the same scene through the standard API.  Together the frames must reach k_chunk_colors,
+    k_chunk_colors_all, dense and sparse k_geom_bwd in raw modes 0 and 2 (and mode 1 in one of them), and both k_geom_bwd_depth
+    variants."""
+    import diff_gaussian_rasterization as dgr
+    from diff_gaussian_rasterization import _native as N
+    from gaussian_params import GaussianParams, Pipe
+    from gaussian_renderer import render
+    from scene import GaussianModel
+    frames = [(_fixture_id(c),) + _fixture_scene(c)[:2] for c in POSED_FIXTURES + EDGE_FIXTURES if c.get("mode", "sh") == "sh"]
+    frames.append(("uncovered half posed",) + _uncovered_half_posed())
+    reached = set()
+    for name, scene, cam in frames:
+        kw = raster_kwargs(scene, cam)
+        inp = _inputs(kw, False)
+        for aux in (False, True):
+            N.profile_enable(True)
+            color, radii, fr = dgr.rasterize_forward(inp["means3D"], inp["shs"], None, inp["opacities"], inp["scales"], inp["rotations"],
+                                                     None, _settings(kw), aux=aux)
+            screen = (dgr.rasterize_backward_screen(fr, torch.ones_like(color)) if not aux else
+                      dgr.rasterize_backward_screen(fr, torch.ones_like(color), grad_depth=torch.ones_like(color[0]),
+                                                    grad_alpha=torch.ones_like(color[0])))
+            dgr.rasterize_backward_geom(fr, screen, (True,) * 8, depth_chain=aux)
+            torch.cuda.synchronize()
+            prof = N.profile_read()
+            N.profile_enable(False)
+            v = _geom_variants(fr.plan, scene.P, True)
+            assert prof.get("geom_bwd", (0, 0))[1] > 0 and prof.get("chunk_colors", (0, 0))[1] > 0, (name, prof)
+            path = "sparse" if "sparse" in v else "dense"
+            if aux:
+                assert prof.get("geom_bwd_depth", (0, 0))[1] > 0, (name, prof)
+                reached.add(f"k_geom_bwd_depth<{'true' if path == 'sparse' else 'false'}>")
+            else:
+                reached |= {k for k in v if k.startswith("k_chunk")}
+                reached.add(f"k_geom_bwd{'_sparse' if path == 'sparse' else ''} raw0")
+            print(f"{name} aux={aux}: {sorted(v)}; plan chunks_run {fr.plan.chunks_run}/{fr.plan.num_chunks} visible {fr.plan.num_visible} "
+                  f"of {scene.P}, filtered {fr.plan.chunks_filtered:#x}")
+        path = "sparse" if "sparse" in v else "dense"
+        gimg = torch.ones(3, cam.image_height, cam.image_width, device=DEV)
+        for raw, mk in ((1, "fused"), (2, "raw leaves")):
+            N.profile_enable(True)
+            if raw == 1:
+                model = GaussianParams(scene.to(DEV), max_sh_degree=scene.sh_degree).to(DEV)
+                model.active_sh_degree = scene.sh_degree
+                pipe = Pipe()
+                pipe.fused_activations = True
+            else:
+                model = GaussianModel(scene.sh_degree)
+                model.adopt_scene(scene, device=DEV)
+                pipe = Pipe()
+            out = render(cam.to(DEV), model, pipe, torch.zeros(3, device=DEV))
+            out["render"].backward(gimg)
+            torch.cuda.synchronize()
+            prof = N.profile_read()
+            N.profile_enable(False)
+            assert prof.get("geom_bwd", (0, 0))[1] > 0, (name, mk, prof)
+            reached.add(f"k_geom_bwd{'_sparse' if path == 'sparse' else ''} raw{raw}")
+    print("reached:", sorted(reached))
+    required = {"k_chunk_colors", "k_chunk_colors_all", "k_geom_bwd raw0", "k_geom_bwd_sparse raw0", "k_geom_bwd raw2",
+                "k_geom_bwd_sparse raw2", "k_geom_bwd_depth<false>", "k_geom_bwd_depth<true>"}
+    assert required <= reached, f"not reached: {sorted(required - reached)}"
+    assert {"k_geom_bwd raw1", "k_geom_bwd_sparse raw1"} & reached
 
 
 def _per_tile_lists(v, plan, Tn):
@@ -432,6 +601,18 @@ def test_api_contract():
     pv_z = kw["means3D"] @ kw["viewmatrix"][:3, 2] + kw["viewmatrix"][3, 2]
     np.testing.assert_array_equal(vis.cpu().numpy(), pv_z > 0.2)
     assert np.all(vis.cpu().numpy()[fr.radii > 0])
+    # ... at a posed camera (no zero in the view matrix), with points at z_view = 0.2 (1 -+ 1e-3) and on both sides further out
+    pcam = PO.posed_camera(128, 128, "b")
+    zv = np.concatenate([np.full(64, 0.2 * (1 - 1e-3)), np.full(64, 0.2 * (1 + 1e-3)), np.linspace(-2, 4, 128)])
+    g = np.random.default_rng(5)
+    pvp = np.stack([g.uniform(-0.6, 0.6, zv.size) * np.abs(zv), g.uniform(-0.6, 0.6, zv.size) * np.abs(zv), zv], 1)
+    M, t = PO.view_rt(pcam)
+    pw = ((pvp - t) @ np.linalg.inv(M)).astype(np.float32)
+    want_vis = PO.view_coords(pw, pcam)[:, 2] > 0.2
+    assert want_vis[64:128].all() and not want_vis[:64].any()
+    rsp = _settings(raster_kwargs(S.make_scene(1, 128, 128, 0, 1), pcam))
+    got_vis = GaussianRasterizer(rsp).markVisible(torch.as_tensor(pw, device=DEV)).cpu().numpy()
+    np.testing.assert_array_equal(got_vis, want_vis)
 
 
 def test_second_backward_follows_autograd_retain_graph_rules():
@@ -1049,14 +1230,24 @@ def test_more_than_2_pow_32_tile_instances_is_an_error_not_a_wrap():
 
 @pytest.mark.parametrize("D,max_D", [(3, 3), (1, 3), (0, 0)])
 def test_raw_parameter_mode_equals_getters_plus_standard_api(D, max_D):
+    _raw_mode_vs_getters(D, max_D)
+
+
+def test_raw_parameter_mode_equals_getters_plus_standard_api_at_a_posed_camera():
+    """Raw mode 1 (split SH tables, activations in the kernels) at a posed camera."""
+    _raw_mode_vs_getters(3, 3, pose="a")
+
+
+def _raw_mode_vs_getters(D, max_D, pose=None):
     """SURVEY 8a row a14 fused (`pipe.fused_activations`, GaussianRasterizer.forward_raw): rendering from the raw
     parameters with the activations inside the kernels gives the image of render() through the getters and the
     same gradients on the raw parameters as torch autograd through exp / sigmoid / normalize / cat."""
     from gaussian_params import GaussianParams, Pipe
     from gaussian_renderer import render
     W, H = 320, 208
-    scene = S.make_scene(20_000, W, H, max_D, 17 + D, scale_lo=0.005, scale_hi=0.06).to(DEV)
-    cam = S.make_camera(W, H).to(DEV)
+    scene = S.make_scene(20_000, W, H, max_D, 17 + D, scale_lo=0.005, scale_hi=0.06)
+    cam = S.make_camera(W, H) if pose is None else PO.posed_camera(W, H, pose)
+    scene, cam = (scene if pose is None else PO.to_world(scene, cam)).to(DEV), cam.to(DEV)
     bg = torch.tensor([0.1, 0.0, 0.2], device=DEV)
     gimg = S.make_grad_image(W, H, 6).to(DEV)
     results = []
@@ -1155,19 +1346,33 @@ def test_randomised_configurations_against_oracle():
     """Seeded sweep over shapes the fixed fixtures do not hit: image sizes off the 16-px tile grid (down to 1x1 and 17x1),
     Gaussian counts around the 64-rank wave boundaries of the binning kernels, splat sizes from sub-pixel to
     screen-filling (all three count/emit variants), every SH degree, non-square pixels, tile-row slabs."""
+    _random_sweep(np.random.default_rng(20241004), 42)
+
+
+def test_randomised_configurations_against_oracle_at_posed_cameras():
+    """The same sweep at posed cameras (tests/posed.py; the view-space scenes placed with to_world), from a generator of its own so
+    that the cases above stay as they are."""
+    _random_sweep(np.random.default_rng(20261016), 21, seed0=3000, posed=True)
+
+
+def _random_sweep(rng, n_cases, seed0=1000, posed=False):
     from diff_gaussian_rasterization import rasterize_forward, rasterize_backward_screen, rasterize_backward_geom
-    rng = np.random.default_rng(20241004)
     sizes = [(1, 1), (17, 1), (16, 16), (33, 47), (250, 130), (640, 360), (96, 300)]
     counts = [1, 63, 64, 65, 129, 1000, 4097]
     scales = [(0.0005, 0.003), (0.005, 0.05), (0.05, 0.6), (0.3, 3.0)]
     n_live = 0
-    for it in range(42):
+    for it in range(n_cases):
         W, H = sizes[it % len(sizes)]
         P = counts[int(rng.integers(len(counts)))]
         lo, hi = scales[int(rng.integers(len(scales)))]
         D = int(rng.integers(0, 4))
-        cam = S.make_camera(W, H, tanfovy=0.5, tanfovx=float(0.5 * W / H * rng.uniform(0.7, 1.4)))
-        scene = S.make_scene(P, W, H, D, 1000 + it, scale_lo=lo, scale_hi=hi)
+        tanfovx = float(0.5 * W / H * rng.uniform(0.7, 1.4))
+        scene = S.make_scene(P, W, H, D, seed0 + it, scale_lo=lo, scale_hi=hi)
+        if posed:
+            cam = PO.posed_camera(W, H, "abc"[it % 3], tanfovy=0.5, tanfovx=tanfovx)
+            scene = PO.to_world(scene, cam)
+        else:
+            cam = S.make_camera(W, H, tanfovy=0.5, tanfovx=tanfovx)
         kw = raster_kwargs(scene, cam, bg=tuple(rng.uniform(0, 1, 3).round(2)), scale_modifier=float(rng.choice([1.0, 0.6, 1.5])))
         Gy = (H + 15) // 16
         rows = None
@@ -1184,7 +1389,7 @@ def test_randomised_configurations_against_oracle():
         screen = rasterize_backward_screen(fr, torch.as_tensor(gimg).to(DEV))
         g = rasterize_backward_geom(fr, screen, (True,) * 8)
         torch.cuda.synchronize()
-        tag = f"case {it}: {W}x{H} P={P} scales=({lo},{hi}) D={D} rows={rows}"
+        tag = f"case {it}: {W}x{H} P={P} scales=({lo},{hi}) D={D} rows={rows}" + (" posed" if posed else "")
         np.testing.assert_array_equal(radii.cpu().numpy(), fr64.radii, err_msg=tag)
         got = color.cpu().numpy()
         if rows is not None:                       # rows outside the slab are left at 0 by the library and by the oracle
@@ -1192,6 +1397,9 @@ def test_randomised_configurations_against_oracle():
             assert np.all(got[:, :y0] == 0) and np.all(got[:, y1:] == 0), tag
         err = np.abs(got - fr64.color).max(0)
         tol = 1e-5 * max(1.0, float(np.abs(fr64.color).max()))      # synthetic SH colours are not confined to [0, 1]
+        if posed:       # sub-pixel splats: the posed view transform rounds the binary32 screen position more than the identity
+            ref = oracle.rasterize(dtype=np.float32, tile_rows=rows, **kw)       # no worse than the binary32 oracle's own worst pixel
+            tol = max(tol, float(np.abs(ref.color.astype(np.float64) - fr64.color).max(0)[strict].max(initial=0.0)))
         assert err[strict].max(initial=0.0) <= tol, f"{tag}: pixel error {err[strict].max():.3e} (tolerance {tol:.1e})"
         assert err.max(initial=0.0) <= 2e-2 * max(1.0, float(np.abs(fr64.color).max())), tag
         want = fr64.backward(gimg)

@@ -16,8 +16,8 @@ import torch
 
 import oracle
 import scene_synth as S
-from test_gpu_parity import (DEV, FRAGILE_CAP, GRAD_ATOL_REL, GRAD_RTOL, _check_forward, _check_grads, _strict_pixels, check_deep_per_gaussian,
-                             fragile_cap)
+from test_gpu_parity import (DEV, FIXTURES, FRAGILE_CAP, GRAD_ATOL_REL, GRAD_RTOL, _check_forward, _check_grads, _fixture_id, _fixture_scene,
+                             _strict_pixels, _uncovered_half_posed, check_deep_per_gaussian, fragile_cap)
 from util import raster_kwargs
 
 pytestmark = pytest.mark.gpu
@@ -95,6 +95,24 @@ def test_timed_path_fixtures_vs_raw_oracle(P, W, H, D, seed, bg):
         scene.means3D[:] = torch.tensor([[0.05, -0.03, 2.0]])
     live = _timed_path_strict(scene, cam, S.make_grad_image(W, H, seed).numpy(), bg, label=f"fixture P={P} {W}x{H} D={D}", parallel=False)
     assert live >= 1
+
+
+@pytest.mark.parametrize("c", [c for c in FIXTURES if "pose" in c], ids=_fixture_id)
+def test_timed_path_posed_fixtures_vs_raw_oracle(c):
+    """The posed fixtures and the two edge frames (tests/posed.py) through the raw-leaves route (raw mode 2) bench.py times (the
+    fixtures' scenes with their SH and scale / rotation leaves, whatever their precomputed mode in test_gpu_parity)."""
+    scene, cam, _ = _fixture_scene(c)
+    live = _timed_path_strict(scene, cam, S.make_grad_image(c["W"], c["H"], c["seed"]).numpy(), c.get("bg", (0.0, 0.0, 0.0)),
+                              label=_fixture_id(c))
+    assert live >= 1000
+
+
+def test_timed_path_posed_uncovered_half_vs_raw_oracle():
+    """test_gpu_parity's 260 k frame with an uncovered lower half, in front of a posed camera: two depth chunks, the second live-
+    filtered, so the chunked colour kernel and the SPARSE geometry backward run in raw mode 2 with every view-matrix entry non-zero."""
+    scene, cam = _uncovered_half_posed()
+    live = _timed_path_strict(scene, cam, S.make_grad_image(cam.image_width, cam.image_height, 4).numpy(), label="uncovered half posed")
+    assert live > 1000, live
 
 
 FRAGILE_MEASURED = {"cfg2": 0.0076, "cfg3": 0.009, "cfg3n": 0.015}      # measured fragile fraction per workload (fragile_cap)

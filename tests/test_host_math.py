@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import oracle
+import posed as PO
 import scene_synth as S
 from util import cov3d_from, raster_kwargs, unscale_records
 
@@ -48,10 +49,34 @@ def _run(hh, kw, slab=(0, 0)):
     return dict(radii=radii, tiles=tiles, clamped=cl, rec=rec, args=(P, D, M, W, H, V, PV, cam, means, sc, ro, cp, shs, col))
 
 
+def _scene_cam(camera, P, W, H, D, seed, scale_lo, scale_hi):
+    """camera: "identity" (scene_synth.make_camera), "posed" (the same view-space scene in front of posed.posed_camera) or "edge"
+    (posed.edge_scene: P ordinary Gaussians next to the clamp / near / culled / needle / opaque / SH-clamp populations, D = 3)."""
+    scene = S.make_scene(P, W, H, D, seed, scale_lo=scale_lo, scale_hi=scale_hi)
+    if camera == "identity":
+        return scene, S.make_camera(W, H)
+    cam = PO.posed_camera(W, H, "a" if camera == "posed" else "b")
+    if camera == "posed":
+        return PO.to_world(scene, cam), cam
+    assert D == 3
+    return PO.edge_scene(W, H, cam, seed, P)[0], cam
+
+
 @pytest.mark.parametrize("mode", ["sh+scale", "color+cov"])
 @pytest.mark.parametrize("D", [0, 3])
 def test_preprocess_matches_oracle(hh, mode, D):
-    scene, cam = S.make_scene(3000, 160, 112, D, 41 + D, scale_lo=0.005, scale_hi=0.08), S.make_camera(160, 112)
+    _check_preprocess(hh, mode, D, "identity")
+
+
+@pytest.mark.parametrize("mode", ["sh+scale", "color+cov"])
+@pytest.mark.parametrize("D,camera", [(0, "posed"), (3, "posed"), (3, "edge")])
+def test_preprocess_matches_oracle_at_posed_cameras(hh, mode, D, camera):
+    """The same checks at a camera whose view matrix has no zero entry (posed.posed_camera), and on the edge frame."""
+    _check_preprocess(hh, mode, D, camera)
+
+
+def _check_preprocess(hh, mode, D, camera):
+    scene, cam = _scene_cam(camera, 3000, 160, 112, D, 41 + D, 0.005, 0.08)
     a = scene.activated()
     extra = {}
     if mode == "color+cov":
@@ -88,8 +113,19 @@ def test_preprocess_matches_oracle(hh, mode, D):
 
 @pytest.mark.parametrize("mode", ["sh+scale", "color+cov"])
 def test_geom_backward_matches_oracle(hh, mode):
+    _check_geom_backward(hh, mode, "identity")
+
+
+@pytest.mark.parametrize("mode", ["sh+scale", "color+cov"])
+@pytest.mark.parametrize("camera", ["posed", "edge"])
+def test_geom_backward_matches_oracle_at_posed_cameras(hh, mode, camera):
+    """The same bound at a posed camera and on the edge frame (clamped tx/tz and ty/tz, near-plane splats, needles, SH clamp)."""
+    _check_geom_backward(hh, mode, camera)
+
+
+def _check_geom_backward(hh, mode, camera):
     D = 3
-    scene, cam = S.make_scene(2000, 128, 96, D, 77, scale_lo=0.005, scale_hi=0.08), S.make_camera(128, 96)
+    scene, cam = _scene_cam(camera, 2000, 128, 96, D, 77, 0.005, 0.08)
     a = scene.activated()
     extra = {}
     if mode == "color+cov":

@@ -10,13 +10,26 @@ import pytest
 import torch
 
 import oracle
+import posed as PO
 import scene_synth as S
 from torch_ref import render_autograd
 from util import cov3d_from, raster_kwargs
 
+# the small edge frame: a handful of each posed.edge_scene population
+SMALL_EDGE = dict(clamp_x=4, clamp_y=4, clamp_xy=3, near=6, culled=4, needle_disc=6, opaque=5, sh_clamp=6)
 
-def _small_scene(P, W, H, D, seed, zmax=4.0):
-    return S.make_scene(P, W, H, D, seed, scale_lo=0.02, scale_hi=0.25, zmax=zmax), S.make_camera(W, H)
+
+def _small_scene(P, W, H, D, seed, zmax=4.0, cam="identity"):
+    """cam: "identity" (scene_synth.make_camera), "posed" (the same view-space scene in front of posed.posed_camera) or "edge"
+    (posed.edge_scene with P ordinary Gaussians next to SMALL_EDGE; D is 3)."""
+    if cam == "edge":
+        c = PO.posed_camera(W, H, "b")
+        return PO.edge_scene(W, H, c, seed, P, counts=SMALL_EDGE)[0], c
+    scene = S.make_scene(P, W, H, D, seed, scale_lo=0.02, scale_hi=0.25, zmax=zmax)
+    if cam == "posed":
+        c = PO.posed_camera(W, H, "a")
+        return PO.to_world(scene, c), c
+    return scene, S.make_camera(W, H)
 
 
 def _to_t64(kw):
@@ -31,12 +44,19 @@ CASES = [
     dict(P=40, W=40, H=56, D=1, seed=12, mode="sh+scale"),
     dict(P=32, W=48, H=48, D=2, seed=13, mode="color+cov"),
     dict(P=24, W=33, H=47, D=0, seed=14, mode="sh+scale", bg=(1.0, 0.5, 0.25)),
+    dict(P=40, W=48, H=40, D=3, seed=15, mode="sh+scale", cam="posed"),
+    dict(P=32, W=40, H=48, D=2, seed=16, mode="color+cov", cam="posed"),
+    dict(P=24, W=48, H=36, D=3, seed=17, mode="sh+scale", cam="edge"),
 ]
 
 
-@pytest.mark.parametrize("case", CASES, ids=lambda c: f"P{c['P']}_{c['W']}x{c['H']}_D{c['D']}_{c['mode']}")
+def _case_id(c):
+    return f"P{c['P']}_{c['W']}x{c['H']}_D{c['D']}_{c['mode']}" + (f"_{c['cam']}" if "cam" in c else "")
+
+
+@pytest.mark.parametrize("case", CASES, ids=_case_id)
 def test_oracle_f64_matches_torch_autograd(case):
-    scene, cam = _small_scene(case["P"], case["W"], case["H"], case["D"], case["seed"])
+    scene, cam = _small_scene(case["P"], case["W"], case["H"], case["D"], case["seed"], cam=case.get("cam", "identity"))
     a = scene.activated()
     extra = {}
     if case["mode"] == "color+cov":
@@ -69,17 +89,47 @@ def test_oracle_f64_matches_torch_autograd(case):
     assert np.all(got["means2D"][:, 2] == 0)
 
 
+def test_edge_frame_exercises_the_clamp_gradient_mask():
+    """A.10: where tx/tz (ty/tz) is clamped, the clamped value carries no gradient.  On the clamp populations of the edge frame the
+    oracle's dL/dmeans3D must differ from naive autograd through the clamp (torch_ref mask_clamp_grad=False) by far more than the
+    GPU tolerance (1e-4 of the population's scale), so a kernel that dropped the mask fails; elsewhere the two agree."""
+    W, H = 64, 48
+    cam = PO.posed_camera(W, H, "b")
+    scene, labels = PO.edge_scene(W, H, cam, 18, 30, counts=SMALL_EDGE)
+    kw = raster_kwargs(scene, cam)
+    fr = oracle.rasterize(dtype=np.float64, **kw)
+    gimg = S.make_grad_image(W, H, 18).double()
+    got = fr.backward(gimg.numpy())["means3D"]
+    tk = _to_t64(kw)
+    tk["means3D"] = tk["means3D"].clone().requires_grad_(True)
+    color, *_ = render_autograd(mask_clamp_grad=False, **tk)
+    (color * gimg).sum().backward()
+    naive = tk["means3D"].grad.numpy()
+    pv = PO.view_coords(kw["means3D"], cam)
+    clamped = ((np.abs(pv[:, 0] / pv[:, 2]) > 1.3 * kw["tanfovx"]) | (np.abs(pv[:, 1] / pv[:, 2]) > 1.3 * kw["tanfovy"])) & (fr.radii > 0)
+    for pop in ("clamp_x", "clamp_y", "clamp_xy"):
+        m = labels == pop
+        assert clamped[m].all() and m.sum() >= 3, pop
+        scale = np.abs(got[m]).max()
+        diff = np.abs(got[m] - naive[m]).max()
+        print(f"{pop}: max |oracle - unmasked| {diff:.3e}, population scale {scale:.3e}")
+        assert scale > 0 and diff > 100 * 1e-4 * scale, (pop, diff, scale)
+    rest = ~clamped
+    assert np.abs(got[rest] - naive[rest]).max() <= 1e-9 * np.abs(got).max()
+
+
 def _raw_settings(kw):
     return {k: kw[k] for k in ("image_height", "image_width", "tanfovx", "tanfovy", "bg", "scale_modifier", "viewmatrix",
                                "projmatrix", "sh_degree", "campos")}
 
 
-@pytest.mark.parametrize("case", CASES[:2] + CASES[3:], ids=lambda c: f"P{c['P']}_{c['W']}x{c['H']}_D{c['D']}")
+@pytest.mark.parametrize("case", [c for c in CASES if c["mode"] == "sh+scale"],
+                         ids=lambda c: f"P{c['P']}_{c['W']}x{c['H']}_D{c['D']}" + (f"_{c['cam']}" if "cam" in c else ""))
 def test_raw_leaves_entry_matches_torch_autograd_through_the_getters(case):
     """oracle.rasterize_raw = the getters of scene/gaussian_model.py:101-125 (exp / normalize / sigmoid / cat) in binary64 in
     front of the oracle and their chain rule behind its explicit backward: against torch autograd through the same torch
     getters and the independent restatement (tests/torch_ref.py), on the raw leaves."""
-    scene, cam = _small_scene(case["P"], case["W"], case["H"], case["D"], case["seed"])
+    scene, cam = _small_scene(case["P"], case["W"], case["H"], case["D"], case["seed"], cam=case.get("cam", "identity"))
     kw = raster_kwargs(scene, cam, bg=case.get("bg", (0, 0, 0)))
     raw = dict(means3D=scene.means3D.numpy(), features=scene.shs.numpy(), opacity_logits=scene.opacity_logits.numpy(),
                log_scales=scene.log_scales.numpy(), raw_rotations=scene.raw_rotations.numpy())

@@ -45,9 +45,10 @@ def quat_to_rot(q):
 
 def render_autograd(*, image_height, image_width, tanfovx, tanfovy, bg, scale_modifier, viewmatrix, projmatrix,
                     sh_degree, campos, means3D, opacities, shs=None, colors_precomp=None, scales=None,
-                    rotations=None, cov3D_precomp=None, tile_rows=None):
+                    rotations=None, cov3D_precomp=None, tile_rows=None, mask_clamp_grad=True):
     """Returns (color[3,H,W], radii[P], means2D_proxy[P,2]).  `means2D_proxy` is a zero tensor added to the
-    NDC position so that its autograd gradient is the reference's `means2D.grad[:, :2]`."""
+    NDC position so that its autograd gradient is the reference's `means2D.grad[:, :2]`.  mask_clamp_grad=False
+    differentiates through the clamped tx/tz (ty/tz) instead of detaching it (naive autograd, not the reference)."""
     dt = torch.float64
     H, W = int(image_height), int(image_width)
     Gx, Gy = (W + 15) // 16, (H + 15) // 16
@@ -77,8 +78,9 @@ def render_autograd(*, image_height, image_width, tanfovx, tanfovy, bg, scale_mo
     tz = pv[:, 2]
     txtz, tytz = pv[:, 0] / tz, pv[:, 1] / tz
     cx, cy = (txtz < -limx) | (txtz > limx), (tytz < -limy) | (tytz > limy)
-    tx = torch.where(cx, (txtz.clamp(-limx, limx) * tz).detach(), pv[:, 0])
-    ty = torch.where(cy, (tytz.clamp(-limy, limy) * tz).detach(), pv[:, 1])
+    keep = (lambda v: v.detach()) if mask_clamp_grad else (lambda v: v)
+    tx = torch.where(cx, keep(txtz.clamp(-limx, limx) * tz), pv[:, 0])
+    ty = torch.where(cy, keep(tytz.clamp(-limy, limy) * tz), pv[:, 1])
     zero = torch.zeros_like(tz)
     J = torch.stack([fx / tz, zero, -fx * tx / (tz * tz), zero, fy / tz, -fy * ty / (tz * tz)], 1).view(-1, 2, 3)
     Wm = V[:3, :3].t()
