@@ -258,6 +258,27 @@ int gsr_backward_geom_aux(const gsr_frame_desc *desc, const gsr_camera *cam, con
                           const int32_t *radii, const void *geom_ws, const float *screen_grads, int32_t g_begin,
                           int32_t g_end, int32_t binned_ranks, const gsr_frame_plan *own_plan, const gsr_grads *out, void *stream);
 
+/* ---- Gradients for the camera: dL/dviewmatrix [4,4], dL/dprojmatrix [4,4], dL/dcampos [3] (additive: every call above keeps its
+ * meaning).  Each is the gradient w.r.t. the tensor as the forward consumed it, in the header's row-vector convention; the three
+ * are returned separately and the caller chains them to its own pose parametrisation (the library has none).  Column 3 of
+ * dL/dviewmatrix and column 2 of dL/dprojmatrix are exact zeros (the forward never reads those entries); dL/dcampos is zero with
+ * colors_precomp.  A clamped tx/tz (ty/tz) contributes nothing through that coordinate, exactly as for means3D.
+ * gsr_backward_camera runs behind gsr_backward_geom / gsr_backward_geom_aux of the same frame, with the same screen_grads, and
+ * visits the rows that call visits: binned_ranks / own_plan mean what they mean there; depth_chain != 0 (screen_grads came from
+ * gsr_backward_render_aux) adds the depth map's chain through slot 9 to dL/dviewmatrix.  The sums over Gaussians are taken in a
+ * fixed order (no atomics): the same frame gives the same bits.  workspace: gsr_camera_grad_workspace_size bytes (room for one
+ * 27-float partial sum per block of 256 Gaussians, padded to 256 bytes).  A frame with nothing rendered writes zeros.  Whole images only
+ * (tile_row_begin = tile_row_end = 0). */
+typedef struct gsr_camera_grads {
+    float *viewmatrix;     /* [16] */
+    float *projmatrix;     /* [16] */
+    float *campos;         /* [3]  */
+} gsr_camera_grads;        /* any may be NULL (not wanted) */
+int gsr_camera_grad_workspace_size(const gsr_frame_desc *desc, size_t *bytes);
+int gsr_backward_camera(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, const int32_t *radii,
+                        const void *geom_ws, const float *screen_grads, int32_t binned_ranks, const gsr_frame_plan *own_plan,
+                        int32_t depth_chain, void *workspace, const gsr_camera_grads *out, void *stream);
+
 /* Device pointers into a frame's geometry workspace (valid after gsr_forward_preprocess):
  *   depth_keys [P]  by Gaussian: the bits of its view depth (a positive binary32: ordered as an integer), 0xFFFFFFFF = not
  *                   visible.  Identical on every rank of a sharded render (visibility is that of the full image).

@@ -706,6 +706,41 @@ int gsr_backward_geom_aux(const gsr_frame_desc *desc, const gsr_camera *cam, con
     return backward_geom_impl(desc, cam, g, radii, geom_ws, screen_grads, g_begin, g_end, binned_ranks, own_plan, out, stream, true);
 }
 
+int gsr_camera_grad_workspace_size(const gsr_frame_desc *desc, size_t *bytes)
+{
+    int rc = validate(desc);
+    if (rc) return rc;
+    if (!bytes) { set_error("gsr_camera_grad_workspace_size: NULL out"); return GSR_ERR_INVALID_ARGUMENT; }
+    *bytes = camera_grad_workspace_bytes(desc->P);
+    return GSR_OK;
+}
+
+int gsr_backward_camera(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, const int32_t *radii,
+                        const void *geom_ws, const float *screen_grads, int32_t binned_ranks, const gsr_frame_plan *own_plan,
+                        int32_t depth_chain, void *workspace, const gsr_camera_grads *out, void *stream)
+{
+    int rc = validate(desc);
+    if (rc) return rc;
+    if (desc->tile_row_begin != 0 || desc->tile_row_end > 0) {
+        set_error("gsr_backward_camera: whole images only (tile_row_begin = tile_row_end = 0)");
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if ((rc = validate_inputs(desc, cam, g))) return rc;
+    if (!out || !workspace) { set_error("gsr_backward_camera: NULL grads / workspace"); return GSR_ERR_INVALID_ARGUMENT; }
+    if (desc->P > 0 && (!radii || !geom_ws || !screen_grads)) { set_error("gsr_backward_camera: NULL argument"); return GSR_ERR_INVALID_ARGUMENT; }
+    const FrameK f = make_frame(*desc);
+    GeomWS gw = carve_geom(const_cast<void *>(geom_ws), f.P);
+    // the rows gsr_backward_geom visits (backward_geom_impl above): its binned_ranks / own_plan decision, repeated
+    bool own_sparse = false;
+    if (own_plan && own_plan->num_rendered > 0 && own_plan->chunks_run > 0) {
+        binned_ranks = own_plan->chunk_rank_begin[own_plan->chunks_run];
+        own_sparse = effective_binned_ranks(*own_plan) * 4 < (long long)desc->P;
+    }
+    const bool sparse = f.P > 0 && geom_bwd_sparse(f, 0, f.P, binned_ranks, own_sparse);
+    return launch_camera_bwd(f, *cam, *g, radii, gw, screen_grads, binned_ranks, sparse, own_sparse, depth_chain != 0, (float *)workspace,
+                             *out, desc->debug != 0, (hipStream_t)stream);
+}
+
 int gsr_backward_geom_rows(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, const int32_t *radii,
                            const void *geom_ws, const float *screen_grads, const int32_t *rows, int32_t n_rows, const gsr_grads *out,
                            void *stream)

@@ -611,6 +611,172 @@ __global__ __launch_bounds__(kGeomBlock) void k_geom_bwd_depth(int g0, int n, in
     dmeans[3 * (size_t)i + 2] += dz * view[10];
 }
 
+// ---- camera gradients: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos = sums over Gaussians of camera_backward_one's
+// 27 terms.  Runs behind the geometry backward over the rows it visited (SPARSE: the ranks of the binned depth prefix through
+// order / cnt_open; otherwise [0, n)).  Every sum has an order the program fixes, so the result is bit-reproducible: the lanes of a
+// wave by DPP adds (each row of 16 lanes by a butterfly that leaves the row's sum in all of its lanes, then the four rows in
+// row order), the waves of a block through LDS in wave order, one 27-float partial per block (at most kCamMaxBlocks blocks, each
+// thread striding over the rows in increasing order); k_camera_reduce adds the partials in block order.  No global atomics.  Invisible, dead (all-zero row) and out-of-range lanes contribute exact zeros.
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v)
+{
+    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
+}
+
+__device__ __forceinline__ float wave_sum_fixed(float v)
+{
+    v = dpp_add<0xB1>(v);          // quad_perm:[1,0,3,2]
+    v = dpp_add<0x4E>(v);          // quad_perm:[2,3,0,1]
+    v = dpp_add<0x141>(v);         // row_half_mirror
+    v = dpp_add<0x140>(v);         // row_mirror: every lane of a row of 16 holds the row's sum
+    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
+    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
+    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
+    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
+    return ((r0 + r1) + r2) + r3;
+}
+
+constexpr int kCamMaxBlocks = 1024;    // four blocks per CU; k_camera_reduce then adds at most 32 partials per thread
+
+template <int DEG, int RAW, bool SPARSE>
+__global__ __launch_bounds__(kGeomBlock) void k_camera_bwd(FrameK f, int n, const uint32_t *__restrict__ order,
+                                                           const uint32_t *__restrict__ cnt_open, const float *__restrict__ view,
+                                                           const float *__restrict__ proj, const float *__restrict__ campos,
+                                                           const float *__restrict__ means, const float *__restrict__ scales,
+                                                           const float *__restrict__ rots, const float *__restrict__ covpre,
+                                                           const float *__restrict__ opac, const float *__restrict__ shs,
+                                                           const float *__restrict__ shs_rest, int has_colpre,
+                                                           const int32_t *__restrict__ radii, const uint8_t *__restrict__ clamped,
+                                                           const float4 *__restrict__ screen, int depth_chain,
+                                                           float *__restrict__ partials)
+{
+    __shared__ float wave_part[kGeomBlock / 64][kCamTerms];
+    float c[kCamTerms];
+#pragma unroll
+    for (int k = 0; k < kCamTerms; ++k) c[k] = 0.f;
+    // grid-stride: at most kCamMaxBlocks blocks (and partials); a thread adds its Gaussians' terms in increasing index order
+    for (int t = blockIdx.x * kGeomBlock + threadIdx.x; t < n; t += (int)gridDim.x * kGeomBlock) {
+        int i = t;
+        if constexpr (SPARSE) {
+            if (cnt_open && cnt_open[t] == 0u) continue;
+            i = (int)order[t];
+            if (i < 0 || i >= f.P) continue;
+        }
+        if (radii[i] <= 0) continue;                 // (an invisible Gaussian's screen row may be undefined)
+        const float4 s0 = screen[3 * (size_t)i], s1 = screen[3 * (size_t)i + 1], s2 = screen[3 * (size_t)i + 2];
+        const bool live = (s0.x != 0.f) | (s0.y != 0.f) | (s0.z != 0.f) | (s0.w != 0.f) | (s1.x != 0.f) | (s1.y != 0.f) |
+                          (s1.z != 0.f) | (s1.w != 0.f) | (s2.x != 0.f);
+        const float dz = depth_chain ? s2.y : 0.f;
+        if (live) {                                  // the geometry backward's own test: its rows and these sums stop together
+            float V[16], PV[16], cp[3];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) { V[k] = view[k]; PV[k] = proj[k]; }
+            cp[0] = campos[0]; cp[1] = campos[1]; cp[2] = campos[2];
+            GaussIn<DEG, RAW> in;
+            load_gaussian<DEG, RAW>(i, f.M, means, scales, rots, covpre, opac, shs, shs_rest, true, in);
+            const float sg[9] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w, s2.x};
+            unsigned clamp_bits = clamped[i];        // (recomputed for SH colours: see k_geom_bwd)
+            if (shs && !has_colpre) { float rgb_[3]; sh_color_one<DEG>(f, cp, in.p, in.sh(), rgb_, clamp_bits); }
+            camera_backward_one<DEG>(f, V, PV, cp, in.p, in.sc, in.q, (!RAW && covpre) ? in.cv : nullptr, in.sh(), has_colpre != 0,
+                                     clamp_bits, sg, c);
+        }
+        if (dz != 0.f) {                             // the depth map's chain (k_geom_bwd_depth's rows): z = sum_r ph_r V[4r+2]
+            c[2] += means[3 * i] * dz; c[5] += means[3 * i + 1] * dz; c[8] += means[3 * i + 2] * dz; c[11] += dz;
+        }
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < kCamTerms; ++k) {
+        const float s = wave_sum_fixed(c[k]);
+        if (lane == 0) wave_part[wv][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < kCamTerms) {
+        float s = wave_part[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < kGeomBlock / 64; ++w) s += wave_part[w][threadIdx.x];
+        partials[(size_t)blockIdx.x * kCamTerms + threadIdx.x] = s;
+    }
+}
+
+// Second launch: one block adds the per-block partials in block order.  The sums cancel (sum |t_i| / |sum t_i| of a few hundred
+// on deep frames), so they are accumulated in binary64, full rate on this part: thread (g, k) adds term k of the blocks
+// [g chunk, (g + 1) chunk) in order, then term k's kCamGroups group sums are added in group order.  Writes the three tensors, the
+// structural zeros (column 3 of dview, column 2 of dproj) included; any output may be NULL.  n_blocks == 0 writes zeros.
+constexpr int kCamReduceBlock = 1024, kCamGroups = kCamReduceBlock / 32;
+
+__global__ __launch_bounds__(kCamReduceBlock) void k_camera_reduce(int n_blocks, const float *__restrict__ partials,
+                                                                   float *__restrict__ dview, float *__restrict__ dproj,
+                                                                   float *__restrict__ dcampos)
+{
+    __shared__ double group_sum[kCamGroups][kCamTerms];
+    const int k = threadIdx.x & 31, g = threadIdx.x >> 5;
+    const int chunk = (n_blocks + kCamGroups - 1) / kCamGroups;
+    if (k < kCamTerms) {
+        double s = 0.0;
+        const int b1 = min(n_blocks, (g + 1) * chunk);
+        for (int b = g * chunk; b < b1; ++b) s += (double)partials[(size_t)b * kCamTerms + k];
+        group_sum[g][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < 35) {
+        const int e = threadIdx.x;                  // dview[16] | dproj[16] | dcampos[3]
+        int term = -1;
+        if (e < 16) { if ((e & 3) != 3) term = 3 * (e >> 2) + (e & 3); }
+        else if (e < 32) { const int col = e & 3; if (col != 2) term = 12 + 3 * ((e - 16) >> 2) + (col == 3 ? 2 : col); }
+        else term = 24 + (e - 32);
+        double s = 0.0;
+        if (term >= 0)
+            for (int gg = 0; gg < kCamGroups; ++gg) s += group_sum[gg][term];
+        const float v = (float)s;
+        if (e < 16) { if (dview) dview[e] = v; }
+        else if (e < 32) { if (dproj) dproj[e - 16] = v; }
+        else if (dcampos) dcampos[e - 32] = v;
+    }
+}
+
+size_t camera_grad_workspace_bytes(int P)
+{
+    const size_t blocks = ((size_t)(P > 0 ? P : 0) + kGeomBlock - 1) / kGeomBlock;
+    return align_up((blocks > 0 ? blocks : 1) * kCamTerms * sizeof(float));
+}
+
+int launch_camera_bwd(const FrameK &f, const gsr_camera &cam, const gsr_gaussians &g, const int32_t *radii, const GeomWS &gw,
+                      const float *screen_grads, int n_ranks, bool sparse, bool own_frame_sparse, bool depth_chain, float *partials,
+                      const gsr_camera_grads &out, bool debug, hipStream_t s)
+{
+    const int n = sparse ? (n_ranks > 0 ? n_ranks : 0) : f.P;
+    const int grid = min((n + kGeomBlock - 1) / kGeomBlock, kCamMaxBlocks);
+    if (grid > 0) {
+        ProfileScope prof("camera_bwd", s);
+        const uint32_t *cnt_open = own_frame_sparse ? gw.cnt_open : nullptr;
+#define GSR_CB(DEG, RAW)                                                                                                          \
+    do {                                                                                                                          \
+        if (sparse)                                                                                                               \
+            hipLaunchKernelGGL((k_camera_bwd<DEG, RAW, true>), dim3(grid), dim3(kGeomBlock), 0, s, f, n, gw.order, cnt_open,       \
+                               cam.viewmatrix, cam.projmatrix, cam.campos, g.means3D, g.scales, g.rotations, g.cov3D_precomp,     \
+                               g.opacities, g.shs, g.shs_rest, g.colors_precomp ? 1 : 0, radii, gw.clamped,                       \
+                               reinterpret_cast<const float4 *>(screen_grads), depth_chain ? 1 : 0, partials);                    \
+        else                                                                                                                      \
+            hipLaunchKernelGGL((k_camera_bwd<DEG, RAW, false>), dim3(grid), dim3(kGeomBlock), 0, s, f, n, nullptr, nullptr,        \
+                               cam.viewmatrix, cam.projmatrix, cam.campos, g.means3D, g.scales, g.rotations, g.cov3D_precomp,     \
+                               g.opacities, g.shs, g.shs_rest, g.colors_precomp ? 1 : 0, radii, gw.clamped,                       \
+                               reinterpret_cast<const float4 *>(screen_grads), depth_chain ? 1 : 0, partials);                    \
+    } while (0)
+        switch ((!g.raw ? 0 : (raw_split_sh(f, g) ? 1 : 2)) * 4 + (f.D > 3 ? 3 : (f.D < 0 ? 0 : f.D))) {
+            case 0: GSR_CB(0, 0); break;  case 1: GSR_CB(1, 0); break;  case 2: GSR_CB(2, 0); break;  case 3: GSR_CB(3, 0); break;
+            case 4: GSR_CB(0, 1); break;  case 5: GSR_CB(1, 1); break;  case 6: GSR_CB(2, 1); break;  case 7: GSR_CB(3, 1); break;
+            case 8: GSR_CB(0, 2); break;  case 9: GSR_CB(1, 2); break;  case 10: GSR_CB(2, 2); break; default: GSR_CB(3, 2); break;
+        }
+#undef GSR_CB
+        GSR_LAUNCH_CHECK("camera_bwd", debug, s);
+    }
+    ProfileScope prof("camera_reduce", s);
+    hipLaunchKernelGGL(k_camera_reduce, dim3(1), dim3(kCamReduceBlock), 0, s, grid, partials, out.viewmatrix, out.projmatrix, out.campos);
+    GSR_LAUNCH_CHECK("camera_reduce", debug, s);
+    return GSR_OK;
+}
+
 // ---- one launch that zero-fills up to nine output tensors (the sparse path's "memset"): the segments are laid end to
 // end in a virtual float index space; each thread clears a float4 where the 16 bytes lie inside one segment.
 __global__ __launch_bounds__(kGeomBlock) void k_zero_segments(ZeroSegs z)

@@ -299,6 +299,12 @@ inline bool geom_bwd_sparse(const FrameK &f, int g0, int g1, int n_ranks, bool o
 // dL/dz = screen_grads slot 9.  cnt_open: as launch_geom_bwd's own_frame_sparse (ranks that emitted nothing are skipped), else NULL.
 int launch_geom_bwd_depth(const FrameK &f, const gsr_camera &cam, const int32_t *radii, const float *screen_grads, int g0, int g1,
                           int n_ranks, const uint32_t *rows, const uint32_t *cnt_open, bool sparse, float *dmeans, bool debug, hipStream_t s);
+// Camera gradients behind launch_geom_bwd (same rows, same sparse choice): k_camera_bwd writes one kCamTerms-float partial per
+// block into `partials` (camera_grad_workspace_bytes(P) bytes), k_camera_reduce adds them in block order into `out`.
+size_t camera_grad_workspace_bytes(int P);
+int launch_camera_bwd(const FrameK &f, const gsr_camera &cam, const gsr_gaussians &g, const int32_t *radii, const GeomWS &gw,
+                      const float *screen_grads, int n_ranks, bool sparse, bool own_frame_sparse, bool depth_chain, float *partials,
+                      const gsr_camera_grads &out, bool debug, hipStream_t s);
 int launch_mark_visible(int P, const float *means3D, const float *view, uint8_t *present, hipStream_t s);
 
 }  // namespace gsr

@@ -452,6 +452,8 @@ struct GeomGrad {
 };
 
 // ---- A.10 for one visible Gaussian.  sg = (dmean2D.x, dmean2D.y, gA, gB, gC, dopacity, drgb[3]).
+// (camera_backward_one below repeats the conic -> cov2D -> T -> J -> p_view chain, the homogeneous divide and the SH direction
+// derivative of this function: a fix to one belongs in both.)
 // dsh (this Gaussian's [K,3] row, written when want_dsh) receives basis_k * dRGB for k < K; the caller zeroes
 // k >= K.  It may point anywhere (registers, an LDS staging row, the output tensor itself) but never depends on a
 // run-time select, so that a register array stays in registers.  clamped: bit c set <=> channel c was clamped.
@@ -573,6 +575,109 @@ GSR_HD void geom_backward_one(const FrameK &f, const float *V, const float *PV, 
         g.drot[1] = 2.f * (y * gR[1] + z * gR[2] + y * gR[3] - 2.f * x * gR[4] - r * gR[5] + z * gR[6] + r * gR[7] - 2.f * x * gR[8]);
         g.drot[2] = 2.f * (-2.f * y * gR[0] + x * gR[1] + r * gR[2] + x * gR[3] + z * gR[5] - r * gR[6] + z * gR[7] - 2.f * y * gR[8]);
         g.drot[3] = 2.f * (-2.f * z * gR[0] - r * gR[1] + x * gR[2] + r * gR[3] - 2.f * z * gR[4] + y * gR[5] + x * gR[6] + y * gR[7]);
+    }
+}
+
+// ---- camera gradients of one visible Gaussian: what A.10 computes on its way to dL/dmeans3D and drops,
+// turned into this Gaussian's contribution to dL/dviewmatrix, dL/dprojmatrix and dL/dcampos.  Row-vector convention of the header
+// (p_view_c = sum_r p_r V[4r+c] + V[12+c]); with ph = (p, 1):
+//   c[3r + k]       dL/dV[4r+k], k = 0..2:  ph_r (dtx, dty, dtz)_k  (p_view; dtx / dty carry xmul / ymul as for means3D)
+//                                           + for r < 3, through T = J R_w2c:  J00 dT0r | J11 dT1r | J02 dT0r + J12 dT1r
+//   c[12 + 3r + k]  dL/dPV[4r + (0, 1, 3)[k]]:  ph_r (mw sg0, mw sg1, -(mul1 sg0 + mul2 sg1))_k
+//   c[24 + k]       dL/dcampos_k = minus the SH view-direction term of dL/dmeans3D (zero with a precomputed colour)
+// Column 3 of V and column 2 of PV are never read by the forward: their gradients are exact zeros and have no slot here.
+// The 27 terms are ADDED to c (the caller zeroes it; a thread that visits several Gaussians keeps one set of accumulators).
+// The statements up to dtz, the homogeneous divide and the SH direction derivative are geom_backward_one's own, kept apart so that
+// its instantiations stay as they are: a change to either copy belongs in both (tests/test_camera_grad_ref.py holds this one to the
+// binary64 reference Gaussian by Gaussian on the host, tests/test_host_math.py the other).
+constexpr int kCamTerms = 27;
+
+template <int DEG = -1>
+GSR_HD void camera_backward_one(const FrameK &f, const float *V, const float *PV, const float *campos, const float p[3],
+                                const float *scale, const float *quat, const float *covpre, const float *sh, bool has_colpre,
+                                unsigned clamped, const float sg[9], float c[kCamTerms])
+{
+    float pv[3];
+    pv[0] = view_coord(p, V, 0);
+    pv[1] = view_coord(p, V, 1);
+    pv[2] = view_coord(p, V, 2);
+    float cov[6];
+    if (covpre) { for (int k = 0; k < 6; ++k) cov[k] = covpre[k]; }
+    else cov3d_from_scale_rot(scale, f.scale_modifier, quat, cov);
+    Ewa e;
+    ewa_project(pv, cov, V, f, e);
+
+    const float den = e.a * e.c - e.b * e.b;
+    const float k2 = 1.f / (den * den + (float)GSR_CONIC_BWD_EPS);
+    const float gA = sg[2], gB = sg[3], gC = sg[4];
+    const float dL_da = k2 * (-e.c * e.c * gA + 2.f * e.b * e.c * gB + (den - e.a * e.c) * gC);
+    const float dL_dc = k2 * (-e.a * e.a * gC + 2.f * e.a * e.b * gB + (den - e.a * e.c) * gA);
+    const float dL_db = k2 * 2.f * (e.b * e.c * gA - (den + 2.f * e.b * e.b) * gB + e.a * e.b * gC);
+    const float dT0[3] = {2.f * e.S0[0] * dL_da + e.S1[0] * dL_db, 2.f * e.S0[1] * dL_da + e.S1[1] * dL_db,
+                          2.f * e.S0[2] * dL_da + e.S1[2] * dL_db};
+    const float dT1[3] = {2.f * e.S1[0] * dL_dc + e.S0[0] * dL_db, 2.f * e.S1[1] * dL_dc + e.S0[1] * dL_db,
+                          2.f * e.S1[2] * dL_dc + e.S0[2] * dL_db};
+    const float dJ00 = V[0] * dT0[0] + V[4] * dT0[1] + V[8] * dT0[2];
+    const float dJ02 = V[2] * dT0[0] + V[6] * dT0[1] + V[10] * dT0[2];
+    const float dJ11 = V[1] * dT1[0] + V[5] * dT1[1] + V[9] * dT1[2];
+    const float dJ12 = V[2] * dT1[0] + V[6] * dT1[1] + V[10] * dT1[2];
+    const float tzi = 1.f / e.tz, tz2 = tzi * tzi, tz3 = tz2 * tzi;
+    const float dtx = e.xmul * -f.focal_x * tz2 * dJ02;
+    const float dty = e.ymul * -f.focal_y * tz2 * dJ12;
+    const float dtz = -f.focal_x * tz2 * dJ00 - f.focal_y * tz2 * dJ11 + (2.f * f.focal_x * e.tx) * tz3 * dJ02 +
+                      (2.f * f.focal_y * e.ty) * tz3 * dJ12;
+    const float J00 = f.focal_x / e.tz, J02 = -(f.focal_x * e.tx) / (e.tz * e.tz);
+    const float J11 = f.focal_y / e.tz, J12 = -(f.focal_y * e.ty) / (e.tz * e.tz);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int r = 0; r < 3; ++r) {
+        c[3 * r + 0] += p[r] * dtx + J00 * dT0[r];
+        c[3 * r + 1] += p[r] * dty + J11 * dT1[r];
+        c[3 * r + 2] += p[r] * dtz + (J02 * dT0[r] + J12 * dT1[r]);
+    }
+    c[9] += dtx; c[10] += dty; c[11] += dtz;
+
+    // projection path: ndc = (hx, hy) mw
+    const float hx = p[0] * PV[0] + p[1] * PV[4] + p[2] * PV[8] + PV[12];
+    const float hy = p[0] * PV[1] + p[1] * PV[5] + p[2] * PV[9] + PV[13];
+    const float hw = p[0] * PV[3] + p[1] * PV[7] + p[2] * PV[11] + PV[15];
+    const float mw = 1.f / (hw + (float)GSR_HOM_EPS);
+    const float mul1 = hx * mw * mw, mul2 = hy * mw * mw;
+    const float dh0 = mw * sg[0], dh1 = mw * sg[1], dh3 = -(mul1 * sg[0] + mul2 * sg[1]);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int r = 0; r < 3; ++r) { c[12 + 3 * r] += p[r] * dh0; c[13 + 3 * r] += p[r] * dh1; c[14 + 3 * r] += p[r] * dh3; }
+    c[21] += dh0; c[22] += dh1; c[23] += dh3;
+
+    // colour path: the view direction is (p - campos) / |p - campos|
+    if (!has_colpre) {
+        const float ox = p[0] - campos[0], oy = p[1] - campos[1], oz = p[2] - campos[2];
+        const float inv = 1.f / sqrtf(ox * ox + oy * oy + oz * oz);
+        const float dxn = ox * inv, dyn = oy * inv, dzn = oz * inv;
+        float bas[16], bx[16], by[16], bz[16];
+        const int D = DEG >= 0 ? DEG : f.D;
+        sh_basis<true>(D, dxn, dyn, dzn, bas, bx, by, bz);
+        const int K = (D + 1) * (D + 1);
+        float ddx = 0.f, ddy = 0.f, ddz = 0.f;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int ch = 0; ch < 3; ++ch) {
+            const float dRGB = ((clamped >> ch) & 1u) ? 0.f : sg[6 + ch];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+            for (int k = 0; k < K; ++k) {
+                const float w = sh[3 * k + ch] * dRGB;
+                ddx += bx[k] * w; ddy += by[k] * w; ddz += bz[k] * w;
+            }
+        }
+        const float dot = dxn * ddx + dyn * ddy + dzn * ddz;           // through normalize()
+        c[24] -= ((ddx - dxn * dot) * inv);
+        c[25] -= ((ddy - dyn * dot) * inv);
+        c[26] -= ((ddz - dzn * dot) * inv);
     }
 }
 

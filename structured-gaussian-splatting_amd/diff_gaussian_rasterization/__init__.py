@@ -14,6 +14,11 @@ the same blend: depth = sum_i w_i z_i (w_i = alpha_i T_i over the splats the col
 background term, not normalised: the mean depth is depth / alpha) and alpha = 1 - T_final.  Both are differentiable; a loss on
 them reaches means3D (through z too) and means2D - so the densification statistics, which read means2D.grad, see it as well.
 
+Extension: camera gradients.  When grad mode is on and raster_settings.viewmatrix, .projmatrix or .campos requires grad, backward()
+also returns dL/dviewmatrix, dL/dprojmatrix and dL/dcampos (camera_grads_wanted), each shaped like the tensor passed and in the
+row-vector convention it is consumed in; they are separate gradients, chained by the caller's own torch graph to its pose
+parametrisation (scene.cameras.camera_with_pose_delta is one).  Two more launches, sums in a fixed order; off: the plain call.
+
 Autograd contract (train.py:106, scene/gaussian_model.py:415-417): gradients for
 (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, None) in that order;
 `means2D.grad[:, :2]` is dL/d(NDC position) with the W/2, H/2 pixel scale folded in, `[:, 2] = 0`.
@@ -118,6 +123,24 @@ def caller_grad_enabled() -> bool:
     return torch.is_grad_enabled() if g is None else g
 
 
+def camera_grads_wanted(rs: GaussianRasterizationSettings, grad_enabled: Optional[bool] = None, tile_rows=None) -> bool:
+    """Does this call return gradients for the camera?  Exactly when grad mode is on (grad_enabled; None: the caller's own) and one
+    of rs.viewmatrix / rs.projmatrix / rs.campos requires grad - what autograd users expect of such a tensor; a caller who does
+    not want them detaches.  Whole images only: with tile_rows (a sharded slab) a wanted camera gradient raises ValueError."""
+    if grad_enabled is None:
+        grad_enabled = caller_grad_enabled()
+    on = bool(grad_enabled) and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (rs.viewmatrix, rs.projmatrix, rs.campos))
+    if on and tile_rows is not None:
+        raise ValueError("camera gradients are computed for whole images only: no tile_rows (sharded slabs) with a viewmatrix, "
+                         "projmatrix or campos that requires grad (detach them)")
+    return on
+
+
+def _camera_args(rs: GaussianRasterizationSettings):
+    """The three extra inputs of the autograd functions: (viewmatrix, projmatrix, campos) when camera gradients are wanted, else ()."""
+    return (rs.viewmatrix, rs.projmatrix, rs.campos) if camera_grads_wanted(rs, torch.is_grad_enabled()) else ()
+
+
 def _aux_outputs(fr: "_Frame", capacity: int):
     """gsr_aux_outputs of an aux frame, with a depth-checkpoint workspace for a binning workspace of `capacity` instances."""
     fr.aux_ws = _workspace(N.aux_workspace_size(fr.desc, capacity), fr.device)
@@ -136,6 +159,8 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
     backward's output tensors are then allocated up front, while the host waits for the plan anyway."""
     if aux and tile_rows is not None:
         raise ValueError("depth / alpha maps are rendered for whole images only: no tile_rows (sharded slabs) with aux=True")
+    if tile_rows is not None:
+        camera_grads_wanted(rs, tile_rows=tile_rows)          # raises when a slab is asked for camera gradients
     device = means3D.device
     if device.type != "cuda":
         raise RuntimeError("diff_gaussian_rasterization (MI355X build) needs tensors on a HIP device; "
@@ -354,6 +379,40 @@ def rasterize_backward_geom(fr: "_Frame", screen: torch.Tensor, needs, g0: int =
     return g_means3D, g_means2D, g_sh, g_col, g_op, g_sc, g_rot, g_cov
 
 
+def rasterize_backward_camera(fr: "_Frame", screen: torch.Tensor, needs=(True, True, True), depth_chain: bool = False):
+    """Camera gradients of this very frame, behind rasterize_backward_geom(fr, screen, ...) of the whole range: (dL/dviewmatrix [4,4],
+    dL/dprojmatrix [4,4], dL/dcampos [3]), None where `needs` says not wanted.  Two launches (per-block partial sums over the rows the
+    geometry backward visited, then their sum in block order): the same frame gives the same bits.
+    depth_chain: `screen` came from the aux backward: the depth map's chain through z is added to dL/dviewmatrix."""
+    dev, plan = fr.device, fr.plan
+    out = torch.empty(35, dtype=torch.float32, device=dev)
+    parts = (out[:16], out[16:32], out[32:35])
+    grads = N.CameraGrads(*(N._ptr(t) if n else None for t, n in zip(parts, needs)))
+    binned_ranks = int(plan.chunk_rank_begin[plan.chunks_run]) if plan.num_rendered > 0 and plan.chunks_run > 0 else 0
+    with torch.cuda.device(dev):
+        ws = _workspace(N.camera_grad_workspace_size(fr.desc), dev)
+        N.backward_camera(fr.desc, fr.cam, fr.gauss, fr.radii, fr.geom_ws, screen, ws, grads, dev, binned_ranks, own_plan=plan,
+                          depth_chain=depth_chain)
+    return tuple((t.view(4, 4) if t.numel() == 16 else t) if n else None for t, n in zip(parts, needs))
+
+
+def _camera_meta(ctx, cam, first):
+    """forward(): remember whether the three camera inputs were passed, which of them want a gradient, their shapes and dtypes."""
+    ctx.cam_needs = tuple(ctx.needs_input_grad[first:first + 3]) if cam[0] is not None else None
+    ctx.cam_meta = tuple((t.shape, t.dtype) for t in cam) if cam[0] is not None else None
+
+
+def _camera_backward(ctx, fr, screen, depth_chain):
+    """backward(): the camera inputs' gradients, each in its input's shape and dtype (a transposed / non-contiguous input: element
+    for element); () when the inputs were not passed."""
+    if ctx.cam_needs is None:
+        return ()
+    if not any(ctx.cam_needs):
+        return (None, None, None)
+    grads = rasterize_backward_camera(fr, screen, ctx.cam_needs, depth_chain)
+    return tuple(None if g is None else g.view(shape).to(dtype) for g, (shape, dtype) in zip(grads, ctx.cam_meta))
+
+
 def _dump(path, payload):
     try:
         torch.save(payload, path)
@@ -405,8 +464,11 @@ def _restash_frame(fr):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, aux=False):
+                raster_settings, aux=False, viewmatrix=None, projmatrix=None, campos=None):
+        # viewmatrix / projmatrix / campos: raster_settings' own tensors, passed as inputs only when camera gradients are wanted
+        # (camera_grads_wanted): the values are read from raster_settings either way
         rs = raster_settings
+        _camera_meta(ctx, (viewmatrix, projmatrix, campos), 10)
         args = (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
         if rs.debug:
             cpu_args = tuple(a.detach().cpu().clone() for a in args)      # README.md:147-150 semantics
@@ -439,7 +501,7 @@ class _RasterizeGaussians(torch.autograd.Function):
 
         def run():
             screen = rasterize_backward_screen(fr, grad_out_color, only_for_own_geom=True, grad_depth=grad_depth, grad_alpha=grad_alpha)
-            return rasterize_backward_geom(fr, screen, order, depth_chain=with_aux)
+            return rasterize_backward_geom(fr, screen, order, depth_chain=with_aux) + (_camera_backward(ctx, fr, screen, with_aux),)
         if rs.debug:
             try:
                 out = run()
@@ -451,13 +513,13 @@ class _RasterizeGaussians(torch.autograd.Function):
                 raise
         else:
             out = run()
-        g_means3D, g_means2D, g_sh, g_col, g_op, g_sc, g_rot, g_cov = out
+        g_means3D, g_means2D, g_sh, g_col, g_op, g_sc, g_rot, g_cov, g_cam = out
         if g_op is not None:
             g_op = g_op.view(ctx.shapes[1])
         if g_means2D is not None:
             g_means2D = g_means2D.view(ctx.shapes[0])
         _restash_frame(fr)
-        return g_means3D, g_means2D, g_sh, g_col, g_op, g_sc, g_rot, g_cov, None, None
+        return (g_means3D, g_means2D, g_sh, g_col, g_op, g_sc, g_rot, g_cov, None, None) + g_cam
 
 
 class _RasterizeGaussiansRaw(torch.autograd.Function):
@@ -466,8 +528,10 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
     the preprocess kernel, their chain rule inside the geometry backward: gradients arrive on the raw parameters."""
 
     @staticmethod
-    def forward(ctx, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations, raster_settings, aux=False):
+    def forward(ctx, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations, raster_settings, aux=False,
+                viewmatrix=None, projmatrix=None, campos=None):
         rs = raster_settings
+        _camera_meta(ctx, (viewmatrix, projmatrix, campos), 9)         # (as _RasterizeGaussians.forward)
         n = ctx.needs_input_grad       # xyz, means2D, f_dc, f_rest, opacity, scales, rotations
         needs = (n[0], n[1], n[2], False, n[4], n[5], n[6], False, n[3])
         # features_rest None: features_dc is the whole interleaved table [P,M,3] (scene.GaussianModel's packed leaf)
@@ -492,18 +556,19 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         with_aux = grad_depth is not None or grad_alpha is not None
         screen = rasterize_backward_screen(fr, grad_out_color, only_for_own_geom=True, grad_depth=grad_depth, grad_alpha=grad_alpha)
         g_xyz, g_means2D, g_dc, _, g_op, g_sc, g_rot, _, g_rest = rasterize_backward_geom(fr, screen, needs, depth_chain=with_aux)
+        g_cam = _camera_backward(ctx, fr, screen, with_aux)
         if g_op is not None:
             g_op = g_op.view(ctx.shapes[1])
         if g_means2D is not None:
             g_means2D = g_means2D.view(ctx.shapes[0])
         _restash_frame(fr)
-        return g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None, None
+        return (g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None, None) + g_cam
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, depth_alpha=False):
     return _apply(_RasterizeGaussians, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                  cov3Ds_precomp, raster_settings, bool(depth_alpha))
+                  cov3Ds_precomp, raster_settings, bool(depth_alpha), *_camera_args(raster_settings))
 
 
 # ---- opt-in: fuse the reference's getters without touching the caller -------------------------------------------
@@ -619,7 +684,7 @@ class GaussianRasterizer(nn.Module):
             leaves = _match_getters(means3D, opacities, shs, scales, rotations)
             if leaves is not None:
                 xyz, dc, rest, op, sc, rot = leaves
-                return _apply(_RasterizeGaussiansRaw, xyz, means2D, dc, rest, op, sc, rot, rs, self.depth_alpha)
+                return _apply(_RasterizeGaussiansRaw, xyz, means2D, dc, rest, op, sc, rot, rs, self.depth_alpha, *_camera_args(rs))
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, rs, self.depth_alpha)
 
@@ -634,4 +699,4 @@ class GaussianRasterizer(nn.Module):
         if not packed and (features_rest is None or features_rest.numel() == 0):
             features_rest = torch.empty(0, dtype=torch.float32, device=xyz.device)
         return _apply(_RasterizeGaussiansRaw, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations, rs,
-                      self.depth_alpha)
+                      self.depth_alpha, *_camera_args(rs))

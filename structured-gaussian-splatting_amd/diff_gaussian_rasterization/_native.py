@@ -48,6 +48,11 @@ class AuxOutputs(C.Structure):
     _fields_ = [("depth", _f32p), ("alpha", _f32p), ("ckpt_ws", C.c_void_p)]
 
 
+class CameraGrads(C.Structure):
+    """gsr_camera_grads: dL/dviewmatrix [16], dL/dprojmatrix [16], dL/dcampos [3]; any may be NULL."""
+    _fields_ = [("viewmatrix", _f32p), ("projmatrix", _f32p), ("campos", _f32p)]
+
+
 MAX_CHUNKS = 8
 LAST_SHIFT = 26
 
@@ -73,7 +78,8 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_workspace_sizes", "gsr_binning_
            "gsr_profile_read", "gsr_loss_workspace_size", "gsr_loss_l1_ssim_forward", "gsr_loss_l1_ssim_backward", "gsr_loss_l1_ssim_forward_rows", "gsr_loss_l1_ssim_backward_rows", "gsr_loss_l1_backward",
            "gsr_debug_sort_temp_bytes", "gsr_debug_sort_pairs", "gsr_debug_sort_pairs_ex", "gsr_dist2_workspace_size", "gsr_dist2_knn3", "gsr_adam_step", "gsr_adam_step_split", "gsr_adam_step_multi", "gsr_densify_stats",
            "gsr_activations_forward", "gsr_activations_backward",
-           "gsr_aux_workspace_size", "gsr_forward_aux", "gsr_forward_render_aux", "gsr_backward_render_aux", "gsr_backward_geom_aux")
+           "gsr_aux_workspace_size", "gsr_forward_aux", "gsr_forward_render_aux", "gsr_backward_render_aux", "gsr_backward_geom_aux",
+           "gsr_camera_grad_workspace_size", "gsr_backward_camera")
 
 _lib = None
 
@@ -241,6 +247,22 @@ def backward_geom(desc, cam: Camera, g: Gaussians, radii, geom_ws, screen_grads,
               _ptr(screen_grads), C.c_int32(g0), C.c_int32(g1), C.c_int32(binned_ranks),
               None if own_plan is None else C.byref(own_plan), C.byref(grads), _stream(device)),
            "gsr_backward_geom_aux" if depth_chain else "gsr_backward_geom")
+
+
+def camera_grad_workspace_size(desc: FrameDesc) -> int:
+    """gsr_camera_grad_workspace_size: bytes of the per-block partial sums of gsr_backward_camera."""
+    b = C.c_size_t(0)
+    _check(load().gsr_camera_grad_workspace_size(C.byref(desc), C.byref(b)), "gsr_camera_grad_workspace_size")
+    return b.value
+
+
+def backward_camera(desc, cam: Camera, g: Gaussians, radii, geom_ws, screen_grads, workspace, out: CameraGrads, device,
+                    binned_ranks: int = -1, own_plan: Optional[FramePlan] = None, depth_chain: bool = False):
+    """gsr_backward_camera, behind backward_geom of the same arguments (binned_ranks / own_plan / depth_chain as there)."""
+    _check(load().gsr_backward_camera(C.byref(desc), C.byref(cam), C.byref(g), _ptr(radii), _ptr(geom_ws), _ptr(screen_grads),
+                                      C.c_int32(binned_ranks), None if own_plan is None else C.byref(own_plan),
+                                      C.c_int32(int(bool(depth_chain))), _ptr(workspace), C.byref(out), _stream(device)),
+           "gsr_backward_camera")
 
 
 def effective_binned_ranks(plan: FramePlan) -> int:
