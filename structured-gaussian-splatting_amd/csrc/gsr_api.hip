@@ -262,7 +262,7 @@ static long long rows_bound(const gsr_frame_plan *plan)
 static size_t valid_bytes(const gsr_frame_plan *plan)
 {
     long long n = rows_bound(plan);
-    const long long cap = plan->binning_capacity > 0 ? plan->binning_capacity : plan->num_rendered;
+    const long long cap = plan_capacity(plan);
     if (n > cap) n = cap;
     return ((size_t)(n < 1 ? 1 : n) + 15) & ~(size_t)15;
 }
@@ -397,7 +397,7 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
     // binningBuffer).  A frame whose tiles saturate runs one small depth chunk and touches a few per cent of R, so
     // callers may size it for the first chunk only; a later chunk that does not fit stops the frame with
     // GSR_ERR_WORKSPACE before anything of that chunk is written (re-run this stage with a workspace for R instances).
-    const int64_t capacity = plan->binning_capacity > 0 ? plan->binning_capacity : plan->num_rendered;
+    const int64_t capacity = plan_capacity(plan);
     BinningWS bw = carve_binning(binning_ws, capacity, f);
     AuxWS ax = carve_aux(aux_out ? aux_out->ckpt_ws : nullptr, capacity, f);
     if (aux_out) { ax.depth = aux_out->depth; ax.alpha = aux_out->alpha; }
@@ -533,7 +533,7 @@ static int forward_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const
     fill.n = 0;
     bool filled = false;
     if (GSR_FILL_BEFORE_WAIT && fill_wanted && plan->num_chunks > 1 && (long long)plan->chunk_rank_begin[1] * 4 < (long long)desc->P) {
-        const long long cap = plan->binning_capacity > 0 ? plan->binning_capacity : plan->num_rendered;
+        const long long cap = plan_capacity(plan);
         const BinningWS bw = carve_binning(binning_ws, cap, f);
         fill = zero_segments(f, *g, nullptr, *early_fill, bw.row_valid, ((size_t)(cap < 1 ? 1 : cap) + 15) & ~(size_t)15);
     }
@@ -542,7 +542,7 @@ static int forward_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const
         return rc;
     if (fill_wanted && plan->chunks_run > 0 && effective_binned_ranks(*plan) * 4 < (long long)desc->P) {
         if (!filled) {
-            const BinningWS bw = carve_binning(binning_ws, plan->binning_capacity > 0 ? plan->binning_capacity : plan->num_rendered, f);
+            const BinningWS bw = carve_binning(binning_ws, plan_capacity(plan), f);
             ProfileScope prof("zero_outputs", (hipStream_t)stream);
             if ((rc = launch_zero_outputs(f, *g, nullptr, *early_fill, (hipStream_t)stream, bw.row_valid, valid_bytes(plan)))) return rc;
         }
@@ -629,14 +629,14 @@ static int backward_render_impl(const gsr_frame_desc *desc, const gsr_camera *ca
     if (f.P == 0) return GSR_OK;
     GeomWS gw = carve_geom(const_cast<void *>(geom_ws), f.P);
     ImageWS iw = carve_image(const_cast<void *>(image_ws), f);
-    BinningWS bw = carve_binning(binning_ws, plan->binning_capacity > 0 ? plan->binning_capacity : plan->num_rendered, f);
+    BinningWS bw = carve_binning(binning_ws, plan_capacity(plan), f);
     bw.grad_rows = (float *)rows_ws;
     long long rows_upper = 0;
     for (int c = 0; c < plan->chunks_run && c < GSR_MAX_CHUNKS; ++c) rows_upper += plan->chunk_instances_max[c];
     if (plan->num_rendered > 0) {
         if (!plan->tile_order_ready) GSR_HIP_CHECK(hipMemsetAsync(bw.row_valid, 0, valid_bytes(plan), s));
         const long long rows_n = plan->instances_emitted >= 0 ? (long long)plan->instances_emitted : rows_upper;
-        AuxWS ax = carve_aux(aux_out ? aux_out->ckpt_ws : nullptr, plan->binning_capacity > 0 ? plan->binning_capacity : plan->num_rendered, f);
+        AuxWS ax = carve_aux(aux_out ? aux_out->ckpt_ws : nullptr, plan_capacity(plan), f);
         if (aux_out) { ax.depth = aux_out->depth; ax.alpha = aux_out->alpha; }
         if ((rc = launch_render_bwd(f, plan->chunks_run, plan->sort_result, rows_n, gw, bw, iw, out_color, dL_dcolor, dbg, s,
                                     aux_out ? &ax : nullptr, dL_ddepth, dL_dalpha)))
@@ -677,19 +677,13 @@ static int backward_geom_impl(const gsr_frame_desc *desc, const gsr_camera *cam,
     if (!radii || !geom_ws || !screen_grads) { set_error("gsr_backward_geom: NULL argument"); return GSR_ERR_INVALID_ARGUMENT; }
     const FrameK f = make_frame(*desc);
     GeomWS gw = carve_geom(const_cast<void *>(geom_ws), f.P);
-    // own_plan: the gradients come from gsr_backward_render of THIS frame: the ranks of the chunks that ran, and among them only
-    // those that emitted an instance, can be non-zero; sparse (fill + visit those) unless unfiltered chunks hold P / 4 Gaussians or more
-    bool own_sparse = false;
-    if (own_plan && g_begin == 0 && g_end == desc->P && own_plan->num_rendered > 0 && own_plan->chunks_run > 0) {
-        binned_ranks = own_plan->chunk_rank_begin[own_plan->chunks_run];
-        own_sparse = effective_binned_ranks(*own_plan) * 4 < (long long)desc->P;
-    }
-    if ((rc = launch_geom_bwd(f, *cam, *g, radii, gw, screen_grads, g_begin, g_end, binned_ranks, *out, desc->debug != 0,
-                              (hipStream_t)stream, nullptr, own_sparse)))
+    const GeomRows rows = geom_rows(f, g_begin, g_end, binned_ranks, own_plan);
+    if ((rc = launch_geom_bwd(f, *cam, *g, radii, gw, screen_grads, g_begin, g_end, rows.n_ranks, *out, desc->debug != 0,
+                              (hipStream_t)stream, nullptr, rows.own_sparse)))
         return rc;
     if (!depth_chain) return GSR_OK;
-    return launch_geom_bwd_depth(f, *cam, radii, screen_grads, g_begin, g_end, binned_ranks, gw.order, own_sparse ? gw.cnt_open : nullptr,
-                                 geom_bwd_sparse(f, g_begin, g_end, binned_ranks, own_sparse), out->means3D, desc->debug != 0, (hipStream_t)stream);
+    return launch_geom_bwd_depth(f, *cam, radii, screen_grads, g_begin, g_end, rows.n_ranks, gw.order, rows.own_sparse ? gw.cnt_open : nullptr,
+                                 rows.sparse, out->means3D, desc->debug != 0, (hipStream_t)stream);
 }
 
 int gsr_backward_geom(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, const int32_t *radii,
@@ -730,15 +724,9 @@ int gsr_backward_camera(const gsr_frame_desc *desc, const gsr_camera *cam, const
     if (desc->P > 0 && (!radii || !geom_ws || !screen_grads)) { set_error("gsr_backward_camera: NULL argument"); return GSR_ERR_INVALID_ARGUMENT; }
     const FrameK f = make_frame(*desc);
     GeomWS gw = carve_geom(const_cast<void *>(geom_ws), f.P);
-    // the rows gsr_backward_geom visits (backward_geom_impl above): its binned_ranks / own_plan decision, repeated
-    bool own_sparse = false;
-    if (own_plan && own_plan->num_rendered > 0 && own_plan->chunks_run > 0) {
-        binned_ranks = own_plan->chunk_rank_begin[own_plan->chunks_run];
-        own_sparse = effective_binned_ranks(*own_plan) * 4 < (long long)desc->P;
-    }
-    const bool sparse = f.P > 0 && geom_bwd_sparse(f, 0, f.P, binned_ranks, own_sparse);
-    return launch_camera_bwd(f, *cam, *g, radii, gw, screen_grads, binned_ranks, sparse, own_sparse, depth_chain != 0, (float *)workspace,
-                             *out, desc->debug != 0, (hipStream_t)stream);
+    const GeomRows rows = geom_rows(f, 0, f.P, binned_ranks, own_plan);          // the rows gsr_backward_geom visits
+    return launch_camera_bwd(f, *cam, *g, radii, gw, screen_grads, rows.n_ranks, rows.sparse, rows.own_sparse, depth_chain != 0,
+                             (float *)workspace, *out, desc->debug != 0, (hipStream_t)stream);
 }
 
 int gsr_backward_geom_rows(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, const int32_t *radii,
@@ -887,7 +875,7 @@ int gsr_debug_get_views(const gsr_frame_desc *desc, const void *geom_ws, const v
         v->clamped = gw.clamped;
     }
     if (binning_ws) {
-        BinningWS bw = carve_binning(const_cast<void *>(binning_ws), plan->binning_capacity > 0 ? plan->binning_capacity : plan->num_rendered, f);
+        BinningWS bw = carve_binning(const_cast<void *>(binning_ws), plan_capacity(plan), f);
         v->sorted_gaussian = bw.gids[1];
         v->bwd_units = reinterpret_cast<const uint32_t *>(bw.units.units); v->bwd_unit_cap_full = bw.units.cap_full; v->bwd_unit_cap_part = bw.units.cap_part;
     }

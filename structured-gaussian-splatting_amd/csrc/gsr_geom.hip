@@ -5,6 +5,12 @@
 // K SH triples) and writes 48 (record) + 4 (radii) + 4 (tiles) + 1 (clamp mask); K8+K9 reads
 // 48 (screen grads) + 44 + 12K + 5 and writes 40 + 12M.  Camera matrices are wave-uniform loads that
 // the compiler scalarises (s_load) — they never cost vector memory bandwidth.
+//
+// The backward kernels (k_geom_bwd, k_geom_bwd_sparse, k_geom_bwd_depth, k_camera_bwd) share their row rule (visit_row), their
+// liveness test (load_screen_row), their inputs (load_backward_inputs) and their stores (store_geom_grad); every launch templated
+// on the SH degree and the raw mode goes through dispatch_deg_raw.
+#include <type_traits>
+
 #include "gsr_internal.h"
 
 namespace gsr {
@@ -23,6 +29,8 @@ struct GaussIn {
     RawAct act;
     // what preprocess_one / geom_backward_one read; no pointer member aliases shl, so the array stays in registers
     __device__ __forceinline__ const float *sh() const { if constexpr (RAW == 1) return shl; else return sh_global; }
+    // the precomputed covariance, when the frame has one (never in raw mode)
+    __device__ __forceinline__ const float *cov(const float *covpre) const { return (!RAW && covpre) ? cv : nullptr; }
 };
 
 template <int DEG, int RAW>
@@ -106,7 +114,7 @@ __global__ __launch_bounds__(kGeomBlock) void k_preprocess(FrameK f, const float
     // reads no coefficient at all (two thirds of its bytes at degree 3)
     load_gaussian<DEG, RAW>(i, f.M, means, scales, rots, covpre, opac, shs, shs_rest, near_ok && !LAZY, in);
     PreOut o;
-    preprocess_one<DEG>(f, V, PV, cp, in.p, in.sc, in.q, (!RAW && covpre) ? in.cv : nullptr, in.opacity, LAZY ? nullptr : in.sh(),
+    preprocess_one<DEG>(f, V, PV, cp, in.p, in.sc, in.q, in.cov(covpre), in.opacity, LAZY ? nullptr : in.sh(),
                         (!RAW && colpre) ? colpre + 3 * (size_t)i : nullptr, o);
     radii[i] = o.radius;
     // mass in fixed point: integer sums are order-independent
@@ -150,7 +158,27 @@ int launch_preprocess(const FrameK &f, const gsr_camera &cam, const gsr_gaussian
 }
 
 // raw mode with the reference's two SH tensors (features_dc + features_rest): raw == 1.  raw == 2: one interleaved [P,M,3] table
-static inline bool raw_split_sh(const FrameK &f, const gsr_gaussians &g) { (void)f; return g.raw == 1; }
+static inline bool raw_split_sh(const gsr_gaussians &g) { return g.raw == 1; }
+// the RAW template argument of the backward kernels: 0 activated input, 1 raw with split SH, 2 raw with one SH table
+static inline int raw_mode(const gsr_gaussians &g) { return !g.raw ? 0 : (raw_split_sh(g) ? 1 : 2); }
+
+// Calls fn(integral_constant<int, DEG>, integral_constant<int, RAW>) with DEG = D clamped to [0, 3] and RAW = mode < NRAW: the one
+// place where the run-time SH degree and raw mode pick a kernel instantiation.
+template <int NRAW, class F>
+static inline void dispatch_deg_raw(int D, int mode, F &&fn)
+{
+    auto with_deg = [&](auto deg) {
+        if (mode == 0) fn(deg, std::integral_constant<int, 0>{});
+        else if (NRAW == 2 || mode == 1) fn(deg, std::integral_constant<int, 1>{});
+        else if constexpr (NRAW > 2) fn(deg, std::integral_constant<int, 2>{});
+    };
+    switch (D > 3 ? 3 : (D < 0 ? 0 : D)) {
+        case 0: with_deg(std::integral_constant<int, 0>{}); break;
+        case 1: with_deg(std::integral_constant<int, 1>{}); break;
+        case 2: with_deg(std::integral_constant<int, 2>{}); break;
+        default: with_deg(std::integral_constant<int, 3>{}); break;
+    }
+}
 
 // ---- A.6, lazily: SH colour (+ clamp flags) of the Gaussians of depth ranks [r0, r1) — one binned chunk — patched into
 // their splat records right before the chunk is blended.  On a depth-complex frame that is a few thousand Gaussians
@@ -293,54 +321,103 @@ int launch_chunk_colors(const FrameK &f, const gsr_camera &cam, const gsr_gaussi
     if (r0 == 0 && r1 >= num_visible && (long long)num_visible * 2 >= (long long)f.P) {
         // the chunk is every visible Gaussian and most Gaussians are visible: walk the tensor in index order
         const int grid_all = (f.P + kGeomBlock - 1) / kGeomBlock;
-#define GSR_CA(DEG, RAW)                                                                                                \
-    hipLaunchKernelGGL((k_chunk_colors_all<DEG, RAW>), dim3(grid_all), dim3(kGeomBlock), 0, s, f, cam.campos, g.means3D, g.shs,  \
-                       g.shs_rest, ws.records, ws.clamped)
-        if (raw_split_sh(f, g)) {              // (no activations in this kernel: RAW only names the SH layout)
-            switch (f.D) {
-                case 0: GSR_CA(0, 1); break;
-                case 1: GSR_CA(1, 1); break;
-                case 2: GSR_CA(2, 1); break;
-                default: GSR_CA(3, 1); break;
-            }
-        } else {
-            switch (f.D) {
-                case 0: GSR_CA(0, 0); break;
-                case 1: GSR_CA(1, 0); break;
-                case 2: GSR_CA(2, 0); break;
-                default: GSR_CA(3, 0); break;
-            }
-        }
-#undef GSR_CA
+        // (no activations in these kernels: RAW only names the SH layout)
+        dispatch_deg_raw<2>(f.D, raw_split_sh(g) ? 1 : 0, [&](auto deg, auto raw) {
+            hipLaunchKernelGGL((k_chunk_colors_all<decltype(deg)::value, decltype(raw)::value>), dim3(grid_all), dim3(kGeomBlock), 0, s, f,
+                               cam.campos, g.means3D, g.shs, g.shs_rest, ws.records, ws.clamped);
+        });
         GSR_LAUNCH_CHECK("chunk_colors_all", debug, s);
         return GSR_OK;
     }
     const int grid = (r1 - r0 + kGeomBlock - 1) / kGeomBlock;
-#define GSR_CC(DEG, RAW)                                                                                             \
-    hipLaunchKernelGGL((k_chunk_colors<DEG, RAW>), dim3(grid), dim3(kGeomBlock), 0, s, f, r0, r1, ws.order, ws.cnt_open, cam.campos, \
-                       g.means3D, g.shs, g.shs_rest, ws.records, ws.clamped)
-    if (raw_split_sh(f, g)) {
-        switch (f.D) {
-            case 0: GSR_CC(0, 1); break;
-            case 1: GSR_CC(1, 1); break;
-            case 2: GSR_CC(2, 1); break;
-            default: GSR_CC(3, 1); break;
-        }
-    } else {
-        switch (f.D) {
-            case 0: GSR_CC(0, 0); break;
-            case 1: GSR_CC(1, 0); break;
-            case 2: GSR_CC(2, 0); break;
-            default: GSR_CC(3, 0); break;
-        }
-    }
-#undef GSR_CC
+    dispatch_deg_raw<2>(f.D, raw_split_sh(g) ? 1 : 0, [&](auto deg, auto raw) {
+        hipLaunchKernelGGL((k_chunk_colors<decltype(deg)::value, decltype(raw)::value>), dim3(grid), dim3(kGeomBlock), 0, s, f, r0, r1,
+                           ws.order, ws.cnt_open, cam.campos, g.means3D, g.shs, g.shs_rest, ws.records, ws.clamped);
+    });
     GSR_LAUNCH_CHECK("chunk_colors", debug, s);
     return GSR_OK;
 }
 
 // ---- K8 + K9: dL/d(screen-space quantities) -> dL/d(inputs) for Gaussians [g0, g1).
 __device__ __forceinline__ bool sh_wanted_or_read(const float *shs, int has_colpre) { return shs != nullptr && !has_colpre; }
+
+// The row rule: the Gaussian that thread t of a backward kernel visits, or -1.  Dense: g0 + t.  SPARSE: rank t of `order` (an
+// exchange list entry nobody filled is -1), skipped when this frame binned no instance of the rank (cnt_open, optional: its
+// screen-space row is zero or was never written).  Invisible Gaussians (their row may be undefined) are skipped.
+template <bool SPARSE>
+__device__ __forceinline__ int visit_row(int t, int g0, const uint32_t *__restrict__ order, const uint32_t *__restrict__ cnt_open, int P,
+                                         const int32_t *__restrict__ radii)
+{
+    int i = g0 + t;
+    if constexpr (SPARSE) {
+        if (cnt_open && cnt_open[t] == 0u) return -1;
+        i = (int)order[t];
+        if (i < 0 || i >= P) return -1;
+    }
+    return radii[i] > 0 ? i : -1;
+}
+
+// Reads Gaussian i's screen-space gradient row; returns whether it is live.  A Gaussian that no pixel accepted (occluded behind
+// saturated tiles, or just too faint everywhere) has an all-zero row; every output of A.10 and every camera term is linear in it,
+// so its results are exact zeros and none of its inputs need to be read.  In depth-complex scenes that is the vast majority of the
+// visible set.  The geometry and the camera kernels share this test: their rows and sums stop together.
+__device__ __forceinline__ bool load_screen_row(const float4 *__restrict__ screen, int i, float4 &s0, float4 &s1, float4 &s2)
+{
+    s0 = screen[3 * (size_t)i]; s1 = screen[3 * (size_t)i + 1]; s2 = screen[3 * (size_t)i + 2];
+    return (s0.x != 0.f) | (s0.y != 0.f) | (s0.z != 0.f) | (s0.w != 0.f) | (s1.x != 0.f) | (s1.y != 0.f) | (s1.z != 0.f) |
+           (s1.w != 0.f) | (s2.x != 0.f);
+}
+
+// What geom_backward_one / camera_backward_one read for one live Gaussian.  STAGED: the SH row is `staged_sh` (k_geom_bwd's LDS
+// row), a compile-time choice so that the RAW == 1 register array never meets a pointer select; otherwise it comes from global memory.
+// The clamp mask of an SH colour is recomputed from the coefficients (the forward's own function), not read: colours are evaluated
+// lazily, only for Gaussians some tile of THIS frame took, and a rank of a sharded render back-propagates Gaussians that only the
+// other ranks binned.
+template <int DEG, int RAW>
+struct BwdIn {
+    float V[16], PV[16], cp[3], sg[9];
+    GaussIn<DEG, RAW> in;
+    unsigned clamp_bits;
+};
+
+template <int DEG, int RAW, bool STAGED>
+__device__ __forceinline__ void load_backward_inputs(const FrameK &f, int i, const float *__restrict__ view, const float *__restrict__ proj,
+                                                     const float *__restrict__ campos, const float *__restrict__ means,
+                                                     const float *__restrict__ scales, const float *__restrict__ rots,
+                                                     const float *__restrict__ covpre, const float *__restrict__ opac,
+                                                     const float *__restrict__ shs, const float *__restrict__ shs_rest, int has_colpre,
+                                                     const uint8_t *__restrict__ clamped, const float4 &s0, const float4 &s1,
+                                                     const float4 &s2, const float *staged_sh, BwdIn<DEG, RAW> &b)
+{
+#pragma unroll
+    for (int k = 0; k < 16; ++k) { b.V[k] = view[k]; b.PV[k] = proj[k]; }
+    b.cp[0] = campos[0]; b.cp[1] = campos[1]; b.cp[2] = campos[2];
+    load_gaussian<DEG, RAW>(i, f.M, means, scales, rots, covpre, opac, STAGED ? nullptr : shs, STAGED ? nullptr : shs_rest, !STAGED, b.in);
+    b.sg[0] = s0.x; b.sg[1] = s0.y; b.sg[2] = s0.z; b.sg[3] = s0.w; b.sg[4] = s1.x; b.sg[5] = s1.y; b.sg[6] = s1.z; b.sg[7] = s1.w; b.sg[8] = s2.x;
+    b.clamp_bits = clamped[i];
+    if (shs && !has_colpre) {
+        float rgb_[3];
+        if constexpr (STAGED) sh_color_one<DEG>(f, b.cp, b.in.p, staged_sh, rgb_, b.clamp_bits);
+        else sh_color_one<DEG>(f, b.cp, b.in.p, b.in.sh(), rgb_, b.clamp_bits);
+    }
+}
+
+// Gaussian i's rows of every wanted parameter gradient except dL/dsh (and means2D's third column, which only the dense kernel writes).
+__device__ __forceinline__ void store_geom_grad(const gsr_grads &out, int i, const GeomGrad &g, int has_colpre, const float *covpre)
+{
+    if (out.means3D) { out.means3D[3 * i] = g.dmean[0]; out.means3D[3 * i + 1] = g.dmean[1]; out.means3D[3 * i + 2] = g.dmean[2]; }
+    if (out.means2D) { out.means2D[3 * i] = g.dmean2D[0]; out.means2D[3 * i + 1] = g.dmean2D[1]; }
+    if (out.opacities) out.opacities[i] = g.dopacity;
+    if (out.colors_precomp && has_colpre) {
+        out.colors_precomp[3 * i] = g.dcolor[0]; out.colors_precomp[3 * i + 1] = g.dcolor[1]; out.colors_precomp[3 * i + 2] = g.dcolor[2];
+    }
+    if (out.scales && !covpre) { out.scales[3 * i] = g.dscale[0]; out.scales[3 * i + 1] = g.dscale[1]; out.scales[3 * i + 2] = g.dscale[2]; }
+    if (out.rotations && !covpre) reinterpret_cast<float4 *>(out.rotations)[i] = make_float4(g.drot[0], g.drot[1], g.drot[2], g.drot[3]);
+    if (out.cov3D_precomp && covpre) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) out.cov3D_precomp[6 * (size_t)i + k] = g.dcov[k];
+    }
+}
 
 template <int DEG, int RAW>
 __global__ __launch_bounds__(kGeomBlock) void k_geom_bwd(FrameK f, int g0, int g1, const float *__restrict__ view,
@@ -356,15 +433,8 @@ __global__ __launch_bounds__(kGeomBlock) void k_geom_bwd(FrameK f, int g0, int g
     const int i = g0 + blockIdx.x * kGeomBlock + threadIdx.x;
     const bool in_range = i < g1;
     const int M = f.M;
-    const bool visible = in_range && radii[i] > 0;
-    GeomGrad g;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { g.dmean[k] = 0.f; g.dcolor[k] = 0.f; g.dscale[k] = 0.f; }
-    g.dmean2D[0] = g.dmean2D[1] = 0.f; g.dopacity = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) g.drot[k] = 0.f;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) g.dcov[k] = 0.f;
+    const bool visible = in_range && visit_row<false>(i - g0, g0, nullptr, nullptr, f.P, radii) >= 0;
+    GeomGrad g{};                                // zeros: the rows of dead and invisible Gaussians
     constexpr int K = (DEG + 1) * (DEG + 1);
     // dL/dsh leaves through LDS: every lane owns one staging row of 3M (+1 pad) floats; geom_backward_one writes the
     // 3K live entries straight into it, the rest is zero-filled, and the wave then stores its 64 rows as one
@@ -373,16 +443,8 @@ __global__ __launch_bounds__(kGeomBlock) void k_geom_bwd(FrameK f, int g0, int g
     const int rowf = 3 * M;                                       // floats per Gaussian incl. the DC triple
     float *my_row = sh_stage + wv * (64 * 49) + lane * (rowf + 1);
     const bool sh_wanted = shs && (out.shs || (RAW == 1 && out.shs_rest));
-    // A Gaussian that no pixel accepted (occluded behind saturated tiles, or just too faint everywhere) has an
-    // all-zero screen-space gradient; every output of A.10 is linear in it, so its rows are exact zeros and none
-    // of its inputs need to be read.  In depth-complex scenes that is the vast majority of the visible set.
-    bool live = visible;
     float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0, s2 = s0;
-    if (visible) {
-        s0 = screen[3 * (size_t)i]; s1 = screen[3 * (size_t)i + 1]; s2 = screen[3 * (size_t)i + 2];
-        live = (s0.x != 0.f) | (s0.y != 0.f) | (s0.z != 0.f) | (s0.w != 0.f) | (s1.x != 0.f) | (s1.y != 0.f) |
-               (s1.z != 0.f) | (s1.w != 0.f) | (s2.x != 0.f);
-    }
+    const bool live = visible && load_screen_row(screen, i, s0, s1, s2);       // a dead row's outputs are exact zeros
     // The wave's SH rows ([M,3] per Gaussian, consecutive Gaussians contiguous in memory) come in through the same LDS
     // staging rows the gradients leave by: 64 lanes x 16 B per load instruction instead of 64 single dwords 192 B apart (the
     // per-lane strided form re-fetches every 64-B sector sixteen times).  geom_backward_one reads coefficient k and then
@@ -448,36 +510,16 @@ __global__ __launch_bounds__(kGeomBlock) void k_geom_bwd(FrameK f, int g0, int g
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
     if (live) {
-        float V[16], PV[16], cp[3];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) { V[k] = view[k]; PV[k] = proj[k]; }
-        cp[0] = campos[0]; cp[1] = campos[1]; cp[2] = campos[2];
-        GaussIn<DEG, RAW> in;
-        load_gaussian<DEG, RAW>(i, M, means, scales, rots, covpre, opac, nullptr, nullptr, false, in);      // SH: from the LDS row
-        const float sg[9] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w, s2.x};
-        // The clamp mask of an SH colour is recomputed from the coefficients (the forward's own function), not read: colours are
-        // evaluated lazily, only for Gaussians some tile of THIS frame took, and a rank of a sharded render back-propagates
-        // Gaussians that only the other ranks binned.
-        unsigned clamp_bits = clamped[i];
-        if (shs && !has_colpre) { float rgb_[3]; sh_color_one<DEG>(f, cp, in.p, my_row, rgb_, clamp_bits); }
-        geom_backward_one<DEG>(f, V, PV, cp, in.p, in.sc, in.q, (!RAW && covpre) ? in.cv : nullptr, shs ? my_row : nullptr, has_colpre != 0,
-                               clamp_bits, sg, g, my_row, sh_wanted);
-        if constexpr (RAW) activate_raw_backward(in.act, g);
+        BwdIn<DEG, RAW> b;
+        load_backward_inputs<DEG, RAW, true>(f, i, view, proj, campos, means, scales, rots, covpre, opac, shs, shs_rest, has_colpre, clamped, s0,
+                                             s1, s2, my_row, b);
+        geom_backward_one<DEG>(f, b.V, b.PV, b.cp, b.in.p, b.in.sc, b.in.q, b.in.cov(covpre), shs ? my_row : nullptr, has_colpre != 0,
+                               b.clamp_bits, b.sg, g, my_row, sh_wanted);
+        if constexpr (RAW) activate_raw_backward(b.in.act, g);
     }
-    if (!in_range) { /* lanes past the end only help with the cooperative SH store below */ }
-    else {
-    if (out.means3D) { out.means3D[3 * i] = g.dmean[0]; out.means3D[3 * i + 1] = g.dmean[1]; out.means3D[3 * i + 2] = g.dmean[2]; }
-    if (out.means2D) { out.means2D[3 * i] = g.dmean2D[0]; out.means2D[3 * i + 1] = g.dmean2D[1]; out.means2D[3 * i + 2] = 0.f; }
-    if (out.opacities) out.opacities[i] = g.dopacity;
-    if (out.colors_precomp && has_colpre) {
-        out.colors_precomp[3 * i] = g.dcolor[0]; out.colors_precomp[3 * i + 1] = g.dcolor[1]; out.colors_precomp[3 * i + 2] = g.dcolor[2];
-    }
-    if (out.scales && !covpre) { out.scales[3 * i] = g.dscale[0]; out.scales[3 * i + 1] = g.dscale[1]; out.scales[3 * i + 2] = g.dscale[2]; }
-    if (out.rotations && !covpre) reinterpret_cast<float4 *>(out.rotations)[i] = make_float4(g.drot[0], g.drot[1], g.drot[2], g.drot[3]);
-    if (out.cov3D_precomp && covpre) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) out.cov3D_precomp[6 * (size_t)i + k] = g.dcov[k];
-    }
+    if (in_range) {                              // (lanes past the end only help with the cooperative SH store below)
+        store_geom_grad(out, i, g, has_colpre, covpre);
+        if (out.means2D) out.means2D[3 * i + 2] = 0.f;
     }
     if (sh_wanted && rowf > 0) {
         const bool any_live = wave_live;
@@ -535,41 +577,20 @@ __global__ __launch_bounds__(kGeomBlock) void k_geom_bwd_sparse(FrameK f, int n_
 {
     const int r = blockIdx.x * kGeomBlock + threadIdx.x;
     if (r >= n_ranks) return;
-    if (cnt_open && cnt_open[r] == 0u) return;   // this frame binned no instance of the rank: its screen-space row is zero (or was never written)
-    const int i = (int)order[r];
-    if (i < 0 || i >= f.P) return;               // (an exchange list entry nobody filled: -1)
-    if (radii[i] <= 0) return;
-    const float4 s0 = screen[3 * (size_t)i], s1 = screen[3 * (size_t)i + 1], s2 = screen[3 * (size_t)i + 2];
-    const bool live = (s0.x != 0.f) | (s0.y != 0.f) | (s0.z != 0.f) | (s0.w != 0.f) | (s1.x != 0.f) | (s1.y != 0.f) |
-                      (s1.z != 0.f) | (s1.w != 0.f) | (s2.x != 0.f);
-    if (!live) return;
+    const int i = visit_row<true>(r, 0, order, cnt_open, f.P, radii);
+    if (i < 0) return;
+    float4 s0, s1, s2;
+    if (!load_screen_row(screen, i, s0, s1, s2)) return;
     const int M = f.M;
-    float V[16], PV[16], cp[3];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { V[k] = view[k]; PV[k] = proj[k]; }
-    cp[0] = campos[0]; cp[1] = campos[1]; cp[2] = campos[2];
-    GaussIn<DEG, RAW> in;
-    load_gaussian<DEG, RAW>(i, M, means, scales, rots, covpre, opac, shs, shs_rest, true, in);
-    const float sg[9] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w, s2.x};
+    BwdIn<DEG, RAW> b;
+    load_backward_inputs<DEG, RAW, false>(f, i, view, proj, campos, means, scales, rots, covpre, opac, shs, shs_rest, has_colpre, clamped, s0,
+                                          s1, s2, nullptr, b);
     GeomGrad g;
     float dsh[3 * (DEG + 1) * (DEG + 1)];          // constant indices only: stays in registers
-    unsigned clamp_bits = clamped[i];               // (recomputed for SH colours: see k_geom_bwd)
-    if (shs && !has_colpre) { float rgb_[3]; sh_color_one<DEG>(f, cp, in.p, in.sh(), rgb_, clamp_bits); }
-    geom_backward_one<DEG>(f, V, PV, cp, in.p, in.sc, in.q, (!RAW && covpre) ? in.cv : nullptr, in.sh(), has_colpre != 0, clamp_bits,
-                           sg, g, dsh, shs != nullptr);
-    if constexpr (RAW) activate_raw_backward(in.act, g);
-    if (out.means3D) { out.means3D[3 * i] = g.dmean[0]; out.means3D[3 * i + 1] = g.dmean[1]; out.means3D[3 * i + 2] = g.dmean[2]; }
-    if (out.means2D) { out.means2D[3 * i] = g.dmean2D[0]; out.means2D[3 * i + 1] = g.dmean2D[1]; }
-    if (out.opacities) out.opacities[i] = g.dopacity;
-    if (out.colors_precomp && has_colpre) {
-        out.colors_precomp[3 * i] = g.dcolor[0]; out.colors_precomp[3 * i + 1] = g.dcolor[1]; out.colors_precomp[3 * i + 2] = g.dcolor[2];
-    }
-    if (out.scales && !covpre) { out.scales[3 * i] = g.dscale[0]; out.scales[3 * i + 1] = g.dscale[1]; out.scales[3 * i + 2] = g.dscale[2]; }
-    if (out.rotations && !covpre) reinterpret_cast<float4 *>(out.rotations)[i] = make_float4(g.drot[0], g.drot[1], g.drot[2], g.drot[3]);
-    if (out.cov3D_precomp && covpre) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) out.cov3D_precomp[6 * (size_t)i + k] = g.dcov[k];
-    }
+    geom_backward_one<DEG>(f, b.V, b.PV, b.cp, b.in.p, b.in.sc, b.in.q, b.in.cov(covpre), b.in.sh(), has_colpre != 0, b.clamp_bits,
+                           b.sg, g, dsh, shs != nullptr);
+    if constexpr (RAW) activate_raw_backward(b.in.act, g);
+    store_geom_grad(out, i, g, has_colpre, covpre);
     constexpr int K3 = 3 * (DEG + 1) * (DEG + 1);
     if constexpr (RAW == 1) {
         if (out.shs) { out.shs[3 * (size_t)i] = dsh[0]; out.shs[3 * (size_t)i + 1] = dsh[1]; out.shs[3 * (size_t)i + 2] = dsh[2]; }
@@ -597,13 +618,8 @@ __global__ __launch_bounds__(kGeomBlock) void k_geom_bwd_depth(int g0, int n, in
 {
     const int t = blockIdx.x * kGeomBlock + threadIdx.x;
     if (t >= n) return;
-    int i = g0 + t;
-    if constexpr (SPARSE) {
-        if (cnt_open && cnt_open[t] == 0u) return;
-        i = (int)order[t];
-        if (i < 0 || i >= P) return;
-    }
-    if (radii[i] <= 0) return;                       // (an invisible Gaussian's screen row may be undefined)
+    const int i = visit_row<SPARSE>(t, g0, order, cnt_open, P, radii);
+    if (i < 0) return;
     const float dz = screen[3 * (size_t)i + 2].y;
     if (dz == 0.f) return;
     dmeans[3 * (size_t)i] += dz * view[2];
@@ -656,29 +672,17 @@ __global__ __launch_bounds__(kGeomBlock) void k_camera_bwd(FrameK f, int n, cons
     for (int k = 0; k < kCamTerms; ++k) c[k] = 0.f;
     // grid-stride: at most kCamMaxBlocks blocks (and partials); a thread adds its Gaussians' terms in increasing index order
     for (int t = blockIdx.x * kGeomBlock + threadIdx.x; t < n; t += (int)gridDim.x * kGeomBlock) {
-        int i = t;
-        if constexpr (SPARSE) {
-            if (cnt_open && cnt_open[t] == 0u) continue;
-            i = (int)order[t];
-            if (i < 0 || i >= f.P) continue;
-        }
-        if (radii[i] <= 0) continue;                 // (an invisible Gaussian's screen row may be undefined)
-        const float4 s0 = screen[3 * (size_t)i], s1 = screen[3 * (size_t)i + 1], s2 = screen[3 * (size_t)i + 2];
-        const bool live = (s0.x != 0.f) | (s0.y != 0.f) | (s0.z != 0.f) | (s0.w != 0.f) | (s1.x != 0.f) | (s1.y != 0.f) |
-                          (s1.z != 0.f) | (s1.w != 0.f) | (s2.x != 0.f);
+        const int i = visit_row<SPARSE>(t, 0, order, cnt_open, f.P, radii);
+        if (i < 0) continue;
+        float4 s0, s1, s2;
+        const bool live = load_screen_row(screen, i, s0, s1, s2);
         const float dz = depth_chain ? s2.y : 0.f;
-        if (live) {                                  // the geometry backward's own test: its rows and these sums stop together
-            float V[16], PV[16], cp[3];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) { V[k] = view[k]; PV[k] = proj[k]; }
-            cp[0] = campos[0]; cp[1] = campos[1]; cp[2] = campos[2];
-            GaussIn<DEG, RAW> in;
-            load_gaussian<DEG, RAW>(i, f.M, means, scales, rots, covpre, opac, shs, shs_rest, true, in);
-            const float sg[9] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w, s2.x};
-            unsigned clamp_bits = clamped[i];        // (recomputed for SH colours: see k_geom_bwd)
-            if (shs && !has_colpre) { float rgb_[3]; sh_color_one<DEG>(f, cp, in.p, in.sh(), rgb_, clamp_bits); }
-            camera_backward_one<DEG>(f, V, PV, cp, in.p, in.sc, in.q, (!RAW && covpre) ? in.cv : nullptr, in.sh(), has_colpre != 0,
-                                     clamp_bits, sg, c);
+        if (live) {
+            BwdIn<DEG, RAW> b;
+            load_backward_inputs<DEG, RAW, false>(f, i, view, proj, campos, means, scales, rots, covpre, opac, shs, shs_rest, has_colpre,
+                                                  clamped, s0, s1, s2, nullptr, b);
+            camera_backward_one<DEG>(f, b.V, b.PV, b.cp, b.in.p, b.in.sc, b.in.q, b.in.cov(covpre), b.in.sh(), has_colpre != 0, b.clamp_bits,
+                                     b.sg, c);
         }
         if (dz != 0.f) {                             // the depth map's chain (k_geom_bwd_depth's rows): z = sum_r ph_r V[4r+2]
             c[2] += means[3 * i] * dz; c[5] += means[3 * i + 1] * dz; c[8] += means[3 * i + 2] * dz; c[11] += dz;
@@ -749,26 +753,15 @@ int launch_camera_bwd(const FrameK &f, const gsr_camera &cam, const gsr_gaussian
     const int grid = min((n + kGeomBlock - 1) / kGeomBlock, kCamMaxBlocks);
     if (grid > 0) {
         ProfileScope prof("camera_bwd", s);
-        const uint32_t *cnt_open = own_frame_sparse ? gw.cnt_open : nullptr;
-#define GSR_CB(DEG, RAW)                                                                                                          \
-    do {                                                                                                                          \
-        if (sparse)                                                                                                               \
-            hipLaunchKernelGGL((k_camera_bwd<DEG, RAW, true>), dim3(grid), dim3(kGeomBlock), 0, s, f, n, gw.order, cnt_open,       \
-                               cam.viewmatrix, cam.projmatrix, cam.campos, g.means3D, g.scales, g.rotations, g.cov3D_precomp,     \
-                               g.opacities, g.shs, g.shs_rest, g.colors_precomp ? 1 : 0, radii, gw.clamped,                       \
-                               reinterpret_cast<const float4 *>(screen_grads), depth_chain ? 1 : 0, partials);                    \
-        else                                                                                                                      \
-            hipLaunchKernelGGL((k_camera_bwd<DEG, RAW, false>), dim3(grid), dim3(kGeomBlock), 0, s, f, n, nullptr, nullptr,        \
-                               cam.viewmatrix, cam.projmatrix, cam.campos, g.means3D, g.scales, g.rotations, g.cov3D_precomp,     \
-                               g.opacities, g.shs, g.shs_rest, g.colors_precomp ? 1 : 0, radii, gw.clamped,                       \
-                               reinterpret_cast<const float4 *>(screen_grads), depth_chain ? 1 : 0, partials);                    \
-    } while (0)
-        switch ((!g.raw ? 0 : (raw_split_sh(f, g) ? 1 : 2)) * 4 + (f.D > 3 ? 3 : (f.D < 0 ? 0 : f.D))) {
-            case 0: GSR_CB(0, 0); break;  case 1: GSR_CB(1, 0); break;  case 2: GSR_CB(2, 0); break;  case 3: GSR_CB(3, 0); break;
-            case 4: GSR_CB(0, 1); break;  case 5: GSR_CB(1, 1); break;  case 6: GSR_CB(2, 1); break;  case 7: GSR_CB(3, 1); break;
-            case 8: GSR_CB(0, 2); break;  case 9: GSR_CB(1, 2); break;  case 10: GSR_CB(2, 2); break; default: GSR_CB(3, 2); break;
-        }
-#undef GSR_CB
+        const uint32_t *cnt_open = sparse && own_frame_sparse ? gw.cnt_open : nullptr;
+        dispatch_deg_raw<3>(f.D, raw_mode(g), [&](auto deg, auto raw) {
+            auto *kernel = sparse ? k_camera_bwd<decltype(deg)::value, decltype(raw)::value, true>
+                                  : k_camera_bwd<decltype(deg)::value, decltype(raw)::value, false>;
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kGeomBlock), 0, s, f, n, sparse ? gw.order : nullptr, cnt_open, cam.viewmatrix,
+                               cam.projmatrix, cam.campos, g.means3D, g.scales, g.rotations, g.cov3D_precomp, g.opacities, g.shs,
+                               g.shs_rest, g.colors_precomp ? 1 : 0, radii, gw.clamped, reinterpret_cast<const float4 *>(screen_grads),
+                               depth_chain ? 1 : 0, partials);
+        });
         GSR_LAUNCH_CHECK("camera_bwd", debug, s);
     }
     ProfileScope prof("camera_reduce", s);
@@ -811,7 +804,7 @@ ZeroSegs zero_segments(const FrameK &f, const gsr_gaussians &g, float *screen, c
     if (g.colors_precomp) add(out.colors_precomp, P * 3);
     if (!g.cov3D_precomp) { add(out.scales, P * 3); add(out.rotations, P * 4); }
     if (g.cov3D_precomp) add(out.cov3D_precomp, P * 6);
-    const bool split = raw_split_sh(f, g);
+    const bool split = raw_split_sh(g);
     if (g.shs) add(out.shs, P * 3 * (size_t)(split ? 1 : f.M));
     if (split && f.M > 1) add(out.shs_rest, P * 3 * (size_t)(f.M - 1));
     if (row_valid && valid_bytes) add(reinterpret_cast<float *>(row_valid), (valid_bytes + 3) / 4);     // (a 256-byte aligned, padded block)
@@ -845,11 +838,8 @@ int launch_geom_bwd_depth(const FrameK &f, const gsr_camera &cam, const int32_t 
     ProfileScope prof("geom_bwd_depth", s);
     const dim3 grid((unsigned)((n + kGeomBlock - 1) / kGeomBlock));
     const float4 *screen = reinterpret_cast<const float4 *>(screen_grads);
-    if (sparse)
-        hipLaunchKernelGGL(k_geom_bwd_depth<true>, grid, dim3(kGeomBlock), 0, s, 0, n, f.P, rows, cnt_open, cam.viewmatrix, radii, screen, dmeans);
-    else
-        hipLaunchKernelGGL(k_geom_bwd_depth<false>, grid, dim3(kGeomBlock), 0, s, g0, n, f.P, nullptr, nullptr, cam.viewmatrix, radii, screen,
-                           dmeans);
+    hipLaunchKernelGGL(sparse ? k_geom_bwd_depth<true> : k_geom_bwd_depth<false>, grid, dim3(kGeomBlock), 0, s, sparse ? 0 : g0, n, f.P,
+                       sparse ? rows : nullptr, sparse ? cnt_open : nullptr, cam.viewmatrix, radii, screen, dmeans);
     GSR_LAUNCH_CHECK("geom_bwd_depth", debug, s);
     return GSR_OK;
 }
@@ -867,33 +857,24 @@ int launch_geom_bwd(const FrameK &f, const gsr_camera &cam, const gsr_gaussians 
         if (!out.prezeroed && (rc0 = launch_zero_outputs(f, g, nullptr, out, s))) return rc0;
         if (n_ranks > 0) {
             const int sgrid = (n_ranks + kGeomBlock - 1) / kGeomBlock;
-#define GSR_GS(DEG, RAW)                                                                                                     \
-    hipLaunchKernelGGL((k_geom_bwd_sparse<DEG, RAW>), dim3(sgrid), dim3(kGeomBlock), 0, s, f, n_ranks, rows, cam.viewmatrix, \
-                       cam.projmatrix, cam.campos, g.means3D, g.scales, g.rotations, g.cov3D_precomp, g.opacities, g.shs,      \
-                       g.shs_rest, g.colors_precomp ? 1 : 0, radii, gw.clamped, reinterpret_cast<const float4 *>(screen_grads),   \
-                       out, own_frame_sparse ? gw.cnt_open : nullptr)
-            switch ((!g.raw ? 0 : (raw_split_sh(f, g) ? 1 : 2)) * 4 + (f.D > 3 ? 3 : (f.D < 0 ? 0 : f.D))) {
-                case 0: GSR_GS(0, 0); break;  case 1: GSR_GS(1, 0); break;  case 2: GSR_GS(2, 0); break;  case 3: GSR_GS(3, 0); break;
-                case 4: GSR_GS(0, 1); break;  case 5: GSR_GS(1, 1); break;  case 6: GSR_GS(2, 1); break;  case 7: GSR_GS(3, 1); break;
-                case 8: GSR_GS(0, 2); break;  case 9: GSR_GS(1, 2); break;  case 10: GSR_GS(2, 2); break; default: GSR_GS(3, 2); break;
-            }
-#undef GSR_GS
+            dispatch_deg_raw<3>(f.D, raw_mode(g), [&](auto deg, auto raw) {
+                hipLaunchKernelGGL((k_geom_bwd_sparse<decltype(deg)::value, decltype(raw)::value>), dim3(sgrid), dim3(kGeomBlock), 0, s, f,
+                                   n_ranks, rows, cam.viewmatrix, cam.projmatrix, cam.campos, g.means3D, g.scales, g.rotations,
+                                   g.cov3D_precomp, g.opacities, g.shs, g.shs_rest, g.colors_precomp ? 1 : 0, radii, gw.clamped,
+                                   reinterpret_cast<const float4 *>(screen_grads), out, own_frame_sparse ? gw.cnt_open : nullptr);
+            });
         }
         GSR_LAUNCH_CHECK("geom_bwd_sparse", debug, s);
         return GSR_OK;
     }
     const int grid = (g1 - g0 + kGeomBlock - 1) / kGeomBlock;
     ProfileScope prof("geom_bwd", s);
-#define GSR_GB(DEG, RAW)                                                                                                  \
-    hipLaunchKernelGGL((k_geom_bwd<DEG, RAW>), dim3(grid), dim3(kGeomBlock), 0, s, f, g0, g1, cam.viewmatrix, cam.projmatrix, \
-                       cam.campos, g.means3D, g.scales, g.rotations, g.cov3D_precomp, g.opacities, g.shs, g.shs_rest,         \
-                       g.colors_precomp ? 1 : 0, radii, gw.clamped, reinterpret_cast<const float4 *>(screen_grads), out)
-    switch ((!g.raw ? 0 : (raw_split_sh(f, g) ? 1 : 2)) * 4 + (f.D > 3 ? 3 : (f.D < 0 ? 0 : f.D))) {
-        case 0: GSR_GB(0, 0); break;  case 1: GSR_GB(1, 0); break;  case 2: GSR_GB(2, 0); break;  case 3: GSR_GB(3, 0); break;
-        case 4: GSR_GB(0, 1); break;  case 5: GSR_GB(1, 1); break;  case 6: GSR_GB(2, 1); break;  case 7: GSR_GB(3, 1); break;
-        case 8: GSR_GB(0, 2); break;  case 9: GSR_GB(1, 2); break;  case 10: GSR_GB(2, 2); break; default: GSR_GB(3, 2); break;
-    }
-#undef GSR_GB
+    dispatch_deg_raw<3>(f.D, raw_mode(g), [&](auto deg, auto raw) {
+        hipLaunchKernelGGL((k_geom_bwd<decltype(deg)::value, decltype(raw)::value>), dim3(grid), dim3(kGeomBlock), 0, s, f, g0, g1,
+                           cam.viewmatrix, cam.projmatrix, cam.campos, g.means3D, g.scales, g.rotations, g.cov3D_precomp, g.opacities,
+                           g.shs, g.shs_rest, g.colors_precomp ? 1 : 0, radii, gw.clamped, reinterpret_cast<const float4 *>(screen_grads),
+                           out);
+    });
     GSR_LAUNCH_CHECK("geom_bwd", debug, s);
     return GSR_OK;
 }

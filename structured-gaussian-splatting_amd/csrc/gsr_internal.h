@@ -295,6 +295,22 @@ inline bool geom_bwd_sparse(const FrameK &f, int g0, int g1, int n_ranks, bool o
 {
     return n_ranks >= 0 && g0 == 0 && g1 == f.P && (own_frame_sparse || (long long)n_ranks * 4 < (long long)f.P);
 }
+// The rows gsr_backward_geom(_aux) and gsr_backward_camera visit.  own_plan (honoured for the whole range [0, P) only): the gradients
+// come from gsr_backward_render of THIS frame: the ranks of the chunks that ran, and among them only those that emitted an instance,
+// can be non-zero; sparse (fill + visit those) unless unfiltered chunks hold P / 4 Gaussians or more.
+struct GeomRows { int n_ranks; bool own_sparse, sparse; };      // launch_geom_bwd's n_ranks and own_frame_sparse; geom_bwd_sparse of them
+inline GeomRows geom_rows(const FrameK &f, int g_begin, int g_end, int binned_ranks, const gsr_frame_plan *own_plan)
+{
+    GeomRows r{binned_ranks, false, false};
+    if (own_plan && g_begin == 0 && g_end == f.P && own_plan->num_rendered > 0 && own_plan->chunks_run > 0) {
+        r.n_ranks = own_plan->chunk_rank_begin[own_plan->chunks_run];
+        r.own_sparse = effective_binned_ranks(*own_plan) * 4 < (long long)f.P;
+    }
+    r.sparse = g_end > g_begin && geom_bwd_sparse(f, g_begin, g_end, r.n_ranks, r.own_sparse);
+    return r;
+}
+// instances the frame's binning workspace holds
+inline long long plan_capacity(const gsr_frame_plan *plan) { return plan->binning_capacity > 0 ? plan->binning_capacity : plan->num_rendered; }
 // The aux backward's z chain behind launch_geom_bwd (same rows, same sparse choice): dmeans3D += dL/dz (view[2], view[6], view[10]),
 // dL/dz = screen_grads slot 9.  cnt_open: as launch_geom_bwd's own_frame_sparse (ranks that emitted nothing are skipped), else NULL.
 int launch_geom_bwd_depth(const FrameK &f, const gsr_camera &cam, const int32_t *radii, const float *screen_grads, int g0, int g1,

@@ -451,17 +451,10 @@ struct GeomGrad {
     float dmean[3], dmean2D[2], dopacity, dcolor[3], dscale[3], drot[4], dcov[6];
 };
 
-// ---- A.10 for one visible Gaussian.  sg = (dmean2D.x, dmean2D.y, gA, gB, gC, dopacity, drgb[3]).
-// (camera_backward_one below repeats the conic -> cov2D -> T -> J -> p_view chain, the homogeneous divide and the SH direction
-// derivative of this function: a fix to one belongs in both.)
-// dsh (this Gaussian's [K,3] row, written when want_dsh) receives basis_k * dRGB for k < K; the caller zeroes
-// k >= K.  It may point anywhere (registers, an LDS staging row, the output tensor itself) but never depends on a
-// run-time select, so that a register array stays in registers.  clamped: bit c set <=> channel c was clamped.
-template <int DEG = -1>
-GSR_HD void geom_backward_one(const FrameK &f, const float *V, const float *PV, const float *campos,
-                              const float p[3], const float *scale, const float *quat, const float *covpre,
-                              const float *sh, bool has_colpre, unsigned clamped, const float sg[9],
-                              GeomGrad &g, float *dsh, bool want_dsh = true)
+// ---- the pieces of A.10 that geom_backward_one and camera_backward_one are both built from.
+// The forward's EWA projection of one Gaussian, recomputed.
+GSR_HD void ewa_of_gaussian(const FrameK &f, const float *V, const float p[3], const float *scale, const float *quat,
+                            const float *covpre, Ewa &e)
 {
     float pv[3];
     pv[0] = view_coord(p, V, 0);
@@ -470,12 +463,18 @@ GSR_HD void geom_backward_one(const FrameK &f, const float *V, const float *PV, 
     float cov[6];
     if (covpre) { for (int k = 0; k < 6; ++k) cov[k] = covpre[k]; }
     else cov3d_from_scale_rot(scale, f.scale_modifier, quat, cov);
-    Ewa e;
     ewa_project(pv, cov, V, f, e);
+}
 
-    g.dmean2D[0] = sg[0]; g.dmean2D[1] = sg[1];
-    g.dopacity = sg[5];
+// The screen chain: conic -> 2D covariance -> T = J R_w2c -> J -> clamped view-space point, for sg = (dmean2D.x, dmean2D.y, gA, gB, gC, ...).
+struct ScreenChain {
+    float dL_da, dL_db, dL_dc;   // dL/d(2D covariance entries)
+    float dT0[3], dT1[3];        // dL/dT rows = 2 G2 T Sigma
+    float dtx, dty, dtz;         // dL/d(tx, ty, tz); dtx / dty carry the frustum clamp's xmul / ymul
+};
 
+GSR_HD void screen_chain_backward(const FrameK &f, const float *V, const Ewa &e, const float sg[9], ScreenChain &s)
+{
     // conic -> 2D covariance (stored gB is half the derivative wrt the scalar B, A.9 note)
     const float den = e.a * e.c - e.b * e.b;
     const float k2 = 1.f / (den * den + (float)GSR_CONIC_BWD_EPS);
@@ -483,6 +482,90 @@ GSR_HD void geom_backward_one(const FrameK &f, const float *V, const float *PV, 
     const float dL_da = k2 * (-e.c * e.c * gA + 2.f * e.b * e.c * gB + (den - e.a * e.c) * gC);
     const float dL_dc = k2 * (-e.a * e.a * gC + 2.f * e.a * e.b * gB + (den - e.a * e.c) * gA);
     const float dL_db = k2 * 2.f * (e.b * e.c * gA - (den + 2.f * e.b * e.b) * gB + e.a * e.b * gC);
+    s.dL_da = dL_da; s.dL_db = dL_db; s.dL_dc = dL_dc;
+    // dL/dT = 2 G2 T Sigma
+    float *dT0 = s.dT0, *dT1 = s.dT1;
+    dT0[0] = 2.f * e.S0[0] * dL_da + e.S1[0] * dL_db; dT0[1] = 2.f * e.S0[1] * dL_da + e.S1[1] * dL_db;
+    dT0[2] = 2.f * e.S0[2] * dL_da + e.S1[2] * dL_db;
+    dT1[0] = 2.f * e.S1[0] * dL_dc + e.S0[0] * dL_db; dT1[1] = 2.f * e.S1[1] * dL_dc + e.S0[1] * dL_db;
+    dT1[2] = 2.f * e.S1[2] * dL_dc + e.S0[2] * dL_db;
+    // dL/dJ (non-zeros of J) = dL/dT R_w2c^T
+    const float dJ00 = V[0] * dT0[0] + V[4] * dT0[1] + V[8] * dT0[2];
+    const float dJ02 = V[2] * dT0[0] + V[6] * dT0[1] + V[10] * dT0[2];
+    const float dJ11 = V[1] * dT1[0] + V[5] * dT1[1] + V[9] * dT1[2];
+    const float dJ12 = V[2] * dT1[0] + V[6] * dT1[1] + V[10] * dT1[2];
+    const float tzi = 1.f / e.tz, tz2 = tzi * tzi, tz3 = tz2 * tzi;
+    s.dtx = e.xmul * -f.focal_x * tz2 * dJ02;
+    s.dty = e.ymul * -f.focal_y * tz2 * dJ12;
+    s.dtz = -f.focal_x * tz2 * dJ00 - f.focal_y * tz2 * dJ11 + (2.f * f.focal_x * e.tx) * tz3 * dJ02 +
+            (2.f * f.focal_y * e.ty) * tz3 * dJ12;
+}
+
+// Homogeneous divide (A.2): ndc = (hx, hy) mw, so d ndc.x / d(hx, hw) = (mw, -mul1) and d ndc.y / d(hy, hw) = (mw, -mul2).
+GSR_HD void hom_divide_backward(const float p[3], const float *PV, float &mw, float &mul1, float &mul2)
+{
+    const float hx = p[0] * PV[0] + p[1] * PV[4] + p[2] * PV[8] + PV[12];
+    const float hy = p[0] * PV[1] + p[1] * PV[5] + p[2] * PV[9] + PV[13];
+    const float hw = p[0] * PV[3] + p[1] * PV[7] + p[2] * PV[11] + PV[15];
+    mw = 1.f / (hw + (float)GSR_HOM_EPS);
+    mul1 = hx * mw * mw; mul2 = hy * mw * mw;
+}
+
+// SH colour (A.6) back to the view direction d = (p - campos) / |p - campos|: dd[k] = dL/dp_k = -dL/dcampos_k, through normalize().
+// DSH (compile time; the camera side passes false) and want_dsh: dsh (this Gaussian's [K,3] row) receives basis_k * dRGB for k < K;
+// the caller zeroes k >= K.  It may point anywhere (registers, an LDS staging row, the output tensor itself) but never depends on a
+// run-time select, so that a register array stays in registers.  clamped: bit c set <=> channel c was clamped.
+template <int DEG, bool DSH>
+GSR_HD void sh_direction_backward(const FrameK &f, const float *campos, const float p[3], const float *sh, unsigned clamped,
+                                  const float sg[9], float dd[3], float *dsh, bool want_dsh, bool has_colpre)
+{
+    dd[0] = dd[1] = dd[2] = 0.f;
+    if (has_colpre) return;
+    const float ox = p[0] - campos[0], oy = p[1] - campos[1], oz = p[2] - campos[2];
+    const float inv = 1.f / sqrtf(ox * ox + oy * oy + oz * oz);
+    const float dxn = ox * inv, dyn = oy * inv, dzn = oz * inv;
+    float bas[16], bx[16], by[16], bz[16];
+    const int D = DEG >= 0 ? DEG : f.D;
+    sh_basis<true>(D, dxn, dyn, dzn, bas, bx, by, bz);
+    const int K = (D + 1) * (D + 1);
+    float ddx = 0.f, ddy = 0.f, ddz = 0.f;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int ch = 0; ch < 3; ++ch) {
+        const float dRGB = ((clamped >> ch) & 1u) ? 0.f : sg[6 + ch];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int k = 0; k < K; ++k) {
+            const float c = sh[3 * k + ch] * dRGB;
+            if (DSH && want_dsh) dsh[3 * k + ch] = bas[k] * dRGB;
+            ddx += bx[k] * c; ddy += by[k] * c; ddz += bz[k] * c;
+        }
+    }
+    const float dot = dxn * ddx + dyn * ddy + dzn * ddz;           // through normalize()
+    dd[0] = (ddx - dxn * dot) * inv;
+    dd[1] = (ddy - dyn * dot) * inv;
+    dd[2] = (ddz - dzn * dot) * inv;
+}
+
+// ---- A.10 for one visible Gaussian.  sg = (dmean2D.x, dmean2D.y, gA, gB, gC, dopacity, drgb[3]).
+// dsh, want_dsh, clamped: see sh_direction_backward.
+template <int DEG = -1>
+GSR_HD void geom_backward_one(const FrameK &f, const float *V, const float *PV, const float *campos,
+                              const float p[3], const float *scale, const float *quat, const float *covpre,
+                              const float *sh, bool has_colpre, unsigned clamped, const float sg[9],
+                              GeomGrad &g, float *dsh, bool want_dsh = true)
+{
+    Ewa e;
+    ewa_of_gaussian(f, V, p, scale, quat, covpre, e);
+
+    g.dmean2D[0] = sg[0]; g.dmean2D[1] = sg[1];
+    g.dopacity = sg[5];
+
+    ScreenChain s;
+    screen_chain_backward(f, V, e, sg, s);
+    const float dL_da = s.dL_da, dL_db = s.dL_db, dL_dc = s.dL_dc;
     const float *T = e.T;
     g.dcov[0] = T[0] * T[0] * dL_da + T[0] * T[3] * dL_db + T[3] * T[3] * dL_dc;
     g.dcov[3] = T[1] * T[1] * dL_da + T[1] * T[4] * dL_db + T[4] * T[4] * dL_dc;
@@ -490,65 +573,22 @@ GSR_HD void geom_backward_one(const FrameK &f, const float *V, const float *PV, 
     g.dcov[1] = 2.f * T[0] * T[1] * dL_da + (T[0] * T[4] + T[1] * T[3]) * dL_db + 2.f * T[3] * T[4] * dL_dc;
     g.dcov[2] = 2.f * T[0] * T[2] * dL_da + (T[0] * T[5] + T[2] * T[3]) * dL_db + 2.f * T[3] * T[5] * dL_dc;
     g.dcov[4] = 2.f * T[2] * T[1] * dL_da + (T[1] * T[5] + T[2] * T[4]) * dL_db + 2.f * T[4] * T[5] * dL_dc;
-    // dL/dT = 2 G2 T Sigma
-    const float dT00 = 2.f * e.S0[0] * dL_da + e.S1[0] * dL_db, dT01 = 2.f * e.S0[1] * dL_da + e.S1[1] * dL_db,
-                dT02 = 2.f * e.S0[2] * dL_da + e.S1[2] * dL_db;
-    const float dT10 = 2.f * e.S1[0] * dL_dc + e.S0[0] * dL_db, dT11 = 2.f * e.S1[1] * dL_dc + e.S0[1] * dL_db,
-                dT12 = 2.f * e.S1[2] * dL_dc + e.S0[2] * dL_db;
-    // dL/dJ (non-zeros of J) = dL/dT R_w2c^T
-    const float dJ00 = V[0] * dT00 + V[4] * dT01 + V[8] * dT02;
-    const float dJ02 = V[2] * dT00 + V[6] * dT01 + V[10] * dT02;
-    const float dJ11 = V[1] * dT10 + V[5] * dT11 + V[9] * dT12;
-    const float dJ12 = V[2] * dT10 + V[6] * dT11 + V[10] * dT12;
-    const float tzi = 1.f / e.tz, tz2 = tzi * tzi, tz3 = tz2 * tzi;
-    const float dtx = e.xmul * -f.focal_x * tz2 * dJ02;
-    const float dty = e.ymul * -f.focal_y * tz2 * dJ12;
-    const float dtz = -f.focal_x * tz2 * dJ00 - f.focal_y * tz2 * dJ11 + (2.f * f.focal_x * e.tx) * tz3 * dJ02 +
-                      (2.f * f.focal_y * e.ty) * tz3 * dJ12;
-    g.dmean[0] = V[0] * dtx + V[1] * dty + V[2] * dtz;
-    g.dmean[1] = V[4] * dtx + V[5] * dty + V[6] * dtz;
-    g.dmean[2] = V[8] * dtx + V[9] * dty + V[10] * dtz;
+    g.dmean[0] = V[0] * s.dtx + V[1] * s.dty + V[2] * s.dtz;
+    g.dmean[1] = V[4] * s.dtx + V[5] * s.dty + V[6] * s.dtz;
+    g.dmean[2] = V[8] * s.dtx + V[9] * s.dty + V[10] * s.dtz;
 
     // projection path
-    const float hx = p[0] * PV[0] + p[1] * PV[4] + p[2] * PV[8] + PV[12];
-    const float hy = p[0] * PV[1] + p[1] * PV[5] + p[2] * PV[9] + PV[13];
-    const float hw = p[0] * PV[3] + p[1] * PV[7] + p[2] * PV[11] + PV[15];
-    const float mw = 1.f / (hw + (float)GSR_HOM_EPS);
-    const float mul1 = hx * mw * mw, mul2 = hy * mw * mw;
+    float mw, mul1, mul2;
+    hom_divide_backward(p, PV, mw, mul1, mul2);
     g.dmean[0] += (PV[0] * mw - PV[3] * mul1) * sg[0] + (PV[1] * mw - PV[3] * mul2) * sg[1];
     g.dmean[1] += (PV[4] * mw - PV[7] * mul1) * sg[0] + (PV[5] * mw - PV[7] * mul2) * sg[1];
     g.dmean[2] += (PV[8] * mw - PV[11] * mul1) * sg[0] + (PV[9] * mw - PV[11] * mul2) * sg[1];
 
     // colour path
     g.dcolor[0] = sg[6]; g.dcolor[1] = sg[7]; g.dcolor[2] = sg[8];
-    if (!has_colpre) {
-        const float ox = p[0] - campos[0], oy = p[1] - campos[1], oz = p[2] - campos[2];
-        const float inv = 1.f / sqrtf(ox * ox + oy * oy + oz * oz);
-        const float dxn = ox * inv, dyn = oy * inv, dzn = oz * inv;
-        float bas[16], bx[16], by[16], bz[16];
-        const int D = DEG >= 0 ? DEG : f.D;
-        sh_basis<true>(D, dxn, dyn, dzn, bas, bx, by, bz);
-        const int K = (D + 1) * (D + 1);
-        float ddx = 0.f, ddy = 0.f, ddz = 0.f;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-        for (int ch = 0; ch < 3; ++ch) {
-            const float dRGB = ((clamped >> ch) & 1u) ? 0.f : sg[6 + ch];
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-            for (int k = 0; k < K; ++k) {
-                const float c = sh[3 * k + ch] * dRGB;
-                if (want_dsh) dsh[3 * k + ch] = bas[k] * dRGB;
-                ddx += bx[k] * c; ddy += by[k] * c; ddz += bz[k] * c;
-            }
-        }
-        const float dot = dxn * ddx + dyn * ddy + dzn * ddz;           // through normalize()
-        g.dmean[0] += (ddx - dxn * dot) * inv;
-        g.dmean[1] += (ddy - dyn * dot) * inv;
-        g.dmean[2] += (ddz - dzn * dot) * inv;
-    }
+    float dd[3];
+    sh_direction_backward<DEG, true>(f, campos, p, sh, clamped, sg, dd, dsh, want_dsh, has_colpre);
+    if (!has_colpre) { g.dmean[0] += dd[0]; g.dmean[1] += dd[1]; g.dmean[2] += dd[2]; }
 
     // 3D covariance path
     for (int k = 0; k < 3; ++k) g.dscale[k] = 0.f;
@@ -587,9 +627,7 @@ GSR_HD void geom_backward_one(const FrameK &f, const float *V, const float *PV, 
 //   c[24 + k]       dL/dcampos_k = minus the SH view-direction term of dL/dmeans3D (zero with a precomputed colour)
 // Column 3 of V and column 2 of PV are never read by the forward: their gradients are exact zeros and have no slot here.
 // The 27 terms are ADDED to c (the caller zeroes it; a thread that visits several Gaussians keeps one set of accumulators).
-// The statements up to dtz, the homogeneous divide and the SH direction derivative are geom_backward_one's own, kept apart so that
-// its instantiations stay as they are: a change to either copy belongs in both (tests/test_camera_grad_ref.py holds this one to the
-// binary64 reference Gaussian by Gaussian on the host, tests/test_host_math.py the other).
+// Built from the same pieces as geom_backward_one (ewa_of_gaussian ... sh_direction_backward above).
 constexpr int kCamTerms = 27;
 
 template <int DEG = -1>
@@ -597,53 +635,26 @@ GSR_HD void camera_backward_one(const FrameK &f, const float *V, const float *PV
                                 const float *scale, const float *quat, const float *covpre, const float *sh, bool has_colpre,
                                 unsigned clamped, const float sg[9], float c[kCamTerms])
 {
-    float pv[3];
-    pv[0] = view_coord(p, V, 0);
-    pv[1] = view_coord(p, V, 1);
-    pv[2] = view_coord(p, V, 2);
-    float cov[6];
-    if (covpre) { for (int k = 0; k < 6; ++k) cov[k] = covpre[k]; }
-    else cov3d_from_scale_rot(scale, f.scale_modifier, quat, cov);
     Ewa e;
-    ewa_project(pv, cov, V, f, e);
+    ewa_of_gaussian(f, V, p, scale, quat, covpre, e);
 
-    const float den = e.a * e.c - e.b * e.b;
-    const float k2 = 1.f / (den * den + (float)GSR_CONIC_BWD_EPS);
-    const float gA = sg[2], gB = sg[3], gC = sg[4];
-    const float dL_da = k2 * (-e.c * e.c * gA + 2.f * e.b * e.c * gB + (den - e.a * e.c) * gC);
-    const float dL_dc = k2 * (-e.a * e.a * gC + 2.f * e.a * e.b * gB + (den - e.a * e.c) * gA);
-    const float dL_db = k2 * 2.f * (e.b * e.c * gA - (den + 2.f * e.b * e.b) * gB + e.a * e.b * gC);
-    const float dT0[3] = {2.f * e.S0[0] * dL_da + e.S1[0] * dL_db, 2.f * e.S0[1] * dL_da + e.S1[1] * dL_db,
-                          2.f * e.S0[2] * dL_da + e.S1[2] * dL_db};
-    const float dT1[3] = {2.f * e.S1[0] * dL_dc + e.S0[0] * dL_db, 2.f * e.S1[1] * dL_dc + e.S0[1] * dL_db,
-                          2.f * e.S1[2] * dL_dc + e.S0[2] * dL_db};
-    const float dJ00 = V[0] * dT0[0] + V[4] * dT0[1] + V[8] * dT0[2];
-    const float dJ02 = V[2] * dT0[0] + V[6] * dT0[1] + V[10] * dT0[2];
-    const float dJ11 = V[1] * dT1[0] + V[5] * dT1[1] + V[9] * dT1[2];
-    const float dJ12 = V[2] * dT1[0] + V[6] * dT1[1] + V[10] * dT1[2];
-    const float tzi = 1.f / e.tz, tz2 = tzi * tzi, tz3 = tz2 * tzi;
-    const float dtx = e.xmul * -f.focal_x * tz2 * dJ02;
-    const float dty = e.ymul * -f.focal_y * tz2 * dJ12;
-    const float dtz = -f.focal_x * tz2 * dJ00 - f.focal_y * tz2 * dJ11 + (2.f * f.focal_x * e.tx) * tz3 * dJ02 +
-                      (2.f * f.focal_y * e.ty) * tz3 * dJ12;
+    ScreenChain s;
+    screen_chain_backward(f, V, e, sg, s);
     const float J00 = f.focal_x / e.tz, J02 = -(f.focal_x * e.tx) / (e.tz * e.tz);
     const float J11 = f.focal_y / e.tz, J12 = -(f.focal_y * e.ty) / (e.tz * e.tz);
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
     for (int r = 0; r < 3; ++r) {
-        c[3 * r + 0] += p[r] * dtx + J00 * dT0[r];
-        c[3 * r + 1] += p[r] * dty + J11 * dT1[r];
-        c[3 * r + 2] += p[r] * dtz + (J02 * dT0[r] + J12 * dT1[r]);
+        c[3 * r + 0] += p[r] * s.dtx + J00 * s.dT0[r];
+        c[3 * r + 1] += p[r] * s.dty + J11 * s.dT1[r];
+        c[3 * r + 2] += p[r] * s.dtz + (J02 * s.dT0[r] + J12 * s.dT1[r]);
     }
-    c[9] += dtx; c[10] += dty; c[11] += dtz;
+    c[9] += s.dtx; c[10] += s.dty; c[11] += s.dtz;
 
     // projection path: ndc = (hx, hy) mw
-    const float hx = p[0] * PV[0] + p[1] * PV[4] + p[2] * PV[8] + PV[12];
-    const float hy = p[0] * PV[1] + p[1] * PV[5] + p[2] * PV[9] + PV[13];
-    const float hw = p[0] * PV[3] + p[1] * PV[7] + p[2] * PV[11] + PV[15];
-    const float mw = 1.f / (hw + (float)GSR_HOM_EPS);
-    const float mul1 = hx * mw * mw, mul2 = hy * mw * mw;
+    float mw, mul1, mul2;
+    hom_divide_backward(p, PV, mw, mul1, mul2);
     const float dh0 = mw * sg[0], dh1 = mw * sg[1], dh3 = -(mul1 * sg[0] + mul2 * sg[1]);
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
@@ -652,33 +663,9 @@ GSR_HD void camera_backward_one(const FrameK &f, const float *V, const float *PV
     c[21] += dh0; c[22] += dh1; c[23] += dh3;
 
     // colour path: the view direction is (p - campos) / |p - campos|
-    if (!has_colpre) {
-        const float ox = p[0] - campos[0], oy = p[1] - campos[1], oz = p[2] - campos[2];
-        const float inv = 1.f / sqrtf(ox * ox + oy * oy + oz * oz);
-        const float dxn = ox * inv, dyn = oy * inv, dzn = oz * inv;
-        float bas[16], bx[16], by[16], bz[16];
-        const int D = DEG >= 0 ? DEG : f.D;
-        sh_basis<true>(D, dxn, dyn, dzn, bas, bx, by, bz);
-        const int K = (D + 1) * (D + 1);
-        float ddx = 0.f, ddy = 0.f, ddz = 0.f;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-        for (int ch = 0; ch < 3; ++ch) {
-            const float dRGB = ((clamped >> ch) & 1u) ? 0.f : sg[6 + ch];
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-            for (int k = 0; k < K; ++k) {
-                const float w = sh[3 * k + ch] * dRGB;
-                ddx += bx[k] * w; ddy += by[k] * w; ddz += bz[k] * w;
-            }
-        }
-        const float dot = dxn * ddx + dyn * ddy + dzn * ddz;           // through normalize()
-        c[24] -= ((ddx - dxn * dot) * inv);
-        c[25] -= ((ddy - dyn * dot) * inv);
-        c[26] -= ((ddz - dzn * dot) * inv);
-    }
+    float dd[3];
+    sh_direction_backward<DEG, false>(f, campos, p, sh, clamped, sg, dd, nullptr, false, has_colpre);
+    if (!has_colpre) { c[24] -= dd[0]; c[25] -= dd[1]; c[26] -= dd[2]; }
 }
 
 // ---- the activations of the reference's parameter store, for the raw-parameter mode

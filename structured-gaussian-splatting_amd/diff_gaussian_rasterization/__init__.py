@@ -369,8 +369,8 @@ def rasterize_backward_geom(fr: "_Frame", screen: torch.Tensor, needs, g0: int =
                 binned_ranks = -2
             own = None
             if rows is None and binned_ranks is None:        # gradients of this very frame: its own binned depth prefix
-                plan = own = fr.plan
-                binned_ranks = int(plan.chunk_rank_begin[plan.chunks_run]) if plan.num_rendered > 0 and plan.chunks_run > 0 else 0
+                own = fr.plan
+                binned_ranks = N.binned_prefix(own)
             if binned_ranks != -2:
                 N.backward_geom(fr.desc, fr.cam, fr.gauss, fr.radii, fr.geom_ws, screen, g0, g1, grads, dev, binned_ranks,
                                 own_plan=None if partial else own, depth_chain=depth_chain)
@@ -388,10 +388,9 @@ def rasterize_backward_camera(fr: "_Frame", screen: torch.Tensor, needs=(True, T
     out = torch.empty(35, dtype=torch.float32, device=dev)
     parts = (out[:16], out[16:32], out[32:35])
     grads = N.CameraGrads(*(N._ptr(t) if n else None for t, n in zip(parts, needs)))
-    binned_ranks = int(plan.chunk_rank_begin[plan.chunks_run]) if plan.num_rendered > 0 and plan.chunks_run > 0 else 0
     with torch.cuda.device(dev):
         ws = _workspace(N.camera_grad_workspace_size(fr.desc), dev)
-        N.backward_camera(fr.desc, fr.cam, fr.gauss, fr.radii, fr.geom_ws, screen, ws, grads, dev, binned_ranks, own_plan=plan,
+        N.backward_camera(fr.desc, fr.cam, fr.gauss, fr.radii, fr.geom_ws, screen, ws, grads, dev, N.binned_prefix(plan), own_plan=plan,
                           depth_chain=depth_chain)
     return tuple((t.view(4, 4) if t.numel() == 16 else t) if n else None for t, n in zip(parts, needs))
 

@@ -265,6 +265,11 @@ def backward_camera(desc, cam: Camera, g: Gaussians, radii, geom_ws, screen_grad
            "gsr_backward_camera")
 
 
+def binned_prefix(plan: FramePlan) -> int:
+    """The depth ranks of the chunks that ran: the binned_ranks of a frame's own backward (csrc/gsr_internal.h geom_rows)."""
+    return int(plan.chunk_rank_begin[plan.chunks_run]) if plan.num_rendered > 0 and plan.chunks_run > 0 else 0
+
+
 def effective_binned_ranks(plan: FramePlan) -> int:
     """csrc/gsr_internal.h effective_binned_ranks: the ranks of the chunks that ran, a live-filtered chunk counted as nothing."""
     if plan.num_rendered <= 0 or plan.chunks_run <= 0:

@@ -238,6 +238,27 @@ def test_camera_grads_wanted_decision():
     assert dgr._camera_args(_rs(*plain())) == ()
 
 
+def test_binned_prefix_of_hand_built_plans():
+    """_native.binned_prefix, the binned_ranks both backward entry points pass for a frame's own gradients: the depth ranks of the
+    chunks that ran.  effective_binned_ranks (the dense / sparse decision) on the same plans stays what it was: it alone skips a
+    live-filtered chunk."""
+    from diff_gaussian_rasterization import _native as N
+
+    def plan(num_rendered, chunks_run, chunks_filtered=0):
+        p = N.FramePlan()
+        p.num_rendered, p.num_visible, p.num_chunks, p.chunks_run, p.chunks_filtered = num_rendered, 60, 3, chunks_run, chunks_filtered
+        for c, r in enumerate((0, 10, 30, 60)):
+            p.chunk_rank_begin[c] = r
+        return p
+    for p, prefix, effective in ((plan(0, 2), 0, 0),               # nothing rendered
+                                 (plan(500, 0), 0, 0),             # no chunk ran
+                                 (plan(500, 2), 30, 30),           # two chunks run of three planned: chunk_rank_begin[2]
+                                 (plan(500, 2, 0b10), 30, 10),     # ... the second through the live filter
+                                 (plan(500, 3), 60, 60)):
+        assert N.binned_prefix(p) == prefix
+        assert N.effective_binned_ranks(p) == effective
+
+
 def test_camera_grads_with_tile_rows_raises():
     import diff_gaussian_rasterization as dgr
     rs = _rs(torch.eye(4).requires_grad_(True), torch.eye(4), torch.zeros(3))
