@@ -398,6 +398,38 @@ int gsr_activations_backward(int64_t P, const float *scales, const float *rotati
                              const float *dL_dscales, const float *dL_drotations, const float *dL_dopacities,
                              float *dL_dscaling_raw, float *dL_drotation_raw, float *dL_dopacity_raw, void *stream);
 
+/* ---- The latent structured model's composition (scene/latent_gaussian_model.py: LatentGaussianModel.forward), additive: every
+ * call above keeps its meaning.  B structures each carry a mean [3], an opacity logit, a log-scale [3] and a raw rotation [4]; a
+ * decoder gives every structure K children of D = 11 + 3 sh_coeffs floats: decoded [B, K D] contiguous, child k of structure b =
+ * decoded[b, k D : (k + 1) D] = (xyz[3], opacity, scale[3], rotation[4], SH [sh_coeffs, 3]).  For child p = b K + k with row c:
+ *   xyz[p] = c[0:3] + means[b]    opacity[p] = c[3] + opacities[b]    scaling[p] = c[4:7] + scales[b]       (one fp32 add each)
+ *   rotation[p] = std(n(rotations[b]) (x) n(c[7:11]))    n(v) = v / max(|v|_2, 1e-12);  (x) = Hamilton product, real part first;
+ *                                                        std(q) = -q where q_w < 0 (q_w == 0 is kept)
+ *   features[p] = c[11 : 11 + 3 sh_coeffs]                                                                   (a copy)
+ * The outputs are what gsr_gaussians takes with raw == 2 (means3D, opacities, scales, rotations, shs), P = B K of them.
+ * One launch forward, one backward; no workspace, no host synchronisation, no state.  The backward recomputes what it needs from
+ * decoded and rotations.  Every wanted gradient is written in full: a NULL incoming gradient counts as zeros.  A structure's
+ * gradient is the sum over its K children taken in ascending k, ((g_0 + g_1) + g_2) + ..., without atomics: the same inputs give
+ * the same bits.  B >= 0 (0: nothing is launched), K >= 1, sh_coeffs in {1, 4, 9, 16}, B K < 2^28.  The child tensors and their
+ * gradients must be 16-byte aligned (decoded and its gradient: 4). */
+typedef struct gsr_structured_desc { int32_t B, K, sh_coeffs; } gsr_structured_desc;
+typedef struct gsr_structures {        /* [B,3] [B] [B,3] [B,4] */
+    const float *means, *opacities, *scales, *rotations;
+} gsr_structures;
+typedef struct gsr_children {          /* [P,3] [P] [P,3] [P,4] [P,sh_coeffs,3] */
+    float *xyz, *opacity, *scaling, *rotation, *features;
+} gsr_children;
+typedef struct gsr_children_grads {    /* incoming gradients, shaped as gsr_children; NULL = zero */
+    const float *xyz, *opacity, *scaling, *rotation, *features;
+} gsr_children_grads;
+typedef struct gsr_structured_grads {  /* decoded [B, K D], the rest shaped as gsr_structures; NULL = not wanted */
+    float *decoded, *means, *opacities, *scales, *rotations;
+} gsr_structured_grads;
+int gsr_structured_compose_forward(const gsr_structured_desc *desc, const float *decoded, const gsr_structures *structures,
+                                   const gsr_children *out, void *stream);
+int gsr_structured_compose_backward(const gsr_structured_desc *desc, const float *decoded, const gsr_structures *structures,
+                                    const gsr_children_grads *grads_in, const gsr_structured_grads *out, void *stream);
+
 /* ---- the densification bookkeeping of one training iteration (train.py:127-130,
  * scene/gaussian_model.py:415-417) in one pass without a host synchronisation: for every Gaussian with
  * radii[i] > 0:  max_radii2D[i] = max(max_radii2D[i], radii[i]);  xyz_gradient_accum[i] += |viewspace_grad[i, :2]|;

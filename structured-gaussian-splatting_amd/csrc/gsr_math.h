@@ -695,6 +695,72 @@ GSR_HD void activate_raw_backward(const RawAct &a, GeomGrad &g)
     g.dopacity *= a.opacity * (1.f - a.opacity);
 }
 
+// ---- The latent structured model's composition (scene/latent_gaussian_model.py forward): child k of structure b is the
+// decoder's 11 + 3M floats c added onto / rotated by the structure's own mean, opacity logit, log-scale and rotation.
+//   xyz = c[0:3] + s_mean     opacity = c[3] + s_opacity     scaling = c[4:7] + s_scale        (one fp32 add each)
+//   rotation = std(n(s_rot) (x) n(c[7:11]))      n(v) = v / max(|v|_2, 1e-12) (a division, as torch.nn.functional.normalize),
+//   (x) the Hamilton product, real part first;  std(q) = -q where q_w < 0 (q_w == 0 is not flipped).
+// The 3M SH floats behind them are copied, not computed: no function here.
+constexpr int kChildGeom = 11;             // floats of a child in front of its SH block; also floats of a structure
+constexpr float kQuatNormEps = 1e-12f;
+
+struct QuatNorm { float v[4], n, inv; };   // v / max(n, eps); inv = 1 / max(n, eps)
+
+GSR_HD void quat_normalize(const float q[4], QuatNorm &o)
+{
+    o.n = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const float nc = fmaxf(o.n, kQuatNormEps);
+    o.inv = 1.f / nc;
+    for (int k = 0; k < 4; ++k) o.v[k] = q[k] / nc;
+}
+
+// d normalize, the rule of k_act_bwd: g / n_c - v (v . g) / (n n_c^2) where n >= eps; below eps the clamp passes nothing and
+// only g / eps remains
+GSR_HD void quat_normalize_backward(const float q[4], const QuatNorm &o, const float g[4], float d[4])
+{
+    const float dot = q[0] * g[0] + q[1] * g[1] + q[2] * g[2] + q[3] * g[3];
+    const float k = o.n >= kQuatNormEps ? dot * o.inv * o.inv / o.n : 0.f;
+    for (int i = 0; i < 4; ++i) d[i] = g[i] * o.inv - q[i] * k;
+}
+
+// c: the child's first 11 decoder outputs; s: the structure's (mean[3], opacity, scale[3], rotation[4]) in the same column
+// order; out: the child's (xyz[3], opacity, scaling[3], rotation[4])
+GSR_HD void compose_child(const float c[kChildGeom], const float s[kChildGeom], float out[kChildGeom])
+{
+    for (int i = 0; i < 7; ++i) out[i] = c[i] + s[i];
+    QuatNorm a, b;
+    quat_normalize(s + 7, a);
+    quat_normalize(c + 7, b);
+    const float *A = a.v, *B = b.v;
+    const float w = A[0] * B[0] - A[1] * B[1] - A[2] * B[2] - A[3] * B[3];
+    const float x = A[0] * B[1] + A[1] * B[0] + A[2] * B[3] - A[3] * B[2];
+    const float y = A[0] * B[2] - A[1] * B[3] + A[2] * B[0] + A[3] * B[1];
+    const float z = A[0] * B[3] + A[1] * B[2] - A[2] * B[1] + A[3] * B[0];
+    const bool flip = w < 0.f;
+    out[7] = flip ? -w : w; out[8] = flip ? -x : x; out[9] = flip ? -y : y; out[10] = flip ? -z : z;
+}
+
+// g: dL/d out of compose_child.  d_c: dL/d c.  d_s: THIS child's term of dL/d s (the caller sums a structure's children).
+// Recomputes the two normalisations and the product's sign from c and s: the forward keeps nothing.
+GSR_HD void compose_child_backward(const float c[kChildGeom], const float s[kChildGeom], const float g[kChildGeom],
+                                   float d_c[kChildGeom], float d_s[kChildGeom])
+{
+    for (int i = 0; i < 7; ++i) { d_c[i] = g[i]; d_s[i] = g[i]; }
+    QuatNorm a, b;
+    quat_normalize(s + 7, a);
+    quat_normalize(c + 7, b);
+    const float *A = a.v, *B = b.v;
+    const float w = A[0] * B[0] - A[1] * B[1] - A[2] * B[2] - A[3] * B[3];
+    const float sg = w < 0.f ? -1.f : 1.f;
+    const float gw = sg * g[7], gx = sg * g[8], gy = sg * g[9], gz = sg * g[10];
+    const float dA[4] = {gw * B[0] + gx * B[1] + gy * B[2] + gz * B[3], -gw * B[1] + gx * B[0] - gy * B[3] + gz * B[2],
+                         -gw * B[2] + gx * B[3] + gy * B[0] - gz * B[1], -gw * B[3] - gx * B[2] + gy * B[1] + gz * B[0]};
+    const float dB[4] = {gw * A[0] + gx * A[1] + gy * A[2] + gz * A[3], -gw * A[1] + gx * A[0] + gy * A[3] - gz * A[2],
+                         -gw * A[2] - gx * A[3] + gy * A[0] + gz * A[1], -gw * A[3] + gx * A[2] - gy * A[1] + gz * A[0]};
+    quat_normalize_backward(s + 7, a, dA, d_s + 7);
+    quat_normalize_backward(c + 7, b, dB, d_c + 7);
+}
+
 // ---- A.1 alone (markVisible).
 GSR_HD bool in_frustum(const float p[3], const float *V)
 {

@@ -53,6 +53,29 @@ class CameraGrads(C.Structure):
     _fields_ = [("viewmatrix", _f32p), ("projmatrix", _f32p), ("campos", _f32p)]
 
 
+class StructuredDesc(C.Structure):
+    """gsr_structured_desc: B structures of K children with sh_coeffs SH coefficients per channel each."""
+    _fields_ = [("B", C.c_int32), ("K", C.c_int32), ("sh_coeffs", C.c_int32)]
+
+
+class Structures(C.Structure):
+    """gsr_structures: means [B,3], opacities [B], scales [B,3], rotations [B,4]."""
+    _fields_ = [("means", _f32p), ("opacities", _f32p), ("scales", _f32p), ("rotations", _f32p)]
+
+
+class Children(C.Structure):
+    """gsr_children (the composed tensors) and gsr_children_grads (their incoming gradients, NULL = zero): one layout."""
+    _fields_ = [("xyz", _f32p), ("opacity", _f32p), ("scaling", _f32p), ("rotation", _f32p), ("features", _f32p)]
+
+
+ChildrenGrads = Children
+
+
+class StructuredGrads(C.Structure):
+    """gsr_structured_grads: dL/ddecoded [B, K D] and the structure gradients; NULL = not wanted."""
+    _fields_ = [("decoded", _f32p), ("means", _f32p), ("opacities", _f32p), ("scales", _f32p), ("rotations", _f32p)]
+
+
 MAX_CHUNKS = 8
 LAST_SHIFT = 26
 
@@ -79,7 +102,8 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_workspace_sizes", "gsr_binning_
            "gsr_debug_sort_temp_bytes", "gsr_debug_sort_pairs", "gsr_debug_sort_pairs_ex", "gsr_dist2_workspace_size", "gsr_dist2_knn3", "gsr_adam_step", "gsr_adam_step_split", "gsr_adam_step_multi", "gsr_densify_stats",
            "gsr_activations_forward", "gsr_activations_backward",
            "gsr_aux_workspace_size", "gsr_forward_aux", "gsr_forward_render_aux", "gsr_backward_render_aux", "gsr_backward_geom_aux",
-           "gsr_camera_grad_workspace_size", "gsr_backward_camera")
+           "gsr_camera_grad_workspace_size", "gsr_backward_camera",
+           "gsr_structured_compose_forward", "gsr_structured_compose_backward")
 
 _lib = None
 
@@ -360,9 +384,8 @@ def profile_enable(on: bool):
     _check(load().gsr_profile_enable(C.c_int(int(on))), "gsr_profile_enable")
 
 
-def profile_read() -> dict:
-    """{kernel name: (total_ms, launches)} since profile_enable(True); synchronises the recorded events."""
-    n_max = 32
+def profile_read(n_max: int = 32) -> dict:
+    """{kernel name: (total_ms, launches)} since profile_enable(True), up to n_max names; synchronises the recorded events."""
     names = ((C.c_char * 32) * n_max)()
     ms = (C.c_float * n_max)()
     cnt = (C.c_int32 * n_max)()
@@ -531,3 +554,35 @@ def activations_backward(scales, rotation_raw, opacities, g_scales, g_rotations,
 def densify_stats(radii, viewspace_grad, max_radii2D, xyz_gradient_accum, denom):
     _check(load().gsr_densify_stats(C.c_int32(radii.shape[0]), _ptr(radii), _ptr(viewspace_grad), _ptr(max_radii2D),
                                     _ptr(xyz_gradient_accum), _ptr(denom), _stream(radii.device)), "gsr_densify_stats")
+
+
+def structured_compose_forward(decoded, means, opacities, scales, rotations, K: int, sh_coeffs: int):
+    """gsr_structured_compose_forward: decoded [B, K (11 + 3 sh_coeffs)] and the four structure tensors (contiguous fp32 on one
+    device) -> (xyz [P,3], opacity [P,1], scaling [P,3], rotation [P,4], features [P,sh_coeffs,3]), P = B K."""
+    B = int(decoded.shape[0])
+    P, kw = B * int(K), dict(dtype=torch.float32, device=decoded.device)
+    outs = (torch.empty(P, 3, **kw), torch.empty(P, 1, **kw), torch.empty(P, 3, **kw), torch.empty(P, 4, **kw),
+            torch.empty(P, int(sh_coeffs), 3, **kw))
+    desc = StructuredDesc(B, int(K), int(sh_coeffs))
+    st = Structures(_ptr(means), _ptr(opacities), _ptr(scales), _ptr(rotations))
+    ch = Children(*(_ptr(t) for t in outs))
+    with torch.cuda.device(decoded.device):
+        _check(load().gsr_structured_compose_forward(C.byref(desc), _ptr(decoded), C.byref(st), C.byref(ch), _stream(decoded.device)),
+               "gsr_structured_compose_forward")
+    return outs
+
+
+def structured_compose_backward(decoded, means, opacities, scales, rotations, K: int, sh_coeffs: int, grads_in, want):
+    """gsr_structured_compose_backward.  grads_in: the five incoming gradients (contiguous, any None = zero); want: five booleans
+    for (decoded, means, opacities, scales, rotations).  Returns the five gradients, None where not wanted."""
+    desc = StructuredDesc(int(decoded.shape[0]), int(K), int(sh_coeffs))
+    outs = [torch.empty_like(t) if w else None for t, w in zip((decoded, means, opacities, scales, rotations), want)]
+    if desc.B == 0 or not any(want):
+        return tuple(outs)
+    st = Structures(_ptr(means), _ptr(opacities), _ptr(scales), _ptr(rotations))
+    gin = ChildrenGrads(*(_ptr(g) for g in grads_in))
+    gout = StructuredGrads(*(_ptr(t) for t in outs))
+    with torch.cuda.device(decoded.device):
+        _check(load().gsr_structured_compose_backward(C.byref(desc), _ptr(decoded), C.byref(st), C.byref(gin), C.byref(gout),
+                                                      _stream(decoded.device)), "gsr_structured_compose_backward")
+    return tuple(outs)
