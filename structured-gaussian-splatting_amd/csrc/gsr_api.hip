@@ -257,14 +257,15 @@ static long long rows_bound(const gsr_frame_plan *plan)
     return n < 1 ? 1 : n;
 }
 
-// row-valid flags to clear ahead of the blend backward: one byte per instance the chunks that ran can have emitted (never more
-// than the binning workspace holds), rounded up to whole 16-byte words of its padded block
+// bytes of the row-valid flags of n instances: one byte each, rounded up to whole 16-byte words of their padded block
+static size_t row_flag_bytes(long long n) { return ((size_t)(n < 1 ? 1 : n) + 15) & ~(size_t)15; }
+
+// row-valid flags to clear ahead of the blend backward: those of the instances the chunks that ran can have emitted (never more
+// than the binning workspace holds)
 static size_t valid_bytes(const gsr_frame_plan *plan)
 {
-    long long n = rows_bound(plan);
-    const long long cap = plan_capacity(plan);
-    if (n > cap) n = cap;
-    return ((size_t)(n < 1 ? 1 : n) + 15) & ~(size_t)15;
+    const long long n = rows_bound(plan), cap = plan_capacity(plan);
+    return row_flag_bytes(n > cap ? cap : n);
 }
 
 }  // namespace gsr
@@ -324,7 +325,7 @@ int gsr_forward_preprocess(const gsr_frame_desc *desc, const gsr_camera *cam, co
     if ((rc = launch_preprocess(f, *cam, *g, gw, radii, desc->prefiltered != 0, dbg, s))) return rc;
     if (image_ws) {                                  // stage 2's reset of ranges / open flags, in the shadow of the readback
         ImageWS iw = carve_image(image_ws, f);
-        if ((rc = launch_depth_select(f, gw, dbg, s, iw.ranges, binning_clear_bytes(f, iw) / 16))) return rc;      // chunk plan + partition by chunk
+        if ((rc = launch_depth_select(f, gw, dbg, s, iw.ranges, binning_clear_bytes(iw) / 16))) return rc;      // chunk plan + partition by chunk
         CtrlMirror mirror;
         if ((rc = next_mirror(&mirror))) return rc;
         if ((rc = launch_binning_init(f, gw, iw, dbg, s, true, mirror))) return rc;
@@ -535,7 +536,7 @@ static int forward_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const
     if (GSR_FILL_BEFORE_WAIT && fill_wanted && plan->num_chunks > 1 && (long long)plan->chunk_rank_begin[1] * 4 < (long long)desc->P) {
         const long long cap = plan_capacity(plan);
         const BinningWS bw = carve_binning(binning_ws, cap, f);
-        fill = zero_segments(f, *g, nullptr, *early_fill, bw.row_valid, ((size_t)(cap < 1 ? 1 : cap) + 15) & ~(size_t)15);
+        fill = zero_segments(f, *g, nullptr, *early_fill, bw.row_valid, row_flag_bytes(cap));
     }
     if ((rc = forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, fill.n > 0 ? &fill : nullptr, &filled,
                                   aux)))

@@ -177,29 +177,24 @@ __global__ __launch_bounds__(1024) void k_open_count(FrameK f, int init, uint32_
     }
 }
 
-size_t binning_clear_bytes(const FrameK &f, const ImageWS &iw)
+size_t binning_clear_bytes(const ImageWS &iw)
 {
     // the per-chunk tile ranges and, directly behind them, the per-tile counters with their padding (carve_image: both are
     // 256-byte aligned blocks, so the size is a multiple of 16)
-    const size_t Tn = (size_t)f.Gx * f.Gy;
-    (void)Tn;
     return (size_t)((char *)iw.unit_count - (char *)iw.ranges) + align_up(kUnitShards * kUnitClasses * sizeof(uint32_t));
 }
 
 int launch_binning_init(const FrameK &f, GeomWS &gw, ImageWS &iw, bool debug, hipStream_t s, bool ranges_cleared, CtrlMirror mirror)
 {
-    if (!ranges_cleared) GSR_HIP_CHECK(hipMemsetAsync(iw.ranges, 0, binning_clear_bytes(f, iw), s));
-    ProfileScope prof("open_count", s);
-    hipLaunchKernelGGL(k_open_count, dim3(1), dim3(1024), 0, s, f, 1, iw.open, iw.open_bits, gw.ctrl, mirror);
-    GSR_LAUNCH_CHECK("open_count(init)", debug, s);
-    return GSR_OK;
+    if (!ranges_cleared) GSR_HIP_CHECK(hipMemsetAsync(iw.ranges, 0, binning_clear_bytes(iw), s));
+    return launch_open_update(f, gw, iw, debug, s, mirror, /*init=*/true);
 }
 
-int launch_open_update(const FrameK &f, GeomWS &gw, ImageWS &iw, bool debug, hipStream_t s, CtrlMirror mirror)
+int launch_open_update(const FrameK &f, GeomWS &gw, ImageWS &iw, bool debug, hipStream_t s, CtrlMirror mirror, bool init)
 {
     ProfileScope prof("open_count", s);
-    hipLaunchKernelGGL(k_open_count, dim3(1), dim3(1024), 0, s, f, 0, iw.open, iw.open_bits, gw.ctrl, mirror);
-    GSR_LAUNCH_CHECK("open_count", debug, s);
+    hipLaunchKernelGGL(k_open_count, dim3(1), dim3(1024), 0, s, f, init ? 1 : 0, iw.open, iw.open_bits, gw.ctrl, mirror);
+    GSR_LAUNCH_CHECK(init ? "open_count(init)" : "open_count", debug, s);
     return GSR_OK;
 }
 
@@ -286,22 +281,15 @@ __global__ __launch_bounds__(W *kWave) void k_count_team(FrameK f, int c, int r0
         for (int s0 = 0; s0 < ns; s0 += T) {                   // exclusive scan of the popcounts of steps [s0, s0 + T)
             const int s = s0 + (int)threadIdx.x;
             const uint32_t pc = s < ns ? (uint32_t)__popcll(masks[mb + (uint32_t)s]) : 0u;
-            uint32_t inc = pc;
-#pragma unroll
-            for (int off = 1; off < kWave; off <<= 1) {
-                const uint32_t v = __shfl_up(inc, off);
-                if (lane >= off) inc += v;
+            uint32_t inc, wtot;
+            if constexpr (W > 1) {
+                __syncthreads();                               // sh_cnt: the count's sum above, then the previous round's scan, read it
+                inc = block_incl_scan<W>(pc, sh_cnt, wtot);
+            } else {
+                inc = wave_incl_scan(pc);
+                wtot = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
             }
-            uint32_t wbase = 0, wtot = inc;
-            if (W > 1) {
-                __syncthreads();
-                if (lane == 63) sh_cnt[wv] = inc;
-                __syncthreads();
-                wtot = 0;
-#pragma unroll
-                for (int i = 0; i < W; ++i) { const uint32_t v = sh_cnt[i]; if (i < wv) wbase += v; wtot += v; }
-            } else wtot = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-            if (s < ns) wprefix[mb + (uint32_t)s] = carry + wbase + inc - pc;
+            if (s < ns) wprefix[mb + (uint32_t)s] = carry + inc - pc;
             carry += wtot;
         }
     }
@@ -347,19 +335,10 @@ __global__ __launch_bounds__(W *kWave) void k_emit_team(FrameK f, int c, int r0,
         const int s = s0 + (int)threadIdx.x;
         const unsigned long long m = s < ns ? masks[mb + (uint32_t)s] : 0ull;
         const uint32_t pc = (uint32_t)__popcll(m);
-        uint32_t inc = pc;
-#pragma unroll
-        for (int off = 1; off < kWave; off <<= 1) {
-            const uint32_t v = __shfl_up(inc, off);
-            if (lane >= off) inc += v;
-        }
-        if (lane == 63) sh_wave[wv] = inc;
-        __syncthreads();
-        uint32_t wbase = 0, wtot = 0;
-#pragma unroll
-        for (int i = 0; i < W; ++i) { const uint32_t v = sh_wave[i]; if (i < wv) wbase += v; wtot += v; }
-        sh_m[threadIdx.x] = m;
-        sh_off[threadIdx.x] = carry + wbase + inc - pc;
+        uint32_t wtot;
+        sh_m[threadIdx.x] = m;                                 // (ahead of the scan: the word is not held across it)
+        const uint32_t inc = block_incl_scan<W>(pc, sh_wave, wtot);
+        sh_off[threadIdx.x] = carry + inc - pc;
         __syncthreads();
         // expansion: one wave per step
         const int nq = min(T, ns - s0);
@@ -378,7 +357,7 @@ __global__ __launch_bounds__(W *kWave) void k_emit_team(FrameK f, int c, int r0,
             }
         }
         carry += wtot;
-        __syncthreads();
+        __syncthreads();                                         // sh_m, sh_off and sh_wave are stored again by the next round (and Gaussian)
     }
     }
 }
@@ -464,12 +443,7 @@ __global__ __launch_bounds__(kBinBlock) void k_bin_chunk(FrameK f, int c, int r0
             sh_b[wv][lane] = make_float4(b.x, b.y, __uint_as_float((uint32_t)t.x0 | ((uint32_t)t.y0 << 16)), __uint_as_float((uint32_t)w));
         }
     }
-    uint32_t end = total;                              // wave inclusive prefix sum
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        const uint32_t v = __shfl_up(end, off);
-        if (lane >= off) end += v;
-    }
+    const uint32_t end = wave_incl_scan(total);
     sh_end[wv][lane] = end;
     sh_cnt[wv][lane] = 0;
     if constexpr (EMIT) { sh_first[wv][lane] = first; sh_gid[wv][lane] = g; }
@@ -549,47 +523,27 @@ __global__ __launch_bounds__(1024) void k_tile_ranges(FrameK f, int c, Ctrl *__r
                                                       uint32_t *__restrict__ offs_open)
 {
     __shared__ uint32_t sh_wave[16];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int t_begin = f.ty0 * f.Gx, t_end = f.ty1 * f.Gx;
     if (scan_n > 0) {
         constexpr int kPer = kRankScanMax / 1024;                // 16 consecutive ranks per thread
         uint32_t v[kPer], mine = 0;
 #pragma unroll
         for (int i = 0; i < kPer; ++i) { const int r = (int)threadIdx.x * kPer + i; v[i] = r < scan_n ? cnt_open[r] : 0u; mine += v[i]; }
-        uint32_t inc = mine;
-#pragma unroll
-        for (int off = 1; off < kWave; off <<= 1) {
-            const uint32_t u = __shfl_up(inc, off);
-            if (lane >= off) inc += u;
-        }
-        if (lane == 63) sh_wave[wv] = inc;
-        __syncthreads();
-        uint32_t run = inc - mine, total = 0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { const uint32_t u = sh_wave[i]; if (i < wv) run += u; total += u; }
+        uint32_t total;
+        uint32_t run = block_incl_scan<16>(mine, sh_wave, total) - mine;
 #pragma unroll
         for (int i = 0; i < kPer; ++i) { const int r = (int)threadIdx.x * kPer + i; run += v[i]; if (r < scan_n) offs_open[r] = run; }
         if (threadIdx.x == 0) { ctrl->chunk_R[c] = total; ctrl->chunk_base[c + 1] = ctrl->chunk_base[c] + total; }
-        __syncthreads();
     }
     uint32_t carry = ctrl->chunk_base[c];
     for (int t0 = t_begin; t0 < t_end; t0 += 1024) {
         const int t = t0 + (int)threadIdx.x;
         const uint32_t v = t < t_end ? tile_cnt[t] : 0u;
         if (v) tile_cnt[t] = 0u;                               // ready for the next chunk / frame
-        uint32_t inc = v;
-#pragma unroll
-        for (int off = 1; off < kWave; off <<= 1) {
-            const uint32_t u = __shfl_up(inc, off);
-            if (lane >= off) inc += u;
-        }
-        __syncthreads();
-        if (lane == 63) sh_wave[wv] = inc;
-        __syncthreads();
-        uint32_t wbase = 0, wtot = 0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { const uint32_t u = sh_wave[i]; if (i < wv) wbase += u; wtot += u; }
-        if (v) { const uint32_t b = carry + wbase + inc - v; ranges_c[t] = make_uint2(b, b + v); }
+        uint32_t wtot;
+        __syncthreads();                                       // sh_wave: the rank scan above, then the previous round, read it
+        const uint32_t inc = block_incl_scan<16>(v, sh_wave, wtot);
+        if (v) { const uint32_t b = carry + inc - v; ranges_c[t] = make_uint2(b, b + v); }
         carry += wtot;
     }
 }
@@ -734,15 +688,6 @@ __global__ __launch_bounds__(kGatherBlock) void k_tile_gather(FrameK f, int c, i
 constexpr int kLiveThreads = 512;
 constexpr int kLiveWaves = kLiveThreads / kWave;
 
-__device__ __forceinline__ void live_block_range(int n, int &lo, int &hi)
-{
-    int per = (n + (int)gridDim.x - 1) / (int)gridDim.x;
-    per = (per + kLiveThreads - 1) / kLiveThreads * kLiveThreads;
-    const long long l = (long long)blockIdx.x * per;
-    lo = l < n ? (int)l : n;
-    hi = l + per < n ? (int)(l + per) : n;
-}
-
 // pass 1: one flag byte per position + the live count of every block
 __global__ __launch_bounds__(kLiveThreads) void k_live_flags(FrameK f, int r0, int n, const uint32_t *__restrict__ order,
                                                              const float4 *__restrict__ records,
@@ -759,7 +704,7 @@ __global__ __launch_bounds__(kLiveThreads) void k_live_flags(FrameK f, int r0, i
     __syncthreads();
     const unsigned long long *bits = in_lds ? sh_bits : open_bits;
     int lo, hi;
-    live_block_range(n, lo, hi);
+    block_slice(n, kLiveThreads, lo, hi);
     uint32_t mine = 0;
     for (int i = lo + (int)threadIdx.x; i < hi; i += kLiveThreads) {
         const float4 cc = records[3 * (size_t)order[r0 + i] + 2];
@@ -767,8 +712,7 @@ __global__ __launch_bounds__(kLiveThreads) void k_live_flags(FrameK f, int r0, i
         flags[i] = live ? 1 : 0;
         mine += live ? 1u : 0u;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mine += (uint32_t)__shfl_xor((int)mine, off);
+    mine = wave_sum(mine);
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&sh_cnt, mine);
     __syncthreads();
     if (threadIdx.x == 0) st->blk_cnt[0][blockIdx.x] = sh_cnt;
@@ -781,45 +725,32 @@ __global__ __launch_bounds__(kLiveThreads) void k_live_scatter(int c, int r0, in
                                                                uint32_t *__restrict__ t_order, uint32_t *__restrict__ t_key,
                                                                uint32_t *__restrict__ t_tiles, LiveParts parts)
 {
-    __shared__ uint32_t sh_w[2][kLiveWaves], sh_pre[2][kLiveWaves], sh_run[2];
+    __shared__ __align__(16) PartitionLds<2, kLiveWaves> sh;     // way 0: live, from the range's start; way 1: the others, behind ALL live ones
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (wv < 2) {                                                // wave 0: live Gaussians in the blocks before this one; wave 1: all live
-        uint32_t s = 0;
-        const int upto = wv == 0 ? (int)blockIdx.x : (int)gridDim.x;
-        for (int b = lane; b < upto; b += kWave) s += st->blk_cnt[0][b];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s += (uint32_t)__shfl_xor((int)s, off);
-        if (lane == 0) sh_run[wv] = s;
+    int lo, hi;
+    block_slice(n, kLiveThreads, lo, hi);
+    if (wv == 0) {                                               // live Gaussians in the blocks before this one
+        const uint32_t before = wave_sum_counters(st->blk_cnt[0], 0, (int)blockIdx.x);
+        if (lane == 0) sh.run[0] = before;
+    } else if (wv == 1) {
+        // live Gaussians from this block on; the first other one of this block has all live ones and the lo - before others of
+        // the blocks in front of it before it: at (before + rest) + (lo - before)
+        const uint32_t rest = wave_sum_counters(st->blk_cnt[0], (int)blockIdx.x, (int)gridDim.x);
+        if (lane == 0) {
+            sh.run[1] = (uint32_t)lo + rest;
+            if (blockIdx.x == 0) ctrl->chunk_live[c] = rest;
+        }
     }
     __syncthreads();
-    int lo, hi;
-    live_block_range(n, lo, hi);
-    const uint32_t live_total = sh_run[1];
-    uint32_t live_before = sh_run[0], dead_before = (uint32_t)lo - live_before;
-    if (blockIdx.x == 0 && threadIdx.x == 0) ctrl->chunk_live[c] = live_total;
-    const unsigned long long below = (1ull << lane) - 1ull;
     for (int i0 = lo; i0 < hi; i0 += kLiveThreads) {
         const int i = i0 + (int)threadIdx.x;
         const bool valid = i < hi;
-        const bool live = valid && flags[i] != 0;
-        const unsigned long long m = __ballot(live), mv = __ballot(valid);
-        __syncthreads();                                         // (sh_pre / sh_run of the previous round have been read)
-        if (lane == 0) { sh_w[0][wv] = (uint32_t)__popcll(m); sh_w[1][wv] = (uint32_t)__popcll(mv & ~m); }
-        __syncthreads();
-        if (threadIdx.x < 2) {
-            uint32_t run = threadIdx.x == 0 ? live_before : live_total + dead_before;
-#pragma unroll
-            for (int w = 0; w < kLiveWaves; ++w) { sh_pre[threadIdx.x][w] = run; run += sh_w[threadIdx.x][w]; }
-            sh_run[threadIdx.x] = run;
-        }
-        __syncthreads();
+        const uint32_t pos = partition_round(!valid ? -1 : flags[i] != 0 ? 0 : 1, 2, sh);
         if (valid) {
-            const uint32_t pos = live ? sh_pre[0][wv] + (uint32_t)__popcll(m & below) : sh_pre[1][wv] + (uint32_t)__popcll(mv & ~m & below);
             uint32_t delta = 0;                                  // (a range merged from several planned chunks: one key base for all)
             for (int j = 0; j + 1 < parts.n; ++j) delta = (uint32_t)i >= parts.end[j] ? parts.delta[j + 1] : delta;
             t_order[pos] = order[r0 + i]; t_key[pos] = pos_key[r0 + i] + delta; t_tiles[pos] = pos_tiles[r0 + i];
         }
-        live_before = sh_run[0]; dead_before = sh_run[1] - live_total;
     }
 }
 
@@ -873,13 +804,6 @@ __global__ __launch_bounds__(kBinBlock) void k_ranges(int c, const Ctrl *__restr
     }
 }
 
-static int msb_plus1(uint32_t n)
-{
-    int b = 0;
-    while (n) { ++b; n >>= 1; }
-    return b;
-}
-
 int launch_chunk_binning(const FrameK &f, int c, int r0, int r1, uint64_t n_max, uint64_t emitted_before, GeomWS &gw, BinningWS &bw,
                          ImageWS &iw,
                          int *sort_result, bool debug, hipStream_t s, bool filtered)
@@ -911,7 +835,7 @@ int launch_chunk_binning(const FrameK &f, int c, int r0, int r1, uint64_t n_max,
     uint4 *meta_a = reinterpret_cast<uint4 *>(scratch);
     float4 *meta_b = reinterpret_cast<float4 *>(scratch + 4 * (size_t)n);
     uint32_t *wprefix = scratch + 8 * (size_t)n;
-    const int tile_bits = msb_plus1((uint32_t)(Tn ? Tn - 1 : 0));
+    const int tile_bits = bit_width((uint32_t)(Tn ? Tn - 1 : 0));
     // The blend kernels find a sorted entry's Gaussian (| quadrant mask) in gids[1], always.  Large sorts carry the word through the
     // radix passes (the emit kernels then write it into the buffer the passes leave in [1]); small ones gather it behind the sort.
     const int sort_passes = ((tile_bits > 0 ? tile_bits : 1) + 7) / 8;

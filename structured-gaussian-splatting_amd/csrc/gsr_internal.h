@@ -8,10 +8,10 @@
 
 #include "../../include/gsrast.h"
 #include "gsr_math.h"
+#include "gsr_wave.h"
 
 namespace gsr {
 
-constexpr int kWave = 64;                 // CDNA wavefront
 constexpr int kRowFloats = 12;            // per-instance gradient row (48 B, 3 x float4; 9 used, 10 by the aux backward)
 constexpr size_t kAlign = 256;
 
@@ -49,6 +49,12 @@ struct ProfileScope {
 };
 
 inline size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
+inline int bit_width(uint32_t v)          // bits needed to write v: 0 for 0, else 1 + the position of its highest set bit
+{
+    int b = 0;
+    while (v) { ++b; v >>= 1; }
+    return b;
+}
 
 inline FrameK make_frame(const gsr_frame_desc &d)
 {
@@ -235,7 +241,7 @@ int launch_chunk_order(const FrameK &f, int r0, int r1, uint32_t key_lo, uint32_
 // parts: the range may span several planned chunks (merged by the caller); their relative keys are re-based to the first one's
 struct LiveParts { int n; uint32_t end[GSR_MAX_CHUNKS]; uint32_t delta[GSR_MAX_CHUNKS]; };      // end: position in the range; delta: added to the key
 int launch_live_filter(const FrameK &f, int c, int r0, int r1, const LiveParts &parts, GeomWS &gw, ImageWS &iw, bool debug, hipStream_t s);
-size_t binning_clear_bytes(const FrameK &f, const ImageWS &iw);      // ranges + tile counters: a multiple of 16
+size_t binning_clear_bytes(const ImageWS &iw);      // ranges + tile counters: a multiple of 16
 // Where k_open_count publishes the control block for the host: sizeof(Ctrl) / 4 words of host-coherent pinned memory (device
 // address) followed by a flag word that receives `seq` last, with system-scope release.  words == nullptr: not wanted.
 struct CtrlMirror { uint32_t *words = nullptr; uint32_t seq = 0; };
@@ -246,7 +252,9 @@ int launch_chunk_colors(const FrameK &f, const gsr_camera &cam, const gsr_gaussi
 int launch_chunk_binning(const FrameK &f, int c, int r0, int r1, uint64_t n_max, uint64_t emitted_before, GeomWS &gw, BinningWS &bw,
                          ImageWS &iw,
                          int *sort_result, bool debug, hipStream_t s, bool filtered = false);
-int launch_open_update(const FrameK &f, GeomWS &gw, ImageWS &iw, bool debug, hipStream_t s, CtrlMirror mirror = CtrlMirror());
+// init: (re)initialise the open flags for the slab instead of reading them (launch_binning_init's call)
+int launch_open_update(const FrameK &f, GeomWS &gw, ImageWS &iw, bool debug, hipStream_t s, CtrlMirror mirror = CtrlMirror(),
+                       bool init = false);
 // Zero fill of up to eleven arrays in one go (the sparse path's "memset"): the segments are laid end to end in a virtual float index
 // space (lengths rounded up to 4 floats).
 struct ZeroSegs {

@@ -31,31 +31,22 @@ __device__ __forceinline__ uint32_t sel_bin2(uint32_t key) { return (key >> kSel
 // each); results into LDS arrays.
 struct Triple { uint32_t n; unsigned long long t, m; };
 __device__ __forceinline__ Triple operator+(const Triple &a, const Triple &b) { return Triple{a.n + b.n, a.t + b.t, a.m + b.m}; }
+__device__ __forceinline__ Triple operator-(const Triple &a, const Triple &b) { return Triple{a.n - b.n, a.t - b.t, a.m - b.m}; }
+__device__ __forceinline__ Triple lane_up(const Triple &a, int off) { return Triple{lane_up(a.n, off), lane_up(a.t, off), lane_up(a.m, off)}; }
 constexpr int kSelPerThread = kSelBins / kSelThreads;
 
 __device__ __forceinline__ void scan_table(const SelTables &tab, Triple base, uint32_t *cum_n, unsigned long long *cum_t, unsigned long long *cum_m,
                                            Triple *sh_wave /* [kSelWaves] */)
 {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, b0 = kSelPerThread * threadIdx.x;
+    const int b0 = kSelPerThread * threadIdx.x;
     Triple v[kSelPerThread], mine{0u, 0ull, 0ull};
 #pragma unroll
     for (int i = 0; i < kSelPerThread; ++i) {
         v[i] = Triple{tab.cnt[b0 + i], tab.tiles[b0 + i], tab.mass[b0 + i]};
         mine = mine + v[i];
     }
-    Triple inc = mine;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        Triple u{(uint32_t)__shfl_up((int)inc.n, off), (unsigned long long)__shfl_up((long long)inc.t, off),
-                 (unsigned long long)__shfl_up((long long)inc.m, off)};
-        if (lane >= off) inc = inc + u;
-    }
     __syncthreads();                                             // (sh_wave and the cum arrays may still be read from a previous use)
-    if (lane == 63) sh_wave[wv] = inc;
-    __syncthreads();
-    Triple run = base;
-    for (int i = 0; i < wv; ++i) run = run + sh_wave[i];
-    run = Triple{run.n + inc.n - mine.n, run.t + inc.t - mine.t, run.m + inc.m - mine.m};
+    Triple run = base + (block_incl_scan_walk(mine, sh_wave) - mine);
 #pragma unroll
     for (int i = 0; i < kSelPerThread; ++i) {
         run = run + v[i];
@@ -250,15 +241,6 @@ __device__ __forceinline__ int sel_chunk_of(uint32_t key, const uint32_t *ends, 
     return c;
 }
 
-__device__ __forceinline__ void sel_block_range(int P, int &lo, int &hi)
-{
-    int per = (P + (int)gridDim.x - 1) / (int)gridDim.x;
-    per = (per + kSelThreads - 1) / kSelThreads * kSelThreads;
-    const long long l = (long long)blockIdx.x * per;
-    lo = l < P ? (int)l : P;
-    hi = l + per < P ? (int)(l + per) : P;
-}
-
 __global__ __launch_bounds__(kSelThreads) void k_part_count(int P, const uint32_t *__restrict__ keys, unsigned long long first_mass, Ctrl *ctrl,
                                                             SelState *st)
 {
@@ -275,7 +257,7 @@ __global__ __launch_bounds__(kSelThreads) void k_part_count(int P, const uint32_
     __syncthreads();
     const int n = (int)sh_n;
     int lo, hi;
-    sel_block_range(P, lo, hi);
+    block_slice(P, kSelThreads, lo, hi);
     uint32_t mine[GSR_MAX_CHUNKS] = {};
     for (int i = lo + (int)threadIdx.x; i < hi; i += kSelThreads) {
         const uint32_t key = keys[i];
@@ -306,42 +288,24 @@ __global__ __launch_bounds__(kSelThreads) void k_part_scatter(int P, const uint3
     for (int z = (int)(blockIdx.x * kSelThreads + threadIdx.x); z < clear16_n; z += (int)gridDim.x * kSelThreads)
         clear16[z] = make_uint4(0u, 0u, 0u, 0u);
     __shared__ uint32_t ends[GSR_MAX_CHUNKS];
-    __shared__ uint32_t sh_run[GSR_MAX_CHUNKS];                  // next free position of chunk k for this block
-    __shared__ uint32_t sh_w[GSR_MAX_CHUNKS][kSelWaves], sh_pre[GSR_MAX_CHUNKS][kSelWaves];
+    __shared__ __align__(16) PartitionLds<GSR_MAX_CHUNKS, kSelWaves> sh;      // way k = chunk k
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int n = (int)ctrl->num_chunks;
     if (threadIdx.x < GSR_MAX_CHUNKS) ends[threadIdx.x] = ctrl->key_end[threadIdx.x];
     if (wv < n) {                                                // wave k: chunk k's Gaussians in the blocks before this one
-        uint32_t s = 0;
-        for (int b = lane; b < (int)blockIdx.x; b += kWave) s += st->blk_cnt[wv][b];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s += (uint32_t)__shfl_xor((int)s, off);
-        if (lane == 0) sh_run[wv] = ctrl->bnd[wv] + s;
+        const uint32_t s = wave_sum_counters(st->blk_cnt[wv], 0, (int)blockIdx.x);
+        if (lane == 0) sh.run[wv] = ctrl->bnd[wv] + s;
     }
     __syncthreads();
     int lo, hi;
-    sel_block_range(P, lo, hi);
-    const unsigned long long below = (1ull << lane) - 1ull;
+    block_slice(P, kSelThreads, lo, hi);
     for (int i0 = lo; i0 < hi; i0 += kSelThreads) {
         const int i = i0 + (int)threadIdx.x;
         const uint32_t key = i < hi ? keys[i] : 0xFFFFFFFFu;
         const int c = key == 0xFFFFFFFFu ? -1 : sel_chunk_of(key, ends, n);
-        uint32_t rank = 0;
-        for (int k = 0; k < n; ++k) {
-            const unsigned long long m = __ballot(c == k);
-            if (c == k) rank = (uint32_t)__popcll(m & below);
-            if (lane == 0) sh_w[k][wv] = (uint32_t)__popcll(m);
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < n) {
-            uint32_t run = sh_run[threadIdx.x];
-#pragma unroll
-            for (int w = 0; w < kSelWaves; ++w) { sh_pre[threadIdx.x][w] = run; run += sh_w[threadIdx.x][w]; }
-            sh_run[threadIdx.x] = run;
-        }
-        __syncthreads();
+        const uint32_t pos = partition_round(c, n, sh);
         if (c >= 0) {
-            const uint32_t pos = sh_pre[c][wv] + rank, base = sel_key_base(c > 0 ? ends[c - 1] : 0u, c == 0);
+            const uint32_t base = sel_key_base(c > 0 ? ends[c - 1] : 0u, c == 0);
             order[pos] = (uint32_t)i;
             pos_key[pos] = key > base ? key - base : 0u;
             pos_tiles[pos] = tiles_mass[i].x;
@@ -383,26 +347,16 @@ int launch_depth_select(const FrameK &f, GeomWS &ws, bool debug, hipStream_t s, 
 // not depend on a rank's slab, so every rank builds the same list.  Two launches (count per block, then scatter with the
 // blocks before it summed in the prologue) instead of eight torch kernels (two compares, and, nonzero's scan, gather, ...).
 constexpr int kRowsThreads = 1024;
-__device__ __forceinline__ void rows_block_range(int P, int &lo, int &hi)
-{
-    int per = (P + (int)gridDim.x - 1) / (int)gridDim.x;
-    per = (per + kRowsThreads - 1) / kRowsThreads * kRowsThreads;
-    const long long l = (long long)blockIdx.x * per;
-    lo = l < P ? (int)l : P;
-    hi = l + per < P ? (int)(l + per) : P;
-}
-
 __global__ __launch_bounds__(kRowsThreads) void k_rows_count(int P, const uint32_t *__restrict__ keys, uint32_t key_max, uint32_t *__restrict__ blk_cnt)
 {
     __shared__ uint32_t sh_n;
     if (threadIdx.x == 0) sh_n = 0;
     __syncthreads();
     int lo, hi;
-    rows_block_range(P, lo, hi);
+    block_slice(P, kRowsThreads, lo, hi);
     uint32_t mine = 0;
     for (int i = lo + (int)threadIdx.x; i < hi; i += kRowsThreads) mine += keys[i] <= key_max ? 1u : 0u;      // invisible = 0xFFFFFFFF
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mine += (uint32_t)__shfl_xor((int)mine, off);
+    mine = wave_sum(mine);
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&sh_n, mine);
     __syncthreads();
     if (threadIdx.x == 0) blk_cnt[blockIdx.x] = sh_n;
@@ -412,42 +366,25 @@ __global__ __launch_bounds__(kRowsThreads) void k_rows_gather(int P, const uint3
                                                               const uint32_t *__restrict__ blk_cnt, const float4 *__restrict__ screen,
                                                               int n_rows, int32_t *__restrict__ rows, float4 *__restrict__ packed)
 {
-    __shared__ uint32_t sh_base, sh_w[kRowsThreads / kWave], sh_pre[kRowsThreads / kWave], sh_tot;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (wv == 0) {                                               // rows of the blocks in front of this one
-        uint32_t s = 0;
-        for (int b = lane; b < (int)blockIdx.x; b += kWave) s += blk_cnt[b];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s += (uint32_t)__shfl_xor((int)s, off);
-        if (lane == 0) sh_base = s;
+    __shared__ __align__(16) PartitionLds<1, kRowsThreads / kWave> sh;      // one way: the rows taken
+    if (threadIdx.x < kWave) {                                   // rows of the blocks in front of this one
+        const uint32_t s = wave_sum_counters(blk_cnt, 0, (int)blockIdx.x);
+        if (threadIdx.x == 0) sh.run[0] = s;
     }
     __syncthreads();
-    uint32_t run = sh_base;
     int lo, hi;
-    rows_block_range(P, lo, hi);
-    const unsigned long long below = (1ull << lane) - 1ull;
+    block_slice(P, kRowsThreads, lo, hi);
     for (int i0 = lo; i0 < hi; i0 += kRowsThreads) {
         const int i = i0 + (int)threadIdx.x;
         const bool take = i < hi && keys[i] <= key_max;
-        const unsigned long long m = __ballot(take);
-        if (lane == 0) sh_w[wv] = (uint32_t)__popcll(m);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t t = 0;
-            for (int w = 0; w < kRowsThreads / kWave; ++w) { sh_pre[w] = t; t += sh_w[w]; }
-            sh_tot = t;
-        }
-        __syncthreads();
+        const uint32_t r = partition_round(take ? 0 : -1, 1, sh);
         if (take) {
-            const uint32_t r = run + sh_pre[wv] + (uint32_t)__popcll(m & below);
             if ((int)r < n_rows) {
                 rows[r] = i;
                 packed[3 * (size_t)r] = screen[3 * (size_t)i]; packed[3 * (size_t)r + 1] = screen[3 * (size_t)i + 1];
                 packed[3 * (size_t)r + 2] = screen[3 * (size_t)i + 2];
             }
         }
-        run += sh_tot;
-        __syncthreads();
     }
 }
 
@@ -554,14 +491,10 @@ __global__ __launch_bounds__(kSmallThreads) void k_chunk_sort_small(int n, uint3
         uint32_t c[kBucketsPer], mine = 0, mx = 0;
 #pragma unroll
         for (int i = 0; i < kBucketsPer; ++i) { c[i] = bcnt[kBucketsPer * threadIdx.x + i]; mine += c[i]; mx = c[i] > mx ? c[i] : mx; }
-        uint32_t inc = mine;
-#pragma unroll
-        for (int off = 1; off < kWave; off <<= 1) {
-            const uint32_t u = (uint32_t)__shfl_up((int)inc, off);
-            if (lane >= off) inc += u;
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) { const uint32_t u = (uint32_t)__shfl_xor((int)mx, off); mx = u > mx ? u : mx; }
+        // The waves' totals by hand here and in the fallback's scan below, not through block_incl_scan_walk, whose walk this is: with either call the 16384-key
+        // instantiation, which is at its 128 registers, spilled 44 - 48 bytes per lane instead of 40 (the third scan, at the end, calls it)
+        const uint32_t inc = wave_incl_scan(mine);
+        mx = wave_max(mx);
         if (lane == 63) sh_wave[wv] = inc;
         if (lane == 0) atomicMax(&sh_max, mx);
         __syncthreads();
@@ -599,8 +532,7 @@ __global__ __launch_bounds__(kSmallThreads) void k_chunk_sort_small(int n, uint3
                 const int lo = mine ? (int)bofs[b] : 0;
                 const uint32_t len = mine ? bcnt[b] : 0u;
                 int m = mine ? (int)len - 1 : 0;
-#pragma unroll
-                for (int off = 32; off >= 1; off >>= 1) { const int u = __shfl_xor(m, off); m = u > m ? u : m; }
+                m = wave_max(m);
                 uint32_t r = 0;
                 for (int d = -m; d <= m; d += 4) {               // four independent neighbours per step
                     unsigned long long nb[4];
@@ -658,13 +590,8 @@ __global__ __launch_bounds__(kSmallThreads) void k_chunk_sort_small(int n, uint3
                 uint32_t c[kSmallCntPer], mine = 0;
 #pragma unroll
                 for (int i = 0; i < kSmallCntPer; ++i) { c[i] = cnt[kSmallCntPer * threadIdx.x + i]; mine += c[i]; }
-                uint32_t inc = mine;
-#pragma unroll
-                for (int off = 1; off < kWave; off <<= 1) {
-                    const uint32_t u = (uint32_t)__shfl_up((int)inc, off);
-                    if (lane >= off) inc += u;
-                }
-                if (lane == 63) sh_wave[wv] = inc;
+                const uint32_t inc = wave_incl_scan(mine);       // (by hand: see the bucket scan above)
+                if (lane == 63) sh_wave[wv] = inc;              // (the barriers of the pass order the last scan's reads before this store)
                 __syncthreads();
                 uint32_t run = inc - mine;
                 for (int i = 0; i < wv; ++i) run += sh_wave[i];
@@ -703,30 +630,14 @@ __global__ __launch_bounds__(kSmallThreads) void k_chunk_sort_small(int n, uint3
         const int e = threadIdx.x * kSmallPer + i;
         if (e < n) order[r0 + e] = gs[i];
     }
-    uint32_t inc = sum;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        const uint32_t v = (uint32_t)__shfl_up((int)inc, off);
-        if (lane >= off) inc += v;
-    }
-    __syncthreads();
-    if (lane == 63) sh_wave[wv] = inc;
-    __syncthreads();
-    uint32_t run = inc - sum;
-    for (int i = 0; i < wv; ++i) run += sh_wave[i];
+    // (sh_wave: the barrier in front of the stores to order[] has the last scan's reads behind it)
+    uint32_t run = block_incl_scan_walk(sum, sh_wave) - sum;
 #pragma unroll
     for (int i = 0; i < kSmallPer; ++i) {
         const int e = threadIdx.x * kSmallPer + i;
         run += t[i];
         if (e < n) offs_full[r0 + e] = run;
     }
-}
-
-static int bits_of(uint32_t v)
-{
-    int b = 0;
-    while (v) { ++b; v >>= 1; }
-    return b;
 }
 
 // live_count (device): only the first *live_count Gaussians of the range need sorting (launch_live_filter put the ones that
@@ -739,7 +650,7 @@ int launch_chunk_order(const FrameK &f, int r0, int r1, uint32_t key_lo, uint32_
     // the partition left, by position, the Gaussian (order), its key relative to the chunk's lower end (sort_keys[1]) and
     // its tile count (sort_vals[1])
     const uint32_t base = sel_key_base(key_lo, first);
-    int bits = bits_of(key_hi > base ? key_hi - base : 0u);
+    int bits = bit_width(key_hi > base ? key_hi - base : 0u);
     if (bits < 1) bits = 1;
     if (n <= kSmallSortMax && !live_count) {
         const int force_radix = getenv("GSR_SORT_FORCE_RADIX") ? 1 : 0;               // test hook (tests set it per case): the fallback path of the LDS sort

@@ -18,75 +18,20 @@ namespace gsr {
 constexpr int kScanBlock = 256;
 constexpr int kScanItems = 8;
 constexpr int kScanTile = kScanBlock * kScanItems;      // 2048 elements per block
+constexpr int kScanWaves = kScanBlock / kWave;
 static_assert(kScanTile == kScanTileElems, "mass_blocks granularity");
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        const uint32_t t = __shfl_up(v, off);
-        if (lane >= off) v += t;
-    }
-    return v;
-}
-
-// block-wide inclusive scan of one value per thread (256 threads); returns inclusive value, total in *total
-__device__ __forceinline__ uint32_t block_incl_scan(uint32_t v, uint32_t *sh_wave /*[4]*/, uint32_t *total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint32_t inc = wave_incl_scan(v, lane);
-    if (lane == 63) sh_wave[w] = inc;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < kScanBlock / kWave; ++i) {
-        const uint32_t s = sh_wave[i];
-        if (i < w) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return inc + base;
-}
-
-// 64-bit flavour for the auxiliary (optical mass) block sums
-__device__ __forceinline__ unsigned long long block_incl_scan64(unsigned long long v, unsigned long long *sh_wave /*[4]*/,
-                                                               unsigned long long *total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    unsigned long long inc = v;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        const unsigned long long t = __shfl_up(inc, off);
-        if (lane >= off) inc += t;
-    }
-    if (lane == 63) sh_wave[w] = inc;
-    __syncthreads();
-    unsigned long long base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < kScanBlock / kWave; ++i) {
-        const unsigned long long s = sh_wave[i];
-        if (i < w) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return inc + base;
-}
-
+// One tile of the scan (k_scan_local: a block's own; k_scan_small: one after the other): kScanItems consecutive elements per
+// thread from t0 on, out = carry + their inclusive scan; returns the tile's sum.
 // gather != nullptr: the scanned sequence is in[gather[i]] (tiles touched, read in depth order)
-// aux != nullptr: the input is (value, auxiliary) PAIRS and replaces `in`; the auxiliary quantity (optical mass) is summed
-// per block alongside: aux_blocks[b] = sum of aux[gather[i]].y over the block's elements (k_scan_tops turns the block
-// sums into their exclusive prefix)
-__global__ __launch_bounds__(kScanBlock) void k_scan_local(const uint32_t *__restrict__ in, const uint32_t *__restrict__ gather,
-                                                           uint32_t *__restrict__ out, uint32_t *__restrict__ block_sums, int n,
-                                                           const uint2 *__restrict__ aux, unsigned long long *__restrict__ aux_blocks)
+// aux != nullptr: the input is (value, auxiliary) PAIRS and replaces `in`; asum = this thread's sum of aux[gather[i]].y
+__device__ __forceinline__ uint32_t scan_tile(const uint32_t *__restrict__ in, const uint32_t *__restrict__ gather,
+                                              const uint2 *__restrict__ aux, uint32_t *__restrict__ out, int t0, int n, uint32_t carry,
+                                              uint32_t *sh_wave, unsigned long long &asum)
 {
-    __shared__ uint32_t sh_wave[kScanBlock / kWave];
-    __shared__ unsigned long long sh_wave64[kScanBlock / kWave];
-    const int base = blockIdx.x * kScanTile + threadIdx.x * kScanItems;
+    const int base = t0 + threadIdx.x * kScanItems;
     uint32_t v[kScanItems], sum = 0;
-    unsigned long long asum = 0;
+    asum = 0;
 #pragma unroll
     for (int i = 0; i < kScanItems; ++i) {
         const bool ok = base + i < n;
@@ -100,13 +45,25 @@ __global__ __launch_bounds__(kScanBlock) void k_scan_local(const uint32_t *__res
         sum += v[i];
     }
     uint32_t total;
-    uint32_t run = block_incl_scan(sum, sh_wave, &total) - sum;
+    uint32_t run = carry + block_incl_scan<kScanWaves>(sum, sh_wave, total) - sum;
 #pragma unroll
     for (int i = 0; i < kScanItems; ++i) { run += v[i]; if (base + i < n) out[base + i] = run; }
+    return total;
+}
+
+// aux: the auxiliary quantity (optical mass) is summed per block alongside: aux_blocks[b] = sum of aux[gather[i]].y over the
+// block's elements (k_scan_tops turns the block sums into their exclusive prefix)
+__global__ __launch_bounds__(kScanBlock) void k_scan_local(const uint32_t *__restrict__ in, const uint32_t *__restrict__ gather,
+                                                           uint32_t *__restrict__ out, uint32_t *__restrict__ block_sums, int n,
+                                                           const uint2 *__restrict__ aux, unsigned long long *__restrict__ aux_blocks)
+{
+    __shared__ uint32_t sh_wave[kScanWaves];
+    __shared__ unsigned long long sh_wave64[kScanWaves];
+    unsigned long long asum, atotal;
+    const uint32_t total = scan_tile(in, gather, aux, out, blockIdx.x * kScanTile, n, 0u, sh_wave, asum);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
     if (aux) {
-        unsigned long long atotal;
-        block_incl_scan64(asum, sh_wave64, &atotal);
+        block_incl_scan<kScanWaves>(asum, sh_wave64, atotal);
         if (threadIdx.x == 0) aux_blocks[blockIdx.x] = atotal;
     }
 }
@@ -116,20 +73,20 @@ __global__ __launch_bounds__(kScanBlock) void k_scan_tops(uint32_t *__restrict__
                                                           const uint32_t *__restrict__ acc_in, uint32_t *__restrict__ acc_out,
                                                           uint32_t *__restrict__ overflow, unsigned long long *__restrict__ aux_blocks)
 {
-    __shared__ uint32_t sh_wave[kScanBlock / kWave];
-    __shared__ unsigned long long sh_wide[kScanBlock / kWave];
+    __shared__ uint32_t sh_wave[kScanWaves];
+    __shared__ unsigned long long sh_wide[kScanWaves];
     if (aux_blocks) {                                          // block sums -> exclusive prefix, [nb] = grand total
         unsigned long long acarry = 0;
         for (int base = 0; base < nb; base += kScanBlock) {
             const int i = base + threadIdx.x;
             const unsigned long long v = i < nb ? aux_blocks[i] : 0ull;
             unsigned long long total;
-            const unsigned long long inc = block_incl_scan64(v, sh_wide, &total);
+            const unsigned long long inc = block_incl_scan<kScanWaves>(v, sh_wide, total);
             if (i < nb) aux_blocks[i] = acarry + inc - v;
             acarry += total;
+            __syncthreads();                                   // sh_wide is stored again by the next round, and by the overflow sum below
         }
         if (threadIdx.x == 0) aux_blocks[nb] = acarry;
-        __syncthreads();
     }
     uint32_t carry = 0;
     unsigned long long wide = 0;                               // the same sum in 64 bits, to detect wrap-around
@@ -138,18 +95,18 @@ __global__ __launch_bounds__(kScanBlock) void k_scan_tops(uint32_t *__restrict__
         const uint32_t v = i < nb ? block_sums[i] : 0u;
         wide += v;
         uint32_t total;
-        const uint32_t inc = block_incl_scan(v, sh_wave, &total);
+        const uint32_t inc = block_incl_scan<kScanWaves>(v, sh_wave, total);
         if (i < nb) block_sums[i] = carry + inc - v;
         carry += total;
+        __syncthreads();                                       // sh_wave is stored again by the next round
     }
     if (overflow) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) wide += __shfl_xor(wide, off);
+        wide = wave_sum(wide);
         if ((threadIdx.x & 63) == 0) sh_wide[threadIdx.x >> 6] = wide;
         __syncthreads();
         if (threadIdx.x == 0) {
             unsigned long long t = 0;
-            for (int i = 0; i < kScanBlock / kWave; ++i) t += sh_wide[i];
+            for (int i = 0; i < kScanWaves; ++i) t += sh_wide[i];
             *overflow = t > 0xFFFFFFFFull ? 1u : 0u;
         }
     }
@@ -176,38 +133,21 @@ __global__ __launch_bounds__(kScanBlock) void k_scan_small(const uint32_t *__res
                                                            uint32_t *__restrict__ acc_out, uint32_t *__restrict__ overflow,
                                                            const uint2 *__restrict__ aux, unsigned long long *__restrict__ aux_blocks)
 {
-    __shared__ uint32_t sh_wave[kScanBlock / kWave];
-    __shared__ unsigned long long sh_wave64[kScanBlock / kWave];
+    __shared__ uint32_t sh_wave[kScanWaves];
+    __shared__ unsigned long long sh_wave64[kScanWaves];
     uint32_t carry = 0;
     unsigned long long wide = 0, acarry = 0;
     for (int t0 = 0; t0 < n; t0 += kScanTile) {
-        const int base = t0 + threadIdx.x * kScanItems;
-        uint32_t v[kScanItems], sum = 0;
-        unsigned long long asum = 0;
-#pragma unroll
-        for (int i = 0; i < kScanItems; ++i) {
-            const bool ok = base + i < n;
-            const uint32_t src = ok ? (gather ? gather[base + i] : (uint32_t)(base + i)) : 0u;
-            if (aux) {
-                const uint2 pr = ok ? aux[src] : make_uint2(0u, 0u);
-                v[i] = pr.x; asum += pr.y;
-            } else {
-                v[i] = ok ? in[src] : 0u;
-            }
-            sum += v[i];
-        }
-        uint32_t total;
-        uint32_t run = carry + block_incl_scan(sum, sh_wave, &total) - sum;
-#pragma unroll
-        for (int i = 0; i < kScanItems; ++i) { run += v[i]; if (base + i < n) out[base + i] = run; }
+        unsigned long long asum, atotal;
+        const uint32_t total = scan_tile(in, gather, aux, out, t0, n, carry, sh_wave, asum);
         wide += total;
         carry += total;
         if (aux) {                                             // exclusive prefix of the per-block sums, written as we go
-            unsigned long long atotal;
-            block_incl_scan64(asum, sh_wave64, &atotal);
+            block_incl_scan<kScanWaves>(asum, sh_wave64, atotal);
             if (threadIdx.x == 0) aux_blocks[t0 / kScanTile] = acarry;
             acarry += atotal;
         }
+        __syncthreads();                                       // sh_wave and sh_wave64 are stored again by the next tile
     }
     if (aux && threadIdx.x == 0) aux_blocks[(n + kScanTile - 1) / kScanTile] = acarry;
     if (threadIdx.x == 0) {
@@ -253,15 +193,6 @@ constexpr int kRadixBins = 256;
 constexpr int kRadixRounds = 4;                                  // 64-key rounds per wave per sub-tile
 constexpr int kRadixSubTile = kRadixBlock * kRadixRounds;        // 1024 keys
 
-__device__ __forceinline__ void block_range(uint32_t n, int nblocks, uint32_t subtile, uint32_t &lo, uint32_t &hi)
-{
-    uint32_t per = (n + nblocks - 1) / nblocks;
-    per = (per + subtile - 1) / subtile * subtile;
-    const uint64_t l = (uint64_t)blockIdx.x * per, h = l + per;
-    lo = l < n ? (uint32_t)l : n;
-    hi = h < n ? (uint32_t)h : n;
-}
-
 template <typename K>
 __global__ __launch_bounds__(kRadixBlock) void k_radix_hist(const K *__restrict__ keys, const uint32_t *__restrict__ n_ptr,
                                                             uint32_t n_host, const uint32_t *__restrict__ base_ptr, int shift, uint32_t dmask,
@@ -273,7 +204,7 @@ __global__ __launch_bounds__(kRadixBlock) void k_radix_hist(const K *__restrict_
     const uint32_t n = n_ptr ? *n_ptr : n_host;
     if (base_ptr) keys += *base_ptr;
     uint32_t lo, hi;
-    block_range(n, gridDim.x, subtile, lo, hi);
+    block_slice(n, subtile, lo, hi);
     for (uint32_t i = lo + threadIdx.x; i < hi; i += kRadixBlock) {
         const uint32_t d = (uint32_t)(keys[i] >> shift) & dmask;
         const uint32_t d0 = __builtin_amdgcn_readfirstlane(d);
@@ -303,7 +234,7 @@ __global__ __launch_bounds__(kRadixBlock) void k_radix_scan(uint32_t *__restrict
 #pragma unroll
     for (int i = 0; i < 8; ++i) { v[i] = (i < per && b0 + i < B) ? row[b0 + i] : 0u; sum += v[i]; }
     uint32_t total;
-    uint32_t run = block_incl_scan(sum, sh_wave, &total) - sum;
+    uint32_t run = block_incl_scan<kRadixBlock / kWave>(sum, sh_wave, total) - sum;
 #pragma unroll
     for (int i = 0; i < 8; ++i)
         if (i < per && b0 + i < B) { row[b0 + i] = run; run += v[i]; }
@@ -332,14 +263,14 @@ __global__ __launch_bounds__(kRadixBlock) void k_radix_scatter(const K *__restri
     {
         const uint32_t tot = totals[threadIdx.x];
         uint32_t all;
-        const uint32_t digit_excl = block_incl_scan(tot, sh_wave, &all) - tot;
+        const uint32_t digit_excl = block_incl_scan<kRadixBlock / kWave>(tot, sh_wave, all) - tot;
         base[threadIdx.x] = digit_excl + table[threadIdx.x * gridDim.x + blockIdx.x];
     }
 #pragma unroll
     for (int i = 0; i < kRadixBlock / kWave; ++i) wave_cnt[i][threadIdx.x] = 0;
     const uint32_t n = n_ptr ? *n_ptr : n_host;
     uint32_t lo, hi;
-    block_range(n, gridDim.x, kRadixSubTile, lo, hi);
+    block_slice(n, (uint32_t)kRadixSubTile, lo, hi);
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     __syncthreads();
     for (uint32_t tile = lo; tile < hi; tile += kRadixSubTile) {
@@ -422,14 +353,14 @@ __global__ __launch_bounds__(kRadixBlock) void k_radix_scatter_big(const K *__re
     {
         const uint32_t tot = totals[threadIdx.x];
         uint32_t all;
-        const uint32_t digit_excl = block_incl_scan(tot, sh_wave, &all) - tot;
+        const uint32_t digit_excl = block_incl_scan<kRadixBlock / kWave>(tot, sh_wave, all) - tot;
         base[threadIdx.x] = digit_excl + table[threadIdx.x * gridDim.x + blockIdx.x];
     }
 #pragma unroll
     for (int i = 0; i < kRadixBlock / kWave; ++i) wave_cnt[i][threadIdx.x] = 0;
     const uint32_t n = n_ptr ? *n_ptr : n_host;
     uint32_t lo, hi;
-    block_range(n, gridDim.x, kBigSubTile, lo, hi);
+    block_slice(n, (uint32_t)kBigSubTile, lo, hi);
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     __syncthreads();
     for (uint32_t tile = lo; tile < hi; tile += kBigSubTile) {
@@ -457,7 +388,9 @@ __global__ __launch_bounds__(kRadixBlock) void k_radix_scatter_big(const K *__re
 #pragma unroll
             for (int i = 0; i < kRadixBlock / kWave; ++i) { c[i] = wave_cnt[i][threadIdx.x]; tot += c[i]; wave_cnt[i][threadIdx.x] = 0; }
             uint32_t all;
-            uint32_t run = block_incl_scan(tot, sh_wave, &all) - tot;   // start of digit d inside the sorted sub-tile
+            // start of digit d inside the sorted sub-tile (sh_wave: the barrier that ends the sub-tile's round, and the one in front
+            // of the loop, order the previous scan's reads before this store)
+            uint32_t run = block_incl_scan<kRadixBlock / kWave>(tot, sh_wave, all) - tot;
             delta[threadIdx.x] = base[threadIdx.x] - run;
             base[threadIdx.x] += tot;
 #pragma unroll

@@ -746,19 +746,36 @@ def test_chunk_sort_paths_agree_and_equal_depths_keep_index_order():
     and the 4-bit radix passes it falls back to when keys crowd into one bucket — give bitwise the same frame and gradients.
     (b) Gaussians with bit-identical depth (4000 of them on one plane facing the camera: every one of them lands in the same
     bucket, so the fallback runs on its own) blend in index order, as the reference's stable sort has it: parity with the oracle
-    at the strict bound."""
-    c = dict(P=5000, W=256, H=192, D=3, seed=109)
-    kw = _fixture_kwargs(c)
+    at the strict bound.
+    (a) runs on two frames: 5000 Gaussians (the sort's 8192-key instantiation) and 13 000 faint 2 px splats, 12 336 of them visible
+    by the oracle's radii and 37 k tile instances in all, below the 2^18 a first chunk may not be smaller than: one chunk by rule,
+    which only the 16384-key instantiation takes (both asserted: the oracle's count, the chunk from the frame's plan).  The two
+    paths share the kernel's last scan and its write of the order, so the faint frame's image is also held to the oracle's."""
+    import diff_gaussian_rasterization as dgr
     gimg = S.make_grad_image(256, 192, 9).numpy()
-    c1, r1, g1 = _run_gpu(kw, gimg)
-    os.environ["GSR_SORT_FORCE_RADIX"] = "1"
-    try:
-        c2, r2, g2 = _run_gpu(kw, gimg)
-    finally:
-        del os.environ["GSR_SORT_FORCE_RADIX"]
-    assert np.array_equal(c1, c2) and np.array_equal(r1, r2)
-    for k in g1:
-        assert np.array_equal(g1[k], g2[k]), k
+    faint = S.make_scene(13000, 256, 192, 0, 137, zmin=2.0, zmax=6.0)
+    faint.log_scales = torch.log(2.0 * faint.means3D[:, 2:3] / (192 / (2 * 0.5))).expand(13000, 3).contiguous()      # sigma = 2 px
+    faint.opacity_logits = torch.full((13000, 1), math.log(0.3 / 0.7))
+    kw_faint = raster_kwargs(faint, S.make_camera(256, 192))
+    fr64_faint = oracle.rasterize(dtype=np.float64, **kw_faint)
+    assert int((fr64_faint.radii > 0).sum()) == 12336 and fr64_faint.num_rendered < 1 << 18
+    inp = _inputs(kw_faint, False)
+    plan = dgr.rasterize_forward(inp["means3D"], inp["shs"], None, inp["opacities"], inp["scales"], inp["rotations"], None,
+                                 _settings(kw_faint))[2].plan
+    assert plan.num_chunks == 1 and 8192 < plan.chunk_rank_begin[1] - plan.chunk_rank_begin[0] <= 16384, \
+        (plan.num_chunks, list(plan.chunk_rank_begin))
+    for kw in (_fixture_kwargs(dict(P=5000, W=256, H=192, D=3, seed=109)), kw_faint):
+        c1, r1, g1 = _run_gpu(kw, gimg)
+        os.environ["GSR_SORT_FORCE_RADIX"] = "1"
+        try:
+            c2, r2, g2 = _run_gpu(kw, gimg)
+        finally:
+            del os.environ["GSR_SORT_FORCE_RADIX"]
+        assert np.array_equal(c1, c2) and np.array_equal(r1, r2)
+        for k in g1:
+            assert np.array_equal(g1[k], g2[k]), k
+        if kw is kw_faint:
+            _check_forward(kw, fr64_faint, c1, r1)
     kw = _fixture_kwargs(dict(P=6000, W=256, H=192, D=1, seed=131))
     kw["means3D"] = kw["means3D"].copy()
     kw["means3D"][:4000, 2] = 1.5                              # S.make_camera looks down +z from the origin: view depth = z

@@ -280,11 +280,12 @@ def test_slab_balancer_moves_the_boundaries_and_keeps_the_result():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("P,frac", [(1, 1.0), (5000, 0.3), (300_000, 0.02), (4_500_000, 0.5)])
+@pytest.mark.parametrize("P,frac", [(1, 1.0), (4097, 0.5), (5000, 0.3), (300_000, 0.02), (4_500_000, 0.5)])
 def test_exchange_rows_gather_and_scatter_equal_the_torch_expression(P, frac):
     """gsr_exchange_rows_gather / _scatter (the sharded backward's gradient exchange) against what they replace:
     idx = nonzero((keys >= 0) & (keys <= k_max)) in index order, packed = partial[idx], screen[idx] = summed rows.  Keys are
-    written into a frame's geometry workspace by hand; 4.5 M Gaussians: more blocks than the 1024 per-block counters."""
+    written into a frame's geometry workspace by hand; 4097: one element past a whole block slice of four rounds of 1024 threads;
+    4.5 M Gaussians: more blocks than the 1024 per-block counters."""
     from diff_gaussian_rasterization import _native as N
     dev = "cuda:0"
     g = torch.Generator().manual_seed(P)
