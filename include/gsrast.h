@@ -430,6 +430,27 @@ int gsr_structured_compose_forward(const gsr_structured_desc *desc, const float 
 int gsr_structured_compose_backward(const gsr_structured_desc *desc, const float *decoded, const gsr_structures *structures,
                                     const gsr_children_grads *grads_in, const gsr_structured_grads *out, void *stream);
 
+/* ---- Anti-aliasing as an opacity compensation (upstream's `antialiasing` switch, the 2D filter of Mip-Splatting), additive: every
+ * call above keeps its meaning, and the rasterizer itself does not change.  The forward low-passes every splat by adding
+ * h = GSR_COV2D_DILATE (0.3 px^2) to the diagonal of its 2D covariance; the radius, the binning rectangle and the conic keep that
+ * dilated covariance.  This op, run IN FRONT of the forward, scales the opacity so that the splat keeps its energy:
+ *   det0 = a0 c0 - b^2     det1 = (a0 + h)(c0 + h) - b^2     (a0, b, c0: the 2D covariance BEFORE the dilation, same frustum clamp of
+ *                                                             tx/tz, ty/tz and same scale_modifier as the preprocess)
+ *   x = det0 / det1        rho = sqrt(max(GSR_AA_MIN_RATIO, x))        opacities_out[i] = opacities[i] rho
+ * A Gaussian the preprocess culls before it has a covariance (view z <= GSR_NEAR_CUT), or one with det1 == 0, passes through:
+ * opacities_out[i] = opacities[i], dL/dopacities[i] = grad_opacities_out[i], its other gradients are zero.  Where x is clamped
+ * the geometry gradients are zero too.  g->raw != 0: opacities are logits, scales log-scales, rotations unnormalised (activated as
+ * in the per-Gaussian kernels); opacities_out is then the LOGIT of sigmoid(opacities) rho and the gradients are those on the raw
+ * tensors.  Read: desc (P, width, height, tanfovx, tanfovy, scale_modifier, debug), cam->viewmatrix, g->means3D, opacities, scales,
+ * rotations (16-byte aligned), raw; the rest is ignored, except that g->cov3D_precomp != NULL is GSR_ERR_INVALID_ARGUMENT.
+ * The backward takes grad_opacities_out [P] = dL/dopacities_out and writes grads->means3D [P,3], opacities [P], scales [P,3],
+ * rotations [P,4] (any may be NULL: not wanted; the other fields of gsr_grads are ignored) in full; no gradient is returned for the
+ * view matrix.  One launch each; every row depends on its own inputs only (no atomics): the same inputs give the same bits. */
+int gsr_opacity_compensation_forward(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, float *opacities_out,
+                                     void *stream);
+int gsr_opacity_compensation_backward(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g,
+                                      const float *grad_opacities_out, const gsr_grads *grads, void *stream);
+
 /* ---- the densification bookkeeping of one training iteration (train.py:127-130,
  * scene/gaussian_model.py:415-417) in one pass without a host synchronisation: for every Gaussian with
  * radii[i] > 0:  max_radii2D[i] = max(max_radii2D[i], radii[i]);  xyz_gradient_accum[i] += |viewspace_grad[i, :2]|;

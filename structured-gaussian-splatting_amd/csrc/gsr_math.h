@@ -473,6 +473,23 @@ struct ScreenChain {
     float dtx, dty, dtz;         // dL/d(tx, ty, tz); dtx / dty carry the frustum clamp's xmul / ymul
 };
 
+// The chain behind dL/dT, shared with the opacity compensation (opacity_compensation_backward_one): s.dT0, s.dT1 -> J -> clamped
+// view-space point (s.dtx, s.dty, s.dtz).
+GSR_HD void jacobian_chain_backward(const FrameK &f, const float *V, const Ewa &e, ScreenChain &s)
+{
+    const float *dT0 = s.dT0, *dT1 = s.dT1;
+    // dL/dJ (non-zeros of J) = dL/dT R_w2c^T
+    const float dJ00 = V[0] * dT0[0] + V[4] * dT0[1] + V[8] * dT0[2];
+    const float dJ02 = V[2] * dT0[0] + V[6] * dT0[1] + V[10] * dT0[2];
+    const float dJ11 = V[1] * dT1[0] + V[5] * dT1[1] + V[9] * dT1[2];
+    const float dJ12 = V[2] * dT1[0] + V[6] * dT1[1] + V[10] * dT1[2];
+    const float tzi = 1.f / e.tz, tz2 = tzi * tzi, tz3 = tz2 * tzi;
+    s.dtx = e.xmul * -f.focal_x * tz2 * dJ02;
+    s.dty = e.ymul * -f.focal_y * tz2 * dJ12;
+    s.dtz = -f.focal_x * tz2 * dJ00 - f.focal_y * tz2 * dJ11 + (2.f * f.focal_x * e.tx) * tz3 * dJ02 +
+            (2.f * f.focal_y * e.ty) * tz3 * dJ12;
+}
+
 GSR_HD void screen_chain_backward(const FrameK &f, const float *V, const Ewa &e, const float sg[9], ScreenChain &s)
 {
     // conic -> 2D covariance (stored gB is half the derivative wrt the scalar B, A.9 note)
@@ -489,16 +506,7 @@ GSR_HD void screen_chain_backward(const FrameK &f, const float *V, const Ewa &e,
     dT0[2] = 2.f * e.S0[2] * dL_da + e.S1[2] * dL_db;
     dT1[0] = 2.f * e.S1[0] * dL_dc + e.S0[0] * dL_db; dT1[1] = 2.f * e.S1[1] * dL_dc + e.S0[1] * dL_db;
     dT1[2] = 2.f * e.S1[2] * dL_dc + e.S0[2] * dL_db;
-    // dL/dJ (non-zeros of J) = dL/dT R_w2c^T
-    const float dJ00 = V[0] * dT0[0] + V[4] * dT0[1] + V[8] * dT0[2];
-    const float dJ02 = V[2] * dT0[0] + V[6] * dT0[1] + V[10] * dT0[2];
-    const float dJ11 = V[1] * dT1[0] + V[5] * dT1[1] + V[9] * dT1[2];
-    const float dJ12 = V[2] * dT1[0] + V[6] * dT1[1] + V[10] * dT1[2];
-    const float tzi = 1.f / e.tz, tz2 = tzi * tzi, tz3 = tz2 * tzi;
-    s.dtx = e.xmul * -f.focal_x * tz2 * dJ02;
-    s.dty = e.ymul * -f.focal_y * tz2 * dJ12;
-    s.dtz = -f.focal_x * tz2 * dJ00 - f.focal_y * tz2 * dJ11 + (2.f * f.focal_x * e.tx) * tz3 * dJ02 +
-            (2.f * f.focal_y * e.ty) * tz3 * dJ12;
+    jacobian_chain_backward(f, V, e, s);
 }
 
 // Homogeneous divide (A.2): ndc = (hx, hy) mw, so d ndc.x / d(hx, hw) = (mw, -mul1) and d ndc.y / d(hy, hw) = (mw, -mul2).
@@ -549,6 +557,24 @@ GSR_HD void sh_direction_backward(const FrameK &f, const float *campos, const fl
     dd[2] = (ddz - dzn * dot) * inv;
 }
 
+// Two steps of A.10 that the opacity compensation takes too.  The view term of dL/dmeans3D from dL/d(tx, ty, tz):
+GSR_HD void view_point_backward(const float *V, const ScreenChain &s, float dmean[3])
+{
+    dmean[0] = V[0] * s.dtx + V[1] * s.dty + V[2] * s.dtz;
+    dmean[1] = V[4] * s.dtx + V[5] * s.dty + V[6] * s.dtz;
+    dmean[2] = V[8] * s.dtx + V[9] * s.dty + V[10] * s.dtz;
+}
+
+// quat_to_rot back: gR = dL/dR (row-major, gR[3 i + j] = dL/dR[i][j]) -> dL/dq for the quaternion as given (not normalised here).
+GSR_HD void quat_to_rot_backward(const float quat[4], const float gR[9], float drot[4])
+{
+    const float r = quat[0], x = quat[1], y = quat[2], z = quat[3];
+    drot[0] = 2.f * (-z * gR[1] + y * gR[2] + z * gR[3] - x * gR[5] - y * gR[6] + x * gR[7]);
+    drot[1] = 2.f * (y * gR[1] + z * gR[2] + y * gR[3] - 2.f * x * gR[4] - r * gR[5] + z * gR[6] + r * gR[7] - 2.f * x * gR[8]);
+    drot[2] = 2.f * (-2.f * y * gR[0] + x * gR[1] + r * gR[2] + x * gR[3] + z * gR[5] - r * gR[6] + z * gR[7] - 2.f * y * gR[8]);
+    drot[3] = 2.f * (-2.f * z * gR[0] - r * gR[1] + x * gR[2] + r * gR[3] - 2.f * z * gR[4] + y * gR[5] + x * gR[6] + y * gR[7]);
+}
+
 // ---- A.10 for one visible Gaussian.  sg = (dmean2D.x, dmean2D.y, gA, gB, gC, dopacity, drgb[3]).
 // dsh, want_dsh, clamped: see sh_direction_backward.
 template <int DEG = -1>
@@ -573,9 +599,7 @@ GSR_HD void geom_backward_one(const FrameK &f, const float *V, const float *PV, 
     g.dcov[1] = 2.f * T[0] * T[1] * dL_da + (T[0] * T[4] + T[1] * T[3]) * dL_db + 2.f * T[3] * T[4] * dL_dc;
     g.dcov[2] = 2.f * T[0] * T[2] * dL_da + (T[0] * T[5] + T[2] * T[3]) * dL_db + 2.f * T[3] * T[5] * dL_dc;
     g.dcov[4] = 2.f * T[2] * T[1] * dL_da + (T[1] * T[5] + T[2] * T[4]) * dL_db + 2.f * T[4] * T[5] * dL_dc;
-    g.dmean[0] = V[0] * s.dtx + V[1] * s.dty + V[2] * s.dtz;
-    g.dmean[1] = V[4] * s.dtx + V[5] * s.dty + V[6] * s.dtz;
-    g.dmean[2] = V[8] * s.dtx + V[9] * s.dty + V[10] * s.dtz;
+    view_point_backward(V, s, g.dmean);
 
     // projection path
     float mw, mul1, mul2;
@@ -610,11 +634,7 @@ GSR_HD void geom_backward_one(const FrameK &f, const float *V, const float *PV, 
             }
             g.dscale[k] = ds;                     // scale_modifier factor omitted (A.10)
         }
-        const float r = quat[0], x = quat[1], y = quat[2], z = quat[3];
-        g.drot[0] = 2.f * (-z * gR[1] + y * gR[2] + z * gR[3] - x * gR[5] - y * gR[6] + x * gR[7]);
-        g.drot[1] = 2.f * (y * gR[1] + z * gR[2] + y * gR[3] - 2.f * x * gR[4] - r * gR[5] + z * gR[6] + r * gR[7] - 2.f * x * gR[8]);
-        g.drot[2] = 2.f * (-2.f * y * gR[0] + x * gR[1] + r * gR[2] + x * gR[3] + z * gR[5] - r * gR[6] + z * gR[7] - 2.f * y * gR[8]);
-        g.drot[3] = 2.f * (-2.f * z * gR[0] - r * gR[1] + x * gR[2] + r * gR[3] - 2.f * z * gR[4] + y * gR[5] + x * gR[6] + y * gR[7]);
+        quat_to_rot_backward(quat, gR, g.drot);
     }
 }
 
@@ -693,6 +713,122 @@ GSR_HD void activate_raw_backward(const RawAct &a, GeomGrad &g)
     const float dot = a.clamped_norm ? 0.f : a.q[0] * g.drot[0] + a.q[1] * g.drot[1] + a.q[2] * g.drot[2] + a.q[3] * g.drot[3];
     for (int k = 0; k < 4; ++k) g.drot[k] = (g.drot[k] - a.q[k] * dot) * a.inv_norm;
     g.dopacity *= a.opacity * (1.f - a.opacity);
+}
+
+// ---- Anti-aliasing as an opacity compensation (the 2D filter of Mip-Splatting, upstream's `antialiasing`).
+// The forward low-passes every splat by h = GSR_COV2D_DILATE on the diagonal of its 2D covariance; this factor pays the energy back:
+//   det0 = a0 c0 - b^2     det1 = (a0 + h)(c0 + h) - b^2 = det0 + h (a0 + c0) + h^2     (a0, b, c0: the entries BEFORE the dilation h)
+//   x = det0 / det1        rho = sqrt(max(GSR_AA_MIN_RATIO, x))        opacity' = opacity rho
+// The entries are formed from the 2x3 factor W = T R diag(scale_modifier s) of the 2D covariance W W^T (T of ewa_project: same
+// frustum clamp), not as e.a - h and not from Sigma: a0 = |W0|^2, c0 = |W1|^2, b = W0 . W1 are sums without a subtraction, and
+//   det0 = m01^2 + m02^2 + m12^2,   m_kl = W0_k W1_l - W0_l W1_k   (Cauchy-Binet)
+// is a sum of squares where a0 c0 - b^2 cancels all but one part in (aspect ratio)^2 of its terms: for a needle a hundred times
+// longer than wide that is every bit of binary32.  The gradient goes back the same way, through W: to the scales directly, to
+// the rotation through dL/dR (quat_to_rot_backward), to means3D through dL/dT (jacobian_chain_backward, view_point_backward).
+// A Gaussian the preprocess culls before it has a covariance (A.1), or one with det1 == 0, passes through (rho = 1 exactly).
+struct AaFactor {
+    float R[9], s[3];           // rotation matrix, scale_modifier * scale
+    float u[3], v[3];           // T0 . R[:, k], T1 . R[:, k]:  W0_k = u_k s_k, W1_k = v_k s_k
+    float w0[3], w1[3];         // rows of W
+    float m01, m02, m12;        // 2x2 minors of W
+    float tr, det0, det1, rho;  // tr = a0 + c0
+    bool pass, clamped;         // pass: rho = 1, no geometry gradient; clamped: x <= GSR_AA_MIN_RATIO, rho is the constant
+};
+
+GSR_HD void aa_factor(const FrameK &f, const float *V, const float p[3], const float *scale, const float *quat, Ewa &e, AaFactor &a)
+{
+    a.pass = true; a.clamped = false; a.rho = 1.f;
+    if (!(view_coord(p, V, 2) > (float)GSR_NEAR_CUT)) return;                   // A.1, as in_frustum below
+    ewa_of_gaussian(f, V, p, scale, quat, nullptr, e);
+    quat_to_rot(quat, a.R);
+    for (int k = 0; k < 3; ++k) {
+        a.s[k] = f.scale_modifier * scale[k];
+        a.u[k] = e.T[0] * a.R[k] + e.T[1] * a.R[3 + k] + e.T[2] * a.R[6 + k];
+        a.v[k] = e.T[3] * a.R[k] + e.T[4] * a.R[3 + k] + e.T[5] * a.R[6 + k];
+        a.w0[k] = a.u[k] * a.s[k];
+        a.w1[k] = a.v[k] * a.s[k];
+    }
+    a.m01 = a.w0[0] * a.w1[1] - a.w0[1] * a.w1[0];
+    a.m02 = a.w0[0] * a.w1[2] - a.w0[2] * a.w1[0];
+    a.m12 = a.w0[1] * a.w1[2] - a.w0[2] * a.w1[1];
+    const float h = (float)GSR_COV2D_DILATE;
+    a.tr = (a.w0[0] * a.w0[0] + a.w0[1] * a.w0[1] + a.w0[2] * a.w0[2]) + (a.w1[0] * a.w1[0] + a.w1[1] * a.w1[1] + a.w1[2] * a.w1[2]);
+    a.det0 = a.m01 * a.m01 + a.m02 * a.m02 + a.m12 * a.m12;
+    a.det1 = a.det0 + h * a.tr + h * h;
+    if (a.det1 == 0.f) return;
+    a.pass = false;
+    const float x = a.det0 / a.det1;
+    a.clamped = !(x > (float)GSR_AA_MIN_RATIO);
+    a.rho = sqrtf(a.clamped ? (float)GSR_AA_MIN_RATIO : x);
+}
+
+// scale, quat, opacity: the ACTIVATED values.  logit (raw mode; else null): the opacity's logit; the result is then the logit of
+// p' = opacity rho, written as log p' - log(1 - p').
+GSR_HD float opacity_compensation_one(const FrameK &f, const float *V, const float p[3], const float *scale, const float *quat,
+                                      float opacity, const float *logit)
+{
+    Ewa e;
+    AaFactor a;
+    aa_factor(f, V, p, scale, quat, e, a);
+    if (a.pass) return logit ? *logit : opacity;
+    const float pp = opacity * a.rho;
+    return logit ? logf(pp) - log1pf(-pp) : pp;
+}
+
+// gin: dL/dopacity' (raw mode: dL/dlogit').  Writes g.dopacity, g.dmean, g.dscale, g.drot: with `act` (raw mode: what activate_raw
+// made of this Gaussian) they are the gradients on the logit, the log-scales and the raw quaternion,
+//   dlogit'/dlogit = (1 - p) / (1 - p')      dlogit'/drho = 1 / (rho (1 - p'))
+// else on the activated values.  As in geom_backward_one, a clamped tx (ty) passes nothing (xmul / ymul) and g.dscale is the
+// gradient on scale_modifier * scale (A.10 omits the factor): the two backwards add up on the same tensors.  No camera gradient.
+GSR_HD void opacity_compensation_backward_one(const FrameK &f, const float *V, const float p[3], const float *scale, const float *quat,
+                                              float opacity, const RawAct *act, float gin, GeomGrad &g)
+{
+    Ewa e;
+    AaFactor a;
+    aa_factor(f, V, p, scale, quat, e, a);
+    for (int k = 0; k < 3; ++k) { g.dmean[k] = 0.f; g.dscale[k] = 0.f; }
+    for (int k = 0; k < 4; ++k) g.drot[k] = 0.f;
+    g.dopacity = gin;
+    if (a.pass) return;
+    float dL_drho;
+    if (act) {
+        const float inv = 1.f / (1.f - opacity * a.rho);
+        g.dopacity = gin * ((1.f - opacity) * inv);
+        dL_drho = gin * (inv / a.rho);
+    } else {
+        g.dopacity = gin * a.rho;
+        dL_drho = gin * opacity;
+    }
+    if (a.clamped) return;
+    // x = det0 / (det0 + h tr + h^2):  dx/ddet0 = (det1 - det0) / det1^2 = h (tr + h) / det1^2,  dx/dtr = -h det0 / det1^2
+    const float h = (float)GSR_COV2D_DILATE;
+    const float k = dL_drho * h / (2.f * a.rho * a.det1 * a.det1);       // dL/dx h / det1^2
+    const float kd = 2.f * k * (a.tr + h), kt = -2.f * k * a.det0;       // twice dL/ddet0, dL/dtr: det0 and tr are quadratic in W
+    const float dw0[3] = {kd * (a.m01 * a.w1[1] + a.m02 * a.w1[2]) + kt * a.w0[0], kd * (a.m12 * a.w1[2] - a.m01 * a.w1[0]) + kt * a.w0[1],
+                          kt * a.w0[2] - kd * (a.m02 * a.w1[0] + a.m12 * a.w1[1])};
+    const float dw1[3] = {kt * a.w1[0] - kd * (a.m01 * a.w0[1] + a.m02 * a.w0[2]), kd * (a.m01 * a.w0[0] - a.m12 * a.w0[2]) + kt * a.w1[1],
+                          kd * (a.m02 * a.w0[0] + a.m12 * a.w0[1]) + kt * a.w1[2]};
+    // W0_k = u_k s_k, u_k = sum_j T0_j R[j][k]
+    ScreenChain s;
+    float gR[9];
+    for (int j = 0; j < 3; ++j) { s.dT0[j] = 0.f; s.dT1[j] = 0.f; }
+    for (int c = 0; c < 3; ++c) {
+        g.dscale[c] = dw0[c] * a.u[c] + dw1[c] * a.v[c];
+        const float du = dw0[c] * a.s[c], dv = dw1[c] * a.s[c];
+        for (int j = 0; j < 3; ++j) {
+            s.dT0[j] += du * a.R[3 * j + c];
+            s.dT1[j] += dv * a.R[3 * j + c];
+            gR[3 * j + c] = e.T[j] * du + e.T[3 + j] * dv;
+        }
+    }
+    quat_to_rot_backward(quat, gR, g.drot);
+    jacobian_chain_backward(f, V, e, s);
+    view_point_backward(V, s, g.dmean);
+    if (act) {
+        const float keep = g.dopacity;
+        activate_raw_backward(*act, g);
+        g.dopacity = keep;
+    }
 }
 
 // ---- The latent structured model's composition (scene/latent_gaussian_model.py forward): child k of structure b is the

@@ -19,6 +19,12 @@ also returns dL/dviewmatrix, dL/dprojmatrix and dL/dcampos (camera_grads_wanted)
 row-vector convention it is consumed in; they are separate gradients, chained by the caller's own torch graph to its pose
 parametrisation (scene.cameras.camera_with_pose_delta is one).  Two more launches, sums in a fixed order; off: the plain call.
 
+Extension: GaussianRasterizer(raster_settings, antialiasing=True) is upstream's anti-aliasing switch (the 2D filter of Mip-Splatting):
+every opacity is scaled by sqrt(det cov2D / det(cov2D + 0.3 I)) by one differentiable per-Gaussian op in front of the rasterizer
+(antialias.compensate_opacity), which then runs exactly as without it; the depth and alpha maps use the compensated opacity too.
+Refused with a ValueError: cov3D_precomp, and a viewmatrix / projmatrix / campos that requires grad (rho's camera gradient is not
+computed).  Off (the default): no extra launch, the same bits.
+
 Autograd contract (train.py:106, scene/gaussian_model.py:415-417): gradients for
 (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, None) in that order;
 `means2D.grad[:, :2]` is dL/d(NDC position) with the W/2, H/2 pixel scale folded in, `[:, 2] = 0`.
@@ -645,11 +651,13 @@ def _match_getters(means3D, opacities, shs, scales, rotations):
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings: GaussianRasterizationSettings, depth_alpha: bool = False):
-        """depth_alpha=True (extension): forward / forward_raw also return the depth and alpha maps [1,H,W] (module docstring)."""
+    def __init__(self, raster_settings: GaussianRasterizationSettings, depth_alpha: bool = False, antialiasing: bool = False):
+        """depth_alpha=True (extension): forward / forward_raw also return the depth and alpha maps [1,H,W] (module docstring).
+        antialiasing=True (upstream's flag): the opacities are compensated for the 0.3 px^2 dilation first (module docstring)."""
         super().__init__()
         self.raster_settings = raster_settings
         self.depth_alpha = bool(depth_alpha)
+        self.antialiasing = bool(antialiasing)
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         """Frustum test per point (the reference's `_C.mark_visible`; unused in-tree, kept for API parity)."""
@@ -671,6 +679,12 @@ class GaussianRasterizer(nn.Module):
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+        if self.antialiasing:
+            if cov3D_precomp is not None:
+                raise ValueError("antialiasing needs scales and rotations: the opacity compensation's gradient goes to them, not to a "
+                                 "precomputed 3D covariance")
+            from .antialias import compensate_opacity
+            opacities = compensate_opacity(opacities, means3D, scales, rotations, rs)
         empty = torch.empty(0, dtype=torch.float32, device=means3D.device)
         shs = empty if shs is None else shs
         colors_precomp = empty if colors_precomp is None else colors_precomp
@@ -694,6 +708,9 @@ class GaussianRasterizer(nn.Module):
         same gradients on the raw parameters as autograd through those getters, to fp32 rounding."""
         rs = self.raster_settings
         rs = rs._replace(sh_degree=int(rs.sh_degree), image_height=int(rs.image_height), image_width=int(rs.image_width))
+        if self.antialiasing:
+            from .antialias import compensate_opacity
+            opacity_logits = compensate_opacity(opacity_logits, xyz, log_scales, raw_rotations, rs, raw=True)
         packed = features_rest is None and features_dc.dim() == 3 and features_dc.shape[1] > 1      # one [P,M,3] table
         if not packed and (features_rest is None or features_rest.numel() == 0):
             features_rest = torch.empty(0, dtype=torch.float32, device=xyz.device)

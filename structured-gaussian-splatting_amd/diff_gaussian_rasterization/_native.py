@@ -103,7 +103,8 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_workspace_sizes", "gsr_binning_
            "gsr_activations_forward", "gsr_activations_backward",
            "gsr_aux_workspace_size", "gsr_forward_aux", "gsr_forward_render_aux", "gsr_backward_render_aux", "gsr_backward_geom_aux",
            "gsr_camera_grad_workspace_size", "gsr_backward_camera",
-           "gsr_structured_compose_forward", "gsr_structured_compose_backward")
+           "gsr_structured_compose_forward", "gsr_structured_compose_backward",
+           "gsr_opacity_compensation_forward", "gsr_opacity_compensation_backward")
 
 _lib = None
 
@@ -585,4 +586,33 @@ def structured_compose_backward(decoded, means, opacities, scales, rotations, K:
     with torch.cuda.device(decoded.device):
         _check(load().gsr_structured_compose_backward(C.byref(desc), _ptr(decoded), C.byref(st), C.byref(gin), C.byref(gout),
                                                       _stream(decoded.device)), "gsr_structured_compose_backward")
+    return tuple(outs)
+
+
+def opacity_compensation_forward(desc: FrameDesc, viewmatrix, means3D, opacities, scales, rotations, raw: bool):
+    """gsr_opacity_compensation_forward: contiguous fp32 tensors on one device -> the compensated opacities, shaped like `opacities`
+    (raw: logits in, logits out)."""
+    out = torch.empty_like(opacities)
+    if desc.P == 0:
+        return out
+    cam = Camera(None, _ptr(viewmatrix), None, None)
+    g = Gaussians(_ptr(means3D), None, None, _ptr(opacities), _ptr(scales), _ptr(rotations), None, None, 2 if raw else 0)
+    with torch.cuda.device(means3D.device):
+        _check(load().gsr_opacity_compensation_forward(C.byref(desc), C.byref(cam), C.byref(g), _ptr(out), _stream(means3D.device)),
+               "gsr_opacity_compensation_forward")
+    return out
+
+
+def opacity_compensation_backward(desc: FrameDesc, viewmatrix, means3D, opacities, scales, rotations, raw: bool, grad_out, want):
+    """gsr_opacity_compensation_backward.  grad_out: dL/d(compensated opacities), contiguous; want: four booleans for (opacities,
+    means3D, scales, rotations).  Returns the four gradients in that order, None where not wanted."""
+    outs = [torch.empty_like(t) if w else None for t, w in zip((opacities, means3D, scales, rotations), want)]
+    if desc.P == 0 or not any(want):
+        return tuple(outs)
+    cam = Camera(None, _ptr(viewmatrix), None, None)
+    g = Gaussians(_ptr(means3D), None, None, _ptr(opacities), _ptr(scales), _ptr(rotations), None, None, 2 if raw else 0)
+    grads = Grads(_ptr(outs[1]), None, None, None, _ptr(outs[0]), _ptr(outs[2]), _ptr(outs[3]), None, None, 0)
+    with torch.cuda.device(means3D.device):
+        _check(load().gsr_opacity_compensation_backward(C.byref(desc), C.byref(cam), C.byref(g), _ptr(grad_out), C.byref(grads),
+                                                        _stream(means3D.device)), "gsr_opacity_compensation_backward")
     return tuple(outs)

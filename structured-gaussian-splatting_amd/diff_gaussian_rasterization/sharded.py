@@ -453,6 +453,9 @@ class ShardedRenderer:
         import math
 
         from . import GaussianRasterizationSettings
+        if getattr(pipe, "antialiasing", False):
+            raise ValueError("pipe.antialiasing is not supported by ShardedRenderer: the opacity compensation is wired into "
+                             "GaussianRasterizer only, the sharded slabs would render uncompensated (render unsharded, or turn it off)")
         xyz = pc.get_xyz
         screenspace_points = torch.zeros_like(xyz, requires_grad=True)     # a leaf keeps its .grad (gaussian_renderer.render)
         rs = GaussianRasterizationSettings(

@@ -55,3 +55,4 @@ class Pipe:
     compute_cov3D_python = False
     debug = False
     fused_activations = None       # extension, see gaussian_renderer.render: None = only for this package's scene.GaussianModel
+    antialiasing = False           # upstream's flag: compensate the opacity for the 0.3 px^2 dilation (gaussian_renderer.render)

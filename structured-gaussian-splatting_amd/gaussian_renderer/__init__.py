@@ -9,6 +9,9 @@ Extension: `pipe.fused_activations` (not a reference flag). 
 (GaussianRasterizer.forward_raw) — same image, same gradients on the parameters, without the ~30 torch kernels of the getters
 and their backward.  Unset (None, the default): that path for this package's scene.GaussianModel (whose SH coefficients are
 one interleaved leaf `_features`: raw mode 2), the getters for any other store.  False: always the getters.
+
+`pipe.antialiasing` (upstream's flag; absent or False: off) turns on the rasterizer's opacity compensation for the 0.3 px^2
+dilation (diff_gaussian_rasterization.antialias), on the fused path and the getter path alike.
 """
 import math
 
@@ -70,7 +73,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         bg=bg_color, scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_view_transform,
         projmatrix=viewpoint_camera.full_proj_transform, sh_degree=pc.active_sh_degree,
         campos=viewpoint_camera.camera_center, prefiltered=False, debug=pipe.debug)
-    rasterizer = GaussianRasterizer(raster_settings=raster_settings, depth_alpha=depth_alpha)
+    rasterizer = GaussianRasterizer(raster_settings=raster_settings, depth_alpha=depth_alpha,
+                                    antialiasing=getattr(pipe, "antialiasing", False))
 
     def result(out):
         d = {"render": out[0], "viewspace_points": screenspace_points, "visibility_filter": out[1] > 0, "radii": out[1]}
