@@ -451,6 +451,29 @@ int gsr_opacity_compensation_forward(const gsr_frame_desc *desc, const gsr_camer
 int gsr_opacity_compensation_backward(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g,
                                       const float *grad_opacities_out, const gsr_grads *grads, void *stream);
 
+/* ---- The latent structured model's decoder (scene/latent_gaussian_model.py: Decoder), additive: every call above keeps its
+ * meaning.  For each of B structures, with x = (pos_emb[b], latents[b]) of in_size floats (the positional dims in FRONT):
+ *   h1 = relu(w0 x + b0)      h2 = relu((w1 h1 + b1) + h1)      decoded[b] = w2 h2 + b2
+ * Weights have nn.Linear's layout: w0 [hidden, in_size], w1 [hidden, hidden], w2 [out_size, hidden], biases [rows].  pos_emb is
+ * [B, in_size - latent_size], NULL exactly when in_size == latent_size; latents [B, latent_size]; decoded [B, out_size]; all
+ * contiguous fp32.  Supported: hidden_size == 32, 1 <= latent_size <= in_size <= 128, 1 <= out_size <= 2^20, 0 <= B <= 2^30 (0: nothing is
+ * launched); anything else is GSR_ERR_INVALID_ARGUMENT.  w1 and w2 must be 16-byte aligned.  Every product is an exact-f32 MFMA:
+ * a fused multiply-add chain in ascending k that starts from the bias.
+ * The backward recomputes h1 and h2 from the inputs (the forward saves nothing) and passes a gradient where the pre-activation is
+ * > 0.  d_decoded [B, out_size] is required; pos_emb gets no gradient.  Each field of gsr_decoder_grads may be NULL (not wanted:
+ * it costs nothing); the wanted ones are written in full.  The weight and bias gradients are sums over B: every block of
+ * k_decoder_bwd walks a contiguous range of structures in ascending order and writes one partial to `workspace`
+ * (gsr_decoder_workspace_size bytes, a function of the desc only; 16-byte aligned; may be NULL when only grads->latents is
+ * wanted), and k_decoder_reduce adds the partials in ascending block order.  No atomics: the same inputs give the same bits. */
+typedef struct gsr_decoder_desc   { int32_t B, in_size, latent_size, hidden_size, out_size; } gsr_decoder_desc;
+typedef struct gsr_decoder_params { const float *w0, *b0, *w1, *b1, *w2, *b2; } gsr_decoder_params; /* nn.Linear layouts: w [out,in] */
+typedef struct gsr_decoder_grads  { float *latents, *w0, *b0, *w1, *b1, *w2, *b2; } gsr_decoder_grads; /* NULL = not wanted */
+int gsr_decoder_workspace_size(const gsr_decoder_desc *desc, size_t *bytes);
+int gsr_decoder_forward(const gsr_decoder_desc *desc, const float *pos_emb, const float *latents, const gsr_decoder_params *params,
+                        float *decoded, void *stream);
+int gsr_decoder_backward(const gsr_decoder_desc *desc, const float *pos_emb, const float *latents, const gsr_decoder_params *params,
+                         const float *d_decoded, const gsr_decoder_grads *grads, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- the densification bookkeeping of one training iteration (train.py:127-130,
  * scene/gaussian_model.py:415-417) in one pass without a host synchronisation: for every Gaussian with
  * radii[i] > 0:  max_radii2D[i] = max(max_radii2D[i], radii[i]);  xyz_gradient_accum[i] += |viewspace_grad[i, :2]|;

@@ -76,6 +76,22 @@ class StructuredGrads(C.Structure):
     _fields_ = [("decoded", _f32p), ("means", _f32p), ("opacities", _f32p), ("scales", _f32p), ("rotations", _f32p)]
 
 
+class DecoderDesc(C.Structure):
+    """gsr_decoder_desc: B structures, an input row of in_size = positional dims + latent_size floats, out_size outputs."""
+    _fields_ = [("B", C.c_int32), ("in_size", C.c_int32), ("latent_size", C.c_int32), ("hidden_size", C.c_int32),
+                ("out_size", C.c_int32)]
+
+
+class DecoderParams(C.Structure):
+    """gsr_decoder_params: nn.Linear layouts, w [out, in]."""
+    _fields_ = [("w0", _f32p), ("b0", _f32p), ("w1", _f32p), ("b1", _f32p), ("w2", _f32p), ("b2", _f32p)]
+
+
+class DecoderGrads(C.Structure):
+    """gsr_decoder_grads: NULL = not wanted."""
+    _fields_ = [("latents", _f32p), ("w0", _f32p), ("b0", _f32p), ("w1", _f32p), ("b1", _f32p), ("w2", _f32p), ("b2", _f32p)]
+
+
 MAX_CHUNKS = 8
 LAST_SHIFT = 26
 
@@ -104,7 +120,8 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_workspace_sizes", "gsr_binning_
            "gsr_aux_workspace_size", "gsr_forward_aux", "gsr_forward_render_aux", "gsr_backward_render_aux", "gsr_backward_geom_aux",
            "gsr_camera_grad_workspace_size", "gsr_backward_camera",
            "gsr_structured_compose_forward", "gsr_structured_compose_backward",
-           "gsr_opacity_compensation_forward", "gsr_opacity_compensation_backward")
+           "gsr_opacity_compensation_forward", "gsr_opacity_compensation_backward",
+           "gsr_decoder_workspace_size", "gsr_decoder_forward", "gsr_decoder_backward")
 
 _lib = None
 
@@ -615,4 +632,48 @@ def opacity_compensation_backward(desc: FrameDesc, viewmatrix, means3D, opacitie
     with torch.cuda.device(means3D.device):
         _check(load().gsr_opacity_compensation_backward(C.byref(desc), C.byref(cam), C.byref(g), _ptr(grad_out), C.byref(grads),
                                                         _stream(means3D.device)), "gsr_opacity_compensation_backward")
+    return tuple(outs)
+
+
+def decoder_desc(latents, w0, w2) -> DecoderDesc:
+    """The desc of one decoder call from its tensors: latents [B, L], w0 [hidden, IN], w2 [OUT, hidden]."""
+    return DecoderDesc(int(latents.shape[0]), int(w0.shape[1]), int(latents.shape[1]), int(w0.shape[0]), int(w2.shape[0]))
+
+
+def decoder_workspace_size(desc: DecoderDesc) -> int:
+    b = C.c_size_t(0)
+    _check(load().gsr_decoder_workspace_size(C.byref(desc), C.byref(b)), "gsr_decoder_workspace_size")
+    return b.value
+
+
+def decoder_forward(pos_emb, latents, params):
+    """gsr_decoder_forward: pos_emb [B, IN - L] or None, latents [B, L], params = (w0, b0, w1, b1, w2, b2), contiguous fp32 on
+    one device -> decoded [B, OUT]."""
+    desc = decoder_desc(latents, params[0], params[4])
+    decoded = torch.empty(desc.B, desc.out_size, dtype=torch.float32, device=latents.device)
+    pr = DecoderParams(*(_ptr(t) for t in params))
+    with torch.cuda.device(latents.device):
+        _check(load().gsr_decoder_forward(C.byref(desc), _ptr(pos_emb), _ptr(latents), C.byref(pr), _ptr(decoded),
+                                          _stream(latents.device)), "gsr_decoder_forward")
+    return decoded
+
+
+def decoder_backward(pos_emb, latents, params, d_decoded, want):
+    """gsr_decoder_backward.  d_decoded [B, OUT] contiguous; want: seven booleans for (latents, w0, b0, w1, b1, w2, b2).  Returns the
+    seven gradients in that order, None where not wanted.  The workspace is a torch allocation that lives for the call."""
+    desc = decoder_desc(latents, params[0], params[4])
+    outs = [torch.empty_like(t) if w else None for t, w in zip((latents,) + tuple(params), want)]
+    if not any(want):
+        return tuple(outs)
+    if desc.B == 0:
+        return tuple(None if o is None else o.zero_() for o in outs)
+    ws, nbytes = None, 0
+    if any(want[1:]):
+        nbytes = decoder_workspace_size(desc)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=latents.device)
+    pr = DecoderParams(*(_ptr(t) for t in params))
+    gr = DecoderGrads(*(_ptr(t) for t in outs))
+    with torch.cuda.device(latents.device):
+        _check(load().gsr_decoder_backward(C.byref(desc), _ptr(pos_emb), _ptr(latents), C.byref(pr), _ptr(d_decoded), C.byref(gr),
+                                           _ptr(ws), C.c_size_t(nbytes), _stream(latents.device)), "gsr_decoder_backward")
     return tuple(outs)

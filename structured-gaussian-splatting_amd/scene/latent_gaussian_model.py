@@ -5,6 +5,8 @@ quaternions normalised, multiplied and standardised).  The composed children are
 
 Same constructor, parameter and buffer names (checkpoints move both ways through state_dict / load_state_dict), initial values,
 decoder and composition rules as the reference class.  Laid out for this package's rasterizer:
+  * the decoder is torch ops by default; `native_decode = True` (or None) runs it as ONE HIP launch forward and two backward on
+    the same parameters (diff_gaussian_rasterization.decoder.decode_structures);
   * the composition is ONE HIP launch forward and one backward (diff_gaussian_rasterization.structured.compose_structures)
     instead of about twenty torch kernels each way; host tensors take the same rules as torch ops;
   * its results `_xyz, _opacity, _scaling, _rotation` and ONE interleaved SH table `_features` [P,M,3] (`_features_dc` /
@@ -90,6 +92,9 @@ class LatentGaussianModel(nn.Module):
         self.freeze_structure_rotations = self.freeze_structure_opacities = False
         self.freeze_means = self.freeze_scales = self.freeze_rotations = self.freeze_opacities = False
         self.native_compose = None           # None: the HIP composition for GPU tensors, torch ops for host tensors; False: torch ops
+        # False: self.decoder as torch ops; True: the fused HIP decoder (diff_gaussian_rasterization.decoder.decode_structures) on the
+        # same parameters, an error where it does not apply; None: the HIP decoder where it applies, torch ops elsewhere
+        self.native_decode = False
         self._decoded = self._xyz = self._opacity = self._scaling = self._rotation = self._features = None
         self._acts = ActivationCache()
         self.optimizer = None
@@ -117,7 +122,13 @@ class LatentGaussianModel(nn.Module):
         pos = None
         if self.use_positional_embedding:
             pos = positional_embedding(self.structure_means.detach(), self.positional_embedding_multires)
-        decoded = self.decoder(latents, pos)
+        if self.native_decode is False:
+            decoded = self.decoder(latents, pos)
+        else:
+            from diff_gaussian_rasterization.decoder import decode_structures
+            d = self.decoder
+            decoded = decode_structures(latents, d.lin0.weight, d.lin0.bias, d.lin1.weight, d.lin1.bias, d.lin2.weight, d.lin2.bias,
+                                        pos_emb=pos, native=self.native_decode)
         B, K, D = self.num_structures, self.gaussians_per_structure, self.gaussian_parameters_size
         assert tuple(decoded.shape) == (B, K * D)
         held = lambda p, frozen: p.detach() if frozen else p
