@@ -80,7 +80,8 @@ typedef struct gsr_frame_plan {
     int64_t binning_capacity;                     /* IN to gsr_forward_render (and the backward): instances the binning
                                                      workspace was sized for (gsr_binning_size of that number); 0 = R   */
     uint32_t chunk_key_end[GSR_MAX_CHUNKS];       /* chunk c = visible Gaussians whose depth bits lie in (key_end[c-1], key_end[c]]:
-                                                     the chunks are SELECTED by depth; each is sorted when it is binned  */
+                                                     the chunks are SELECTED by depth; each is sorted when it is binned.
+                                                     The last planned chunk's end, and every entry behind it, is 0xFFFFFFFE  */
     int32_t chunks_sorted;                        /* chunks [0, chunks_sorted) of the depth order are already sorted: a re-run of
                                                      gsr_forward_render (after GSR_ERR_WORKSPACE) does not sort them again   */
     int32_t chunks_filtered;                      /* bit c: chunk c was put through the live filter (only the Gaussians that can still

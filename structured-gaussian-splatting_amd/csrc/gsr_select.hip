@@ -153,6 +153,7 @@ __device__ void sel_plan2(unsigned long long first_mass, const SelState *st, Ctr
             }
         }
         if (cnt <= begin) continue;
+        if (cnt >= V) key = 0xFFFFFFFEu;                         // the last chunk ends at "everything", also when a boundary's bin holds the rest
         const unsigned long long full = tiles - begin_tiles;
         p_key[n] = key; p_cnt[n] = cnt; p_full[n] = full > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)full;
         begin = cnt; begin_tiles = tiles;
