@@ -387,6 +387,18 @@ typedef struct gsr_adam_tensor {
 } gsr_adam_tensor;
 int gsr_adam_step_multi(int32_t count, const gsr_adam_tensor *tensors, float beta1, float beta2, float eps, void *stream);
 
+/* The same step over the rows a frame saw (upstream's optimizer_type = "sparse_adam"), still ONE launch.  Every tensor has `rows`
+ * rows: n = rows * w with a width w >= 1 of its own, and row_len is 0 or w.  visible: DEVICE array of one entry per row, of
+ * visible_elem_bytes = 1 (bool / uint8, non-zero = visible) or 4 (int32, > 0 = visible: the rasterizer's radii as they are).
+ * An element of a visible row steps exactly as in gsr_adam_step_multi (an all-visible mask gives the same bits); of a hidden row,
+ * param, exp_avg and exp_avg_sq keep their bits and grad is not read.  `step` counts every call, whatever the mask showed: it
+ * enters the bias corrections only.  step = GSR_ADAM_STEP_UNCORRECTED applies none (step size lr, second moment as it is), which is
+ * upstream's arithmetic.  rows == 0, count == 0 and an all-hidden mask touch nothing. */
+#define GSR_ADAM_STEP_UNCORRECTED INT64_MAX
+int gsr_adam_step_sparse_multi(int32_t count, const gsr_adam_tensor *tensors, int64_t rows,
+                               const void *visible, int32_t visible_elem_bytes,
+                               float beta1, float beta2, float eps, void *stream);
+
 /* ---- the activations between the optimizer's raw parameters and the rasterizer's inputs, the
  * getters of scene/gaussian_model.py:101-125 (setup_functions :47-60):
  *   scales [P,3] = exp(scaling_raw)   rotations [P,4] = rotation_raw / max(|rotation_raw|_2, 1e-12)   opacities [P] = sigmoid(opacity_raw)

@@ -115,7 +115,7 @@ class DebugViews(C.Structure):
 EXPORTS = ("gsr_version", "gsr_last_error", "gsr_workspace_sizes", "gsr_binning_size", "gsr_binning_first_chunk_capacity", "gsr_forward_preprocess", "gsr_forward",
            "gsr_forward_render", "gsr_bwd_segment_entries", "gsr_backward_rows_size", "gsr_backward_prepare", "gsr_backward_render", "gsr_backward_geom", "gsr_backward_geom_rows", "gsr_frame_arrays", "gsr_exchange_rows_gather", "gsr_exchange_rows_scatter", "gsr_mark_visible", "gsr_debug_get_views", "gsr_profile_enable",
            "gsr_profile_read", "gsr_loss_workspace_size", "gsr_loss_l1_ssim_forward", "gsr_loss_l1_ssim_backward", "gsr_loss_l1_ssim_forward_rows", "gsr_loss_l1_ssim_backward_rows", "gsr_loss_l1_backward",
-           "gsr_debug_sort_temp_bytes", "gsr_debug_sort_pairs", "gsr_debug_sort_pairs_ex", "gsr_dist2_workspace_size", "gsr_dist2_knn3", "gsr_adam_step", "gsr_adam_step_split", "gsr_adam_step_multi", "gsr_densify_stats",
+           "gsr_debug_sort_temp_bytes", "gsr_debug_sort_pairs", "gsr_debug_sort_pairs_ex", "gsr_dist2_workspace_size", "gsr_dist2_knn3", "gsr_adam_step", "gsr_adam_step_split", "gsr_adam_step_multi", "gsr_adam_step_sparse_multi", "gsr_densify_stats",
            "gsr_activations_forward", "gsr_activations_backward",
            "gsr_aux_workspace_size", "gsr_forward_aux", "gsr_forward_render_aux", "gsr_backward_render_aux", "gsr_backward_geom_aux",
            "gsr_camera_grad_workspace_size", "gsr_backward_camera",
@@ -544,6 +544,26 @@ def adam_step_multi(items, beta1, beta2, eps):
         a.lr, a.lr_tail, a.step, a.row_len, a.split = float(lr), float(lr_tail), int(step), int(row_len), int(split)
     _check(load().gsr_adam_step_multi(C.c_int32(len(items)), arr, C.c_float(beta1), C.c_float(beta2), C.c_float(eps),
                                       _stream(items[0][0].device)), "gsr_adam_step_multi")
+
+
+ADAM_STEP_UNCORRECTED = 2 ** 63 - 1        # GSR_ADAM_STEP_UNCORRECTED: a `step` that applies no bias correction
+
+
+def adam_step_sparse_multi(items, visible, beta1, beta2, eps):
+    """adam_step_multi over the rows that `visible` [rows] marks (gsr_adam_step_sparse_multi): bool / uint8 (non-zero) or int32
+    (> 0, the rasterizer's radii) on the tensors' device; every param is [rows, ...].  A hidden row keeps param and both moments."""
+    if visible.dtype not in (torch.bool, torch.uint8, torch.int32) or visible.dim() != 1:
+        raise TypeError(f"adam_step_sparse_multi: visible must be a [rows] bool, uint8 or int32 tensor, got {visible.dtype} {tuple(visible.shape)}")
+    if visible.device != items[0][0].device:
+        raise ValueError(f"adam_step_sparse_multi: visible is on {visible.device}, the tensors on {items[0][0].device}")
+    visible = visible.contiguous()
+    arr = (AdamTensor * len(items))()
+    for a, (p, g, m, v, lr, lr_tail, step, row_len, split) in zip(arr, items):
+        a.param, a.grad, a.exp_avg, a.exp_avg_sq, a.n = _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel()
+        a.lr, a.lr_tail, a.step, a.row_len, a.split = float(lr), float(lr_tail), int(step), int(row_len), int(split)
+    _check(load().gsr_adam_step_sparse_multi(C.c_int32(len(items)), arr, C.c_int64(visible.shape[0]), _ptr(visible),
+                                             C.c_int32(visible.element_size()), C.c_float(beta1), C.c_float(beta2), C.c_float(eps),
+                                             _stream(items[0][0].device)), "gsr_adam_step_sparse_multi")
 
 
 def activations_forward(scaling_raw, rotation_raw, opacity_raw):

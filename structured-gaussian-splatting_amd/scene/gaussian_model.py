@@ -67,6 +67,7 @@ class OptimizationDefaults:
     densify_until_iter: int = 15_000
     densify_grad_threshold: float = 0.0002
     random_background: bool = False
+    optimizer_type: str = "default"           # "sparse_adam": step only the Gaussians the frame saw (fused_adam.SparseFusedAdam)
 
 
 def expon_lr(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1_000_000):
@@ -203,8 +204,12 @@ class GaussianModel:
                 groups.append({"params": [], "lr": lrs[k], "name": k})
             else:
                 groups.append({"params": [self._t[k]], "lr": lrs[k], "name": k})
-        from fused_adam import FusedAdam              # torch.optim.Adam's arithmetic and state layout; one HIP kernel per tensor
-        self.optimizer = FusedAdam(groups, lr=0.0, eps=1e-15, native=getattr(opt, "fused_adam", True) and self.device.type == "cuda")
+        from fused_adam import FusedAdam, SparseFusedAdam   # torch.optim.Adam's arithmetic and state layout; one HIP launch per step
+        kind = getattr(opt, "optimizer_type", "default")
+        if kind not in ("default", "sparse_adam"):
+            raise ValueError(f"optimizer_type = {kind!r}: \"default\" or \"sparse_adam\"")
+        cls = SparseFusedAdam if kind == "sparse_adam" else FusedAdam
+        self.optimizer = cls(groups, lr=0.0, eps=1e-15, native=getattr(opt, "fused_adam", True) and self.device.type == "cuda")
         self._xyz_lr = expon_lr(opt.position_lr_init * self.spatial_lr_scale, opt.position_lr_final * self.spatial_lr_scale,
                                 lr_delay_mult=opt.position_lr_delay_mult, max_steps=opt.position_lr_max_steps)
 

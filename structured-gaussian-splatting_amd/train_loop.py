@@ -5,6 +5,7 @@ import random
 
 import torch
 
+from fused_adam import SparseFusedAdam
 from gaussian_renderer import render
 from loss_utils import training_loss
 
@@ -34,7 +35,10 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
                 if it % opt.opacity_reset_interval == 0 or (white_background and it == opt.densify_from_iter):
                     gaussians.reset_opacity()
             if it < iterations:
-                gaussians.optimizer.step()
+                if isinstance(gaussians.optimizer, SparseFusedAdam):
+                    gaussians.optimizer.step(visibility=radii)           # optimizer_type = "sparse_adam": the frame's radii are the mask
+                else:
+                    gaussians.optimizer.step()
                 gaussians.optimizer.zero_grad(set_to_none=True)
         if on_iteration is not None:
             on_iteration(it, loss, gaussians)
