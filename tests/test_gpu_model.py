@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import scene_synth as S
+import training_ref as R
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -51,6 +52,12 @@ def test_native_activations_match_torch(P):
         scale = float(ref[finite].abs().max()) if finite.any() else 1.0
         err = (mine - ref)[finite].abs()
         assert bool((err <= 1e-6 * scale + 1e-5 * ref[finite].abs()).all()), (name, float(err.max()), scale)
+    # the bound above takes one maximum over the tensor, and the edge rows set it (g / 1e-12 for rotation[0], exp(20) for scaling[6]):
+    # beside it, every element against float64 on its own scale (tests/training_ref.py)
+    want64, scl = R.activations_backward64(got[0].cpu(), ro.detach().cpu(), got[2].cpu(), *(t.cpu() for t in grads))
+    for name, mine, w, s in zip(("d_scaling", "d_rotation", "d_opacity"), d, want64, scl):
+        ratio = R.worst(mine.cpu(), w, s)
+        assert ratio <= R.K[name], (name, ratio)
     # a None gradient skips that tensor
     d2 = N.activations_backward(got[0], ro.detach(), got[2], grads[0], None, grads[2])
     assert d2[1] is None and torch.equal(d2[0], d[0]) and torch.equal(d2[2], d[2])
@@ -205,7 +212,8 @@ def test_render_from_the_model_equals_render_from_the_reference_getters(mode, P,
 
 @pytest.mark.parametrize("M", [16, 9, 4, 1])
 def test_split_adam_equals_adam_on_the_two_tensors(M):
-    """gsr_adam_step_split over the packed table [P, M, 3] (group "f_dc" lr for column 0, group "f_rest" lr for the others)
+    """FusedAdam's split group, which is gsr_adam_step_multi with row_len / split (k_adam_multi; gsr_adam_step_split is exercised by
+    tests/test_gpu_training_kernels.py), over the packed table [P, M, 3] (group "f_dc" lr for column 0, group "f_rest" lr for the others)
     against torch.optim.Adam over the reference's two tensors (scene/gaussian_model.py:166-168), and against the library's
     own plain step on the two tensors, which it must equal bit for bit."""
     from fused_adam import FusedAdam
