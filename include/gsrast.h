@@ -30,7 +30,8 @@ extern "C" {
 #define GSR_VERSION 12
 #define GSR_SCREEN_GRAD_STRIDE 12   /* floats per Gaussian in `screen_grads`: (dmean2D.x, dmean2D.y,
                                        dconic A, B, C, dopacity, drgb[3], dz (gsr_backward_render_aux;
-                                       0 otherwise), 2 pad) */
+                                       0 otherwise), 2 pad: the absolute sums of gsr_backward_render_abs,
+                                       0 otherwise) */
 
 typedef enum gsr_status {
     GSR_OK = 0,
@@ -279,6 +280,21 @@ int gsr_camera_grad_workspace_size(const gsr_frame_desc *desc, size_t *bytes);
 int gsr_backward_camera(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, const int32_t *radii,
                         const void *geom_ws, const float *screen_grads, int32_t binned_ranks, const gsr_frame_plan *own_plan,
                         int32_t depth_chain, void *workspace, const gsr_camera_grads *out, void *stream);
+
+/* ---- Absgrad (AbsGS / Gaussian Opacity Fields; additive: every call above keeps its meaning): per Gaussian, the sum over pixels of
+ * the ABSOLUTE value of that pixel's dL/dmean2D, per axis - what the signed sum in slots 0, 1 loses when a splat's pixels pull in
+ * opposite directions.  It can only be formed inside the blend backward.
+ * gsr_backward_render_abs is gsr_backward_render (same arguments, same work, the same values in slots 0..9) whose screen_grads slots
+ * 10 and 11 receive the absolute sums, with the W/2, H/2 factors of slots 0 and 1.  Sums in a fixed order (no atomics): the same
+ * frame gives the same bits.  Whole images only (tile_row_begin = tile_row_end = 0). */
+int gsr_backward_render_abs(const gsr_frame_desc *desc, const gsr_camera *cam, const void *geom_ws, void *binning_ws,
+                            const void *image_ws, void *rows_ws, const gsr_frame_plan *plan_host, const float *out_color,
+                            const float *dL_dcolor, float *screen_grads, void *stream);
+/* out [P,3] (laid out like gsr_grads.means2D) = (slot 10, slot 11, 0) of screen_grads for the rows gsr_backward_geom visits with
+ * the same radii / binned_ranks / own_plan, zeros for every other row: every row of out is written.  Rows of screen_grads outside
+ * the binned prefix are not read when that call would not read them (plan_host->screen_prezeroed == 2 never wrote them). */
+int gsr_screen_absgrad(const gsr_frame_desc *desc, const int32_t *radii, const void *geom_ws, const float *screen_grads,
+                       int32_t binned_ranks, const gsr_frame_plan *own_plan, float *out, void *stream);
 
 /* Device pointers into a frame's geometry workspace (valid after gsr_forward_preprocess):
  *   depth_keys [P]  by Gaussian: the bits of its view depth (a positive binary32: ordered as an integer), 0xFFFFFFFF = not

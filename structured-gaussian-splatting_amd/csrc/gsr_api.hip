@@ -611,10 +611,14 @@ int gsr_bwd_segment_entries(void) { return kSeg; }
 static int backward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const void *geom_ws, void *binning_ws,
                                 const void *image_ws, void *rows_ws, const gsr_frame_plan *plan, const float *out_color,
                                 const gsr_aux_outputs *aux_out, const float *dL_dcolor, const float *dL_ddepth, const float *dL_dalpha,
-                                float *screen_grads, void *stream)
+                                float *screen_grads, void *stream, bool abs = false)
 {
     int rc = validate(desc);
     if (rc) return rc;
+    if (abs && (desc->tile_row_begin != 0 || desc->tile_row_end > 0)) {
+        set_error("gsr_backward_render_abs: whole images only (tile_row_begin = tile_row_end = 0)");
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
     if (aux_out && (!aux_out->depth || (plan && plan->num_rendered > 0 && !aux_out->ckpt_ws))) {
         set_error("gsr_backward_render_aux: aux->depth and (for a frame that binned anything) aux->ckpt_ws are required");
         return GSR_ERR_INVALID_ARGUMENT;
@@ -640,11 +644,11 @@ static int backward_render_impl(const gsr_frame_desc *desc, const gsr_camera *ca
         AuxWS ax = carve_aux(aux_out ? aux_out->ckpt_ws : nullptr, plan_capacity(plan), f);
         if (aux_out) { ax.depth = aux_out->depth; ax.alpha = aux_out->alpha; }
         if ((rc = launch_render_bwd(f, plan->chunks_run, plan->sort_result, rows_n, gw, bw, iw, out_color, dL_dcolor, dbg, s,
-                                    aux_out ? &ax : nullptr, dL_ddepth, dL_dalpha)))
+                                    aux_out ? &ax : nullptr, dL_ddepth, dL_dalpha, abs)))
             return rc;
     }
     // only the depth ranks of chunks that ran can own gradient rows
-    if ((rc = launch_reduce_rows(f, *plan, gw, bw, screen_grads, plan->screen_prezeroed, dbg, s, aux_out != nullptr))) return rc;
+    if ((rc = launch_reduce_rows(f, *plan, gw, bw, screen_grads, plan->screen_prezeroed, dbg, s, aux_out != nullptr, abs))) return rc;
     return GSR_OK;
 }
 
@@ -654,6 +658,32 @@ int gsr_backward_render(const gsr_frame_desc *desc, const gsr_camera *cam, const
 {
     return backward_render_impl(desc, cam, geom_ws, binning_ws, image_ws, rows_ws, plan, out_color, nullptr, dL_dcolor, nullptr, nullptr,
                                 screen_grads, stream);
+}
+
+int gsr_backward_render_abs(const gsr_frame_desc *desc, const gsr_camera *cam, const void *geom_ws, void *binning_ws,
+                            const void *image_ws, void *rows_ws, const gsr_frame_plan *plan, const float *out_color, const float *dL_dcolor,
+                            float *screen_grads, void *stream)
+{
+    return backward_render_impl(desc, cam, geom_ws, binning_ws, image_ws, rows_ws, plan, out_color, nullptr, dL_dcolor, nullptr, nullptr,
+                                screen_grads, stream, true);
+}
+
+int gsr_screen_absgrad(const gsr_frame_desc *desc, const int32_t *radii, const void *geom_ws, const float *screen_grads,
+                       int32_t binned_ranks, const gsr_frame_plan *own_plan, float *out, void *stream)
+{
+    int rc = validate(desc);
+    if (rc) return rc;
+    if (desc->tile_row_begin != 0 || desc->tile_row_end > 0) {
+        set_error("gsr_screen_absgrad: whole images only (tile_row_begin = tile_row_end = 0)");
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if (desc->P == 0) return GSR_OK;
+    if (!radii || !geom_ws || !screen_grads || !out) { set_error("gsr_screen_absgrad: NULL argument"); return GSR_ERR_INVALID_ARGUMENT; }
+    const FrameK f = make_frame(*desc);
+    GeomWS gw = carve_geom(const_cast<void *>(geom_ws), f.P);
+    const GeomRows rows = geom_rows(f, 0, f.P, binned_ranks, own_plan);          // the rows gsr_backward_geom visits
+    return launch_screen_absgrad(f, radii, screen_grads, rows.n_ranks, gw.order, rows.own_sparse ? gw.cnt_open : nullptr, rows.sparse, out,
+                                 desc->debug != 0, (hipStream_t)stream);
 }
 
 int gsr_backward_render_aux(const gsr_frame_desc *desc, const gsr_camera *cam, const void *geom_ws, void *binning_ws,

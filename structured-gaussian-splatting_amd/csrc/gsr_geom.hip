@@ -627,6 +627,26 @@ __global__ __launch_bounds__(kGeomBlock) void k_geom_bwd_depth(int g0, int n, in
     dmeans[3 * (size_t)i + 2] += dz * view[10];
 }
 
+// ---- absgrad: screen_grads slots 10, 11 (the abs blend backward's per-pixel absolute sums of d/dmean2D) as a [P,3] tensor laid out
+// like the means2D gradient.  The rows the geometry backward visits (visit_row) get (slot 10, slot 11, 0); every other row is zero:
+// DENSE writes it here, SPARSE relies on the caller's fill - rows outside the binned prefix are never read.
+template <bool SPARSE>
+__global__ __launch_bounds__(kGeomBlock) void k_screen_absgrad(int n, int P, const uint32_t *__restrict__ order,
+                                                               const uint32_t *__restrict__ cnt_open, const int32_t *__restrict__ radii,
+                                                               const float4 *__restrict__ screen, float *__restrict__ out)
+{
+    const int t = blockIdx.x * kGeomBlock + threadIdx.x;
+    if (t >= n) return;
+    const int i = visit_row<SPARSE>(t, 0, order, cnt_open, P, radii);
+    if constexpr (SPARSE) {
+        if (i < 0) return;
+    }
+    const int row = SPARSE ? i : t;
+    float ax = 0.f, ay = 0.f;
+    if (i >= 0) { const float4 s2 = screen[3 * (size_t)i + 2]; ax = s2.z; ay = s2.w; }
+    out[3 * (size_t)row] = ax; out[3 * (size_t)row + 1] = ay; out[3 * (size_t)row + 2] = 0.f;
+}
+
 // ---- camera gradients: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos = sums over Gaussians of camera_backward_one's
 // 27 terms.  Runs behind the geometry backward over the rows it visited (SPARSE: the ranks of the binned depth prefix through
 // order / cnt_open; otherwise [0, n)).  Every sum has an order the program fixes, so the result is bit-reproducible: the lanes of a
@@ -841,6 +861,23 @@ int launch_geom_bwd_depth(const FrameK &f, const gsr_camera &cam, const int32_t 
     hipLaunchKernelGGL(sparse ? k_geom_bwd_depth<true> : k_geom_bwd_depth<false>, grid, dim3(kGeomBlock), 0, s, sparse ? 0 : g0, n, f.P,
                        sparse ? rows : nullptr, sparse ? cnt_open : nullptr, cam.viewmatrix, radii, screen, dmeans);
     GSR_LAUNCH_CHECK("geom_bwd_depth", debug, s);
+    return GSR_OK;
+}
+
+int launch_screen_absgrad(const FrameK &f, const int32_t *radii, const float *screen_grads, int n_ranks, const uint32_t *rows,
+                          const uint32_t *cnt_open, bool sparse, float *out, bool debug, hipStream_t s)
+{
+    if (f.P <= 0) return GSR_OK;
+    ProfileScope prof("screen_absgrad", s);
+    if (sparse) GSR_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)f.P * 3 * sizeof(float), s));
+    const int n = sparse ? n_ranks : f.P;
+    if (n > 0) {
+        const dim3 grid((unsigned)((n + kGeomBlock - 1) / kGeomBlock));
+        const float4 *screen = reinterpret_cast<const float4 *>(screen_grads);
+        hipLaunchKernelGGL(sparse ? k_screen_absgrad<true> : k_screen_absgrad<false>, grid, dim3(kGeomBlock), 0, s, n, f.P,
+                           sparse ? rows : nullptr, sparse ? cnt_open : nullptr, radii, screen, out);
+    }
+    GSR_LAUNCH_CHECK("screen_absgrad", debug, s);
     return GSR_OK;
 }
 

@@ -12,7 +12,7 @@
 
 namespace gsr {
 
-constexpr int kRowFloats = 12;            // per-instance gradient row (48 B, 3 x float4; 9 used, 10 by the aux backward)
+constexpr int kRowFloats = 12;            // per-instance gradient row (48 B, 3 x float4; 9 used, 10 by the aux backward; 10, 11 by abs)
 constexpr size_t kAlign = 256;
 
 void set_error(const char *fmt, ...);     // thread-local message behind gsr_last_error()
@@ -271,17 +271,20 @@ int launch_render_fwd(const FrameK &f, const gsr_camera &cam, int c, bool last_c
                       ImageWS &iw, float *out_color, bool debug, hipStream_t s, bool groups = false, const AuxWS *aux = nullptr);
 // rows_upper: bound of the instances the chunks that ran emitted (sizes the launch: the unit count lives on the device)
 // aux (optional): the aux backward - dL_dcolor, dL_ddepth, dL_dalpha may each be NULL (zero); rows get slot 9 = sum of w dL/ddepth
-// (dL/dz of the splat)
+// (dL/dz of the splat).  abs (without aux): the abs backward - rows get slots 10, 11 = the per-pixel absolute sums of d/dmean2D
 int launch_render_bwd(const FrameK &f, int chunks_run, int sort_result, long long rows_upper, const GeomWS &gw, BinningWS &bw,
                       const ImageWS &iw, const float *out_color, const float *dL_dcolor, bool debug, hipStream_t s, const AuxWS *aux = nullptr,
-                      const float *dL_ddepth = nullptr, const float *dL_dalpha = nullptr);
+                      const float *dL_ddepth = nullptr, const float *dL_dalpha = nullptr, bool abs = false);
 // row_valid / valid_bytes: also clear that many bytes of the blend backward's row-valid flags
 int launch_zero_segments(const ZeroSegs &z, hipStream_t s);
 int launch_zero_outputs(const FrameK &f, const gsr_gaussians &g, float *screen, const gsr_grads &out, hipStream_t s,
                         uint8_t *row_valid = nullptr, size_t valid_bytes = 0);
 // aux: the rows come from the aux backward - slot 9 (dL/dz) is carried into screen_grads too
 int launch_reduce_rows(const FrameK &f, const gsr_frame_plan &plan, const GeomWS &gw, const BinningWS &bw, float *screen_grads,
-                       int prezeroed, bool debug, hipStream_t s, bool aux = false);
+                       int prezeroed, bool debug, hipStream_t s, bool aux = false, bool abs = false);
+// gsr_screen_absgrad: out [P,3] = (slot 10, slot 11, 0) of the rows launch_geom_bwd visits (same arguments), zeros elsewhere
+int launch_screen_absgrad(const FrameK &f, const int32_t *radii, const float *screen_grads, int n_ranks, const uint32_t *rows,
+                          const uint32_t *cnt_open, bool sparse, float *out, bool debug, hipStream_t s);
 // Depth ranks that can own a gradient, as far as the host knows: the chunks that ran, a chunk that went through the live filter
 // counted as nothing (only the Gaussians that still reached an open tile were binned: few, and how few is the device's knowledge).
 // Decides "sparse geometry backward + zero fill" against "dense geometry backward" (sparse below P / 4).

@@ -80,6 +80,36 @@ __device__ __forceinline__ void row_sum10_transpose(float (&a)[10])
 #undef GSR_DPP
 }
 
+// The abs backward's butterfly: values 9 and 10 (the sums of |d/dmean2D.x|, |d/dmean2D.y| per pixel) are reduced over the row like
+// value 8, each step's adds right behind value 8's (more instructions between a write and its DPP read, never fewer):
+//   a[9], a[10]: values 9, 10 in every lane of the row
+__device__ __forceinline__ void row_sum11_transpose(float (&a)[11])
+{
+#define GSR_DPP(d, s_, ctrl, bank) "v_add_f32_dpp %" #d ", %" #s_ ", %" #s_ " " ctrl " row_mask:0xf bank_mask:" bank "\n\t"
+    asm volatile("s_nop 1\n\t"
+                 GSR_DPP(0, 0, "row_ror:8", "0x3") GSR_DPP(1, 1, "row_ror:8", "0x3") GSR_DPP(2, 2, "row_ror:8", "0x3")
+                 GSR_DPP(3, 3, "row_ror:8", "0x3") GSR_DPP(8, 8, "row_ror:8", "0xf") GSR_DPP(9, 9, "row_ror:8", "0xf")
+                 GSR_DPP(10, 10, "row_ror:8", "0xf")
+                 GSR_DPP(0, 4, "row_ror:8", "0xc") GSR_DPP(1, 5, "row_ror:8", "0xc") GSR_DPP(2, 6, "row_ror:8", "0xc")
+                 GSR_DPP(3, 7, "row_ror:8", "0xc")
+                 "s_nop 1\n\t"
+                 GSR_DPP(0, 0, "row_half_mirror", "0x5") GSR_DPP(2, 2, "row_half_mirror", "0x5") GSR_DPP(8, 8, "row_half_mirror", "0xf")
+                 GSR_DPP(9, 9, "row_half_mirror", "0xf") GSR_DPP(10, 10, "row_half_mirror", "0xf")
+                 GSR_DPP(0, 1, "row_half_mirror", "0xa") GSR_DPP(2, 3, "row_half_mirror", "0xa")
+                 "s_nop 1\n\t"
+                 GSR_DPP(0, 0, "quad_perm:[1,0,3,2]", "0xf") GSR_DPP(2, 2, "quad_perm:[1,0,3,2]", "0xf")
+                 GSR_DPP(8, 8, "quad_perm:[1,0,3,2]", "0xf") GSR_DPP(9, 9, "quad_perm:[1,0,3,2]", "0xf")
+                 GSR_DPP(10, 10, "quad_perm:[1,0,3,2]", "0xf")
+                 "s_nop 0\n\t"
+                 GSR_DPP(0, 0, "quad_perm:[2,3,0,1]", "0xf") GSR_DPP(2, 2, "quad_perm:[2,3,0,1]", "0xf")
+                 GSR_DPP(8, 8, "quad_perm:[2,3,0,1]", "0xf") GSR_DPP(9, 9, "quad_perm:[2,3,0,1]", "0xf")
+                 GSR_DPP(10, 10, "quad_perm:[2,3,0,1]", "0xf")
+                 "s_nop 1"
+                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]), "+v"(a[8]),
+                   "+v"(a[9]), "+v"(a[10]));
+#undef GSR_DPP
+}
+
 __device__ __forceinline__ int wave_max_uniform(int v)
 {
 #pragma unroll
@@ -604,6 +634,10 @@ struct BwdPairAux {          // aux: the same pair's dL/ddepth and dL/dalpha T_f
 // the lane's partial sums of one splat, per pair element: X = sum tA dx, Y = sum tA dy (dL/dmean2D = ln2 (2 qA X + qB Y, 2 qC Y + qB X):
 // formed once per splat by the lane that stores the row), S2..S4 the conic's, S5 the opacity's, S6..S8 the colour's, S9 (aux) the depth's
 struct BwdAcc { v2f X, Y, S2, S3, S4, S5, S6, S7, S8; };
+// abs (k_render_bwd<false, true>): the same expression PER PIXEL, u = (2 qA tx + qB ty, 2 qC ty + qB tx), and the lane's sums of |u|:
+// what the signed sums lose when a splat's pixels pull in opposite directions.  A rejected pixel has tA = 0 and adds exactly 0.
+struct BwdAbsQ { float qA2, qB, qC2; };        // 2 qA, qB, 2 qC of the staged record
+struct BwdAbs { v2f AX, AY; };
 __device__ __forceinline__ float add_halves(v2f v)
 {
     float r;
@@ -611,9 +645,10 @@ __device__ __forceinline__ float add_halves(v2f v)
     return r;
 }
 
-template <bool INIT, bool kAux = false>         // INIT: the splat's first pair, the sums start here (A comes in undefined)
+template <bool INIT, bool kAux = false, bool kAbs = false>         // INIT: the splat's first pair, the sums start here (A comes in undefined)
 __device__ __forceinline__ void bwd_pair(const BwdSplat sp, v2f lp, v2f dx, float dy, int pos, BwdPair &P, BwdAcc &A,
-                                         const BwdPairAux &PA = BwdPairAux{}, v2f *S9 = nullptr)
+                                         const BwdPairAux &PA = BwdPairAux{}, v2f *S9 = nullptr, const BwdAbsQ &Q = BwdAbsQ{},
+                                         BwdAbs *AB = nullptr)
 {
     const bool valid0 = (pos < P.limit0) && !(lp[0] > sp.lop) && !(lp[0] < kLog2AlphaMin);      // power > 0 <=> lp > lop
     const bool valid1 = (pos < P.limit1) && !(lp[1] > sp.lop) && !(lp[1] < kLog2AlphaMin);
@@ -639,6 +674,10 @@ __device__ __forceinline__ void bwd_pair(const BwdSplat sp, v2f lp, v2f dx, floa
         A.S5 = tA;
         A.S6 = w * P.dpr; A.S7 = w * P.dpg; A.S8 = w * P.dpb;
         if constexpr (kAux) *S9 = w * PA.dpz;
+        if constexpr (kAbs) {
+            AB->AX = __builtin_elementwise_abs(Q.qA2 * tx + Q.qB * ty);
+            AB->AY = __builtin_elementwise_abs(Q.qC2 * ty + Q.qB * tx);
+        }
     } else {
         A.X += tx; A.Y += ty;
         A.S2 += tx * dx;
@@ -647,6 +686,10 @@ __device__ __forceinline__ void bwd_pair(const BwdSplat sp, v2f lp, v2f dx, floa
         A.S5 += tA;
         A.S6 += w * P.dpr; A.S7 += w * P.dpg; A.S8 += w * P.dpb;
         if constexpr (kAux) *S9 += w * PA.dpz;
+        if constexpr (kAbs) {
+            AB->AX += __builtin_elementwise_abs(Q.qA2 * tx + Q.qB * ty);
+            AB->AY += __builtin_elementwise_abs(Q.qC2 * ty + Q.qB * tx);
+        }
     }
 }
 
@@ -659,12 +702,14 @@ __device__ __forceinline__ void bwd_pair(const BwdSplat sp, v2f lp, v2f dx, floa
 // j's gradient row and stores it whole (48 B) - rows are written for every entry some group attempted (row_valid).
 // A batch ends when its slowest group does (measured imbalance over a frame: 1.01 .. 1.14, tools/quad_stats.py).
 // kAux (k_render_bwd<true>): a tenth sum per entry (dL/dz, row slot 9); the LDS stride goes to 11 words, odd, still conflict-free.
+// kAbs (k_render_bwd<false, true>): eleven sums per entry, the last two the per-pixel absolute sums (BwdAbs) -> row slots 10, 11 with
+// the W/2, H/2 of slots 0, 1; stride 11.  Every other value is computed exactly as in k_render_bwd<false>.
 struct AuxBwdK {
     const float *depth;                // [H, W] the forward's depth map (final)
     const float *dL_ddepth, *dL_dalpha;      // [H, W] each, NULL = zero
     const float *ckpt, *ckpt_start;    // the aux checkpoints (AuxWS)
 };
-template <bool kAux>
+template <bool kAux, bool kAbs>
 __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const uint2 *__restrict__ ranges,
                                                       const uint32_t *__restrict__ tile_walk,
                                                       const uint32_t *__restrict__ sorted_gid, const uint32_t *__restrict__ sorted_slot,
@@ -675,8 +720,9 @@ __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const
                                                       uint8_t *__restrict__ row_valid, UnitLists units,
                                                       const uint32_t *__restrict__ unit_count, AuxBwdK ax)
 {
-    constexpr int kSums = kAux ? 10 : 9;         // per-entry sums
-    constexpr int kAccStride = kAux ? 11 : 9;
+    static_assert(!(kAux && kAbs), "the aux x abs blend backward is not built");
+    constexpr int kSums = kAux ? 10 : kAbs ? 11 : 9;         // per-entry sums
+    constexpr int kAccStride = (kAux || kAbs) ? 11 : 9;
     __shared__ float4 sh_rec[kWave * 3];
     __shared__ float sh_acc[kWave * kAccStride];      // the batch's sums, [entry][value]: stride 9 (11) words, conflict-free by lane
 #ifdef GSR_BWD_TRACE
@@ -697,9 +743,9 @@ __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const
     const float half_w = 0.5f * (float)f.W, half_h = 0.5f * (float)f.H;
     // where the butterfly leaves this lane's share of a group's totals: which value (of which register), if any
     const int quad = (lane >> 2) & 3, in_quad = lane & 3;
-    const unsigned acc_idx = (unsigned)(in_quad == 0 ? (quad < 2 ? quad : quad + 2) : in_quad == 1 ? (quad < 2 ? quad + 2 : quad + 4) : (kAux ? 8 + quad : 8));
+    const unsigned acc_idx = (unsigned)(in_quad == 0 ? (quad < 2 ? quad : quad + 2) : in_quad == 1 ? (quad < 2 ? quad + 2 : quad + 4) : ((kAux || kAbs) ? 8 + quad : 8));
     const unsigned grp_shift = 8u * (unsigned)map.grp;
-    const bool acc_on = in_quad < 2 || (in_quad == 2 && (kAux ? quad < 2 : quad == 0));
+    const bool acc_on = in_quad < 2 || (in_quad == 2 && (kAbs ? quad < 3 : kAux ? quad < 2 : quad == 0));
 #pragma unroll
     for (int k = 0; k < kSums; ++k) sh_acc[lane * kAccStride + k] = 0.f;
     for (uint32_t u = blockIdx.x / kUnitShards; u < n_units; u += gridDim.x / kUnitShards) {
@@ -799,18 +845,27 @@ __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const
                 const LpTerms lt = lp_terms(a.z, a.w, b.y, dx);
                 BwdAcc A;
                 v2f S9;                                  // aux: the lane's sum of w dL/ddepth
+                BwdAbs AB;                               // abs: the lane's sums of |u|
+                const BwdAbsQ Q{2.f * a.z, a.w, 2.f * b.x};
                 {
                     const float dy = a.y - fy0;
-                    if constexpr (kAux) bwd_pair<true, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P0, A, PA0, &S9);
+                    if constexpr (kAbs) bwd_pair<true, false, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P0, A, PA0, nullptr, Q, &AB);
+                    else if constexpr (kAux) bwd_pair<true, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P0, A, PA0, &S9);
                     else bwd_pair<true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P0, A);
                 }
                 {
                     const float dy = a.y - fy1;
-                    if constexpr (kAux) bwd_pair<false, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P1, A, PA1, &S9);
+                    if constexpr (kAbs) bwd_pair<false, false, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P1, A, PA1, nullptr, Q, &AB);
+                    else if constexpr (kAux) bwd_pair<false, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P1, A, PA1, &S9);
                     else bwd_pair<false>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P1, A);
                 }
                 float mine;
-                if constexpr (kAux) {
+                if constexpr (kAbs) {
+                    float s[11] = {add_halves(A.X), add_halves(A.Y), add_halves(A.S2), add_halves(A.S3), add_halves(A.S4), add_halves(A.S5),
+                                   add_halves(A.S6), add_halves(A.S7), add_halves(A.S8), add_halves(AB.AX), add_halves(AB.AY)};
+                    row_sum11_transpose(s);
+                    mine = in_quad == 0 ? s[0] : in_quad == 1 ? s[2] : (quad == 0 ? s[8] : quad == 1 ? s[9] : s[10]);
+                } else if constexpr (kAux) {
                     float s[10] = {add_halves(A.X), add_halves(A.Y), add_halves(A.S2), add_halves(A.S3), add_halves(A.S4), add_halves(A.S5),
                                    add_halves(A.S6), add_halves(A.S7), add_halves(A.S8), add_halves(S9)};
                     row_sum10_transpose(s);
@@ -839,7 +894,8 @@ __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const
                 float4 *row = grad_rows + 3 * (size_t)slot;
                 row[0] = make_float4(gx * (0.69314718f * half_w), gy * (0.69314718f * half_h), v[2] * -0.5f, v[3] * -0.5f);
                 row[1] = make_float4(v[4] * -0.5f, v[5] * __builtin_amdgcn_exp2f(-b.y), v[6], v[7]);
-                row[2] = make_float4(v[8], kAux ? v[kSums - 1] : 0.f, 0.f, 0.f);
+                if constexpr (kAbs) row[2] = make_float4(v[8], 0.f, v[9] * (0.69314718f * half_w), v[10] * (0.69314718f * half_h));
+                else row[2] = make_float4(v[8], kAux ? v[kSums - 1] : 0.f, 0.f, 0.f);
                 row_valid[slot] = 1;
             }
         }
@@ -848,7 +904,7 @@ __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const
 
 int launch_render_bwd(const FrameK &f, int chunks_run, int sort_result, long long rows_upper, const GeomWS &gw, BinningWS &bw,
                       const ImageWS &iw, const float *out_color, const float *dL_dcolor, bool debug, hipStream_t s, const AuxWS *aux,
-                      const float *dL_ddepth, const float *dL_dalpha)
+                      const float *dL_ddepth, const float *dL_dalpha, bool abs)
 {
     const int n_tiles = (f.ty1 - f.ty0) * f.Gx;
     if (n_tiles <= 0 || chunks_run <= 0) return GSR_OK;
@@ -858,10 +914,10 @@ int launch_render_bwd(const FrameK &f, int chunks_run, int sort_result, long lon
     if (per_shard > (long long)bw.units.shard_stride()) per_shard = (long long)bw.units.shard_stride();
     if (per_shard > (1 << 13)) per_shard = 1 << 13;
     // the two instantiations take the same arguments; the colour-only one ignores the aux block
-    const char *name = aux ? "render_bwd_aux" : "render_bwd";
+    const char *name = aux ? "render_bwd_aux" : abs ? "render_bwd_abs" : "render_bwd";
     const AuxBwdK ax = aux ? AuxBwdK{aux->depth, dL_ddepth, dL_dalpha, aux->ckpt, aux->ckpt_start} : AuxBwdK{};
     ProfileScope prof(name, s);
-    hipLaunchKernelGGL(aux ? k_render_bwd<true> : k_render_bwd<false>, dim3((unsigned)(per_shard * kUnitShards)), dim3(kWave), 0, s, f,
+    hipLaunchKernelGGL((aux ? k_render_bwd<true, false> : abs ? k_render_bwd<false, true> : k_render_bwd<false, false>), dim3((unsigned)(per_shard * kUnitShards)), dim3(kWave), 0, s, f,
                        iw.ranges, iw.tile_walk, bw.gids[1], bw.vals[sort_result], gw.records, out_color, iw.T_state, iw.last_enc, dL_dcolor,
                        bw.ckpt, iw.ckpt_start, reinterpret_cast<float4 *>(bw.grad_rows), bw.row_valid, bw.units, iw.unit_count, ax);
     GSR_LAUNCH_CHECK(name, debug, s);
@@ -874,8 +930,9 @@ int launch_render_bwd(const FrameK &f, int chunks_run, int sort_result, long lon
 // rows each; one thread per Gaussian left a tail of a few thousand threads walking them serially.
 // Only ranks of chunks that actually ran can own rows; every other Gaussian's gradient row is zero (memset).
 // kAux: rows of the aux backward - slot 9 (dL/dz) is summed too, in the same order as the others.
+// kAbs: rows of the abs backward - slots 10, 11 likewise, into screen[3 g + 2].zw.
 constexpr int kRedBlock = 256;
-template <int kRedGroup, bool kAux = false>
+template <int kRedGroup, bool kAux = false, bool kAbs = false>
 __global__ __launch_bounds__(kRedBlock) void k_reduce_rows(int r_begin, int n_ranks, const uint32_t *__restrict__ order,
                                                            const uint32_t *__restrict__ cnt_open,
                                                            const uint32_t *__restrict__ row_begin,
@@ -889,28 +946,31 @@ __global__ __launch_bounds__(kRedBlock) void k_reduce_rows(int r_begin, int n_ra
     // the rank's three words in one round trip (the chain was count -> first row -> rows -> Gaussian: four)
     const uint32_t cnt = live ? cnt_open[r] : 0u, begin = live ? row_begin[r] : 0u, g = live ? order[r] : 0u;
     float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
-    float a8 = 0.f, a9 = 0.f;
+    float a8 = 0.f, a9 = 0.f, a10 = 0.f, a11 = 0.f;
     if (cnt) {
         for (uint32_t sl = begin + sub; sl < begin + cnt; sl += kRedGroup) {
             // a clear valid byte: nobody walked that far into the tile's list, or no pixel accepted the splat — the row was never
             // written.  Wide groups (big splats: most rows of a saturating frame are invalid) test the byte first; narrow ones (small
             // splats, nearly every row valid) load the row beside its byte — one memory round trip instead of two — and drop it after
             float4 r0, r1;
-            float r2, r9 = 0.f;
+            float r2, r9 = 0.f, r10 = 0.f, r11 = 0.f;
             if constexpr (kRedGroup >= 64) {
                 if (!row_valid[sl]) continue;
                 r0 = grad_rows[3 * (size_t)sl]; r1 = grad_rows[3 * (size_t)sl + 1]; r2 = grad_rows[3 * (size_t)sl + 2].x;
                 if constexpr (kAux) r9 = grad_rows[3 * (size_t)sl + 2].y;
+                if constexpr (kAbs) { r10 = grad_rows[3 * (size_t)sl + 2].z; r11 = grad_rows[3 * (size_t)sl + 2].w; }
             } else {
                 const uint8_t ok = row_valid[sl];
                 r0 = grad_rows[3 * (size_t)sl]; r1 = grad_rows[3 * (size_t)sl + 1]; r2 = grad_rows[3 * (size_t)sl + 2].x;
                 if constexpr (kAux) r9 = grad_rows[3 * (size_t)sl + 2].y;
+                if constexpr (kAbs) { r10 = grad_rows[3 * (size_t)sl + 2].z; r11 = grad_rows[3 * (size_t)sl + 2].w; }
                 if (!ok) continue;                      // (whatever the unwritten row holds — NaN patterns included — is never added)
             }
             a0.x += r0.x; a0.y += r0.y; a0.z += r0.z; a0.w += r0.w;
             a1.x += r1.x; a1.y += r1.y; a1.z += r1.z; a1.w += r1.w;
             a8 += r2;
             if constexpr (kAux) a9 += r9;
+            if constexpr (kAbs) { a10 += r10; a11 += r11; }
         }
     }
 #pragma unroll
@@ -919,9 +979,10 @@ __global__ __launch_bounds__(kRedBlock) void k_reduce_rows(int r_begin, int n_ra
         a1.x += __shfl_xor(a1.x, off); a1.y += __shfl_xor(a1.y, off); a1.z += __shfl_xor(a1.z, off); a1.w += __shfl_xor(a1.w, off);
         a8 += __shfl_xor(a8, off);
         if constexpr (kAux) a9 += __shfl_xor(a9, off);
+        if constexpr (kAbs) { a10 += __shfl_xor(a10, off); a11 += __shfl_xor(a11, off); }
     }
     if (live && (cnt || write_empty) && sub < 3)
-        screen[3 * (size_t)g + sub] = sub == 0 ? a0 : (sub == 1 ? a1 : make_float4(a8, a9, 0.f, 0.f));
+        screen[3 * (size_t)g + sub] = sub == 0 ? a0 : (sub == 1 ? a1 : make_float4(a8, a9, a10, a11));
 }
 
 // One launch per depth chunk that ran, each with its own lanes-per-Gaussian: a whole wave where the chunk's Gaussians own many
@@ -929,12 +990,12 @@ __global__ __launch_bounds__(kRedBlock) void k_reduce_rows(int r_begin, int n_ra
 // through the live filter, whose instance bound says nothing about what it emitted (a training frame's last chunk is most of the
 // scene with a bound of tens of millions: 64 lanes for each of its 1e6 ranks was 100 us of idle threads).
 int launch_reduce_rows(const FrameK &f, const gsr_frame_plan &plan, const GeomWS &gw, const BinningWS &bw, float *screen_grads,
-                       int prezeroed, bool debug, hipStream_t s, bool aux)
+                       int prezeroed, bool debug, hipStream_t s, bool aux, bool abs)
 {
     // prezeroed: 0 = clear the whole tensor first; 1 = the caller already has; 2 = only the rows of the binned prefix will ever
     // be read (the sparse geometry backward of the same frame): every prefix row is written, zeros included, nothing else
     if (f.P == 0) return GSR_OK;
-    ProfileScope prof(aux ? "reduce_rows_aux" : "reduce_rows", s);
+    ProfileScope prof(aux ? "reduce_rows_aux" : abs ? "reduce_rows_abs" : "reduce_rows", s);
     if (prezeroed == 0) GSR_HIP_CHECK(hipMemsetAsync(screen_grads, 0, (size_t)f.P * kRowFloats * sizeof(float), s));
     const int write_empty = prezeroed == 2 ? 1 : 0;
     const int chunks = (plan.num_rendered > 0 && plan.chunks_run > 0) ? plan.chunks_run : 0;
@@ -947,7 +1008,9 @@ int launch_reduce_rows(const FrameK &f, const gsr_frame_plan &plan, const GeomWS
         // (two lanes per Gaussian for small splats, measured: 89 us against 81 at cfg3n, 352 against 374 at cfg5n — not kept)
         const long long threads = (long long)(r1 - r0) * (wide ? 64 : 8);
         const dim3 grid((unsigned)((threads + kRedBlock - 1) / kRedBlock));
-        hipLaunchKernelGGL(aux ? (wide ? k_reduce_rows<64, true> : k_reduce_rows<8, true>) : (wide ? k_reduce_rows<64> : k_reduce_rows<8>), grid, dim3(kRedBlock), 0, s, r0, r1, gw.order, gw.cnt_open, gw.row_begin,
+        hipLaunchKernelGGL((aux ? (wide ? k_reduce_rows<64, true> : k_reduce_rows<8, true>)
+                                : abs ? (wide ? k_reduce_rows<64, false, true> : k_reduce_rows<8, false, true>)
+                                      : (wide ? k_reduce_rows<64> : k_reduce_rows<8>)), grid, dim3(kRedBlock), 0, s, r0, r1, gw.order, gw.cnt_open, gw.row_begin,
                            bw.row_valid, reinterpret_cast<const float4 *>(bw.grad_rows), reinterpret_cast<float4 *>(screen_grads), write_empty);
     }
     GSR_LAUNCH_CHECK("reduce_rows", debug, s);

@@ -25,6 +25,13 @@ every opacity is scaled by sqrt(det cov2D / det(cov2D + 0.3 I)) by one different
 Refused with a ValueError: cov3D_precomp, and a viewmatrix / projmatrix / campos that requires grad (rho's camera gradient is not
 computed).  Off (the default): no extra launch, the same bits.
 
+Extension: GaussianRasterizer(raster_settings, absgrad=True) is gsplat's `absgrad` (AbsGS / Gaussian Opacity Fields): backward() also
+assigns `means2D.absgrad` [P,3] on the very tensor passed as means2D - per Gaussian, the sum over pixels of the ABSOLUTE value of that
+pixel's dL/dmean2D, in the layout and scaling of means2D.grad (column 2 exactly 0) - from one more instantiation of the blend backward
+and one small extraction launch.  It is assigned, not accumulated, by every backward (a second one under retain_graph included),
+whether or not means2D requires grad.  Refused with a ValueError: depth_alpha=True and tile_rows / ShardedRenderer.  Off (the
+default): no attribute, no extra launch, the same bits.
+
 Autograd contract (train.py:106, scene/gaussian_model.py:415-417): gradients for
 (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, None) in that order;
 `means2D.grad[:, :2]` is dL/d(NDC position) with the W/2, H/2 pixel scale folded in, `[:, 2] = 0`.
@@ -116,12 +123,15 @@ import threading as _threading
 _tls = _threading.local()
 
 
-def _apply(fn, *args):
+def _apply(fn, *args, absgrad_to=None):
+    """absgrad_to: the caller's means2D tensor when the backward is to assign its .absgrad (GaussianRasterizer(absgrad=True))."""
     _tls.caller_grad = torch.is_grad_enabled()
+    _tls.absgrad_to = absgrad_to
     try:
         return fn.apply(*args)
     finally:
         _tls.caller_grad = None
+        _tls.absgrad_to = None
 
 
 def caller_grad_enabled() -> bool:
@@ -274,10 +284,12 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
 
 
 def rasterize_backward_screen(fr: "_Frame", grad_color: torch.Tensor, only_for_own_geom: bool = False, grad_depth=None,
-                              grad_alpha=None) -> torch.Tensor:
+                              grad_alpha=None, absgrad: bool = False) -> torch.Tensor:
     """K7 + deterministic per-Gaussian reduction -> screen-space gradients [P, 12].
     grad_depth / grad_alpha ([1,H,W] or [H,W], an aux frame only; None = zero): when either is given the aux backward runs and slot 9
     holds dL/dz; otherwise the colour-only kernels (the plain frame's bits).
+    absgrad: the abs instantiation of the colour-only kernels - slots 10, 11 also hold the per-pixel absolute sums of d/dmean2D
+    (rasterize_screen_absgrad extracts them); whole images, no aux gradients.
     only_for_own_geom: the tensor goes straight into this frame's geometry backward and nowhere else (the autograd path): rows it
     never reads may stay undefined.  The dense geometry backward reads the rows of VISIBLE Gaussians; when every planned chunk ran,
     all of them sit in the binned prefix, whose rows the reduction writes (zeros included): no 48 P-byte memset."""
@@ -285,6 +297,8 @@ def rasterize_backward_screen(fr: "_Frame", grad_color: torch.Tensor, only_for_o
     grad_color = _f32c(grad_color, fr.device)
     grad_depth, grad_alpha = _f32c(grad_depth, fr.device), _f32c(grad_alpha, fr.device)
     with_aux = fr.aux is not None and (grad_depth is not None or grad_alpha is not None)
+    if absgrad and (fr.aux is not None or fr.desc.tile_row_end > 0 or fr.desc.tile_row_begin != 0):
+        raise ValueError("absgrad: the abs blend backward is built for whole colour-only frames: no depth / alpha maps, no tile_rows")
     screen = fr.pre.pop("screen", None) if fr.pre is not None else None        # allocated (and, on sparse frames, zero-filled) by the forward
     if screen is None:
         screen = torch.empty(max(P, 1), N.SCREEN_GRAD_STRIDE, dtype=torch.float32, device=fr.device)
@@ -300,7 +314,7 @@ def rasterize_backward_screen(fr: "_Frame", grad_color: torch.Tensor, only_for_o
                                   grad_depth, grad_alpha, screen, fr.device)
         else:
             N.backward_render(fr.desc, fr.cam, fr.geom_ws, fr.binning_ws, fr.image_ws, rows, fr.plan, fr.color, grad_color, screen,
-                              fr.device)
+                              fr.device, absgrad=absgrad)
         fr.plan.screen_prezeroed = 0
     return screen[:P]
 
@@ -401,6 +415,24 @@ def rasterize_backward_camera(fr: "_Frame", screen: torch.Tensor, needs=(True, T
     return tuple((t.view(4, 4) if t.numel() == 16 else t) if n else None for t, n in zip(parts, needs))
 
 
+def rasterize_screen_absgrad(fr: "_Frame", screen: torch.Tensor) -> torch.Tensor:
+    """The absolute sums [P,3] = (slot 10, slot 11, 0) of this very frame's rasterize_backward_screen(..., absgrad=True), over the
+    rows rasterize_backward_geom(fr, screen, ...) of the whole range visits; zeros elsewhere.  One launch (a fill first on sparse frames)."""
+    P, dev = fr.desc.P, fr.device
+    out = torch.empty(P, 3, dtype=torch.float32, device=dev)
+    if P > 0:
+        with torch.cuda.device(dev):
+            N.screen_absgrad(fr.desc, fr.radii, fr.geom_ws, screen, out, dev, N.binned_prefix(fr.plan), own_plan=fr.plan)
+    return out
+
+
+def _assign_absgrad(ctx, fr, screen):
+    """backward() of an absgrad call: means2D.absgrad = the frame's absolute sums, on the tensor the caller passed (assigned, not added)."""
+    target = ctx.absgrad_to
+    if target is not None:
+        target.absgrad = rasterize_screen_absgrad(fr, screen).view(ctx.shapes[0])
+
+
 def _camera_meta(ctx, cam, first):
     """forward(): remember whether the three camera inputs were passed, which of them want a gradient, their shapes and dtypes."""
     ctx.cam_needs = tuple(ctx.needs_input_grad[first:first + 3]) if cam[0] is not None else None
@@ -490,6 +522,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         maps = (frame.depth, frame.alpha)
         _stash_frame(ctx, frame)
         ctx.raster_settings = rs
+        ctx.absgrad_to = getattr(_tls, "absgrad_to", None)
         ctx.shapes = (means2D.shape, opacities.shape)
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)         # radii's "gradient" would arrive as a zero-filled int32 [P] tensor: one launch per step
@@ -505,8 +538,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         with_aux = grad_depth is not None or grad_alpha is not None
 
         def run():
-            screen = rasterize_backward_screen(fr, grad_out_color, only_for_own_geom=True, grad_depth=grad_depth, grad_alpha=grad_alpha)
-            return rasterize_backward_geom(fr, screen, order, depth_chain=with_aux) + (_camera_backward(ctx, fr, screen, with_aux),)
+            screen = rasterize_backward_screen(fr, grad_out_color, only_for_own_geom=True, grad_depth=grad_depth, grad_alpha=grad_alpha,
+                                               absgrad=ctx.absgrad_to is not None)
+            out = rasterize_backward_geom(fr, screen, order, depth_chain=with_aux) + (_camera_backward(ctx, fr, screen, with_aux),)
+            _assign_absgrad(ctx, fr, screen)
+            return out
         if rs.debug:
             try:
                 out = run()
@@ -548,6 +584,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         prepare_backward(frame, needs, screen_prefix_only=True)
         maps = (frame.depth, frame.alpha)
         _stash_frame(ctx, frame)
+        ctx.absgrad_to = getattr(_tls, "absgrad_to", None)
         ctx.shapes = (means2D.shape, opacity_logits.shape)
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)         # radii's "gradient" would arrive as a zero-filled int32 [P] tensor: one launch per step
@@ -559,9 +596,11 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         n = ctx.needs_input_grad       # xyz, means2D, f_dc, f_rest, opacity, scales, rotations
         needs = (n[0], n[1], n[2], False, n[4], n[5], n[6], False, n[3])
         with_aux = grad_depth is not None or grad_alpha is not None
-        screen = rasterize_backward_screen(fr, grad_out_color, only_for_own_geom=True, grad_depth=grad_depth, grad_alpha=grad_alpha)
+        screen = rasterize_backward_screen(fr, grad_out_color, only_for_own_geom=True, grad_depth=grad_depth, grad_alpha=grad_alpha,
+                                           absgrad=ctx.absgrad_to is not None)
         g_xyz, g_means2D, g_dc, _, g_op, g_sc, g_rot, _, g_rest = rasterize_backward_geom(fr, screen, needs, depth_chain=with_aux)
         g_cam = _camera_backward(ctx, fr, screen, with_aux)
+        _assign_absgrad(ctx, fr, screen)
         if g_op is not None:
             g_op = g_op.view(ctx.shapes[1])
         if g_means2D is not None:
@@ -571,9 +610,16 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, depth_alpha=False):
+                        raster_settings, depth_alpha=False, absgrad=False):
+    if absgrad and depth_alpha:
+        raise ValueError(_ABSGRAD_NO_AUX)
     return _apply(_RasterizeGaussians, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                  cov3Ds_precomp, raster_settings, bool(depth_alpha), *_camera_args(raster_settings))
+                  cov3Ds_precomp, raster_settings, bool(depth_alpha), *_camera_args(raster_settings),
+                  absgrad_to=means2D if absgrad else None)
+
+
+_ABSGRAD_NO_AUX = ("absgrad=True with depth_alpha=True: the blend backward that carries both the depth / alpha gradients and the "
+                   "absolute sums is not built; render the two in separate calls")
 
 
 # ---- opt-in: fuse the reference's getters without touching the caller -------------------------------------------
@@ -651,13 +697,18 @@ def _match_getters(means3D, opacities, shs, scales, rotations):
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings: GaussianRasterizationSettings, depth_alpha: bool = False, antialiasing: bool = False):
-        """depth_alpha=True (extension): forward / forward_raw also return the depth and alpha maps [1,H,W] (module docstring).
+    def __init__(self, raster_settings: GaussianRasterizationSettings, depth_alpha: bool = False, antialiasing: bool = False,
+                 absgrad: bool = False):
+        """absgrad=True (gsplat's flag): backward() also assigns means2D.absgrad [P,3] (module docstring); not with depth_alpha.
+        depth_alpha=True (extension): forward / forward_raw also return the depth and alpha maps [1,H,W] (module docstring).
         antialiasing=True (upstream's flag): the opacities are compensated for the 0.3 px^2 dilation first (module docstring)."""
         super().__init__()
         self.raster_settings = raster_settings
         self.depth_alpha = bool(depth_alpha)
         self.antialiasing = bool(antialiasing)
+        self.absgrad = bool(absgrad)
+        if self.absgrad and self.depth_alpha:
+            raise ValueError(_ABSGRAD_NO_AUX)
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         """Frustum test per point (the reference's `_C.mark_visible`; unused in-tree, kept for API parity)."""
@@ -697,9 +748,10 @@ class GaussianRasterizer(nn.Module):
             leaves = _match_getters(means3D, opacities, shs, scales, rotations)
             if leaves is not None:
                 xyz, dc, rest, op, sc, rot = leaves
-                return _apply(_RasterizeGaussiansRaw, xyz, means2D, dc, rest, op, sc, rot, rs, self.depth_alpha, *_camera_args(rs))
+                return _apply(_RasterizeGaussiansRaw, xyz, means2D, dc, rest, op, sc, rot, rs, self.depth_alpha, *_camera_args(rs),
+                              absgrad_to=means2D if self.absgrad else None)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, rs, self.depth_alpha)
+                                   cov3D_precomp, rs, self.depth_alpha, self.absgrad)
 
     def forward_raw(self, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations):
         """Extension (not in the reference API): render straight from the reference GaussianModel's raw parameters
@@ -715,4 +767,4 @@ class GaussianRasterizer(nn.Module):
         if not packed and (features_rest is None or features_rest.numel() == 0):
             features_rest = torch.empty(0, dtype=torch.float32, device=xyz.device)
         return _apply(_RasterizeGaussiansRaw, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations, rs,
-                      self.depth_alpha, *_camera_args(rs))
+                      self.depth_alpha, *_camera_args(rs), absgrad_to=means2D if self.absgrad else None)

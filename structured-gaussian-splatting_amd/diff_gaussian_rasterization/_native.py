@@ -119,6 +119,7 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_workspace_sizes", "gsr_binning_
            "gsr_activations_forward", "gsr_activations_backward",
            "gsr_aux_workspace_size", "gsr_forward_aux", "gsr_forward_render_aux", "gsr_backward_render_aux", "gsr_backward_geom_aux",
            "gsr_camera_grad_workspace_size", "gsr_backward_camera",
+           "gsr_backward_render_abs", "gsr_screen_absgrad",
            "gsr_structured_compose_forward", "gsr_structured_compose_backward",
            "gsr_opacity_compensation_forward", "gsr_opacity_compensation_backward",
            "gsr_decoder_workspace_size", "gsr_decoder_forward", "gsr_decoder_backward")
@@ -256,10 +257,17 @@ def backward_prepare(desc, g: Gaussians, plan: FramePlan, screen_grads, grads: G
 
 
 def backward_render(desc, cam: Camera, geom_ws, binning_ws, image_ws, rows_ws, plan: FramePlan, out_color, dL_dcolor, screen_grads,
-                    device):
-    _check(load().gsr_backward_render(C.byref(desc), C.byref(cam), _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws),
-                                      _ptr(rows_ws), C.byref(plan), _ptr(out_color), _ptr(dL_dcolor), _ptr(screen_grads), _stream(device)),
-           "gsr_backward_render")
+                    device, absgrad: bool = False):
+    """absgrad: gsr_backward_render_abs - screen_grads slots 10, 11 also receive the per-pixel absolute sums of d/dmean2D."""
+    fn, name = (load().gsr_backward_render_abs, "gsr_backward_render_abs") if absgrad else (load().gsr_backward_render, "gsr_backward_render")
+    _check(fn(C.byref(desc), C.byref(cam), _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws),
+              _ptr(rows_ws), C.byref(plan), _ptr(out_color), _ptr(dL_dcolor), _ptr(screen_grads), _stream(device)), name)
+
+
+def screen_absgrad(desc, radii, geom_ws, screen_grads, out, device, binned_ranks: int = -1, own_plan: Optional[FramePlan] = None):
+    """gsr_screen_absgrad, behind backward_geom of the same arguments: out [P,3] = (slot 10, slot 11, 0) of the rows it visits."""
+    _check(load().gsr_screen_absgrad(C.byref(desc), _ptr(radii), _ptr(geom_ws), _ptr(screen_grads), C.c_int32(binned_ranks),
+                                     None if own_plan is None else C.byref(own_plan), _ptr(out), _stream(device)), "gsr_screen_absgrad")
 
 
 def backward_render_aux(desc, cam: Camera, geom_ws, binning_ws, image_ws, rows_ws, plan: FramePlan, out_color, aux: AuxOutputs,

@@ -456,6 +456,9 @@ class ShardedRenderer:
         if getattr(pipe, "antialiasing", False):
             raise ValueError("pipe.antialiasing is not supported by ShardedRenderer: the opacity compensation is wired into "
                              "GaussianRasterizer only, the sharded slabs would render uncompensated (render unsharded, or turn it off)")
+        if getattr(pipe, "absgrad", False):
+            raise ValueError("pipe.absgrad is not supported by ShardedRenderer: the abs blend backward runs on whole images only, a "
+                             "slab's absolute sums would miss the other ranks' pixels (render unsharded, or turn it off)")
         xyz = pc.get_xyz
         screenspace_points = torch.zeros_like(xyz, requires_grad=True)     # a leaf keeps its .grad (gaussian_renderer.render)
         rs = GaussianRasterizationSettings(

@@ -56,3 +56,4 @@ class Pipe:
     debug = False
     fused_activations = None       # extension, see gaussian_renderer.render: None = only for this package's scene.GaussianModel
     antialiasing = False           # upstream's flag: compensate the opacity for the 0.3 px^2 dilation (gaussian_renderer.render)
+    absgrad = False                # gsplat's flag: backward() also leaves viewspace_points.absgrad (gaussian_renderer.render)

@@ -12,6 +12,10 @@ one interleaved leaf `_features`: raw mode 2), the getters for any other store. 
 
 `pipe.antialiasing` (upstream's flag; absent or False: off) turns on the rasterizer's opacity compensation for the 0.3 px^2
 dilation (diff_gaussian_rasterization.antialias), on the fused path and the getter path alike.
+
+`pipe.absgrad` (gsplat's flag; absent or False: off): after backward() the returned `viewspace_points` also carries `.absgrad`
+[P,3], the per-pixel absolute sums of the means2D gradient (diff_gaussian_rasterization, "absgrad"), on both paths; not together
+with depth_alpha=True (ValueError).
 """
 import math
 
@@ -74,7 +78,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         projmatrix=viewpoint_camera.full_proj_transform, sh_degree=pc.active_sh_degree,
         campos=viewpoint_camera.camera_center, prefiltered=False, debug=pipe.debug)
     rasterizer = GaussianRasterizer(raster_settings=raster_settings, depth_alpha=depth_alpha,
-                                    antialiasing=getattr(pipe, "antialiasing", False))
+                                    antialiasing=getattr(pipe, "antialiasing", False), absgrad=getattr(pipe, "absgrad", False))
 
     def result(out):
         d = {"render": out[0], "viewspace_points": screenspace_points, "visibility_filter": out[1] > 0, "radii": out[1]}

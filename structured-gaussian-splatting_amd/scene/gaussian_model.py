@@ -68,6 +68,7 @@ class OptimizationDefaults:
     densify_grad_threshold: float = 0.0002
     random_background: bool = False
     optimizer_type: str = "default"           # "sparse_adam": step only the Gaussians the frame saw (fused_adam.SparseFusedAdam)
+    densify_absgrad: bool = False             # densification statistics from viewspace_points.absgrad (frames rendered with pipe.absgrad)
 
 
 def expon_lr(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1_000_000):
@@ -110,6 +111,7 @@ class GaussianModel:
         self.percent_dense = 0.0
         self.spatial_lr_scale = 0.0
         self.freeze_means = self.freeze_scales = self.freeze_rotations = self.freeze_opacities = False
+        self.densify_absgrad = False
 
     # ---- the reference's attribute names -------------------------------------------------------------------
     packed_features = True                                   # _features_dc / _features_rest are views of _features
@@ -190,6 +192,7 @@ class GaussianModel:
     def training_setup(self, opt):
         P = self._xyz.shape[0]
         self.percent_dense = opt.percent_dense
+        self.densify_absgrad = bool(getattr(opt, "densify_absgrad", False))
         self.xyz_gradient_accum = torch.zeros(P, 1, device=self.device)
         self.denom = torch.zeros(P, 1, device=self.device)
         lrs = dict(xyz=opt.position_lr_init * self.spatial_lr_scale, f_dc=opt.feature_lr, f_rest=opt.feature_lr / 20.0,
@@ -279,14 +282,26 @@ class GaussianModel:
         capped = inverse_sigmoid(torch.min(self.get_opacity.detach(), torch.full_like(self._opacity, 0.01)))
         self._rebuild(replace={"opacity": capped})
 
+    def _densify_grad(self, viewspace_point_tensor):
+        """The tensor whose row norms the statistics accumulate: .grad, or with densify_absgrad the frame's .absgrad."""
+        if not self.densify_absgrad:
+            return viewspace_point_tensor.grad
+        absgrad = getattr(viewspace_point_tensor, "absgrad", None)
+        if absgrad is None:
+            raise ValueError("densify_absgrad is on but viewspace_points has no .absgrad: the frame was not rendered with pipe.absgrad "
+                             "(or no backward ran)")
+        return absgrad
+
     def add_densification_stats(self, viewspace_point_tensor, update_filter):
-        self.xyz_gradient_accum[update_filter] += torch.norm(viewspace_point_tensor.grad[update_filter, :2], dim=-1, keepdim=True)
+        grad = self._densify_grad(viewspace_point_tensor)
+        self.xyz_gradient_accum[update_filter] += torch.norm(grad[update_filter, :2], dim=-1, keepdim=True)
         self.denom[update_filter] += 1
 
     def update_densification_stats(self, viewspace_point_tensor, radii):
         """train.py:127-130 in one native pass (gsr_densify_stats): max_radii2D and add_densification_stats for the
-        visible set `radii > 0`, without the four boolean-mask compactions (each a host synchronisation)."""
-        grad = viewspace_point_tensor.grad
+        visible set `radii > 0`, without the four boolean-mask compactions (each a host synchronisation).
+        densify_absgrad: the same pass over viewspace_points.absgrad ([P,3], the layout of .grad) instead of .grad."""
+        grad = self._densify_grad(viewspace_point_tensor)
         if grad is None or not self.max_radii2D.is_cuda:
             vis = radii > 0
             self.max_radii2D[vis] = torch.max(self.max_radii2D[vis], radii[vis])

@@ -22,6 +22,8 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
             stack = list(range(len(cameras)))
         idx = stack.pop(random.randint(0, len(stack) - 1))
         bg = torch.rand(3, device=background.device) if opt.random_background else background
+        if getattr(opt, "densify_absgrad", False):             # the abs blend backward costs a little: only while its statistics are read
+            pipe.absgrad = it < opt.densify_until_iter
         pkg = render(cameras[idx], gaussians, pipe, bg)
         image, vsp, vis, radii = pkg["render"], pkg["viewspace_points"], pkg["visibility_filter"], pkg["radii"]
         loss = training_loss(image, targets[idx], opt.lambda_dssim)
