@@ -503,6 +503,59 @@ int gsr_decoder_forward(const gsr_decoder_desc *desc, const float *pos_emb, cons
 int gsr_decoder_backward(const gsr_decoder_desc *desc, const float *pos_emb, const float *latents, const gsr_decoder_params *params,
                          const float *d_decoded, const gsr_decoder_grads *grads, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- The MCMC densification strategy ("3D Gaussian Splatting as Markov Chain Monte Carlo"; gsplat's MCMCStrategy), additive: every
+ * call above keeps its meaning.  The tensors are the raw parameters: opacity_raw [P] logits, scaling_raw [P,3] logs, rotation_raw
+ * [P,4] unnormalised quaternions, xyz [P,3]; o = sigmoid(opacity_raw), s = exp(scaling_raw), q^ = q / max(|q|, 1e-12).
+ *
+ * gsr_mcmc_relocation: sampled [n] (int64, DEVICE, every entry in [0, P): not checked) lists the sources, one entry per Gaussian
+ * that is to become a copy of it.  With N_j = min(GSR_MCMC_MAX_RATIO, 1 + occurrences of sampled[j] in sampled), and o, s of the
+ * source BEFORE the call:
+ *   o' = 1 - (1 - o)^(1/N)      D = sum_{i=1..N} sum_{k=0..i-1} C(i-1, k) (-1)^k (k+1)^(-1/2) o'^(k+1)
+ *   new_opacity_raw[j] = logit(clamp(o', min_opacity, 1 - 2^-23))      new_scaling_raw[j, :] = scaling_raw[sampled[j], :] + log(o / D)
+ * (the clamp comes after D).  Evaluated in binary64 and rounded to binary32 once: the alternating sum loses up to 8e-5 in binary32.
+ * workspace: gsr_mcmc_relocation_workspace_size(P) bytes, 4-byte aligned, contents irrelevant before and after (occurrence counters,
+ * summed with integer atomics: the result does not depend on their order).  Only the two outputs are written.  Three launches over
+ * n, none over P; no host synchronisation.  0 < min_opacity < 1.  P == 0 or n == 0: nothing is launched. */
+int gsr_mcmc_relocation_workspace_size(int64_t P, size_t *bytes);
+int gsr_mcmc_relocation(int64_t P, int64_t n, const float *opacity_raw, const float *scaling_raw, const int64_t *sampled,
+                        float min_opacity, void *workspace, float *new_opacity_raw, float *new_scaling_raw, void *stream);
+
+/* gsr_mcmc_relocate_rows: applies the result of gsr_mcmc_relocation (same sampled, same stream or ordered behind it) to up to
+ * GSR_MCMC_MAX_TENSORS tensors of P rows.  tensors: HOST array; tensor t has `width` >= 1 contiguous floats per row and a role:
+ *   GSR_MCMC_ROLE_OPACITY (width 1):  param[sampled[j]] = new_opacity_raw[j]
+ *   GSR_MCMC_ROLE_SCALING (width 3):  param[sampled[j], :] = new_scaling_raw[j, :]
+ *   GSR_MCMC_ROLE_COPY:               source rows keep their values
+ * dead != NULL ([n] int64, DEVICE, distinct rows, none of them in sampled): row dead[j] of every tensor becomes row sampled[j] as it
+ * is after the call (copied values bit for bit), and exp_avg / exp_avg_sq (both or neither NULL) of every SOURCE row are set to
+ * zero; the dead rows' moments are left alone.  dead == NULL (growth: the caller appends the copies itself): only the new values
+ * are written, no moment is touched.  ONE launch whatever n, P and count are; it reads nothing that it writes, a source listed k
+ * times is written k times with one value, so the result does not depend on thread order.  P == 0, n == 0 or count == 0: nothing
+ * is launched. */
+#define GSR_MCMC_MAX_TENSORS 8
+#define GSR_MCMC_ROLE_COPY    0
+#define GSR_MCMC_ROLE_OPACITY 1
+#define GSR_MCMC_ROLE_SCALING 2
+typedef struct gsr_mcmc_tensor {
+    float *param; float *exp_avg; float *exp_avg_sq;      /* [P, width]; the moments: both or neither NULL */
+    int32_t width, role;
+} gsr_mcmc_tensor;
+int gsr_mcmc_relocate_rows(int32_t count, const gsr_mcmc_tensor *tensors, int64_t P, int64_t n, const int64_t *sampled,
+                           const int64_t *dead, const float *new_opacity_raw, const float *new_scaling_raw, void *stream);
+
+/* gsr_mcmc_inject_noise: xyz[i] += R(q^_i) diag(s_i^2) R(q^_i)^T (noise[i] g(o_i) c),  g(o) = 1 / (1 + exp(100 o - 0.5)), in
+ * place; noise [P,3] is the caller's standard-normal draw, c a host scalar (noise_lr x the position learning rate).  Where the
+ * exponential overflows g is 0 and the row keeps xyz + 0.  One launch, 56 B read and 12 B written per Gaussian, every row from its
+ * own inputs (no atomics): the same inputs give the same bits.  All five tensors 16-byte aligned.  P == 0: nothing is launched.
+ *
+ * gsr_mcmc_reg_grads: the gradient of lambda_opacity mean(o) + lambda_scale mean(s) added in place:
+ *   grad_opacity[i] += lambda_opacity / P o_i (1 - o_i)        grad_scaling[i, j] += lambda_scale / (3 P) s_ij
+ * Either gradient may be NULL (its lambda and raw tensor are then ignored); a given one and its raw tensor are 16-byte aligned.
+ * One launch.  The loss value itself is not computed. */
+int gsr_mcmc_inject_noise(int64_t P, float *xyz, const float *scaling_raw, const float *rotation_raw, const float *opacity_raw,
+                          const float *noise, float c, void *stream);
+int gsr_mcmc_reg_grads(int64_t P, const float *opacity_raw, const float *scaling_raw, float lambda_opacity, float lambda_scale,
+                       float *grad_opacity, float *grad_scaling, void *stream);
+
 /* ---- the densification bookkeeping of one training iteration (train.py:127-130,
  * scene/gaussian_model.py:415-417) in one pass without a host synchronisation: for every Gaussian with
  * radii[i] > 0:  max_radii2D[i] = max(max_radii2D[i], radii[i]);  xyz_gradient_accum[i] += |viewspace_grad[i, :2]|;

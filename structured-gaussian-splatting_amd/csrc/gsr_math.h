@@ -897,6 +897,83 @@ GSR_HD void compose_child_backward(const float c[kChildGeom], const float s[kChi
     quat_normalize_backward(c + 7, b, dB, d_c + 7);
 }
 
+// ---- The MCMC densification strategy ("3D Gaussian Splatting as Markov Chain Monte Carlo"): the arithmetic of
+// one Gaussian for the relocation rule, the position noise and the regulariser gradient (kernels: gsr_mcmc.hip).
+//
+// Relocation: a source of opacity o and scale s that stands for N Gaussians afterwards (N = 1 + the times it was sampled, clamped to
+// 1 .. GSR_MCMC_MAX_RATIO) becomes
+//   o' = 1 - (1 - o)^(1/N)      D = sum_{i=1..N} sum_{k=0..i-1} C(i-1, k) (-1)^k (k+1)^(-1/2) o'^(k+1)      s' = (o / D) s
+//   opacity_raw' = logit(clamp(o', min_opacity, 1 - 2^-23))        scaling_raw' = scaling_raw + log(o / D)
+// The inner sums over i collapse (sum_{i=k+1..N} C(i-1, k) = C(N, k+1)): D = sum_{j=1..N} C(N, j) (-1)^(j-1) j^(-1/2) o'^j, with
+// C(N, j) = C(N, j-1) (N-j+1) / j exact in binary64 (every product stays below 2^53 for N <= 51).  The sum alternates and cancels:
+// everything here is binary64 (o and 1 - o as the two sigmoids, o' through expm1 of log(1 - o) / N, so that a small o loses
+// nothing), rounded to binary32 once at the end.  N = 1 is the identity: the inputs are returned as they are.
+GSR_HD void mcmc_relocation_one(float opacity_raw, const float scaling_raw[3], int N, float min_opacity, float &new_opacity_raw,
+                                float new_scaling_raw[3])
+{
+    if (N <= 1) {
+        new_opacity_raw = opacity_raw;
+        for (int k = 0; k < 3; ++k) new_scaling_raw[k] = scaling_raw[k];
+        return;
+    }
+    if (N > GSR_MCMC_MAX_RATIO) N = GSR_MCMC_MAX_RATIO;
+    const double x = (double)opacity_raw;
+    const double o = 1.0 / (1.0 + exp(-x)), om = 1.0 / (1.0 + exp(x));       // o, 1 - o
+    const double log_om1 = log(om) / (double)N;                              // log(1 - o')
+    const double o1 = -expm1(log_om1);                                       // o'
+    double D = 0.0, c = 1.0, pw = 1.0;
+    for (int j = 1; j <= N; ++j) {
+        c = c * (double)(N - j + 1) / (double)j;                             // C(N, j)
+        pw *= o1;
+        const double term = c * pw / sqrt((double)j);
+        D += (j & 1) ? term : -term;
+    }
+    const double lo = (double)min_opacity, hi = 1.0 - 1.1920928955078125e-07;
+    const double logit = o1 < lo ? log(lo) - log1p(-lo) : (o1 > hi ? log(hi) - log1p(-hi) : log(o1) - log_om1);
+    new_opacity_raw = (float)logit;
+    const double shift = log(o / D);
+    for (int k = 0; k < 3; ++k) new_scaling_raw[k] = (float)((double)scaling_raw[k] + shift);
+}
+
+// Position noise: delta = R(q^) diag(s^2) R(q^)^T (xi g(o) c),   g(o) = 1 / (1 + exp(100 o - 0.5)),   q^ = q / max(|q|, 1e-12),
+// s = exp(log_scale), o = sigmoid(logit).  exp may overflow to +inf for o near 1: g is then 0 and the delta exactly zero (a zero g
+// returns before anything is multiplied by it, so that no 0 * inf can form).
+GSR_HD void mcmc_noise_one(const float log_scale[3], const float raw_q[4], float logit, const float xi[3], float c, float delta[3])
+{
+    const float o = 1.f / (1.f + expf(-logit));
+    const float g = 1.f / (1.f + expf(100.f * o - 0.5f));
+    delta[0] = delta[1] = delta[2] = 0.f;
+    if (!(g > 0.f)) return;
+    const float n = sqrtf(raw_q[0] * raw_q[0] + raw_q[1] * raw_q[1] + raw_q[2] * raw_q[2] + raw_q[3] * raw_q[3]);
+    const float nc = fmaxf(n, 1e-12f);
+    const float q[4] = {raw_q[0] / nc, raw_q[1] / nc, raw_q[2] / nc, raw_q[3] / nc};
+    float R[9];
+    quat_to_rot(q, R);
+    const float gc = g * c;
+    const float w[3] = {xi[0] * gc, xi[1] * gc, xi[2] * gc};
+    float v[3];
+    for (int k = 0; k < 3; ++k) {                                            // v = diag(s^2) R^T w
+        const float s = expf(log_scale[k]);
+        v[k] = (R[k] * w[0] + R[3 + k] * w[1] + R[6 + k] * w[2]) * (s * s);
+    }
+    for (int k = 0; k < 3; ++k) delta[k] = R[3 * k] * v[0] + R[3 * k + 1] * v[1] + R[3 * k + 2] * v[2];
+}
+
+// Regulariser gradient: d/d opacity_raw of k_o o = k_o o (1 - o), d/d scaling_raw of k_s s = k_s s (k_o = lambda_o / P,
+// k_s = lambda_s / (3 P): the gradients of lambda_o mean(o) + lambda_s mean(s)).  o (1 - o) = e / (1 + e)^2 with e = exp(-|x|):
+// no subtraction from 1 and no overflow for any logit.
+GSR_HD float mcmc_reg_opacity_one(float logit, float k_o)
+{
+    const float e = expf(-fabsf(logit)), d = 1.f + e;
+    return k_o * (e / (d * d));
+}
+GSR_HD float mcmc_reg_scale_one(float log_scale, float k_s) { return k_s * expf(log_scale); }
+GSR_HD void mcmc_reg_one(float logit, const float log_scale[3], float k_o, float k_s, float &d_opacity, float d_scaling[3])
+{
+    d_opacity = mcmc_reg_opacity_one(logit, k_o);
+    for (int k = 0; k < 3; ++k) d_scaling[k] = mcmc_reg_scale_one(log_scale[k], k_s);
+}
+
 // ---- A.1 alone (markVisible).
 GSR_HD bool in_frustum(const float p[3], const float *V)
 {

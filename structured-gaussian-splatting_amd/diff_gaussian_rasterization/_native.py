@@ -122,7 +122,8 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_workspace_sizes", "gsr_binning_
            "gsr_backward_render_abs", "gsr_screen_absgrad",
            "gsr_structured_compose_forward", "gsr_structured_compose_backward",
            "gsr_opacity_compensation_forward", "gsr_opacity_compensation_backward",
-           "gsr_decoder_workspace_size", "gsr_decoder_forward", "gsr_decoder_backward")
+           "gsr_decoder_workspace_size", "gsr_decoder_forward", "gsr_decoder_backward",
+           "gsr_mcmc_relocation_workspace_size", "gsr_mcmc_relocation", "gsr_mcmc_relocate_rows", "gsr_mcmc_inject_noise", "gsr_mcmc_reg_grads")
 
 _lib = None
 
@@ -705,3 +706,61 @@ def decoder_backward(pos_emb, latents, params, d_decoded, want):
         _check(load().gsr_decoder_backward(C.byref(desc), _ptr(pos_emb), _ptr(latents), C.byref(pr), _ptr(d_decoded), C.byref(gr),
                                            _ptr(ws), C.c_size_t(nbytes), _stream(latents.device)), "gsr_decoder_backward")
     return tuple(outs)
+
+
+class McmcTensor(C.Structure):
+    """gsr_mcmc_tensor: a [P, width] tensor, its Adam moments (both or neither None) and its role."""
+    _fields_ = [("param", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("width", C.c_int32), ("role", C.c_int32)]
+
+
+MCMC_MAX_TENSORS = 8
+MCMC_ROLES = {"copy": 0, "opacity": 1, "scaling": 2}
+
+
+def mcmc_relocation(opacity_raw, scaling_raw, sampled, min_opacity: float):
+    """gsr_mcmc_relocation: opacity_raw [P,1] / [P], scaling_raw [P,3] (contiguous fp32), sampled [n] int64 on their device ->
+    (new_opacity_raw [n], new_scaling_raw [n,3]).  The counter workspace is a torch allocation that lives for the call."""
+    P, n = int(opacity_raw.shape[0]), int(sampled.shape[0])
+    new_o = torch.empty(n, dtype=torch.float32, device=opacity_raw.device)
+    new_s = torch.empty(n, 3, dtype=torch.float32, device=opacity_raw.device)
+    b = C.c_size_t(0)
+    _check(load().gsr_mcmc_relocation_workspace_size(C.c_int64(P), C.byref(b)), "gsr_mcmc_relocation_workspace_size")
+    if P == 0 or n == 0:
+        return new_o, new_s
+    ws = torch.empty(b.value, dtype=torch.uint8, device=opacity_raw.device)
+    with torch.cuda.device(opacity_raw.device):
+        _check(load().gsr_mcmc_relocation(C.c_int64(P), C.c_int64(n), _ptr(opacity_raw), _ptr(scaling_raw), _ptr(sampled),
+                                          C.c_float(min_opacity), _ptr(ws), _ptr(new_o), _ptr(new_s), _stream(opacity_raw.device)),
+               "gsr_mcmc_relocation")
+    return new_o, new_s
+
+
+def mcmc_relocate_rows(items, P: int, sampled, dead, new_opacity_raw, new_scaling_raw):
+    """gsr_mcmc_relocate_rows.  items: up to MCMC_MAX_TENSORS tuples (param, exp_avg or None, exp_avg_sq or None, role) with role
+    one of MCMC_ROLES; dead: [n] int64 or None."""
+    arr = (McmcTensor * len(items))()
+    for a, (p, m, v, role) in zip(arr, items):
+        a.param, a.exp_avg, a.exp_avg_sq = _ptr(p), _ptr(m), _ptr(v)
+        a.width, a.role = p.numel() // max(int(p.shape[0]), 1), MCMC_ROLES[role]
+    dev = sampled.device
+    with torch.cuda.device(dev):
+        _check(load().gsr_mcmc_relocate_rows(C.c_int32(len(items)), arr, C.c_int64(int(P)), C.c_int64(int(sampled.shape[0])), _ptr(sampled),
+                                             _ptr(dead), _ptr(new_opacity_raw), _ptr(new_scaling_raw), _stream(dev)), "gsr_mcmc_relocate_rows")
+
+
+def mcmc_inject_noise(xyz, scaling_raw, rotation_raw, opacity_raw, noise, c: float):
+    """gsr_mcmc_inject_noise: in place on xyz [P,3]; all tensors contiguous fp32 on one device."""
+    with torch.cuda.device(xyz.device):
+        _check(load().gsr_mcmc_inject_noise(C.c_int64(int(xyz.shape[0])), _ptr(xyz), _ptr(scaling_raw), _ptr(rotation_raw), _ptr(opacity_raw),
+                                            _ptr(noise), C.c_float(c), _stream(xyz.device)), "gsr_mcmc_inject_noise")
+
+
+def mcmc_reg_grads(opacity_raw, scaling_raw, lambda_opacity: float, lambda_scale: float, grad_opacity, grad_scaling):
+    """gsr_mcmc_reg_grads: in place on the given gradients (either may be None)."""
+    some = grad_opacity if grad_opacity is not None else grad_scaling
+    if some is None:
+        return
+    P = int(some.shape[0])
+    with torch.cuda.device(some.device):
+        _check(load().gsr_mcmc_reg_grads(C.c_int64(P), _ptr(opacity_raw), _ptr(scaling_raw), C.c_float(lambda_opacity), C.c_float(lambda_scale),
+                                         _ptr(grad_opacity), _ptr(grad_scaling), _stream(some.device)), "gsr_mcmc_reg_grads")

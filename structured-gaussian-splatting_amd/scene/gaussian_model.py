@@ -69,6 +69,12 @@ class OptimizationDefaults:
     random_background: bool = False
     optimizer_type: str = "default"           # "sparse_adam": step only the Gaussians the frame saw (fused_adam.SparseFusedAdam)
     densify_absgrad: bool = False             # densification statistics from viewspace_points.absgrad (frames rendered with pipe.absgrad)
+    densify_strategy: str = "default"         # "mcmc": relocation, 5 % growth to a cap and position noise (GaussianModel.mcmc_*)
+    mcmc_cap_max: int = 1_000_000             # the budget of Gaussians the "mcmc" strategy grows to and then keeps
+    mcmc_noise_lr: float = 5e5                # position noise scale, times the xyz learning rate
+    mcmc_min_opacity: float = 0.005           # at or below it a Gaussian is dead: relocated onto a live one
+    mcmc_opacity_reg: float = 0.01            # lambda of mean(opacity)
+    mcmc_scale_reg: float = 0.01              # lambda of mean(scale)
 
 
 def expon_lr(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1_000_000):
@@ -112,6 +118,7 @@ class GaussianModel:
         self.spatial_lr_scale = 0.0
         self.freeze_means = self.freeze_scales = self.freeze_rotations = self.freeze_opacities = False
         self.densify_absgrad = False
+        self.densify_strategy = "default"
 
     # ---- the reference's attribute names -------------------------------------------------------------------
     packed_features = True                                   # _features_dc / _features_rest are views of _features
@@ -193,6 +200,12 @@ class GaussianModel:
         P = self._xyz.shape[0]
         self.percent_dense = opt.percent_dense
         self.densify_absgrad = bool(getattr(opt, "densify_absgrad", False))
+        strategy = getattr(opt, "densify_strategy", "default")
+        if strategy not in ("default", "mcmc"):
+            raise ValueError(f"densify_strategy = {strategy!r}: \"default\" or \"mcmc\"")
+        if strategy == "mcmc" and self.densify_absgrad:
+            raise ValueError("densify_strategy = \"mcmc\" reads no gradient statistics: densify_absgrad cannot be combined with it")
+        self.densify_strategy = strategy
         self.xyz_gradient_accum = torch.zeros(P, 1, device=self.device)
         self.denom = torch.zeros(P, 1, device=self.device)
         lrs = dict(xyz=opt.position_lr_init * self.spatial_lr_scale, f_dc=opt.feature_lr, f_rest=opt.feature_lr / 20.0,
@@ -339,6 +352,73 @@ class GaussianModel:
         if max_screen_size:
             drop = drop | (self.max_radii2D > max_screen_size) | (self.get_scaling.detach().max(dim=1).values > 0.1 * extent)
         self.prune_points(drop)
+
+    # ---- the MCMC strategy (diff_gaussian_rasterization/mcmc.py) ---------------------------------------
+    MULTINOMIAL_MAX = 2 ** 24                                # torch.multinomial's limit on the number of categories
+
+    def _mcmc_tensors(self):
+        """(param, exp_avg, exp_avg_sq, role) of the five leaves; the moments as _rebuild finds them (None before the first step
+        and without an optimizer)."""
+        roles = {"opacity": "opacity", "scaling": "scaling"}
+        out = []
+        for name in TABLE:
+            st = self.optimizer.state.get(self._t[name]) if self.optimizer is not None else None
+            has = st is not None and "exp_avg" in st
+            out.append((self._t[name], st["exp_avg"] if has else None, st["exp_avg_sq"] if has else None, roles.get(name, "copy")))
+        return out
+
+    def _mcmc_probs(self, rows=None):
+        o = torch.sigmoid(self._opacity.detach()).reshape(-1)
+        o = o if rows is None else o[rows]
+        if o.shape[0] > self.MULTINOMIAL_MAX:
+            raise ValueError(f"the MCMC strategy samples with torch.multinomial, which takes at most 2^24 categories: {o.shape[0]} Gaussians")
+        return o
+
+    def mcmc_relocate(self, min_opacity, generator=None, native=None):
+        """Dead Gaussians (opacity <= min_opacity) become copies of live ones sampled by opacity; the sources take the relocation
+        rule's opacity and scale and lose their Adam moments.  P does not change.  Returns the number relocated."""
+        from diff_gaussian_rasterization import mcmc
+        dead_mask = torch.sigmoid(self._opacity.detach()).reshape(-1) <= min_opacity
+        dead, alive = torch.nonzero(dead_mask).reshape(-1), torch.nonzero(~dead_mask).reshape(-1)      # one host synchronisation
+        if dead.numel() == 0 or alive.numel() == 0:
+            return 0
+        sampled = alive[torch.multinomial(self._mcmc_probs(alive), dead.numel(), replacement=True, generator=generator)]
+        new_o, new_s = mcmc.compute_relocation(self._opacity, self._scaling, sampled, min_opacity, native=native)
+        mcmc.relocate_rows(self._mcmc_tensors(), sampled, dead, new_o, new_s, native=native)
+        self._acts.invalidate()
+        return int(dead.numel())
+
+    def mcmc_grow(self, cap_max, min_opacity, generator=None, native=None):
+        """5 % more Gaussians, up to cap_max: copies of Gaussians sampled by opacity (all rows), sources and copies at the relocation
+        rule's opacity and scale; the sources keep their moments, the copies start at zero.  Returns the number added."""
+        from diff_gaussian_rasterization import mcmc
+        P = self._xyz.shape[0]
+        n_new = max(0, min(int(cap_max), int(1.05 * P)) - P)
+        if n_new == 0:
+            return 0
+        sampled = torch.multinomial(self._mcmc_probs(), n_new, replacement=True, generator=generator)
+        new_o, new_s = mcmc.compute_relocation(self._opacity, self._scaling, sampled, min_opacity, native=native)
+        mcmc.relocate_rows([(p, None, None, role) for p, _, _, role in self._mcmc_tensors()], sampled, None, new_o, new_s, native=native)
+        self._rebuild(extra={k: self._t[k].detach()[sampled] for k in TABLE})
+        self._reset_stats()
+        return n_new
+
+    def mcmc_inject_noise(self, c, noise=None, native=None):
+        """xyz += Sigma (noise g(opacity) c): covariance-shaped, opacity-gated position noise; noise = None draws randn_like(_xyz)."""
+        from diff_gaussian_rasterization import mcmc
+        if noise is None:
+            noise = torch.randn_like(self._xyz)
+        mcmc.inject_position_noise(self._xyz, self._scaling, self._rotation, self._opacity, noise, c, native=native)
+
+    def mcmc_add_regularizer_grads(self, lambda_opacity, lambda_scale, native=None):
+        """Adds the gradient of lambda_opacity mean(opacity) + lambda_scale mean(scale) to _opacity.grad and _scaling.grad (a missing
+        .grad starts as zeros).  The loss value is not computed."""
+        from diff_gaussian_rasterization import mcmc
+        for t in (self._opacity, self._scaling):
+            if t.grad is None:
+                t.grad = torch.zeros_like(t)
+        mcmc.add_regularizer_grads(self._opacity, self._scaling, lambda_opacity, lambda_scale, self._opacity.grad, self._scaling.grad,
+                                   native=native)
 
     # ---- persistence -----------------------------------------------------------------------------------------
     # The checkpoint tuple is the reference's (scene/gaussian_model.py:67-99, saved by train.py as chkpnt*.pth), its optimizer

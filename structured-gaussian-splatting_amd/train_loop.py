@@ -1,6 +1,7 @@
 """The reference's training iteration (train.py:63-146) around the drop-in rasterizer, for synthetic scenes:
 LR schedule, SH-degree ramp, render -> L1/D-SSIM -> backward, densification bookkeeping, densify/prune,
-opacity reset, Adam step.  SURVEY 8f row f1."""
+opacity reset, Adam step.  SURVEY 8f row f1.  opt.densify_strategy = "mcmc" replaces the densification part:
+regulariser gradients before the step; relocation and growth after it, inside the refinement window; position noise every iteration."""
 import random
 
 import torch
@@ -14,8 +15,9 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
           white_background=False, on_iteration=None):
     """cameras / targets: lists of equal length (Camera-like objects and [3,H,W] ground-truth images)."""
     stack = []
+    mcmc = getattr(opt, "densify_strategy", "default") == "mcmc"
     for it in range(first_iter, iterations + 1):
-        gaussians.update_learning_rate(it)
+        xyz_lr = gaussians.update_learning_rate(it)
         if it % 1000 == 0:
             gaussians.oneupSHdegree()
         if not stack:
@@ -29,7 +31,9 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
         loss = training_loss(image, targets[idx], opt.lambda_dssim)
         loss.backward()
         with torch.no_grad():
-            if it < opt.densify_until_iter:
+            if mcmc:
+                gaussians.mcmc_add_regularizer_grads(opt.mcmc_opacity_reg, opt.mcmc_scale_reg)
+            elif it < opt.densify_until_iter:
                 gaussians.update_densification_stats(vsp, radii)       # train.py:127-130, one native pass
                 if it > opt.densify_from_iter and it % opt.densification_interval == 0:
                     size_threshold = 20 if it > opt.opacity_reset_interval else None
@@ -42,6 +46,11 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
                 else:
                     gaussians.optimizer.step()
                 gaussians.optimizer.zero_grad(set_to_none=True)
+                if mcmc and opt.densify_from_iter < it < opt.densify_until_iter and it % opt.densification_interval == 0:
+                    gaussians.mcmc_relocate(opt.mcmc_min_opacity)
+                    gaussians.mcmc_grow(opt.mcmc_cap_max, opt.mcmc_min_opacity)
+            if mcmc:
+                gaussians.mcmc_inject_noise(opt.mcmc_noise_lr * xyz_lr)
         if on_iteration is not None:
             on_iteration(it, loss, gaussians)
     return gaussians
