@@ -556,6 +556,41 @@ int gsr_mcmc_inject_noise(int64_t P, float *xyz, const float *scaling_raw, const
 int gsr_mcmc_reg_grads(int64_t P, const float *opacity_raw, const float *scaling_raw, float lambda_opacity, float lambda_scale,
                        float *grad_opacity, float *grad_scaling, void *stream);
 
+/* ---- The per-image bilateral grid (gsplat's lib_bilagrid): every training image
+ * owns a grid of 3x4 affine colour transforms indexed by pixel position and luma, and the rendered image goes through its grid
+ * before the loss.  grids is [N, 12, L, Gy, Gx] (gsplat's layout), image / out / grad_out / grad_image are [3, H, W], all contiguous
+ * fp32; idx in [0, N) picks the grid.  For pixel (py, px) with in = (r, g, b, 1):
+ *   fx = (px + 0.5) / W (Gx - 1)    fy = (py + 0.5) / H (Gy - 1)    fz = clamp(0.299 r + 0.587 g + 0.114 b, 0, 1) (L - 1)
+ *   per axis  i0 = clamp(floor f, 0, G - 1), i1 = min(i0 + 1, G - 1), t = f - i0  (an axis of size 1: t = 0)
+ *   A_k = sum over the 8 corners of w grids[idx, k, z, y, x],  w = the product of the three (1 - t | t) factors
+ *   out_c = A[4c] r + A[4c+1] g + A[4c+2] b + A[4c+3]
+ * which is torch's grid_sample(mode="bilinear", padding_mode="border", align_corners=True) on a 5-D input and the affine product.
+ *
+ * gsr_bilagrid_forward: one launch.  gsr_bilagrid_backward: grad_grids [N, 12, L, Gy, Gx] (dense: the rows of every image but idx
+ * are written as zero) and grad_image, either may be NULL (both NULL: nothing is launched).  One launch for grad_image and the
+ * per-block partial sums of grad_grids (in `workspace`, backward_bytes of gsr_bilagrid_workspace_size; not read when grad_grids is
+ * NULL), one that adds the partials in a fixed order.  The luma term of grad_image is zero where the luma is outside (0, 1).  No
+ * floating-point atomics: the same inputs give the same bits.
+ *
+ * gsr_bilagrid_tv_forward: out[0] = the sum, over the grid axes (x, y, luma) longer than 1, of the mean squared forward difference
+ * along the axis (gsplat's total_variation_loss; an axis of size 1 adds 0).  One launch.  `workspace` is tv_bytes of
+ * gsr_bilagrid_workspace_size; its bytes must be ZERO before the first call and every call puts its ticket word back to zero, so a
+ * workspace cleared once serves any number of calls, one in flight at a time.  gsr_bilagrid_tv_backward: grad_grids = grad_out[0]
+ * d tv / d grids, one launch, every element gathered from its six neighbours.
+ *
+ * Every size of the grid is 1 .. 1024 and N 12 L Gy Gx < 2^31; H, W are 0 .. 32768 and H W == 0 returns GSR_OK with nothing
+ * launched.  Arguments are checked before anything touches the device. */
+int gsr_bilagrid_workspace_size(int32_t H, int32_t W, int32_t L, int32_t Gy, int32_t Gx, size_t *backward_bytes, size_t *tv_bytes);
+int gsr_bilagrid_forward(int32_t N, int32_t L, int32_t Gy, int32_t Gx, int32_t H, int32_t W, int32_t idx, const float *grids,
+                         const float *image, float *out, void *stream);
+int gsr_bilagrid_backward(int32_t N, int32_t L, int32_t Gy, int32_t Gx, int32_t H, int32_t W, int32_t idx, const float *grids,
+                          const float *image, const float *grad_out, float *grad_grids, float *grad_image, void *workspace,
+                          size_t workspace_bytes, void *stream);
+int gsr_bilagrid_tv_forward(int32_t N, int32_t L, int32_t Gy, int32_t Gx, const float *grids, void *workspace, float *out,
+                            void *stream);
+int gsr_bilagrid_tv_backward(int32_t N, int32_t L, int32_t Gy, int32_t Gx, const float *grids, const float *grad_out,
+                             float *grad_grids, void *stream);
+
 /* ---- the densification bookkeeping of one training iteration (train.py:127-130,
  * scene/gaussian_model.py:415-417) in one pass without a host synchronisation: for every Gaussian with
  * radii[i] > 0:  max_radii2D[i] = max(max_radii2D[i], radii[i]);  xyz_gradient_accum[i] += |viewspace_grad[i, :2]|;

@@ -123,7 +123,8 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_workspace_sizes", "gsr_binning_
            "gsr_structured_compose_forward", "gsr_structured_compose_backward",
            "gsr_opacity_compensation_forward", "gsr_opacity_compensation_backward",
            "gsr_decoder_workspace_size", "gsr_decoder_forward", "gsr_decoder_backward",
-           "gsr_mcmc_relocation_workspace_size", "gsr_mcmc_relocation", "gsr_mcmc_relocate_rows", "gsr_mcmc_inject_noise", "gsr_mcmc_reg_grads")
+           "gsr_mcmc_relocation_workspace_size", "gsr_mcmc_relocation", "gsr_mcmc_relocate_rows", "gsr_mcmc_inject_noise", "gsr_mcmc_reg_grads",
+           "gsr_bilagrid_workspace_size", "gsr_bilagrid_forward", "gsr_bilagrid_backward", "gsr_bilagrid_tv_forward", "gsr_bilagrid_tv_backward")
 
 _lib = None
 
@@ -764,3 +765,82 @@ def mcmc_reg_grads(opacity_raw, scaling_raw, lambda_opacity: float, lambda_scale
     with torch.cuda.device(some.device):
         _check(load().gsr_mcmc_reg_grads(C.c_int64(P), _ptr(opacity_raw), _ptr(scaling_raw), C.c_float(lambda_opacity), C.c_float(lambda_scale),
                                          _ptr(grad_opacity), _ptr(grad_scaling), _stream(some.device)), "gsr_mcmc_reg_grads")
+
+
+def _bilagrid_dims(grids):
+    N, twelve, L, Gy, Gx = (int(v) for v in grids.shape)
+    if twelve != 12:
+        raise ValueError(f"bilagrid: grids must be [N, 12, L, Gy, Gx], got {tuple(grids.shape)}")
+    return N, L, Gy, Gx
+
+
+def bilagrid_workspace_sizes(H: int, W: int, L: int, Gy: int, Gx: int):
+    """gsr_bilagrid_workspace_size -> (bytes of the backward's per-block partial sums, bytes of the TV workspace)."""
+    b, t = C.c_size_t(0), C.c_size_t(0)
+    _check(load().gsr_bilagrid_workspace_size(C.c_int32(H), C.c_int32(W), C.c_int32(L), C.c_int32(Gy), C.c_int32(Gx), C.byref(b), C.byref(t)),
+           "gsr_bilagrid_workspace_size")
+    return b.value, t.value
+
+
+def bilagrid_forward(grids, image, idx: int):
+    """gsr_bilagrid_forward: grids [N,12,L,Gy,Gx], image [3,H,W], contiguous fp32 on one device -> the corrected image [3,H,W]."""
+    N, L, Gy, Gx = _bilagrid_dims(grids)
+    H, W = int(image.shape[1]), int(image.shape[2])
+    out = torch.empty_like(image)
+    with torch.cuda.device(image.device):
+        _check(load().gsr_bilagrid_forward(C.c_int32(N), C.c_int32(L), C.c_int32(Gy), C.c_int32(Gx), C.c_int32(H), C.c_int32(W), C.c_int32(int(idx)),
+                                           _ptr(grids), _ptr(image), _ptr(out), _stream(image.device)), "gsr_bilagrid_forward")
+    return out
+
+
+def bilagrid_backward(grids, image, idx: int, grad_out, want_grids: bool, want_image: bool):
+    """gsr_bilagrid_backward -> (grad_grids [N,12,L,Gy,Gx] dense, grad_image [3,H,W]), None where not wanted.  The partial-sum
+    workspace is a torch allocation that lives for the call."""
+    N, L, Gy, Gx = _bilagrid_dims(grids)
+    H, W = int(image.shape[1]), int(image.shape[2])
+    if H * W == 0:
+        return (torch.zeros_like(grids) if want_grids else None, torch.empty_like(image) if want_image else None)
+    dgrids = torch.empty_like(grids) if want_grids else None
+    dimage = torch.empty_like(image) if want_image else None
+    ws, nbytes = None, 0
+    if want_grids:
+        nbytes = bilagrid_workspace_sizes(H, W, L, Gy, Gx)[0]
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=image.device)
+    with torch.cuda.device(image.device):
+        _check(load().gsr_bilagrid_backward(C.c_int32(N), C.c_int32(L), C.c_int32(Gy), C.c_int32(Gx), C.c_int32(H), C.c_int32(W), C.c_int32(int(idx)),
+                                            _ptr(grids), _ptr(image), _ptr(grad_out), _ptr(dgrids), _ptr(dimage), _ptr(ws), C.c_size_t(nbytes),
+                                            _stream(image.device)), "gsr_bilagrid_backward")
+    return dgrids, dimage
+
+
+_tv_ws = {}
+
+
+def _bilagrid_tv_workspace(device):
+    """The TV forward's workspace of a (device, stream): cleared once, every call leaves its ticket at zero."""
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    ws = _tv_ws.get(key)
+    if ws is None:
+        ws = _tv_ws[key] = torch.zeros(bilagrid_workspace_sizes(1, 1, 1, 1, 1)[1], dtype=torch.uint8, device=device)
+    return ws
+
+
+def bilagrid_tv_forward(grids):
+    """gsr_bilagrid_tv_forward -> the total variation, a 0-dim tensor."""
+    N, L, Gy, Gx = _bilagrid_dims(grids)
+    out = torch.empty(1, dtype=torch.float32, device=grids.device)
+    ws = _bilagrid_tv_workspace(grids.device)
+    with torch.cuda.device(grids.device):
+        _check(load().gsr_bilagrid_tv_forward(C.c_int32(N), C.c_int32(L), C.c_int32(Gy), C.c_int32(Gx), _ptr(grids), _ptr(ws), _ptr(out),
+                                              _stream(grids.device)), "gsr_bilagrid_tv_forward")
+    return out.reshape(())
+
+
+def bilagrid_tv_backward(grids, grad_out):
+    """gsr_bilagrid_tv_backward: grad_out a one-element fp32 device tensor -> grad_grids."""
+    N, L, Gy, Gx = _bilagrid_dims(grids)
+    dgrids = torch.empty_like(grids)
+    with torch.cuda.device(grids.device):
+        _check(load().gsr_bilagrid_tv_backward(C.c_int32(N), C.c_int32(L), C.c_int32(Gy), C.c_int32(Gx), _ptr(grids), _ptr(grad_out), _ptr(dgrids),
+                                               _stream(grids.device)), "gsr_bilagrid_tv_backward")
+    return dgrids

@@ -373,7 +373,8 @@ class ShardedRenderer:
     gaussian_renderer.render, reference gaussian_renderer/__init__.py:18-100)."""
 
     def __init__(self, dist, world: int, rank: int, backend=None, group=None, row_weights=None,
-                 backward_mode: str = "allreduce_screen", balance_every: int = 0, async_gather: bool = True):
+                 backward_mode: str = "allreduce_screen", balance_every: int = 0, async_gather: bool = True,
+                 bilateral_grid: bool = False):
         """row_weights: fixed per-tile-row weights for the slab boundaries (None = equal rows).  balance_every = k > 0:
         SURVEY 7 "slab load balance" — every k-th frame the ranks' measured per-tile-row work (instances binned) rides
         on the all-gather and the next frames' slabs are cut at equal cumulative work.  async_gather=False: the slabs'
@@ -381,6 +382,9 @@ class ShardedRenderer:
         between — the asynchronous form has only ever run at world size 1 on real RCCL (no multi-GPU lease so far): the switch
         lets a 2-GPU run A/B the two (tests/test_gpu_sharded.py::test_two_rank_rccl_equals_single_render does)."""
         assert backward_mode in ("allreduce_screen", "reduce_scatter")
+        if bilateral_grid:
+            raise ValueError("bilateral_grid is not supported by ShardedRenderer: the slice reads whole images and sums the grid's gradient "
+                             "over all of an image's pixels, a rank holds a slab of rows (train unsharded, or turn it off)")
         self.balance_every, self._frames, self._pending = int(balance_every), 0, None
         self.comm = _Comm(dist, world, rank, group, async_gather=async_gather)
         self.backend = NativeBackend() if backend is None else backend

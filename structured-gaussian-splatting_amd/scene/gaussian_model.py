@@ -75,6 +75,10 @@ class OptimizationDefaults:
     mcmc_min_opacity: float = 0.005           # at or below it a Gaussian is dead: relocated onto a live one
     mcmc_opacity_reg: float = 0.01            # lambda of mean(opacity)
     mcmc_scale_reg: float = 0.01              # lambda of mean(scale)
+    bilateral_grid: bool = False              # a bilateral grid per training image between render() and the loss (train_loop.train)
+    bilateral_grid_shape: tuple = (16, 16, 8)     # (grid_x, grid_y, luma levels)
+    bilateral_grid_lr: float = 2e-3           # the grids' Adam; warmed up over 1000 iterations, decayed to 1 % (bilagrid.bilateral_grid_lr)
+    bilateral_grid_tv: float = 10.0           # weight of the grids' total variation in the loss
 
 
 def expon_lr(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1_000_000):

@@ -1,20 +1,34 @@
 """The reference's training iteration (train.py:63-146) around the drop-in rasterizer, for synthetic scenes:
 LR schedule, SH-degree ramp, render -> L1/D-SSIM -> backward, densification bookkeeping, densify/prune,
 opacity reset, Adam step.  SURVEY 8f row f1.  opt.densify_strategy = "mcmc" replaces the densification part:
-regulariser gradients before the step; relocation and growth after it, inside the refinement window; position noise every iteration."""
+regulariser gradients before the step; relocation and growth after it, inside the refinement window; position noise every iteration.
+opt.bilateral_grid puts the per-image bilateral grid between render() and the loss; off, the loop is as before."""
 import random
 
 import torch
 
-from fused_adam import SparseFusedAdam
+from fused_adam import FusedAdam, SparseFusedAdam
 from gaussian_renderer import render
 from loss_utils import training_loss
 
 
 def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_iter=1, scene_extent=5.0,
-          white_background=False, on_iteration=None):
-    """cameras / targets: lists of equal length (Camera-like objects and [3,H,W] ground-truth images)."""
+          white_background=False, on_iteration=None, bilagrid=None):
+    """cameras / targets: lists of equal length (Camera-like objects and [3,H,W] ground-truth images).
+    opt.bilateral_grid: every camera owns a bilateral grid (`bilagrid`, or a new BilateralGrid of opt.bilateral_grid_shape on the
+    model's device, kept as gaussians.bilagrid); the rendered image goes through its grid before the loss, the grids' total variation
+    joins the loss with weight opt.bilateral_grid_tv, and the grids step with an Adam of their own.  render() and evaluation are
+    untouched: correcting test views is the caller's business."""
     stack = []
+    use_bilagrid = bool(getattr(opt, "bilateral_grid", False))
+    if use_bilagrid:
+        from diff_gaussian_rasterization.bilagrid import BilateralGrid, bilateral_grid_lr, total_variation_loss
+        if bilagrid is None:
+            bilagrid = BilateralGrid(len(cameras), *opt.bilateral_grid_shape).to(gaussians.get_xyz.device)
+        if bilagrid.grids.shape[0] != len(cameras):
+            raise ValueError(f"train: {bilagrid.grids.shape[0]} bilateral grids for {len(cameras)} cameras")
+        gaussians.bilagrid = bilagrid
+        bilagrid_optimizer = FusedAdam([bilagrid.grids], lr=opt.bilateral_grid_lr, eps=1e-15, native=bilagrid.grids.is_cuda)
     mcmc = getattr(opt, "densify_strategy", "default") == "mcmc"
     for it in range(first_iter, iterations + 1):
         xyz_lr = gaussians.update_learning_rate(it)
@@ -28,7 +42,11 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
             pipe.absgrad = it < opt.densify_until_iter
         pkg = render(cameras[idx], gaussians, pipe, bg)
         image, vsp, vis, radii = pkg["render"], pkg["viewspace_points"], pkg["visibility_filter"], pkg["radii"]
+        if use_bilagrid:
+            image = bilagrid(image, idx)
         loss = training_loss(image, targets[idx], opt.lambda_dssim)
+        if use_bilagrid:
+            loss = loss + opt.bilateral_grid_tv * total_variation_loss(bilagrid.grids)
         loss.backward()
         with torch.no_grad():
             if mcmc:
@@ -46,6 +64,10 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
                 else:
                     gaussians.optimizer.step()
                 gaussians.optimizer.zero_grad(set_to_none=True)
+                if use_bilagrid:
+                    bilagrid_optimizer.param_groups[0]["lr"] = bilateral_grid_lr(opt.bilateral_grid_lr, it - 1, iterations)
+                    bilagrid_optimizer.step()
+                    bilagrid_optimizer.zero_grad(set_to_none=True)
                 if mcmc and opt.densify_from_iter < it < opt.densify_until_iter and it % opt.densification_interval == 0:
                     gaussians.mcmc_relocate(opt.mcmc_min_opacity)
                     gaussians.mcmc_grow(opt.mcmc_cap_max, opt.mcmc_min_opacity)
