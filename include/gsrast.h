@@ -591,6 +591,34 @@ int gsr_bilagrid_tv_forward(int32_t N, int32_t L, int32_t Gy, int32_t Gx, const 
 int gsr_bilagrid_tv_backward(int32_t N, int32_t L, int32_t Gy, int32_t Gx, const float *grids, const float *grad_out,
                              float *grad_grids, void *stream);
 
+/* ---- Vector quantisation (csrc/gsr_vq.hip): Lloyd's two steps for a table x [P, D] against a codebook
+ * [K, D], all contiguous fp32 device arrays.  What scene/compression.py clusters the higher-order SH rows with.
+ *
+ * gsr_vq_assign: idx[p] (int32) = the code nearest to x_p in squared Euclidean distance, ties to the LOWEST index, and dist2[p]
+ * (fp32) that distance.  Per (point, code) the kernel evaluates  score = |c|^2 - 2 x.c  as one fmaf of the dot product and the
+ * code's norm, takes the minimum, and returns  dist2 = max(0, |x|^2 + score).  The dot product is a k-ascending binary32 fmaf chain
+ * from 0 (v_mfma_f32_32x32x2_f32), each norm the same chain of the row with itself, so with
+ *   B(p) = (D + 4) 2^-24 (|x_p| + max_k |c_k|)^2
+ * the chosen code is within 2 B(p) of the true minimum distance and dist2[p] within B(p) of the true distance to the chosen code
+ * (DESIGN.md section 18 derives the count); a point that equals a code bit for bit gets dist2 == 0.  Distances lose digits when the
+ * cloud sits far from the origin (B grows with the norms): centre the table first, as diff_gaussian_rasterization.vq.kmeans does.
+ * The P x K distances are never written.  Two launches (the codes' norms into the workspace, the fused product + argmin).  x and
+ * codebook are only read.  P == 0 returns GSR_OK with nothing launched.
+ *
+ * gsr_vq_update: new_codebook[k] = the mean of the rows x_p with idx[p] == k, counts[k] (int32) their number; a code without a
+ * member keeps codebook[k] bit for bit; an idx[p] outside [0, K) is no one's member.  The rows of a code are added one by one in
+ * ascending p (the library's stable radix sort of (idx, p) puts them in one run) and divided by the count: no floating-point
+ * atomics, the same inputs give the same bits.  new_codebook may be codebook itself.
+ *
+ * `workspace`: gsr_vq_workspace_size(P, K, D) bytes, 16-byte aligned, scratch (one size serves both calls; nothing is kept between
+ * calls).  1 <= D <= 128, 1 <= K <= 2^30, 0 <= P <= 2^30: anything else is refused with the argument's name in gsr_last_error(),
+ * before anything touches the device.  Non-finite inputs are the caller's business. */
+int gsr_vq_workspace_size(int64_t P, int32_t K, int32_t D, size_t *bytes);
+int gsr_vq_assign(int64_t P, int32_t K, int32_t D, const float *x, const float *codebook, int32_t *idx, float *dist2,
+                  void *workspace, size_t workspace_bytes, void *stream);
+int gsr_vq_update(int64_t P, int32_t K, int32_t D, const float *x, const int32_t *idx, const float *codebook,
+                  float *new_codebook, int32_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- the densification bookkeeping of one training iteration (train.py:127-130,
  * scene/gaussian_model.py:415-417) in one pass without a host synchronisation: for every Gaussian with
  * radii[i] > 0:  max_radii2D[i] = max(max_radii2D[i], radii[i]);  xyz_gradient_accum[i] += |viewspace_grad[i, :2]|;

@@ -124,7 +124,8 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_workspace_sizes", "gsr_binning_
            "gsr_opacity_compensation_forward", "gsr_opacity_compensation_backward",
            "gsr_decoder_workspace_size", "gsr_decoder_forward", "gsr_decoder_backward",
            "gsr_mcmc_relocation_workspace_size", "gsr_mcmc_relocation", "gsr_mcmc_relocate_rows", "gsr_mcmc_inject_noise", "gsr_mcmc_reg_grads",
-           "gsr_bilagrid_workspace_size", "gsr_bilagrid_forward", "gsr_bilagrid_backward", "gsr_bilagrid_tv_forward", "gsr_bilagrid_tv_backward")
+           "gsr_bilagrid_workspace_size", "gsr_bilagrid_forward", "gsr_bilagrid_backward", "gsr_bilagrid_tv_forward", "gsr_bilagrid_tv_backward",
+           "gsr_vq_workspace_size", "gsr_vq_assign", "gsr_vq_update")
 
 _lib = None
 
@@ -844,3 +845,40 @@ def bilagrid_tv_backward(grids, grad_out):
         _check(load().gsr_bilagrid_tv_backward(C.c_int32(N), C.c_int32(L), C.c_int32(Gy), C.c_int32(Gx), _ptr(grids), _ptr(grad_out), _ptr(dgrids),
                                                _stream(grids.device)), "gsr_bilagrid_tv_backward")
     return dgrids
+
+
+def vq_workspace_size(P: int, K: int, D: int) -> int:
+    """gsr_vq_workspace_size: bytes of scratch gsr_vq_assign and gsr_vq_update need (one size serves both)."""
+    b = C.c_size_t(0)
+    _check(load().gsr_vq_workspace_size(C.c_int64(int(P)), C.c_int32(int(K)), C.c_int32(int(D)), C.byref(b)), "gsr_vq_workspace_size")
+    return b.value
+
+
+def vq_assign(x, codebook):
+    """gsr_vq_assign: x [P,D], codebook [K,D], contiguous fp32 on one device -> (idx int32 [P], dist2 fp32 [P])."""
+    P, D = int(x.shape[0]), int(x.shape[1])
+    K = int(codebook.shape[0])
+    nbytes = vq_workspace_size(P, K, D)
+    idx = torch.empty(P, dtype=torch.int32, device=x.device)
+    dist2 = torch.empty(P, dtype=torch.float32, device=x.device)
+    if P == 0:
+        return idx, dist2
+    with torch.cuda.device(x.device):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        _check(load().gsr_vq_assign(C.c_int64(P), C.c_int32(K), C.c_int32(D), _ptr(x), _ptr(codebook), _ptr(idx), _ptr(dist2), _ptr(ws),
+                                    C.c_size_t(nbytes), _stream(x.device)), "gsr_vq_assign")
+    return idx, dist2
+
+
+def vq_update(x, idx, codebook):
+    """gsr_vq_update: x [P,D] fp32, idx [P] int32, codebook [K,D] fp32, contiguous on one device -> (new_codebook [K,D], counts int32 [K])."""
+    P, D = int(x.shape[0]), int(x.shape[1])
+    K = int(codebook.shape[0])
+    nbytes = vq_workspace_size(P, K, D)
+    out = torch.empty_like(codebook)
+    counts = torch.empty(K, dtype=torch.int32, device=codebook.device)
+    with torch.cuda.device(codebook.device):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=codebook.device)
+        _check(load().gsr_vq_update(C.c_int64(P), C.c_int32(K), C.c_int32(D), _ptr(x), _ptr(idx), _ptr(codebook), _ptr(out), _ptr(counts),
+                                    _ptr(ws), C.c_size_t(nbytes), _stream(codebook.device)), "gsr_vq_update")
+    return out, counts

@@ -506,3 +506,16 @@ class GaussianModel:
         self._adopt(dict(xyz=t(d["xyz"]), f_dc=t(d["f_dc"]), f_rest=t(d["f_rest"]), opacity=t(d["opacity"]),
                          scaling=t(d["scaling"]), rotation=t(d["rotation"])))
         self.active_sh_degree = self.max_sh_degree
+
+    def save_compressed(self, path, **kw):
+        """The vector-quantised checkpoint (scene/compression.py; kw: sh_clusters, iters, generator)."""
+        from . import compression
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        compression.save_compressed(path, compression.compress(self, **kw))
+
+    def load_compressed(self, path, device="cuda"):
+        from . import compression
+        d = compression.load_compressed(path)
+        assert int(d["sh_degree"]) == self.max_sh_degree, "the checkpoint's SH degree does not match the model"
+        self._adopt({k: v.to(device) for k, v in compression.decompress(d).items()})
+        self.active_sh_degree = self.max_sh_degree
