@@ -379,7 +379,8 @@ int gsr_dist2_workspace_size(int32_t P, size_t *bytes);
 int gsr_dist2_knn3(int32_t P, const float *xyz, float *mean_dist2, void *workspace, void *stream);
 
 /* ---- one torch.optim.Adam step (no weight decay / amsgrad; the reference uses eps = 1e-15,
- * scene/gaussian_model.py:173) over n contiguous fp32 elements in a single pass.  step = 1 for the first update. */
+ * scene/gaussian_model.py:173) over n contiguous fp32 elements in a single pass.  step = 1 for the first update.
+ * This call and gsr_adam_step_split are gsr_adam_step_multi with one tensor (row_len = 0; row_len and split): same kernel, same bits. */
 int gsr_adam_step(int64_t n, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, float lr, float beta1,
                   float beta2, float eps, int64_t step, void *stream);
 /* The same step over `rows` rows of `row_len` >= 4 contiguous elements whose first `split` elements use

@@ -974,6 +974,29 @@ GSR_HD void mcmc_reg_one(float logit, const float log_scale[3], float k_o, float
     for (int k = 0; k < 3; ++k) d_scaling[k] = mcmc_reg_scale_one(log_scale[k], k_s);
 }
 
+// ---- the Adam update of one element (torch.optim.Adam without weight decay or amsgrad), the one statement of the rule:
+// every path of the dense and the sparse step (gsr_optim.hip: float4 bodies and trailing elements) calls it.
+//   m' = m + (g - m)(1 - b1);  v' = b2 v + (1 - b2) g^2;  p' = p - step (m' / (sqrt(v') inv_bc2_sqrt + eps))
+// with step = lr / (1 - b1^t) and inv_bc2_sqrt = 1 / sqrt(1 - b2^t) from the host.  Every multiply-add is an explicit fmaf, so no
+// contraction is left to a compiler and the bits are the same under any -ffp-contract and on the host.  v' rounds v b2 and fuses the
+// other product; m' and p' have one product each.
+struct AdamConsts { float one_minus_b1, b2, one_minus_b2, eps; };
+
+GSR_HD void adam_update(float &p, float &m, float &v, float g, float step, float inv_bc2_sqrt, const AdamConsts &c)
+{
+    m = fmaf(g - m, c.one_minus_b1, m);
+    v = fmaf(c.one_minus_b2 * g, g, v * c.b2);
+    p = fmaf(-step, m / fmaf(sqrtf(v), inv_bc2_sqrt, c.eps), p);
+}
+
+// The step size of column c of a row of w floats whose first `split` step with `head` and the others with `tail`.  c may lie in a
+// following row: in the next one at most if `wide` (the four columns under a float4 when w >= 3), in any otherwise.
+GSR_HD float adam_step_size(uint32_t c, uint32_t w, uint32_t split, float head, float tail, bool wide)
+{
+    c = wide ? (c >= w ? c - w : c) : c % w;
+    return c < split ? head : tail;
+}
+
 // ---- A.1 alone (markVisible).
 GSR_HD bool in_frustum(const float p[3], const float *V)
 {

@@ -546,14 +546,19 @@ class AdamTensor(C.Structure):
 ADAM_MAX_TENSORS = 8
 
 
-def adam_step_multi(items, beta1, beta2, eps):
-    """items: up to ADAM_MAX_TENSORS tuples (param, grad, exp_avg, exp_avg_sq, lr, lr_tail, step, row_len, split) — the whole
-    optimizer step in one launch (row_len = 0: one learning rate for the tensor)."""
+def _adam_tensors(items):
+    """The C ABI's gsr_adam_tensor array of up to ADAM_MAX_TENSORS tuples (param, grad, exp_avg, exp_avg_sq, lr, lr_tail, step, row_len,
+    split); row_len = 0: one learning rate for the tensor."""
     arr = (AdamTensor * len(items))()
     for a, (p, g, m, v, lr, lr_tail, step, row_len, split) in zip(arr, items):
         a.param, a.grad, a.exp_avg, a.exp_avg_sq, a.n = _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel()
         a.lr, a.lr_tail, a.step, a.row_len, a.split = float(lr), float(lr_tail), int(step), int(row_len), int(split)
-    _check(load().gsr_adam_step_multi(C.c_int32(len(items)), arr, C.c_float(beta1), C.c_float(beta2), C.c_float(eps),
+    return C.c_int32(len(items)), arr
+
+
+def adam_step_multi(items, beta1, beta2, eps):
+    """The whole optimizer step in one launch; items: see _adam_tensors."""
+    _check(load().gsr_adam_step_multi(*_adam_tensors(items), C.c_float(beta1), C.c_float(beta2), C.c_float(eps),
                                       _stream(items[0][0].device)), "gsr_adam_step_multi")
 
 
@@ -568,11 +573,7 @@ def adam_step_sparse_multi(items, visible, beta1, beta2, eps):
     if visible.device != items[0][0].device:
         raise ValueError(f"adam_step_sparse_multi: visible is on {visible.device}, the tensors on {items[0][0].device}")
     visible = visible.contiguous()
-    arr = (AdamTensor * len(items))()
-    for a, (p, g, m, v, lr, lr_tail, step, row_len, split) in zip(arr, items):
-        a.param, a.grad, a.exp_avg, a.exp_avg_sq, a.n = _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel()
-        a.lr, a.lr_tail, a.step, a.row_len, a.split = float(lr), float(lr_tail), int(step), int(row_len), int(split)
-    _check(load().gsr_adam_step_sparse_multi(C.c_int32(len(items)), arr, C.c_int64(visible.shape[0]), _ptr(visible),
+    _check(load().gsr_adam_step_sparse_multi(*_adam_tensors(items), C.c_int64(visible.shape[0]), _ptr(visible),
                                              C.c_int32(visible.element_size()), C.c_float(beta1), C.c_float(beta2), C.c_float(eps),
                                              _stream(items[0][0].device)), "gsr_adam_step_sparse_multi")
 

@@ -18,6 +18,8 @@ import torch
 
 
 class FusedAdam(torch.optim.Optimizer):
+    bias_correction = True      # SparseFusedAdam can switch it off
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, native=True):
         self.native = native
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
@@ -42,10 +44,23 @@ class FusedAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
+        return self._step(closure, None)
+
+    def _step(self, closure, visibility):
+        """The step of both classes.  visibility None: every element steps (adam_step_multi); a [P] mask: SparseFusedAdam's step over
+        the rows it marks (adam_step_sparse_multi), every parameter being [P, ...]."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        who = "FusedAdam" if visibility is None else "SparseFusedAdam"
+        rows = None
+        if visibility is not None:
+            if visibility.dim() != 1 or visibility.dtype not in (torch.bool, torch.uint8, torch.int32):
+                raise TypeError(f"SparseFusedAdam: visibility must be a [P] bool, uint8 or int32 tensor, got {visibility.dtype} "
+                                f"{tuple(visibility.shape)}")
+            rows = visibility.shape[0]
+        seen = None         # the visible rows' indices, for the torch arithmetic of host tensors
         batch = []          # native tensors of this step: ONE launch for all of them (groups that share betas and eps: the reference's do)
         for group in self.param_groups:
             b1, b2 = group["betas"]
@@ -54,6 +69,9 @@ class FusedAdam(torch.optim.Optimizer):
             for p in group["params"]:
                 if p.grad is None:
                     continue
+                if rows is not None and (p.dim() == 0 or p.shape[0] != rows):
+                    raise ValueError(f"SparseFusedAdam: group {group.get('name')!r} holds a parameter of shape {tuple(p.shape)}, "
+                                     f"the visibility mask has {rows} rows")
                 st = self.state[p]
                 if len(st) == 0:
                     st["step"] = torch.tensor(0.0)
@@ -64,27 +82,48 @@ class FusedAdam(torch.optim.Optimizer):
                 lr = float(group["lr"])
                 if not (self.native and p.is_cuda):
                     if self.native:
-                        raise RuntimeError("FusedAdam(native=True) (MI355X build) needs parameters on a HIP device")
-                    bc1 = 1 - b1 ** step
-                    self._torch_step(p, p.grad, st, (lr / bc1, None if lr_tail is None else lr_tail / bc1), b1, b2, group["eps"], step,
-                                     head_cols)
+                        raise RuntimeError(f"{who}(native=True) (MI355X build) needs parameters on a HIP device")
+                    bc1 = 1 - b1 ** step if self.bias_correction else 1.0
+                    args = ((lr / bc1, None if lr_tail is None else lr_tail / bc1), b1, b2, group["eps"],
+                            step if self.bias_correction else math.inf, head_cols)
+                    if visibility is None:
+                        self._torch_step(p, p.grad, st, *args)
+                        continue
+                    if seen is None:
+                        seen = (visibility > 0 if visibility.dtype == torch.int32 else visibility != 0).nonzero().squeeze(1)
+                    if seen.numel() == 0:
+                        continue
+                    # the same arithmetic on copies of the visible rows, written back to them
+                    pr = p[seen]
+                    rst = {"exp_avg": st["exp_avg"][seen], "exp_avg_sq": st["exp_avg_sq"][seen]}
+                    self._torch_step(pr, p.grad[seen], rst, *args)
+                    p.index_copy_(0, seen, pr)
+                    st["exp_avg"].index_copy_(0, seen, rst["exp_avg"])
+                    st["exp_avg_sq"].index_copy_(0, seen, rst["exp_avg_sq"])
                     continue
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                 if head_cols is None or p.shape[1] <= head_cols:
                     item = (p, g, st["exp_avg"], st["exp_avg_sq"], lr, lr, step, 0, 0)
                 else:
-                    per_col = p.numel() // max(p.shape[0] * p.shape[1], 1)
-                    item = (p, g, st["exp_avg"], st["exp_avg_sq"], lr, lr_tail, step, p.numel() // max(p.shape[0], 1), head_cols * per_col)
+                    width = p.numel() // max(p.shape[0], 1)
+                    item = (p, g, st["exp_avg"], st["exp_avg_sq"], lr, lr_tail, step, width, head_cols * (width // p.shape[1]))
                 batch.append(((b1, b2, group["eps"], p.device), item))
         if batch:
             from diff_gaussian_rasterization import _native as N
+            if not self.bias_correction:
+                batch = [(k, it[:6] + (N.ADAM_STEP_UNCORRECTED,) + it[7:]) for k, it in batch]
             while batch:
                 key = batch[0][0]
                 now = [it for k, it in batch if k == key][:N.ADAM_MAX_TENSORS]
                 taken = {id(it[0]) for it in now}
                 batch = [(k, it) for k, it in batch if id(it[0]) not in taken]
+                if rows == 0:
+                    continue
                 with torch.cuda.device(key[3]):
-                    N.adam_step_multi(now, key[0], key[1], key[2])
+                    if visibility is None:
+                        N.adam_step_multi(now, *key[:3])
+                    else:
+                        N.adam_step_sparse_multi(now, visibility, *key[:3])
                 for it in now:
                     torch.autograd.graph.increment_version(it[0])    # the kernel wrote through the raw pointer: tell autograd (and
                                                                      # the model's activation cache, which keys on versions)
@@ -94,7 +133,7 @@ class FusedAdam(torch.optim.Optimizer):
 class SparseFusedAdam(FusedAdam):
     """FusedAdam that steps only the rows a frame saw (upstream 3DGS's optimizer_type = "sparse_adam"): step(visibility) takes a
     [P] mask — bool or uint8 (non-zero = visible) or int32 (> 0 = visible: the rasterizer's `radii` as they are) — and updates,
-    in ONE launch (csrc/gsr_sparse_adam.hip), the visible rows of every parameter [P, ...] that has a gradient.  A hidden row keeps
+    in ONE launch (k_adam_sparse_multi of csrc/gsr_optim.hip), the visible rows of every parameter [P, ...] that has a gradient.  A hidden row keeps
     its parameter and both moments bit for bit and its gradient is not read.
 
     state[p]["step"] counts every call in which the tensor had a gradient, whatever the mask showed, and enters the bias corrections
@@ -112,71 +151,4 @@ class SparseFusedAdam(FusedAdam):
                 raise ValueError("SparseFusedAdam(bias_correction=False).step() needs a visibility mask: the dense step is "
                                  "FusedAdam's, which corrects the bias")
             return super().step(closure)
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        if visibility.dim() != 1 or visibility.dtype not in (torch.bool, torch.uint8, torch.int32):
-            raise TypeError(f"SparseFusedAdam: visibility must be a [P] bool, uint8 or int32 tensor, got {visibility.dtype} "
-                            f"{tuple(visibility.shape)}")
-        rows = visibility.shape[0]
-        seen = None                  # the visible rows' indices, for the torch arithmetic of host tensors
-        batch = []
-        for group in self.param_groups:
-            b1, b2 = group["betas"]
-            head_cols = group.get("head_cols") if group.get("tail") else None
-            lr_tail = self._tail_lr(group) if head_cols is not None else None
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if p.dim() == 0 or p.shape[0] != rows:
-                    raise ValueError(f"SparseFusedAdam: group {group.get('name')!r} holds a parameter of shape {tuple(p.shape)}, "
-                                     f"the visibility mask has {rows} rows")
-                st = self.state[p]
-                if len(st) == 0:
-                    st["step"] = torch.tensor(0.0)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["step"] += 1
-                step = int(st["step"])
-                lr = float(group["lr"])
-                if not (self.native and p.is_cuda):
-                    if self.native:
-                        raise RuntimeError("SparseFusedAdam(native=True) (MI355X build) needs parameters on a HIP device")
-                    if seen is None:
-                        seen = (visibility > 0 if visibility.dtype == torch.int32 else visibility != 0).nonzero().squeeze(1)
-                    if seen.numel() == 0:
-                        continue
-                    # FusedAdam's torch arithmetic on copies of the visible rows, written back to them
-                    bc1 = 1 - b1 ** step if self.bias_correction else 1.0
-                    pr = p[seen]
-                    rst = {"exp_avg": st["exp_avg"][seen], "exp_avg_sq": st["exp_avg_sq"][seen]}
-                    self._torch_step(pr, p.grad[seen], rst, (lr / bc1, None if lr_tail is None else lr_tail / bc1), b1, b2, group["eps"],
-                                     step if self.bias_correction else math.inf, head_cols)
-                    p.index_copy_(0, seen, pr)
-                    st["exp_avg"].index_copy_(0, seen, rst["exp_avg"])
-                    st["exp_avg_sq"].index_copy_(0, seen, rst["exp_avg_sq"])
-                    continue
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                width = p.numel() // max(rows, 1)
-                if head_cols is None or p.shape[1] <= head_cols:
-                    item = (p, g, st["exp_avg"], st["exp_avg_sq"], lr, lr, step, 0, 0)
-                else:
-                    item = (p, g, st["exp_avg"], st["exp_avg_sq"], lr, lr_tail, step, width, head_cols * (width // p.shape[1]))
-                batch.append(((b1, b2, group["eps"], p.device), item))
-        if batch:
-            from diff_gaussian_rasterization import _native as N
-            if not self.bias_correction:
-                batch = [(k, it[:6] + (N.ADAM_STEP_UNCORRECTED,) + it[7:]) for k, it in batch]
-            while batch:
-                key = batch[0][0]
-                now = [it for k, it in batch if k == key][:N.ADAM_MAX_TENSORS]
-                taken = {id(it[0]) for it in now}
-                batch = [(k, it) for k, it in batch if id(it[0]) not in taken]
-                if rows == 0:
-                    continue
-                with torch.cuda.device(key[3]):
-                    N.adam_step_sparse_multi(now, visibility, key[0], key[1], key[2])
-                for it in now:
-                    torch.autograd.graph.increment_version(it[0])    # as FusedAdam.step: the kernel wrote through the raw pointer
-        return loss
+        return self._step(closure, visibility)

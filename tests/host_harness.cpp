@@ -115,6 +115,19 @@ extern "C" void hh_activate_raw(int n, const float *log_scales, const float *raw
     }
 }
 
+// f1: one Adam step over n elements by the kernels' own rule (gsr_math.h adam_update, adam_step_size), with the scalars the host side
+// of gsr_adam_step_multi derives (tests/training_ref.py adam_scalars).  row_len = 0: one step size, else columns below `split` take
+// step_head and the others step_tail.
+extern "C" void hh_adam_step(int64_t n, float *p, const float *g, float *m, float *v, float one_minus_b1, float b2, float one_minus_b2,
+                             float eps, float step_head, float step_tail, float inv_bc2_sqrt, int32_t row_len, int32_t split)
+{
+    const AdamConsts c = {one_minus_b1, b2, one_minus_b2, eps};
+    for (int64_t i = 0; i < n; ++i) {
+        const float st = row_len ? adam_step_size((uint32_t)(i % row_len), (uint32_t)row_len, (uint32_t)split, step_head, step_tail, true) : step_head;
+        adam_update(p[i], m[i], v[i], g[i], st, inv_bc2_sqrt, c);
+    }
+}
+
 // ---- exact host reference of the progressive binning (tests/binning_ref.py).  Input: the device's own records, depth order and
 // chunk plan.  For every chunk c and tile t: the Gaussians of chunk c whose rectangle holds t (inside the slab) and which
 // tile_may_contribute accepts, in (binary32 depth key, index) order, each with the quadrant mask of the chunk's path (quadrant_mask_q

@@ -1,4 +1,4 @@
-"""csrc/gsr_sparse_adam.hip on the GPU, held BITWISE to the dense kernel (k_adam_multi of csrc/gsr_optim.hip): a visible row of a
+"""k_adam_sparse_multi on the GPU, held BITWISE to the dense kernel (k_adam_multi; both in csrc/gsr_optim.hip): a visible row of a
 sparse step is the dense step's row, a hidden row is what it was.  Shapes: the model's five tensors [P,3] [P,M,3] [P,1] [P,3]
 [P,4] in one launch, the SH table with its two learning rates (head_cols = 1, tail) for M in {1, 4, 9, 16}, i.e. every width the
 kernel specialises (1, 3, 4, 12, 27, 48); P in {1, 3, 257, 1366, 4099}: P = 1366 makes a width-3 tensor of 4098 floats = one full

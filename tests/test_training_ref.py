@@ -158,6 +158,32 @@ def test_correct_float32_adam_stays_inside_the_ceilings():
         print(f"{impl}: worst ratios m' {t['adam_m']:.2f} u S_m, v' {t['adam_v']:.2f} u S_v, p' beyond u |p'|: {t['adam_p']:.2f} u U")
 
 
+def test_the_kernels_own_adam_rule_stays_inside_the_asserted_bounds(tmp_path):
+    """csrc/gsr_math.h adam_update and adam_step_size, the functions every path of k_adam_multi and k_adam_sparse_multi calls, compiled for
+    the host without contraction (tests/host_harness.cpp hh_adam_step): every multiply-add of the rule is an explicit fmaf, so this is the
+    arithmetic of the device, held to the bounds the GPU tests assert (R.K, not the looser R.CEIL) on their inputs."""
+    import binning_ref
+    hh = binning_ref.build_harness(str(tmp_path))
+    ptr, f = (lambda t: C.c_void_p(t.data_ptr())), C.c_float
+    top = dict.fromkeys(("adam_m", "adam_v", "adam_p"), 0.0)
+    for n, row_len, split, step, lr, lr_tail, seed in R.adam_cases() + R.ADAM_EIGHT:
+        p, g, m, v = R.adam_state(n, seed)
+        s = R.adam_scalars(lr, lr_tail, step, B1, B2, EPS)
+        out = [t.clone() for t in (p, m, v)]
+        hh.hh_adam_step(C.c_int64(n), ptr(out[0]), ptr(g), ptr(out[1]), ptr(out[2]), f(s.omb1), f(s.b2), f(s.omb2), f(s.eps), f(s.head), f(s.tail),
+                        f(s.inv), C.c_int32(row_len), C.c_int32(split))
+        if n == 0:
+            continue
+        ref, scl = R.adam_step64(p, g, m, v, lr, lr_tail, step, row_len, split, B1, B2, EPS)
+        assert all(bool(torch.isfinite(t).all()) for t in out), (n, row_len, split, step)
+        for k, r in _adam_ratios(out, ref, scl).items():
+            assert r <= R.K[k], (k, r, n, row_len, split, step)
+            top[k] = max(top[k], r)
+        for i in R.adam_planted(n):                                    # g = m = v = 0: p keeps its bits
+            assert R.bits_equal(out[0][i:i + 1], p[i:i + 1]), (n, i)
+    print(f"adam_update on the host: worst ratios m' {top['adam_m']:.3f} u S_m, v' {top['adam_v']:.3f} u S_v, p' beyond u |p'|: {top['adam_p']:.3f} u U")
+
+
 def _normalize_bwd32(q, g, mutate=None):
     """k_act_bwd's quaternion branch in float32 torch ops."""
     eps = torch.tensor(R.NORMALIZE_EPS, dtype=torch.float32)

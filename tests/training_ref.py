@@ -37,8 +37,12 @@ ADAM_SIZES = (1, 3, 4, 5, 4095, 4096, 4097, 4098, 8194)
 ADAM_ROW_LENS = (4, 5, 12, 27, 48)
 ADAM_STEPS = (1, 2, 7, 10 ** 6)
 ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-15
-ADAM_WRAP_PLAIN = 4096 * 256 * 4 + 1024 + 3                # k_adam<false>: just past the 4096-block grid, 3-float tail
-ADAM_WRAP_SPLIT = (155_401, 27)                            # k_adam<true>: 4 195 827 floats, 3-float tail
+ADAM_WRAP_PLAIN = 4096 * 256 * 4 + 1024 + 3                # gsr_adam_step: 1025 work items and a 3-float tail
+ADAM_WRAP_SPLIT = (155_401, 27)                            # gsr_adam_step_split: 4 195 827 floats, 3-float tail
+# (n, row_len, split, step, lr, lr_tail, seed) of one launch: eight tensors, one of them empty, each with its own step count and learning
+# rates; tail-only items in the middle of the item list
+ADAM_EIGHT = [(4098, 0, 0, 1, 0.01, 0.01, 1), (0, 0, 0, 2, 0.02, 0.02, 2), (1, 0, 0, 7, 0.03, 0.03, 3), (8194, 0, 0, 10 ** 6, 0.04, 0.04, 4),
+              (4095, 0, 0, 3, 0.05, 0.05, 5), (153 * 27, 27, 3, 5, 0.0025, 0.000125, 6), (821 * 5, 5, 4, 2, 0.06, 0.001, 7), (3, 0, 0, 1000, 0.07, 0.07, 8)]
 ACT_SIZES = (1, 2, 3, 6, 1000, 2_098_179)                  # the last: all three block ranges wrap, P % 4 = 3, 3P % 4 = 1
 DENSIFY_SIZES = (1, 255, 256, 257, 1000)
 
