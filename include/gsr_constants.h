@@ -21,6 +21,8 @@
 #define GSR_CONIC_BWD_EPS     1e-7    /* k = 1/(den^2 + 1e-7) (A.10)                   */
 #define GSR_SH_OFFSET         0.5     /* rgb = sh_eval + 0.5; gaussian_renderer/__init__.py:78 */
 #define GSR_AA_MIN_RATIO      0.000025 /* anti-aliasing: floor of det(cov2D) / det(cov2D + dilation); rho >= 0.005 */
+#define GSR_F3D_VARIANCE      0.2     /* 3D smoothing filter: filter = depth / focal * sqrt(0.2) (Mip-Splatting)        */
+#define GSR_F3D_MARGIN        0.15    /* 3D smoothing filter: a camera sees a centre within its image grown by 15 % a side */
 #define GSR_MCMC_MAX_RATIO    51      /* MCMC relocation: a source stands for at most this many Gaussians (3DGS-MCMC's N_max) */
 
 /* Real spherical-harmonics constants, utils/sh_utils.py:26-54 */

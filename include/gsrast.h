@@ -620,6 +620,40 @@ int gsr_vq_assign(int64_t P, int32_t K, int32_t D, const float *x, const float *
 int gsr_vq_update(int64_t P, int32_t K, int32_t D, const float *x, const int32_t *idx, const float *codebook,
                   float *new_codebook, int32_t *counts, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Mip-Splatting's 3D smoothing filter (the world-space half of its anti-aliasing; the 2D half is the opacity compensation
+ * above), additive: every call above keeps its meaning.  DESIGN.md section 19.
+ *
+ * gsr_filter3d_compute: `cameras` is a device table [C,16] of floats, 16-byte aligned: per camera the 12 entries of its row-vector
+ * view matrix V that the rule reads, coordinate by coordinate (V00 V10 V20 V30, V01 V11 V21 V31, V02 V12 V22 V32), then fx, fy, W,
+ * H (focal lengths and image size in pixels).  For Gaussian p with (x, y, z) = xyz_p V[:3,:3] + V[3,:3]:
+ *   valid(p,c) = z > GSR_NEAR_CUT  and  |x fx| <= (0.5 + GSR_F3D_MARGIN) W z  and  |y fy| <= (0.5 + GSR_F3D_MARGIN) H z
+ *   d_p = min over the valid cameras of z;  a Gaussian no camera saw takes the maximum d over the others
+ *   filter_out[p] = d_p sqrt(GSR_F3D_VARIANCE) / focal_max          (focal_max: the largest fx of the table, the caller's number)
+ * min and max are exact: the same inputs give the same bits, in any order of the cameras.  Two launches whatever C is.
+ * `workspace`: gsr_filter3d_workspace_size(P) bytes, 4-byte aligned, scratch.  any_seen (host pointer, may be NULL): when given, the
+ * call synchronises the stream and writes 1 if any Gaussian was seen by any camera, else 0 (every filter_out is then 0); NULL: no
+ * synchronisation.  xyz [P,3] and filter_out [P] need 4-byte alignment.
+ *
+ * gsr_filter3d_apply_forward, with f = filter[p], per axis s' = sqrt(s^2 + f^2) and o' = o sqrt(prod s^2 / prod s'^2):
+ *   raw == 0: opacities [P] and scales [P,3] are activated, so are the outputs;
+ *   raw != 0: logits and log-scales in, the logit of o' and log s' out (what the raw mode of gsr_gaussians takes).
+ * A row with f <= 0 passes through bit for bit.  gsr_filter3d_apply_backward recomputes from the same inputs; grad_opacities_out [P]
+ * and grad_scales_out [P,3] are the incoming gradients (NULL = zero), grad_opacities [P] and grad_scales [P,3] the results (NULL =
+ * not wanted, both NULL: nothing runs).  No gradient goes to the filter.  One launch each, no atomics: the same inputs give the same
+ * bits.  All pointers need 4-byte alignment.
+ *
+ * Refused with the argument's name in gsr_last_error(), before anything touches the device: P < 0 or P > 2^30, C <= 0, a focal_max
+ * that is not positive and finite, a required pointer that is NULL, a misaligned pointer, a workspace that is too small.  P == 0
+ * returns GSR_OK and reads nothing. */
+int gsr_filter3d_workspace_size(int64_t P, size_t *bytes);
+int gsr_filter3d_compute(int64_t P, int32_t C, const float *cameras, float focal_max, const float *xyz, float *filter_out,
+                         void *workspace, size_t workspace_bytes, int32_t *any_seen, void *stream);
+int gsr_filter3d_apply_forward(int64_t P, int32_t raw, const float *opacities, const float *scales, const float *filter,
+                               float *opacities_out, float *scales_out, void *stream);
+int gsr_filter3d_apply_backward(int64_t P, int32_t raw, const float *opacities, const float *scales, const float *filter,
+                                const float *grad_opacities_out, const float *grad_scales_out, float *grad_opacities,
+                                float *grad_scales, void *stream);
+
 /* ---- the densification bookkeeping of one training iteration (train.py:127-130,
  * scene/gaussian_model.py:415-417) in one pass without a host synchronisation: for every Gaussian with
  * radii[i] > 0:  max_radii2D[i] = max(max_radii2D[i], radii[i]);  xyz_gradient_accum[i] += |viewspace_grad[i, :2]|;

@@ -125,7 +125,8 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_workspace_sizes", "gsr_binning_
            "gsr_decoder_workspace_size", "gsr_decoder_forward", "gsr_decoder_backward",
            "gsr_mcmc_relocation_workspace_size", "gsr_mcmc_relocation", "gsr_mcmc_relocate_rows", "gsr_mcmc_inject_noise", "gsr_mcmc_reg_grads",
            "gsr_bilagrid_workspace_size", "gsr_bilagrid_forward", "gsr_bilagrid_backward", "gsr_bilagrid_tv_forward", "gsr_bilagrid_tv_backward",
-           "gsr_vq_workspace_size", "gsr_vq_assign", "gsr_vq_update")
+           "gsr_vq_workspace_size", "gsr_vq_assign", "gsr_vq_update",
+           "gsr_filter3d_workspace_size", "gsr_filter3d_compute", "gsr_filter3d_apply_forward", "gsr_filter3d_apply_backward")
 
 _lib = None
 
@@ -883,3 +884,44 @@ def vq_update(x, idx, codebook):
         _check(load().gsr_vq_update(C.c_int64(P), C.c_int32(K), C.c_int32(D), _ptr(x), _ptr(idx), _ptr(codebook), _ptr(out), _ptr(counts),
                                     _ptr(ws), C.c_size_t(nbytes), _stream(codebook.device)), "gsr_vq_update")
     return out, counts
+
+
+def filter3d_compute(xyz, cameras, focal_max: float):
+    """gsr_filter3d_compute: xyz [P,3] and the camera table [C,16] (contiguous fp32 on one device; the table's layout: include/gsrast.h)
+    -> (filter [P,1], any_seen).  The workspace is a torch allocation that lives for the call; reading any_seen is the call's one host
+    synchronisation."""
+    P, Cn = int(xyz.shape[0]), int(cameras.shape[0])
+    out = torch.empty(P, 1, dtype=torch.float32, device=xyz.device)
+    b = C.c_size_t(0)
+    _check(load().gsr_filter3d_workspace_size(C.c_int64(P), C.byref(b)), "gsr_filter3d_workspace_size")
+    seen = C.c_int32(0)
+    with torch.cuda.device(xyz.device):
+        ws = torch.empty(b.value, dtype=torch.uint8, device=xyz.device)
+        _check(load().gsr_filter3d_compute(C.c_int64(P), C.c_int32(Cn), _ptr(cameras), C.c_float(focal_max), _ptr(xyz), _ptr(out), _ptr(ws),
+                                           C.c_size_t(b.value), C.byref(seen), _stream(xyz.device)), "gsr_filter3d_compute")
+    return out, bool(seen.value)
+
+
+def filter3d_apply_forward(opacities, scales, filter_3D, raw: bool):
+    """gsr_filter3d_apply_forward: opacities [P] / [P,1], scales [P,3], filter_3D [P] / [P,1], contiguous fp32 on one device ->
+    (opacities', scales') shaped like the inputs."""
+    P = int(scales.shape[0])
+    o_out, s_out = torch.empty_like(opacities), torch.empty_like(scales)
+    with torch.cuda.device(scales.device):
+        _check(load().gsr_filter3d_apply_forward(C.c_int64(P), C.c_int32(int(bool(raw))), _ptr(opacities), _ptr(scales), _ptr(filter_3D),
+                                                 _ptr(o_out), _ptr(s_out), _stream(scales.device)), "gsr_filter3d_apply_forward")
+    return o_out, s_out
+
+
+def filter3d_apply_backward(opacities, scales, filter_3D, raw: bool, grad_opacities_out, grad_scales_out, want):
+    """gsr_filter3d_apply_backward.  The incoming gradients are contiguous or None (zero); want: two booleans for (opacities, scales).
+    Returns the two gradients, None where not wanted."""
+    P = int(scales.shape[0])
+    outs = [torch.empty_like(t) if w else None for t, w in zip((opacities, scales), want)]
+    if P == 0 or not any(want):
+        return tuple(outs)
+    with torch.cuda.device(scales.device):
+        _check(load().gsr_filter3d_apply_backward(C.c_int64(P), C.c_int32(int(bool(raw))), _ptr(opacities), _ptr(scales), _ptr(filter_3D),
+                                                  _ptr(grad_opacities_out), _ptr(grad_scales_out), _ptr(outs[0]), _ptr(outs[1]),
+                                                  _stream(scales.device)), "gsr_filter3d_apply_backward")
+    return tuple(outs)

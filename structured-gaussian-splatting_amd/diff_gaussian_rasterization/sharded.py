@@ -463,6 +463,9 @@ class ShardedRenderer:
         if getattr(pipe, "absgrad", False):
             raise ValueError("pipe.absgrad is not supported by ShardedRenderer: the abs blend backward runs on whole images only, a "
                              "slab's absolute sums would miss the other ranks' pixels (render unsharded, or turn it off)")
+        if getattr(pc, "filter_3D", None) is not None:
+            raise ValueError("a model with a 3D filter (filter_3D) is not supported by ShardedRenderer: it renders the unfiltered "
+                             "parameters (render unsharded, or save_ply(path, fuse_filter=True) and load the fused model)")
         xyz = pc.get_xyz
         screenspace_points = torch.zeros_like(xyz, requires_grad=True)     # a leaf keeps its .grad (gaussian_renderer.render)
         rs = GaussianRasterizationSettings(

@@ -13,6 +13,10 @@ one interleaved leaf `_features`: raw mode 2), the getters for any other store. 
 `pipe.antialiasing` (upstream's flag; absent or False: off) turns on the rasterizer's opacity compensation for the 0.3 px^2
 dilation (diff_gaussian_rasterization.antialias), on the fused path and the getter path alike.
 
+A model whose `filter_3D` is not None (scene.GaussianModel.compute_3D_filter, Mip-Splatting's 3D smoothing filter) is rendered with
+its filtered opacities and scales (diff_gaussian_rasterization.filter3d), on both paths; a filter whose row count is not the model's
+is a ValueError.
+
 `pipe.absgrad` (gsplat's flag; absent or False: off): after backward() the returned `viewspace_points` also carries `.absgrad`
 [P,3], the per-pixel absolute sums of the means2D gradient (diff_gaussian_rasterization, "absgrad"), on both paths; not together
 with depth_alpha=True (ValueError).
@@ -94,19 +98,32 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     fused = getattr(pipe, "fused_activations", None)
     if fused is None:            # not set: this package's own model renders from its raw leaves, any other store through its getters
         fused = packed
+    # the 3D smoothing filter (scene.GaussianModel.compute_3D_filter): a per-Gaussian op in front of the rasterizer, independent of
+    # the camera being rendered.  None: no launch, the frame is what it was.  A stale filter raises here (checked_filter_3D)
+    if hasattr(pc, "checked_filter_3D"):
+        filter_3D = pc.checked_filter_3D()
+    else:                        # another store with the attribute: the same rule
+        filter_3D = getattr(pc, "filter_3D", None)
+        if filter_3D is not None and filter_3D.shape[0] != xyz.shape[0]:
+            raise ValueError(f"filter_3D has {filter_3D.shape[0]} rows for {xyz.shape[0]} Gaussians: call compute_3D_filter(cameras)")
     if (fused and override_color is None and not pipe.compute_cov3D_python and not pipe.convert_SHs_python and not frozen
             and (packed or hasattr(pc, "_features_rest"))):
+        opacity, scaling = pc._opacity, pc._scaling
+        if filter_3D is not None:
+            from diff_gaussian_rasterization.filter3d import apply_filter_3d
+            opacity, scaling = apply_filter_3d(opacity, scaling, filter_3D, raw=True)
         if packed:               # exp / normalize / sigmoid inside the kernels, the SH table as it is: no getter runs at all
             return result(rasterizer.forward_raw(pc._xyz, screenspace_points, pc._features, None,
-                                                 pc._opacity, pc._scaling, pc._rotation))
+                                                 opacity, scaling, pc._rotation))
         return result(rasterizer.forward_raw(pc._xyz, screenspace_points, pc._features_dc, pc._features_rest,
-                                             pc._opacity, pc._scaling, pc._rotation))
+                                             opacity, scaling, pc._rotation))
 
+    filtered = filter_3D is not None
     scales = rotations = cov3D_precomp = None
     if pipe.compute_cov3D_python:
-        cov3D_precomp = pc.get_covariance(scaling_modifier)
+        cov3D_precomp = pc.get_covariance(scaling_modifier)              # (the model's own: filtered scales when it has a filter)
     else:
-        scales, rotations = pc.get_scaling, pc.get_rotation
+        scales, rotations = (pc.get_scaling_with_3D_filter if filtered else pc.get_scaling), pc.get_rotation
 
     shs = colors_precomp = None
     if override_color is None:
@@ -122,4 +139,5 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         colors_precomp = override_color
 
     return result(rasterizer(means3D=xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp,
-                             opacities=pc.get_opacity, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp))
+                             opacities=pc.get_opacity_with_3D_filter if filtered else pc.get_opacity, scales=scales, rotations=rotations,
+                             cov3D_precomp=cov3D_precomp))

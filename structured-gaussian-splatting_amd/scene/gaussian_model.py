@@ -79,6 +79,7 @@ class OptimizationDefaults:
     bilateral_grid_shape: tuple = (16, 16, 8)     # (grid_x, grid_y, luma levels)
     bilateral_grid_lr: float = 2e-3           # the grids' Adam; warmed up over 1000 iterations, decayed to 1 % (bilagrid.bilateral_grid_lr)
     bilateral_grid_tv: float = 10.0           # weight of the grids' total variation in the loss
+    filter_3d: bool = False                   # Mip-Splatting's 3D smoothing filter, recomputed from the training cameras (train_loop.train)
 
 
 def expon_lr(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1_000_000):
@@ -123,6 +124,7 @@ class GaussianModel:
         self.freeze_means = self.freeze_scales = self.freeze_rotations = self.freeze_opacities = False
         self.densify_absgrad = False
         self.densify_strategy = "default"
+        self.filter_3D = None                                # [P,1] buffer of compute_3D_filter, or None: no 3D smoothing filter
 
     # ---- the reference's attribute names -------------------------------------------------------------------
     packed_features = True                                   # _features_dc / _features_rest are views of _features
@@ -157,8 +159,45 @@ class GaussianModel:
     def get_features(self):
         return self._t["features"]                           # = torch.cat((_features_dc, _features_rest), dim=1), see the header
 
+    # ---- the 3D smoothing filter (diff_gaussian_rasterization/filter3d.py) ------------------------------
+    def compute_3D_filter(self, cameras, native=None):
+        """filter_3D [P,1] from the training cameras: every Gaussian's minimum depth over the cameras that see it, over the largest
+        focal length, times sqrt(0.2).  A buffer: recompute it after every edit that adds, removes or moves Gaussians."""
+        from diff_gaussian_rasterization.filter3d import compute_filter_3d
+        self.filter_3D = compute_filter_3d(self._xyz.detach(), cameras, native=native)
+
+    def checked_filter_3D(self):
+        """filter_3D, or None; a filter that a structural edit left behind is an error, never a quiet unfiltered frame."""
+        f = self.filter_3D
+        if f is not None and f.shape[0] != self._xyz.shape[0]:
+            raise ValueError(f"filter_3D has {f.shape[0]} rows for {self._xyz.shape[0]} Gaussians: the model was edited since; "
+                             "call compute_3D_filter(cameras)")
+        return f
+
+    def _filtered_raw(self):
+        """(logits', log-scales') of the filtered model: what render() hands to forward_raw and what the fused PLY stores."""
+        from diff_gaussian_rasterization.filter3d import apply_filter_3d
+        opacity = self._opacity.detach() if self.freeze_opacities else self._opacity
+        scaling = self._scaling.detach() if self.freeze_scales else self._scaling
+        return apply_filter_3d(opacity, scaling, self.checked_filter_3D(), raw=True)
+
+    def _filtered(self, which):
+        """The activation of the filtered raw parameters, by the getters' own activation (scene/activations.py): the getter path and
+        the raw path render the same numbers.  Nothing is kept: each getter evaluates the filter for itself (the raw path is the one
+        a training step takes)."""
+        logits, log_scales = self._filtered_raw()
+        return ActivationCache().get(which, log_scales, self._rotation.detach(), logits)
+
+    @property
+    def get_scaling_with_3D_filter(self):
+        return self.get_scaling if self.checked_filter_3D() is None else self._filtered(0)
+
+    @property
+    def get_opacity_with_3D_filter(self):
+        return self.get_opacity if self.checked_filter_3D() is None else self._filtered(2)
+
     def get_covariance(self, scaling_modifier=1):
-        L = quat_to_rotmat(self._rotation) @ torch.diag_embed(self.get_scaling * scaling_modifier)
+        L = quat_to_rotmat(self._rotation) @ torch.diag_embed(self.get_scaling_with_3D_filter * scaling_modifier)
         S = L @ L.transpose(1, 2)
         return torch.stack([S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2]], 1)
 
@@ -174,6 +213,7 @@ class GaussianModel:
         tensors = _pack(tensors)
         self._t = {k: nn.Parameter(tensors[k].detach().clone().contiguous().requires_grad_(True)) for k in TABLE}
         self._acts.invalidate()
+        self.filter_3D = None                                # a new table: the filter of the old one says nothing about it
         P = self._xyz.shape[0]
         self.max_radii2D = torch.zeros(P, device=self.device)
 
@@ -296,7 +336,19 @@ class GaussianModel:
         self.xyz_gradient_accum, self.denom, self.max_radii2D = self.xyz_gradient_accum[keep], self.denom[keep], self.max_radii2D[keep]
 
     def reset_opacity(self):
-        capped = inverse_sigmoid(torch.min(self.get_opacity.detach(), torch.full_like(self._opacity, 0.01)))
+        if self.checked_filter_3D() is None:
+            capped = inverse_sigmoid(torch.min(self.get_opacity.detach(), torch.full_like(self._opacity, 0.01)))
+        else:
+            # Mip-Splatting's: the FILTERED opacity is capped, then taken back through coef = o' / o.  The cap sits 2^-20 under
+            # 0.01, so that the filtered opacity of the reset model stays at or under 0.01 through the roundings of the way back
+            from diff_gaussian_rasterization.filter3d import apply_filter_3d
+            with torch.no_grad():
+                coef = apply_filter_3d(torch.ones_like(self._opacity), self.get_scaling.detach(), self.filter_3D)[0]
+                cap = torch.full_like(self._opacity, 0.01 * (1 - 2.0 ** -20))
+                # (a scale so far under its filter that coef underflows: 0 / 0 would be a NaN, and logit(0) is -inf)
+                tiny = torch.finfo(coef.dtype).tiny
+                opacity = torch.min(self.get_opacity_with_3D_filter.detach(), cap) / coef.clamp_min(tiny)
+                capped = inverse_sigmoid(opacity.clamp(min=tiny, max=1 - 2.0 ** -23))
         self._rebuild(replace={"opacity": capped})
 
     def _densify_grad(self, viewspace_point_tensor):
@@ -493,11 +545,20 @@ class GaussianModel:
         self.xyz_gradient_accum, self.denom = accum, denom
         self._load_optimizer_state(opt_state)
 
-    def save_ply(self, path):
+    def save_ply(self, path, fuse_filter=False):
+        """Without a 3D filter: the reference's file.  With one: Mip-Splatting's layout, one more property `filter_3D` after rot_3;
+        fuse_filter=True (its save_fused_ply): the filtered logits and log-scales in the opacity and scale columns and no filter
+        column, the file any viewer shows as the filtered model."""
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         n = lambda t: t.detach().cpu().numpy()
-        ply_io.write_gaussian_ply(path, n(self._xyz), n(self._features_dc), n(self._features_rest), n(self._opacity),
-                                  n(self._scaling), n(self._rotation))
+        opacity, scaling, filter_3D = self._opacity, self._scaling, self.checked_filter_3D()
+        if filter_3D is not None and fuse_filter:
+            from diff_gaussian_rasterization.filter3d import apply_filter_3d
+            with torch.no_grad():
+                opacity, scaling = apply_filter_3d(opacity, scaling, filter_3D, raw=True)
+            filter_3D = None
+        ply_io.write_gaussian_ply(path, n(self._xyz), n(self._features_dc), n(self._features_rest), n(opacity),
+                                  n(scaling), n(self._rotation), filter_3D=None if filter_3D is None else n(filter_3D))
 
     def load_ply(self, path, device="cuda"):
         d = ply_io.read_gaussian_ply(path)
@@ -505,10 +566,15 @@ class GaussianModel:
         t = lambda a: torch.tensor(a, dtype=torch.float32, device=device)
         self._adopt(dict(xyz=t(d["xyz"]), f_dc=t(d["f_dc"]), f_rest=t(d["f_rest"]), opacity=t(d["opacity"]),
                          scaling=t(d["scaling"]), rotation=t(d["rotation"])))
+        if "filter_3D" in d:
+            self.filter_3D = t(d["filter_3D"])
         self.active_sh_degree = self.max_sh_degree
 
     def save_compressed(self, path, **kw):
         """The vector-quantised checkpoint (scene/compression.py; kw: sh_clusters, iters, generator)."""
+        if self.filter_3D is not None:
+            raise ValueError("save_compressed: the archive does not store a 3D filter; save_ply(path, fuse_filter=True) writes the "
+                             "filtered model, or set filter_3D = None to compress the unfiltered parameters")
         from . import compression
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         compression.save_compressed(path, compression.compress(self, **kw))

@@ -12,13 +12,18 @@ def property_names(n_rest: int):
     return names
 
 
-def write_gaussian_ply(path, xyz, f_dc, f_rest, opacity, scaling, rotation):
-    """xyz[P,3] f_dc[P,1,3] f_rest[P,M-1,3] opacity[P,1] scaling[P,3] rotation[P,4] (numpy, raw parameters)."""
+def write_gaussian_ply(path, xyz, f_dc, f_rest, opacity, scaling, rotation, filter_3D=None):
+    """xyz[P,3] f_dc[P,1,3] f_rest[P,M-1,3] opacity[P,1] scaling[P,3] rotation[P,4] (numpy, raw parameters).
+    filter_3D [P,1] (optional): one more property `filter_3D` behind rot_3, Mip-Splatting's layout; None: the file is the reference's."""
     P = xyz.shape[0]
     rest = np.ascontiguousarray(np.transpose(f_rest, (0, 2, 1))).reshape(P, -1)
     dc = np.ascontiguousarray(np.transpose(f_dc, (0, 2, 1))).reshape(P, -1)
     names = property_names(rest.shape[1])
-    table = np.concatenate([xyz, np.zeros_like(xyz), dc, rest, opacity.reshape(P, 1), scaling, rotation], axis=1).astype("<f4")
+    columns = [xyz, np.zeros_like(xyz), dc, rest, opacity.reshape(P, 1), scaling, rotation]
+    if filter_3D is not None:
+        names = names + ["filter_3D"]
+        columns.append(filter_3D.reshape(P, 1))
+    table = np.concatenate(columns, axis=1).astype("<f4")
     assert table.shape[1] == len(names)
     header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % P
     header += "".join(f"property float {n}\n" for n in names) + "end_header\n"
@@ -51,8 +56,11 @@ def read_gaussian_ply(path):
     pick = lambda prefix: [col[n] for n in sorted((n for n in names if n.startswith(prefix)), key=lambda s: int(s.split("_")[-1]))]
     rest_cols = pick("f_rest_")
     n_rest = len(rest_cols) // 3
-    return dict(names=names, xyz=data[:, [col["x"], col["y"], col["z"]]].copy(),
-                f_dc=data[:, pick("f_dc_")].reshape(count, 3, 1).transpose(0, 2, 1).copy(),
-                f_rest=data[:, rest_cols].reshape(count, 3, n_rest).transpose(0, 2, 1).copy(),
-                opacity=data[:, [col["opacity"]]].copy(), scaling=data[:, pick("scale_")].copy(),
-                rotation=data[:, pick("rot_")].copy())
+    out = dict(names=names, xyz=data[:, [col["x"], col["y"], col["z"]]].copy(),
+               f_dc=data[:, pick("f_dc_")].reshape(count, 3, 1).transpose(0, 2, 1).copy(),
+               f_rest=data[:, rest_cols].reshape(count, 3, n_rest).transpose(0, 2, 1).copy(),
+               opacity=data[:, [col["opacity"]]].copy(), scaling=data[:, pick("scale_")].copy(),
+               rotation=data[:, pick("rot_")].copy())
+    if "filter_3D" in col:                    # Mip-Splatting's extra property (write_gaussian_ply)
+        out["filter_3D"] = data[:, [col["filter_3D"]]].copy()
+    return out

@@ -2,7 +2,9 @@
 LR schedule, SH-degree ramp, render -> L1/D-SSIM -> backward, densification bookkeeping, densify/prune,
 opacity reset, Adam step.  SURVEY 8f row f1.  opt.densify_strategy = "mcmc" replaces the densification part:
 regulariser gradients before the step; relocation and growth after it, inside the refinement window; position noise every iteration.
-opt.bilateral_grid puts the per-image bilateral grid between render() and the loss; off, the loop is as before."""
+opt.bilateral_grid puts the per-image bilateral grid between render() and the loss; off, the loop is as before.
+opt.filter_3d keeps the model's 3D smoothing filter current: computed from `cameras` before the first render, after
+every edit that changes or moves the Gaussians, and every 100 iterations after densification; off, the loop is as before."""
 import random
 
 import torch
@@ -30,6 +32,9 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
         gaussians.bilagrid = bilagrid
         bilagrid_optimizer = FusedAdam([bilagrid.grids], lr=opt.bilateral_grid_lr, eps=1e-15, native=bilagrid.grids.is_cuda)
     mcmc = getattr(opt, "densify_strategy", "default") == "mcmc"
+    filter_3d = bool(getattr(opt, "filter_3d", False))
+    if filter_3d:
+        gaussians.compute_3D_filter(cameras)
     for it in range(first_iter, iterations + 1):
         xyz_lr = gaussians.update_learning_rate(it)
         if it % 1000 == 0:
@@ -56,6 +61,8 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
                 if it > opt.densify_from_iter and it % opt.densification_interval == 0:
                     size_threshold = 20 if it > opt.opacity_reset_interval else None
                     gaussians.densify_and_prune(opt.densify_grad_threshold, 0.005, scene_extent, size_threshold)
+                    if filter_3d:
+                        gaussians.compute_3D_filter(cameras)
                 if it % opt.opacity_reset_interval == 0 or (white_background and it == opt.densify_from_iter):
                     gaussians.reset_opacity()
             if it < iterations:
@@ -71,8 +78,13 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
                 if mcmc and opt.densify_from_iter < it < opt.densify_until_iter and it % opt.densification_interval == 0:
                     gaussians.mcmc_relocate(opt.mcmc_min_opacity)
                     gaussians.mcmc_grow(opt.mcmc_cap_max, opt.mcmc_min_opacity)
+                    if filter_3d:
+                        gaussians.compute_3D_filter(cameras)
             if mcmc:
                 gaussians.mcmc_inject_noise(opt.mcmc_noise_lr * xyz_lr)
+            # Mip-Splatting's schedule once densification is over: every 100 iterations, not in the last 100
+            if filter_3d and it % 100 == 0 and opt.densify_until_iter < it < iterations - 100:
+                gaussians.compute_3D_filter(cameras)
         if on_iteration is not None:
             on_iteration(it, loss, gaussians)
     return gaussians
