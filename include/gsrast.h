@@ -260,6 +260,36 @@ int gsr_backward_geom_aux(const gsr_frame_desc *desc, const gsr_camera *cam, con
                           const int32_t *radii, const void *geom_ws, const float *screen_grads, int32_t g_begin,
                           int32_t g_end, int32_t binned_ranks, const gsr_frame_plan *own_plan, const gsr_grads *out, void *stream);
 
+/* ---- Per-Gaussian blend statistics of a frame (additive: every call above keeps its meaning).  A pixel composites a splat when
+ * the blend gives it a weight w = alpha T > 0 (the alpha >= 1/255 test, the 0.99 clamp and the stop rule of the colour image: the
+ * event that advances n_contrib).  Per Gaussian g, over every pixel of the frame:
+ *   count[g]           += the pixels that composited it
+ *   weight_sum_q32[g]  += the sum of its w, in units of 2^-32 (weight_sum = weight_sum_q32 * 2^-32)
+ *   weight_max_bits[g]  = max(., the largest single w), as the bits of the binary32 value: w >= 0, so the unsigned bit patterns
+ *                         order like the values and the array reads as float [P]
+ * The arrays are the caller's, each [P], and are ACCUMULATED INTO, never cleared: zero them once, then call for every camera.  All
+ * three are updated with integer atomics (64-bit add, 32-bit max) of per-(tile, Gaussian) totals that are themselves taken in a
+ * fixed order, so the same frames give the same bits whatever the tile scheduling, the chunking or the order of the calls.
+ * Range: a (tile, Gaussian) total is below 256, so weight_sum_q32 holds 2^32 units of weight per Gaussian before it wraps - a
+ * full-screen opaque splat over about 2 000 views at 1920x1080; count holds 2^64 pixels.
+ * gsr_forward_render_contrib / gsr_forward_contrib are gsr_forward_render / gsr_forward that also add the frame into *stats
+ * (stats NULL: exactly the plain call).  Colour, radii, plan and every workspace are the plain call's, bit for bit: the frame can
+ * be followed by its backward.  Whole images only (tile_row_begin = tile_row_end = 0); a slab, or a NULL member with P > 0, is
+ * GSR_ERR_INVALID_ARGUMENT before any device work.  A call that stops with GSR_ERR_WORKSPACE in a later depth chunk has already
+ * added the earlier chunks: give the frame a binning workspace for num_rendered instances, or keep a copy of the arrays and put it
+ * back before the re-run. */
+typedef struct gsr_contrib_stats {
+    uint64_t *count;             /* [P] */
+    uint64_t *weight_sum_q32;    /* [P] */
+    uint32_t *weight_max_bits;   /* [P] */
+} gsr_contrib_stats;
+int gsr_forward_render_contrib(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws,
+                               void *binning_ws, void *image_ws, gsr_frame_plan *plan_host, float *out_color,
+                               const gsr_contrib_stats *stats, void *stream);
+int gsr_forward_contrib(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *image_ws,
+                        int32_t *radii, gsr_frame_plan *plan_host, void *binning_ws, int64_t binning_capacity, float *out_color,
+                        gsr_grads *early_fill, const gsr_contrib_stats *stats, void *stream);
+
 /* ---- Gradients for the camera: dL/dviewmatrix [4,4], dL/dprojmatrix [4,4], dL/dcampos [3] (additive: every call above keeps its
  * meaning).  Each is the gradient w.r.t. the tensor as the forward consumed it, in the header's row-vector convention; the three
  * are returned separately and the caller chains them to its own pose parametrisation (the library has none).  Column 3 of

@@ -359,11 +359,29 @@ int gsr_forward_preprocess(const gsr_frame_desc *desc, const gsr_camera *cam, co
 // fill (optional): a zero fill to enqueue behind the FIRST chunk's blend and readback kernels, ahead of the wait for that readback
 // (gsr_forward's early fill); *fill_done reports whether it was enqueued
 // aux (optional): the depth / alpha outputs (gsr_forward_render_aux)
-static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *binning_ws,
-                               void *image_ws, gsr_frame_plan *plan, float *out_color, void *stream, const ZeroSegs *fill, bool *fill_done,
-                               const gsr_aux_outputs *aux_out = nullptr)
+// stats (optional, without aux): the per-Gaussian blend statistics (gsr_forward_render_contrib), added by every chunk's blend
+// What gsr_forward_render_contrib / gsr_forward_contrib ask of their arguments beyond the plain calls, checked on the host alone
+static int validate_contrib(const gsr_frame_desc *desc, const gsr_contrib_stats *stats, const char *who)
 {
     int rc = validate(desc);
+    if (rc || !stats) return rc;
+    const FrameK f = make_frame(*desc);
+    if (f.ty0 != 0 || f.ty1 != f.Gy) {
+        set_error("%s: the blend statistics are taken over whole images only (tile_row_begin = tile_row_end = 0)", who);
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if (desc->P > 0 && (!stats->count || !stats->weight_sum_q32 || !stats->weight_max_bits)) {
+        set_error("%s: stats->count, ->weight_sum_q32 and ->weight_max_bits are required ([P] each)", who);
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    return GSR_OK;
+}
+
+static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *binning_ws,
+                               void *image_ws, gsr_frame_plan *plan, float *out_color, void *stream, const ZeroSegs *fill, bool *fill_done,
+                               const gsr_aux_outputs *aux_out = nullptr, const gsr_contrib_stats *stats = nullptr)
+{
+    int rc = validate_contrib(desc, stats, "gsr_forward_render_contrib");
     if (rc) return rc;
     if ((rc = validate_inputs(desc, cam, g))) return rc;
     if (!cam || !cam->bg || !image_ws || !out_color || !plan || plan->num_rendered < 0 ||
@@ -389,7 +407,7 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
         if ((rc = launch_binning_init(f, gw0, iw, dbg, s))) return rc;
         AuxWS ax0 = carve_aux(nullptr, 0, f);          // (no list entries: the checkpoints are never touched)
         if (aux_out) { ax0.depth = aux_out->depth; ax0.alpha = aux_out->alpha; ax0.ckpt = ax0.ckpt_start = nullptr; }
-        if ((rc = launch_render_fwd(f, *cam, 0, true, 0, gw0, bw0, iw, out_color, dbg, s, false, aux_out ? &ax0 : nullptr))) return rc;
+        if ((rc = launch_render_fwd(f, *cam, 0, true, 0, gw0, bw0, iw, out_color, dbg, s, false, aux_out ? &ax0 : nullptr, stats))) return rc;
         plan->chunks_run = 1;
         return GSR_OK;
     }
@@ -474,7 +492,7 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
         // small splats (fewer than 4.5 tiles per Gaussian on average; filtered chunks bin a small, unknown part of their bound):
         // the blend forward with one 16-lane group per quadrant
         const bool small_splats = kFwdGroups >= 0 ? kFwdGroups != 0 : (!((plan->chunks_filtered >> c) & 1) && chunk_n > 0 && chunk_max * 2 < chunk_n * 9);
-        if ((rc = launch_render_fwd(f, *cam, c, last, sort_result, gw, bw, iw, out_color, dbg, s, small_splats, aux_out ? &ax : nullptr))) return rc;
+        if ((rc = launch_render_fwd(f, *cam, c, last, sort_result, gw, bw, iw, out_color, dbg, s, small_splats, aux_out ? &ax : nullptr, stats))) return rc;
         plan->chunks_run = c + 1;
         plan->instances_emitted = -1;                 // the last chunk's count stays on the device
         if (last) break;
@@ -507,10 +525,11 @@ int gsr_forward_render(const gsr_frame_desc *desc, const gsr_camera *cam, const 
 
 static int forward_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *image_ws, int32_t *radii,
                         gsr_frame_plan *plan, void *binning_ws, int64_t binning_capacity, float *out_color, gsr_grads *early_fill, void *stream,
-                        const gsr_aux_outputs *aux)
+                        const gsr_aux_outputs *aux, const gsr_contrib_stats *stats = nullptr)
 {
-    int rc = gsr_forward_preprocess(desc, cam, g, geom_ws, image_ws, radii, plan, stream);
+    int rc = validate_contrib(desc, stats, "gsr_forward_contrib");      // (before stage 1: a refused call launches nothing)
     if (rc) return rc;
+    if ((rc = gsr_forward_preprocess(desc, cam, g, geom_ws, image_ws, radii, plan, stream))) return rc;
     int64_t need = 0;
     if ((rc = gsr_binning_first_chunk_capacity(plan, &need))) return rc;
     if (plan->num_rendered > 0 && (!binning_ws || binning_capacity < need)) {
@@ -539,7 +558,7 @@ static int forward_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const
         fill = zero_segments(f, *g, nullptr, *early_fill, bw.row_valid, row_flag_bytes(cap));
     }
     if ((rc = forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, fill.n > 0 ? &fill : nullptr, &filled,
-                                  aux)))
+                                  aux, stats)))
         return rc;
     if (fill_wanted && plan->chunks_run > 0 && effective_binned_ranks(*plan) * 4 < (long long)desc->P) {
         if (!filled) {
@@ -571,6 +590,20 @@ int gsr_forward_render_aux(const gsr_frame_desc *desc, const gsr_camera *cam, co
 {
     bool unused = false;
     return forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, nullptr, &unused, aux);
+}
+
+int gsr_forward_contrib(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *image_ws, int32_t *radii,
+                        gsr_frame_plan *plan, void *binning_ws, int64_t binning_capacity, float *out_color, gsr_grads *early_fill,
+                        const gsr_contrib_stats *stats, void *stream)
+{
+    return forward_impl(desc, cam, g, geom_ws, image_ws, radii, plan, binning_ws, binning_capacity, out_color, early_fill, stream, nullptr, stats);
+}
+
+int gsr_forward_render_contrib(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *binning_ws,
+                               void *image_ws, gsr_frame_plan *plan, float *out_color, const gsr_contrib_stats *stats, void *stream)
+{
+    bool unused = false;
+    return forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, nullptr, &unused, nullptr, stats);
 }
 
 int gsr_aux_workspace_size(const gsr_frame_desc *desc, int64_t binning_capacity, size_t *bytes)

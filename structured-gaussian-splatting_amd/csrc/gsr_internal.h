@@ -267,8 +267,11 @@ ZeroSegs zero_segments(const FrameK &f, const gsr_gaussians &g, float *screen, c
                        size_t valid_bytes = 0);
 // groups: the chunk's splats are small (fewer than 4.5 tiles per Gaussian): the quadrant-group kernel (gsr_render.hip)
 // aux (optional): also render the depth and alpha maps (the aux kernels)
+// stats (optional, without aux): also add the chunk's per-Gaussian blend statistics to the caller's accumulators (k_render_fwd_contrib,
+// whatever `groups` says)
 int launch_render_fwd(const FrameK &f, const gsr_camera &cam, int c, bool last_chunk, int sort_result, const GeomWS &gw, const BinningWS &bw,
-                      ImageWS &iw, float *out_color, bool debug, hipStream_t s, bool groups = false, const AuxWS *aux = nullptr);
+                      ImageWS &iw, float *out_color, bool debug, hipStream_t s, bool groups = false, const AuxWS *aux = nullptr,
+                      const gsr_contrib_stats *stats = nullptr);
 // rows_upper: bound of the instances the chunks that ran emitted (sizes the launch: the unit count lives on the device)
 // aux (optional): the aux backward - dL_dcolor, dL_ddepth, dL_dalpha may each be NULL (zero); rows get slot 9 = sum of w dL/ddepth
 // (dL/dz of the splat).  abs (without aux): the abs backward - rows get slots 10, 11 = the per-pixel absolute sums of d/dmean2D

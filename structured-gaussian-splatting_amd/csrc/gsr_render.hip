@@ -144,13 +144,15 @@ __device__ __forceinline__ v2f lp_at(const LpTerms &t, float qC, float dy)
 }
 
 // Stage up to 64 records (one per lane) of a tile's list into LDS; returns the lane's quadrant mask (bits 28..31 of the
-// sorted list's entry, put there by the emit kernels: gsr_binning.hip).
+// sorted list's entry, put there by the emit kernels: gsr_binning.hip).  entry (optional): the lane's whole list entry (mask and
+// Gaussian index) for a caller that needs the index behind the batch; untouched in the lanes behind a short batch's end.
 __device__ __forceinline__ unsigned stage_batch(float4 *sh_rec, int lane, int n, const uint32_t *__restrict__ sorted_gid, uint32_t first,
-                                                const float4 *__restrict__ records)
+                                                const float4 *__restrict__ records, uint32_t *entry = nullptr)
 {
     unsigned m = 0;
     if (lane < n) {
         const uint32_t v = sorted_gid[first + lane];
+        if (entry) *entry = v;
         m = v >> kQuadMaskShift;
         const float4 *r = records + 3 * (size_t)(v & kGidMask);
         sh_rec[3 * lane + 0] = r[0];
@@ -358,14 +360,27 @@ struct AuxFwdK {
     float *ckpt;                       // [R / kSeg + 2][kAuxCkptFloats]: Z in front of the checkpoint of the same slot (BinningWS::ckpt)
     float *ckpt_start_c;               // [Tn][kAuxCkptFloats]: Z when this chunk (>= 1) starts on a tile (ImageWS::ckpt_start)
 };
-template <class Map, bool kAux>
+// kStats (gsr_forward_render_contrib; lock step only): the same blend also takes, per blended splat, three totals over the wave's 256
+// pixels of the weights w that fwd_pair returns - n = the pixels with w > 0 (ballots: scalar), s = their sum (the lane's four in a
+// fixed order, then wave_sum's fixed tree), m = their maximum (wave_max).  The splat is wave-uniform, so each is a whole-wave
+// reduction; lane j keeps the totals of entry j of the staged batch, and behind the batch the lanes whose n > 0 add them to the
+// caller's per-Gaussian accumulators: three wave instructions per batch of 64 entries, every one an INTEGER add or max (ContribK), so
+// the accumulators do not depend on the order in which tiles, chunks or launches arrive.  Everything else is written as by the plain
+// kernel: a statistics frame is a complete frame.
+struct ContribK {
+    unsigned long long *count;         // [P] += n
+    unsigned long long *sum_q32;       // [P] += (uint64)(s 2^32): s < 256, the product is below 2^40 and exact but for what lies under 2^-32
+    uint32_t *max_bits;                // [P] = max(., bits of m): w >= 0, so the bit patterns order like the values
+};
+template <class Map, bool kAux, bool kStats = false>
 __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, const uint2 *__restrict__ ranges_c, uint32_t *__restrict__ open,
                                            const uint32_t *__restrict__ sorted_gid, const float4 *__restrict__ records,
                                            const float *__restrict__ bg, float *__restrict__ out_color, float *__restrict__ T_state,
                                            int32_t *__restrict__ last_enc, uint32_t *__restrict__ tile_walk_c, float *__restrict__ ckpt,
                                            float *__restrict__ ckpt_start_c, const UnitLists &units, uint32_t *__restrict__ unit_count,
-                                           const AuxFwdK &ax)
+                                           const AuxFwdK &ax, const ContribK &cs = ContribK{})
 {
+    static_assert(!kStats || (Map::kLockStep && !kAux), "the statistics are built for the lock-step colour kernel");
     __shared__ float4 sh_rec[kWave * 3];
 #ifdef GSR_FWD_TRACE
     TraceEnd trace_end{(unsigned long long)wall_clock64(), (int)blockIdx.x};
@@ -425,8 +440,10 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
             zdst[map.aux(0)] = Z0[0]; zdst[map.aux(1)] = Z0[1]; zdst[map.aux(2)] = Z1[0]; zdst[map.aux(3)] = Z1[1];
         }
     };
+    v2f sw0 = {0.f, 0.f}, sw1 = {0.f, 0.f};              // kStats: the weights of the splat blended last (0 for a pair it skipped)
     // blend entry j of the batch into the pairs m names (bits 0-1: P0, 2-3: P1; active: the lane's group has an entry in this pass)
     auto blend = [&](int base, unsigned j, bool active, unsigned m) {
+        if constexpr (kStats) sw0 = sw1 = v2f{0.f, 0.f};
         const float4 a = sh_rec[3u * j], b = sh_rec[3u * j + 1u];
         const float cbl = sh_rec[3u * j + 2u].x;
         const int contributor = enc_base | (int)((unsigned)base + j + 1u);
@@ -436,11 +453,13 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
             const float dy = a.y - fy0;
             const v2f w = fwd_pair(active, lp_at(lt, b.x, dy), b.y, b.z, b.w, cbl, contributor, P0);
             if constexpr (kAux) { const float z = sh_rec[3u * j + 2u].y; Z0 = __builtin_elementwise_fma(v2f{z, z}, w, Z0); }
+            if constexpr (kStats) sw0 = w;
         }
         if (m & 12u) {
             const float dy = a.y - fy1;
             const v2f w = fwd_pair(active, lp_at(lt, b.x, dy), b.y, b.z, b.w, cbl, contributor, P1);
             if constexpr (kAux) { const float z = sh_rec[3u * j + 2u].y; Z1 = __builtin_elementwise_fma(v2f{z, z}, w, Z1); }
+            if constexpr (kStats) sw1 = w;
         }
     };
     if (c > 0 && n_total > 0)
@@ -454,7 +473,10 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
         }
         const int n = min(kWave, n_total - base);
         __syncthreads();
-        const unsigned mymask = stage_batch(sh_rec, lane, n, sorted_gid, rng.x + base, records);
+        uint32_t entry = 0;                                // kStats: the lane's list entry, and its totals over the wave's pixels
+        uint32_t st_n = 0;
+        float st_s = 0.f, st_m = 0.f;
+        const unsigned mymask = stage_batch(sh_rec, lane, n, sorted_gid, rng.x + base, records, kStats ? &entry : nullptr);
         __syncthreads();
         // every 8 blended splats (passes, with groups) the live mask is refreshed: quadrants (and tiles) that saturate mid-batch stop there
         int since_refresh = 0;
@@ -465,6 +487,15 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
                 const int j = __ffsll((long long)act) - 1;
                 act &= act - 1ull;
                 blend(base, (unsigned)j, true, (unsigned)__builtin_amdgcn_readlane((int)mymask, j) & live);
+                if constexpr (kStats) {
+                    const uint32_t cnt = (uint32_t)(__popcll(__ballot(sw0[0] > 0.f)) + __popcll(__ballot(sw0[1] > 0.f)) +
+                                                    __popcll(__ballot(sw1[0] > 0.f)) + __popcll(__ballot(sw1[1] > 0.f)));
+                    if (cnt != 0u) {                       // (wave-uniform: a splat no pixel composited costs the ballots only)
+                        const float sum = wave_sum(((sw0[0] + sw0[1]) + sw1[0]) + sw1[1]);
+                        const float top = wave_max(fmaxf(fmaxf(sw0[0], sw0[1]), fmaxf(sw1[0], sw1[1])));
+                        if (lane == j) { st_n = cnt; st_s = sum; st_m = top; }      // an entry is blended at most once
+                    }
+                }
                 if (++since_refresh == 8) {
                     since_refresh = 0;
                     live = map.live(P0, P1);
@@ -483,6 +514,14 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
                     live = map.live(P0, P1);
                     walk.keep(live);
                 }
+            }
+        }
+        if constexpr (kStats) {
+            if (st_n != 0u) {
+                const uint32_t gid = entry & kGidMask;
+                atomicAdd(cs.count + gid, (unsigned long long)st_n);
+                atomicAdd(cs.sum_q32 + gid, (unsigned long long)(st_s * 4294967296.f));
+                atomicMax(cs.max_bits + gid, __float_as_uint(st_m));
             }
         }
     }
@@ -566,12 +605,36 @@ __global__ __launch_bounds__(kWave, 4) void k_render_fwd_aux(FrameK f, int n_til
     render_fwd<Map, true>(f, c, finalize_all, ranges_c, open, sorted_gid, records, bg, out_color, T_state, last_enc, tile_walk_c, ckpt, ckpt_start_c, units, unit_count, ax);
 }
 
+// the statistics instantiation (lock step, whatever the chunk's splats are like: both mappings render the same bits)
+__global__ __launch_bounds__(kWave, 4) void k_render_fwd_contrib(FrameK f, int n_tiles, int c, int finalize_all,
+                                                                 const uint2 *__restrict__ ranges_c, uint32_t *__restrict__ open,
+                                                                 const uint32_t *__restrict__ sorted_gid,
+                                                                 const float4 *__restrict__ records, const float *__restrict__ bg,
+                                                                 float *__restrict__ out_color, float *__restrict__ T_state,
+                                                                 int32_t *__restrict__ last_enc, uint32_t *__restrict__ tile_walk_c,
+                                                                 float *__restrict__ ckpt, float *__restrict__ ckpt_start_c,
+                                                                 UnitLists units, uint32_t *__restrict__ unit_count, ContribK cs)
+{
+    render_fwd<QuadrantLanes, false, true>(f, c, finalize_all, ranges_c, open, sorted_gid, records, bg, out_color, T_state, last_enc, tile_walk_c, ckpt, ckpt_start_c, units,
+                                           unit_count, AuxFwdK{}, cs);
+}
+
 int launch_render_fwd(const FrameK &f, const gsr_camera &cam, int c, bool last_chunk, int sort_result, const GeomWS &gw, const BinningWS &bw,
-                      ImageWS &iw, float *out_color, bool debug, hipStream_t s, bool groups, const AuxWS *aux)
+                      ImageWS &iw, float *out_color, bool debug, hipStream_t s, bool groups, const AuxWS *aux, const gsr_contrib_stats *stats)
 {
     const int n_tiles = (f.ty1 - f.ty0) * f.Gx;
     if (n_tiles <= 0) return GSR_OK;
     const size_t Tn = (size_t)f.Gx * f.Gy;
+    if (stats) {
+        ProfileScope prof("render_fwd_contrib", s);
+        const ContribK cs{(unsigned long long *)stats->count, (unsigned long long *)stats->weight_sum_q32, stats->weight_max_bits};
+        hipLaunchKernelGGL(k_render_fwd_contrib, dim3(n_tiles), dim3(kWave), 0, s, f, n_tiles, c, last_chunk ? 1 : 0,
+                           iw.ranges + (size_t)c * Tn, iw.open, bw.gids[1], gw.records, cam.bg, out_color, iw.T_state,
+                           iw.last_enc, iw.tile_walk + (size_t)c * Tn, bw.ckpt,
+                           c > 0 ? iw.ckpt_start + (size_t)(c - 1) * Tn * kCkptFloats : nullptr, bw.units, iw.unit_count, cs);
+        GSR_LAUNCH_CHECK("render_fwd_contrib", debug, s);
+        return GSR_OK;
+    }
     if (aux) {
         ProfileScope prof("render_fwd_aux", s);
         const AuxFwdK ax{aux->depth, aux->alpha, aux->ckpt, c > 0 ? aux->ckpt_start + (size_t)(c - 1) * Tn * kAuxCkptFloats : nullptr};

@@ -32,6 +32,13 @@ and one small extraction launch.  It is assigned, not accumulated, by every back
 whether or not means2D requires grad.  Refused with a ValueError: depth_alpha=True and tile_rows / ShardedRenderer.  Off (the
 default): no attribute, no extra launch, the same bits.
 
+Extension: GaussianRasterizer(raster_settings, contributions=stats) with a contrib.ContributionStats also adds the frame's per-Gaussian
+blend statistics into `stats` - the pixels that composited each Gaussian, the sum and the maximum of its blend weights w = alpha T -
+from one more instantiation of the blend forward (module contrib).  forward / forward_raw return what they return
+without it, bit for bit; with antialiasing the compensated opacity is what gets blended.  A statistics frame has no backward.  Refused
+with a ValueError: a `stats` of another P or device, depth_alpha=True, absgrad=True, tile_rows / ShardedRenderer, and grad mode on
+with an input that requires grad (render under torch.no_grad()).  Off (the default): no extra launch, the same bits.
+
 Autograd contract (train.py:106, scene/gaussian_model.py:415-417): gradients for
 (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, None) in that order;
 `means2D.grad[:, :2]` is dL/d(NDC position) with the W/2, H/2 pixel scale folded in, `[:, 2] = 0`.
@@ -166,18 +173,27 @@ def _aux_outputs(fr: "_Frame", capacity: int):
 
 def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                       rs: GaussianRasterizationSettings, tile_rows=None, out_color=None, sh_rest=None, raw=False,
-                      prepare_needs=None, aux=False):
+                      prepare_needs=None, aux=False, contrib=None):
     """Stage 1 + stage 2 of the native forward.  Returns (color, radii, frame).
     aux=True: the same blend also renders frame.depth and frame.alpha ([1,H,W] each; whole images only).
+    contrib (a contrib.ContributionStats of this P and device; whole images, no aux): the blend also adds the frame's per-Gaussian
+    statistics into it.  Such a frame runs the two stages as two calls: a stage 2 that stops for want of room in a later chunk has
+    already added its earlier chunks, so a frame that can stop that way (several chunks planned, a workspace for fewer than all
+    num_rendered instances) first copies the three accumulators, and the re-run starts from the copies.
     raw=True: the tensors are the parameter store's RAW values (sh = _features_dc, sh_rest = _features_rest,
     opacities = logits, scales = log-scales, rotations = unnormalised) and the activations run in the kernels.
     prepare_needs: which gradients a backward will want (as rasterize_backward_geom's `needs`), when one will follow: the
     backward's output tensors are then allocated up front, while the host waits for the plan anyway."""
     if aux and tile_rows is not None:
         raise ValueError("depth / alpha maps are rendered for whole images only: no tile_rows (sharded slabs) with aux=True")
+    if contrib is not None and (aux or tile_rows is not None):
+        raise ValueError(_CONTRIB_PLAIN_ONLY)
     if tile_rows is not None:
         camera_grads_wanted(rs, tile_rows=tile_rows)          # raises when a slab is asked for camera gradients
     device = means3D.device
+    if contrib is not None:
+        from .contrib import check_inputs
+        check_inputs(contrib, (means3D,), "rasterize_forward")
     if device.type != "cuda":
         raise RuntimeError("diff_gaussian_rasterization (MI355X build) needs tensors on a HIP device; "
                            "there is no CPU path")
@@ -237,7 +253,7 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
         # stream is idle from the plan readback until stage 2's first launch, and a trip through the interpreter in between
         # doubles that gap.  The call also enqueues the backward's zero fill itself, right after stage 2's last readback.
         done = False
-        if binning is not None:
+        if binning is not None and contrib is None:
             plan, done = N.forward_both(fr.desc, fr.cam, fr.gauss, fr.geom_ws, fr.image_ws, fr.radii, binning, guess, color, device,
                                         early_fill=early[2] if early is not None else None,
                                         aux=_aux_outputs(fr, guess) if aux else None)
@@ -260,8 +276,10 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
             first = int(plan.chunk_instances_max[0])
             capacity = min(first + first // 4 + (1 << 20), R) if plan.num_chunks > 1 else R        # = gsr_binning_first_chunk_capacity
             capacity = max(capacity, min(guess, R))
-            if binning is not None and capacity <= guess:
+            if binning is not None and capacity <= guess and contrib is None:
                 capacity = R                                   # the guessed workspace covered the first chunk, a later one did not fit
+        # a statistics frame that may stop in a later chunk: what the accumulators held before it
+        saved = [t.clone() for t in (contrib.count, contrib.weight_sum_q32, contrib.weight_max)] if contrib is not None and capacity < R else None
         while not done:
             need = _binning_bytes(capacity, tiles)
             if binning is None or binning.numel() < need:
@@ -270,12 +288,18 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
             fr.binning_ws = binning
             try:
                 N.forward_render(fr.desc, fr.cam, fr.gauss, fr.geom_ws, binning, fr.image_ws, plan, color, device,
-                                 aux=_aux_outputs(fr, capacity) if aux else None)
+                                 aux=_aux_outputs(fr, capacity) if aux else None,
+                                 contrib=contrib.native() if contrib is not None else None)
+                if contrib is not None:
+                    contrib.frames += 1
                 break
             except N.GsrError as e:
                 if e.status != N.ERR_WORKSPACE or capacity >= R:
                     raise
                 capacity, binning = R, None
+                if saved is not None:                          # (behind the chunks that ran, on the same stream)
+                    for t, t0 in zip((contrib.count, contrib.weight_sum_q32, contrib.weight_max), saved):
+                        t.copy_(t0)
         _binning_guess[guess_key] = capacity
         if len(_binning_guess) > 64:
             _binning_guess.pop(next(iter(_binning_guess)))
@@ -618,6 +642,10 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                   absgrad_to=means2D if absgrad else None)
 
 
+_CONTRIB_PLAIN_ONLY = ("contributions: the statistics kernel is the plain colour forward's - no depth_alpha=True, no absgrad=True and no "
+                       "tile_rows (sharded slabs); render those in separate calls")
+
+
 _ABSGRAD_NO_AUX = ("absgrad=True with depth_alpha=True: the blend backward that carries both the depth / alpha gradients and the "
                    "absolute sums is not built; render the two in separate calls")
 
@@ -698,8 +726,10 @@ def _match_getters(means3D, opacities, shs, scales, rotations):
 
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings: GaussianRasterizationSettings, depth_alpha: bool = False, antialiasing: bool = False,
-                 absgrad: bool = False):
-        """absgrad=True (gsplat's flag): backward() also assigns means2D.absgrad [P,3] (module docstring); not with depth_alpha.
+                 absgrad: bool = False, contributions=None):
+        """contributions (a contrib.ContributionStats, extension): every frame is also added into it (module docstring); the frame has
+        no backward; not with depth_alpha or absgrad.
+        absgrad=True (gsplat's flag): backward() also assigns means2D.absgrad [P,3] (module docstring); not with depth_alpha.
         depth_alpha=True (extension): forward / forward_raw also return the depth and alpha maps [1,H,W] (module docstring).
         antialiasing=True (upstream's flag): the opacities are compensated for the 0.3 px^2 dilation first (module docstring)."""
         super().__init__()
@@ -709,6 +739,22 @@ class GaussianRasterizer(nn.Module):
         self.absgrad = bool(absgrad)
         if self.absgrad and self.depth_alpha:
             raise ValueError(_ABSGRAD_NO_AUX)
+        self.contributions = contributions
+        if contributions is not None:
+            from .contrib import ContributionStats
+            if not isinstance(contributions, ContributionStats):
+                raise ValueError(f"contributions must be a ContributionStats, got {type(contributions).__name__}")
+            if self.depth_alpha or self.absgrad:
+                raise ValueError(_CONTRIB_PLAIN_ONLY)
+
+    def _contrib_frame(self, *args, **kw):
+        """A statistics frame (its inputs checked by the caller): the native forward itself - no autograd node, nothing can follow
+        it - and the plain call's (color, radii)."""
+        with torch.no_grad():
+            color, radii, _ = rasterize_forward(*args, contrib=self.contributions, **kw)
+            if self.raster_settings.debug:
+                torch.cuda.synchronize(radii.device)
+        return color, radii
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         """Frustum test per point (the reference's `_C.mark_visible`; unused in-tree, kept for API parity)."""
@@ -725,6 +771,10 @@ class GaussianRasterizer(nn.Module):
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None):
         rs = self.raster_settings
+        if self.contributions is not None:       # (before anything runs: a refused call has launched nothing)
+            from .contrib import check_inputs
+            check_inputs(self.contributions, (means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp,
+                                              rs.viewmatrix, rs.projmatrix, rs.campos), "GaussianRasterizer.forward")
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -744,6 +794,9 @@ class GaussianRasterizer(nn.Module):
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
         rs = rs._replace(sh_degree=int(rs.sh_degree), image_height=int(rs.image_height),
                          image_width=int(rs.image_width))
+        if self.contributions is not None:
+            return self._contrib_frame(means3D, shs, colors_precomp, opacities, scales, rotations,
+                                       cov3D_precomp, rs)
         if FUSE_GETTERS and torch.is_grad_enabled() and not rs.debug and shs.numel() and scales.numel() and rotations.numel():
             leaves = _match_getters(means3D, opacities, shs, scales, rotations)
             if leaves is not None:
@@ -760,11 +813,18 @@ class GaussianRasterizer(nn.Module):
         same gradients on the raw parameters as autograd through those getters, to fp32 rounding."""
         rs = self.raster_settings
         rs = rs._replace(sh_degree=int(rs.sh_degree), image_height=int(rs.image_height), image_width=int(rs.image_width))
+        if self.contributions is not None:
+            from .contrib import check_inputs
+            check_inputs(self.contributions, (xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations,
+                                              rs.viewmatrix, rs.projmatrix, rs.campos), "GaussianRasterizer.forward_raw")
         if self.antialiasing:
             from .antialias import compensate_opacity
             opacity_logits = compensate_opacity(opacity_logits, xyz, log_scales, raw_rotations, rs, raw=True)
         packed = features_rest is None and features_dc.dim() == 3 and features_dc.shape[1] > 1      # one [P,M,3] table
         if not packed and (features_rest is None or features_rest.numel() == 0):
             features_rest = torch.empty(0, dtype=torch.float32, device=xyz.device)
+        if self.contributions is not None:
+            return self._contrib_frame(xyz, features_dc, None, opacity_logits, log_scales, raw_rotations,
+                                       None, rs, sh_rest=features_rest, raw=2 if features_rest is None else 1)
         return _apply(_RasterizeGaussiansRaw, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations, rs,
                       self.depth_alpha, *_camera_args(rs), absgrad_to=means2D if self.absgrad else None)

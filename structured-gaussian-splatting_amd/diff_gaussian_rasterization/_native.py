@@ -48,6 +48,12 @@ class AuxOutputs(C.Structure):
     _fields_ = [("depth", _f32p), ("alpha", _f32p), ("ckpt_ws", C.c_void_p)]
 
 
+class ContribStats(C.Structure):
+    """gsr_contrib_stats: the per-Gaussian accumulators of the blend statistics, [P] each (count and weight_sum_q32 64-bit, weight_max_bits
+    the bits of a float)."""
+    _fields_ = [("count", C.c_void_p), ("weight_sum_q32", C.c_void_p), ("weight_max_bits", C.c_void_p)]
+
+
 class CameraGrads(C.Structure):
     """gsr_camera_grads: dL/dviewmatrix [16], dL/dprojmatrix [16], dL/dcampos [3]; any may be NULL."""
     _fields_ = [("viewmatrix", _f32p), ("projmatrix", _f32p), ("campos", _f32p)]
@@ -126,7 +132,8 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_workspace_sizes", "gsr_binning_
            "gsr_mcmc_relocation_workspace_size", "gsr_mcmc_relocation", "gsr_mcmc_relocate_rows", "gsr_mcmc_inject_noise", "gsr_mcmc_reg_grads",
            "gsr_bilagrid_workspace_size", "gsr_bilagrid_forward", "gsr_bilagrid_backward", "gsr_bilagrid_tv_forward", "gsr_bilagrid_tv_backward",
            "gsr_vq_workspace_size", "gsr_vq_assign", "gsr_vq_update",
-           "gsr_filter3d_workspace_size", "gsr_filter3d_compute", "gsr_filter3d_apply_forward", "gsr_filter3d_apply_backward")
+           "gsr_filter3d_workspace_size", "gsr_filter3d_compute", "gsr_filter3d_apply_forward", "gsr_filter3d_apply_backward",
+           "gsr_forward_contrib", "gsr_forward_render_contrib")
 
 _lib = None
 
@@ -217,13 +224,19 @@ def forward_preprocess(desc, cam: Camera, g: Gaussians, geom_ws, radii, device, 
 
 
 def forward_both(desc, cam: Camera, g: Gaussians, geom_ws, image_ws, radii, binning_ws, binning_capacity, out_color, device,
-                 early_fill: Optional[Grads] = None, aux: Optional[AuxOutputs] = None):
-    """gsr_forward (gsr_forward_aux with `aux`): both stages in one call.  Returns (plan, done): done = False when the binning workspace
-    was too small for the first chunk (nothing of stage 2 ran: allocate and call forward_render)."""
+                 early_fill: Optional[Grads] = None, aux: Optional[AuxOutputs] = None, contrib: Optional[ContribStats] = None):
+    """gsr_forward (gsr_forward_aux with `aux`, gsr_forward_contrib with `contrib`; not both): both stages in one call.  Returns
+    (plan, done): done = False when the binning workspace was too small for the first chunk (nothing of stage 2 ran: allocate and
+    call forward_render) - or, when the plan has more than one chunk, for a later one: a statistics frame has then already added
+    its earlier chunks (include/gsrast.h), so its caller sizes the workspace for num_rendered."""
     plan = FramePlan()
     args = (C.byref(desc), C.byref(cam), C.byref(g), _ptr(geom_ws), _ptr(image_ws), _ptr(radii), C.byref(plan),
             _ptr(binning_ws), C.c_int64(int(binning_capacity)), _ptr(out_color), None if early_fill is None else C.byref(early_fill))
-    if aux is None:
+    if aux is not None and contrib is not None:
+        raise ValueError("forward_both: aux and contrib together (that kernel is not built)")
+    if contrib is not None:
+        rc = load().gsr_forward_contrib(*args, C.byref(contrib), _stream(device))
+    elif aux is None:
         rc = load().gsr_forward(*args, _stream(device))
     else:
         rc = load().gsr_forward_aux(*args, C.byref(aux), _stream(device))
@@ -234,9 +247,13 @@ def forward_both(desc, cam: Camera, g: Gaussians, geom_ws, image_ws, radii, binn
 
 
 def forward_render(desc, cam: Camera, g: Gaussians, geom_ws, binning_ws, image_ws, plan: FramePlan, out_color, device,
-                   aux: Optional[AuxOutputs] = None):
+                   aux: Optional[AuxOutputs] = None, contrib: Optional[ContribStats] = None):
     args = (C.byref(desc), C.byref(cam), C.byref(g), _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws), C.byref(plan), _ptr(out_color))
-    if aux is None:
+    if aux is not None and contrib is not None:
+        raise ValueError("forward_render: aux and contrib together (that kernel is not built)")
+    if contrib is not None:
+        _check(load().gsr_forward_render_contrib(*args, C.byref(contrib), _stream(device)), "gsr_forward_render_contrib")
+    elif aux is None:
         _check(load().gsr_forward_render(*args, _stream(device)), "gsr_forward_render")
     else:
         _check(load().gsr_forward_render_aux(*args, C.byref(aux), _stream(device)), "gsr_forward_render_aux")

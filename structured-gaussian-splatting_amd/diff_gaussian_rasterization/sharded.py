@@ -368,6 +368,10 @@ class _ShardedRasterize(torch.autograd.Function):
         return g_means3D, g_means2D, g_sh, g_col, g_op, g_sc, g_rot, g_cov, None, None, g_rest, None
 
 
+_NO_CONTRIBUTIONS = ("contributions is not supported by ShardedRenderer: the blend statistics are taken over whole images, a rank "
+                     "renders a slab of tile rows (render the statistics frames unsharded)")
+
+
 class ShardedRenderer:
     """render()-shaped front end for world_size > 1 (same arguments and returned dict as
     gaussian_renderer.render, reference gaussian_renderer/__init__.py:18-100)."""
@@ -439,7 +443,9 @@ class ShardedRenderer:
         return slab_bounds(Gy, self.comm.world, self.row_weights if self.row_weights and len(self.row_weights) == Gy else None)
 
     def rasterize(self, rs, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                  cov3D_precomp=None):
+                  cov3D_precomp=None, contributions=None):
+        if contributions is not None:
+            raise ValueError(_NO_CONTRIBUTIONS)
         if (shs is None) == (colors_precomp is None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -453,8 +459,10 @@ class ShardedRenderer:
                       e if scales is None else scales, e if rotations is None else rotations,
                       e if cov3D_precomp is None else cov3D_precomp, rs, self)
 
-    def render(self, viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None):
+    def render(self, viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, contributions=None):
         import math
+        if contributions is not None:
+            raise ValueError(_NO_CONTRIBUTIONS)
 
         from . import GaussianRasterizationSettings
         if getattr(pipe, "antialiasing", False):

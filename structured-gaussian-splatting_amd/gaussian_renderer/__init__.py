@@ -20,6 +20,13 @@ is a ValueError.
 `pipe.absgrad` (gsplat's flag; absent or False: off): after backward() the returned `viewspace_points` also carries `.absgrad`
 [P,3], the per-pixel absolute sums of the means2D gradient (diff_gaussian_rasterization, "absgrad"), on both paths; not together
 with depth_alpha=True (ValueError).
+
+`contributions` (a diff_gaussian_rasterization.contrib.ContributionStats; None: off): the frame's per-Gaussian blend statistics are
+added into it, under torch.no_grad() (a statistics frame has no backward).  Such a frame always goes through the model's getters,
+whatever `pipe.fused_activations` says: fusing the activations into the kernels saves the getters' backward, which a statistics
+frame does not have, and the two paths round the activations differently in the last bit - so the statistics are the model's and
+the camera's, the same bits under either setting of that switch (the image is the one the getter path renders).  The rasterizer
+itself takes `contributions` on forward and forward_raw alike.  Not together with depth_alpha=True or pipe.absgrad (ValueError).
 """
 import math
 
@@ -66,9 +73,19 @@ def _zero_points(like: torch.Tensor) -> torch.Tensor:
     return z
 
 
-def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, depth_alpha=False):
+def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, depth_alpha=False,
+           contributions=None):
     """Render the scene.  Background tensor (bg_color) must be on the GPU.
-    depth_alpha=True (extension): the dict also holds "depth" and "alpha" [1,H,W], differentiable (diff_gaussian_rasterization)."""
+    depth_alpha=True (extension): the dict also holds "depth" and "alpha" [1,H,W], differentiable (diff_gaussian_rasterization).
+    contributions (extension): a ContributionStats the frame's blend statistics are added into; rendered under torch.no_grad(),
+    through the getters whatever pipe.fused_activations says (module docstring)."""
+    if contributions is not None:
+        with torch.no_grad():
+            return _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, depth_alpha, contributions)
+    return _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, depth_alpha, None)
+
+
+def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, depth_alpha, contributions):
     xyz = pc.get_xyz
     # (the reference builds this as zeros_like(...) + 0 and retain_grad()s the non-leaf result; a leaf with requires_grad keeps
     # its .grad by itself.  Its VALUES are never read, by the rasterizer or by the training loop, only its .grad: every frame
@@ -82,7 +99,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         projmatrix=viewpoint_camera.full_proj_transform, sh_degree=pc.active_sh_degree,
         campos=viewpoint_camera.camera_center, prefiltered=False, debug=pipe.debug)
     rasterizer = GaussianRasterizer(raster_settings=raster_settings, depth_alpha=depth_alpha,
-                                    antialiasing=getattr(pipe, "antialiasing", False), absgrad=getattr(pipe, "absgrad", False))
+                                    antialiasing=getattr(pipe, "antialiasing", False), absgrad=getattr(pipe, "absgrad", False),
+                                    contributions=contributions)
 
     def result(out):
         d = {"render": out[0], "viewspace_points": screenspace_points, "visibility_filter": out[1] > 0, "radii": out[1]}
@@ -98,6 +116,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     fused = getattr(pipe, "fused_activations", None)
     if fused is None:            # not set: this package's own model renders from its raw leaves, any other store through its getters
         fused = packed
+    if contributions is not None:      # one path for every statistics frame: the statistics do not depend on a performance switch
+        fused = False
     # the 3D smoothing filter (scene.GaussianModel.compute_3D_filter): a per-Gaussian op in front of the rasterizer, independent of
     # the camera being rendered.  None: no launch, the frame is what it was.  A stale filter raises here (checked_filter_3D)
     if hasattr(pc, "checked_filter_3D"):

@@ -80,6 +80,10 @@ class OptimizationDefaults:
     bilateral_grid_lr: float = 2e-3           # the grids' Adam; warmed up over 1000 iterations, decayed to 1 % (bilagrid.bilateral_grid_lr)
     bilateral_grid_tv: float = 10.0           # weight of the grids' total variation in the loss
     filter_3d: bool = False                   # Mip-Splatting's 3D smoothing filter, recomputed from the training cameras (train_loop.train)
+    significance_prune_iterations: tuple = ()     # at the k-th listed iteration: prune by significance over all training cameras (train_loop.train)
+    significance_prune_fraction: float = 0.6      # the fraction of the Gaussians the first listed iteration removes (LightGaussian's 60 %)
+    significance_prune_decay: float = 0.6         # the k-th removes fraction * decay ** k
+    significance_prune_score: str = "volume_weighted"     # GaussianModel.significance's `score`
 
 
 def expon_lr(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1_000_000):
@@ -408,6 +412,76 @@ class GaussianModel:
         if max_screen_size:
             drop = drop | (self.max_radii2D > max_screen_size) | (self.get_scaling.detach().max(dim=1).values > 0.1 * extent)
         self.prune_points(drop)
+
+    # ---- significance pruning (diff_gaussian_rasterization/contrib.py) ---------------------------------
+    SIGNIFICANCE_SCORES = ("weight_sum", "weight_max", "volume_weighted")
+
+    def contribution_stats(self, cameras, pipe=None, bg=None):
+        """The blend statistics of this model over `cameras`: every camera rendered once under torch.no_grad() (render(...,
+        contributions=)), the model's 3D filter applied as in any render.  pipe: default Pipe(); bg: default black."""
+        from diff_gaussian_rasterization.contrib import ContributionStats
+        from gaussian_renderer import render
+        if pipe is None:
+            from gaussian_params import Pipe
+            pipe = Pipe()
+        if bg is None:
+            bg = torch.zeros(3, device=self.device)
+        stats = ContributionStats(self._xyz.shape[0], self.device)
+        absgrad = getattr(pipe, "absgrad", False)            # a training loop's switch: it asks something of the backward, and these
+        if absgrad:                                          # frames have none
+            pipe.absgrad = False
+        try:
+            with torch.no_grad():
+                for cam in cameras:
+                    render(cam, self, pipe, bg, contributions=stats)
+        finally:
+            if absgrad:
+                pipe.absgrad = absgrad
+        return stats
+
+    def significance(self, stats, score="volume_weighted", v_pow=0.1):
+        """float64 [P]: one score per Gaussian from a ContributionStats of this model.
+        "weight_sum": the sum of its blend weights over all pixels of all frames (LightGaussian's global significance without the
+        volume term; Mini-Splatting's importance).  "weight_max": its largest single blend weight (RadSplat).
+        "volume_weighted": weight_sum * (V / V_ref) ** v_pow with V = prod(get_scaling, 1) and V_ref = sort(V, descending)[int(0.9 P)],
+        the volume that 90 % of the Gaussians exceed (LightGaussian's rule; the ratio is not clipped).
+        stats.count stays available for rules of the caller's own."""
+        if score not in self.SIGNIFICANCE_SCORES:
+            raise ValueError(f"significance: score = {score!r}: one of {', '.join(repr(n) for n in self.SIGNIFICANCE_SCORES)}")
+        P = self._xyz.shape[0]
+        if stats.P != P:
+            raise ValueError(f"significance: the statistics hold {stats.P} Gaussians, the model {P}: collect them again after an edit")
+        if score == "weight_max":
+            return stats.weight_max.double()
+        if score == "weight_sum" or P == 0:
+            return stats.weight_sum
+        V = torch.prod(self.get_scaling.detach().double(), dim=1)
+        V_ref = torch.sort(V, descending=True).values[int(0.9 * P)]
+        return stats.weight_sum * (V / V_ref) ** float(v_pow)
+
+    def prune_by_significance(self, scores, fraction=None, threshold=None):
+        """Remove the least significant Gaussians (prune_points: Adam moments and densification statistics follow their rows; a 3D
+        filter goes stale as after any structural edit).  Exactly one of: fraction - the floor(fraction * P) lowest scores, ties to
+        the lower index (a stable sort: deterministic); threshold - every score < threshold.  Returns the number of rows removed."""
+        if (fraction is None) == (threshold is None):
+            raise ValueError("prune_by_significance: exactly one of fraction and threshold")
+        P = self._xyz.shape[0]
+        scores = torch.as_tensor(scores).reshape(-1)
+        if scores.shape[0] != P:
+            raise ValueError(f"prune_by_significance: {scores.shape[0]} scores for {P} Gaussians")
+        scores = scores.to(self.device)
+        if threshold is not None:
+            drop = scores < threshold
+        else:
+            if not 0.0 <= float(fraction) <= 1.0:
+                raise ValueError(f"prune_by_significance: fraction = {fraction} outside [0, 1]")
+            n = int(math.floor(float(fraction) * P))
+            drop = torch.zeros(P, dtype=torch.bool, device=self.device)
+            drop[torch.sort(scores, stable=True).indices[:n]] = True
+        removed = int(drop.sum())
+        if removed:
+            self.prune_points(drop)
+        return removed
 
     # ---- the MCMC strategy (diff_gaussian_rasterization/mcmc.py, DESIGN section 16) ---------------------------------------
     MULTINOMIAL_MAX = 2 ** 24                                # torch.multinomial's limit on the number of categories

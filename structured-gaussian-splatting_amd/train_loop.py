@@ -4,7 +4,10 @@ opacity reset, Adam step.  SURVEY 8f row f1.  opt.densify_strategy = "mcmc" repl
 regulariser gradients before the step; relocation and growth after it, inside the refinement window; position noise every iteration.
 opt.bilateral_grid puts the per-image bilateral grid between render() and the loss; off, the loop is as before.
 opt.filter_3d keeps the model's 3D smoothing filter current: computed from `cameras` before the first render, after
-every edit that changes or moves the Gaussians, and every 100 iterations after densification; off, the loop is as before."""
+every edit that changes or moves the Gaussians, and every 100 iterations after densification; off, the loop is as before.
+opt.significance_prune_iterations lists iterations at which the model is pruned by significance: behind the
+optimizer step, the blend statistics of all `cameras` are collected and the least significant fraction removed; empty (the default),
+the loop is as before."""
 import random
 
 import torch
@@ -33,6 +36,10 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
         bilagrid_optimizer = FusedAdam([bilagrid.grids], lr=opt.bilateral_grid_lr, eps=1e-15, native=bilagrid.grids.is_cuda)
     mcmc = getattr(opt, "densify_strategy", "default") == "mcmc"
     filter_3d = bool(getattr(opt, "filter_3d", False))
+    prune_at = tuple(int(i) for i in getattr(opt, "significance_prune_iterations", ()))
+    if prune_at and mcmc:
+        raise ValueError("significance_prune_iterations with densify_strategy = \"mcmc\": the MCMC strategy keeps its tables at a fixed "
+                         "size (relocation and growth to a cap), pruning by significance shrinks them")
     if filter_3d:
         gaussians.compute_3D_filter(cameras)
     for it in range(first_iter, iterations + 1):
@@ -80,6 +87,13 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
                     gaussians.mcmc_grow(opt.mcmc_cap_max, opt.mcmc_min_opacity)
                     if filter_3d:
                         gaussians.compute_3D_filter(cameras)
+            if it in prune_at:
+                k = prune_at.index(it)
+                stats = gaussians.contribution_stats(cameras, pipe)
+                gaussians.prune_by_significance(gaussians.significance(stats, opt.significance_prune_score),
+                                                fraction=opt.significance_prune_fraction * opt.significance_prune_decay ** k)
+                if filter_3d:
+                    gaussians.compute_3D_filter(cameras)
             if mcmc:
                 gaussians.mcmc_inject_noise(opt.mcmc_noise_lr * xyz_lr)
             # Mip-Splatting's schedule once densification is over: every 100 iterations, not in the last 100
