@@ -290,6 +290,33 @@ int gsr_forward_contrib(const gsr_frame_desc *desc, const gsr_camera *cam, const
                         int32_t *radii, gsr_frame_plan *plan_host, void *binning_ws, int64_t binning_capacity, float *out_color,
                         gsr_grads *early_fill, const gsr_contrib_stats *stats, void *stream);
 
+/* ---- Error-weighted blend statistics (additive: every call above keeps its meaning).  With a per-pixel error map E in [0, 1], the
+ * image error a Gaussian g is responsible for in a view is E_g = sum over the pixels u of w_g(u) E(u), w = alpha T the blend weight
+ * above ("Revising Densification in Gaussian Splatting" scores by the maximum of E_g over views, Taming-3DGS by its sum).
+ * gsr_forward_render_contrib_error / gsr_forward_contrib_error are the _contrib calls that also add
+ *   error_frame_q32[g] += E_g of this frame, in units of 2^-32
+ * taken by the same kernel next to the three totals of *stats: per (tile, Gaussian) the products in a fixed order, then one more
+ * 64-bit integer atomic add, so the result does not depend on the order of arrival.  pixel_error is read once per tile and depth
+ * chunk, clamped to [0, 1] on the way (a NaN reads as 0); it is never written.  Range: E <= 1, so the bound of weight_sum_q32 holds.
+ * err NULL: exactly the _contrib call.  err non-NULL: stats is required, as are both members when P > 0, and whole images (a slab is
+ * refused as by the _contrib calls); each refusal is GSR_ERR_INVALID_ARGUMENT before any device work.  A frame that bins nothing
+ * (P == 0, where both members may be NULL, or num_rendered == 0) reads no map and adds nothing: it runs the _contrib call's kernel.
+ * gsr_contrib_error_fold closes a frame: for every g, q = error_frame_q32[g]; error_sum_q32[g] += q; error_max[g] = max(error_max[g],
+ * (float)(q 2^-32)); error_frame_q32[g] = 0.  Call it on the same stream behind the frame (behind its LAST call, when a frame that
+ * stopped with GSR_ERR_WORKSPACE is run again - restore error_frame_q32 with the arrays of *stats first).  All three arrays are the
+ * caller's, [P] each, zeroed once.  P < 0, or a NULL pointer with P > 0, is GSR_ERR_INVALID_ARGUMENT; P == 0 launches nothing. */
+typedef struct gsr_contrib_error {
+    const float *pixel_error;     /* [H*W] row-major; read clamped to [0,1], NaN as 0 */
+    uint64_t *error_frame_q32;    /* [P]  += this frame's sum of w * E, in units of 2^-32 */
+} gsr_contrib_error;
+int gsr_forward_render_contrib_error(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws,
+                                     void *binning_ws, void *image_ws, gsr_frame_plan *plan_host, float *out_color,
+                                     const gsr_contrib_stats *stats, const gsr_contrib_error *err, void *stream);
+int gsr_forward_contrib_error(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *image_ws,
+                              int32_t *radii, gsr_frame_plan *plan_host, void *binning_ws, int64_t binning_capacity, float *out_color,
+                              gsr_grads *early_fill, const gsr_contrib_stats *stats, const gsr_contrib_error *err, void *stream);
+int gsr_contrib_error_fold(int64_t P, uint64_t *error_frame_q32, uint64_t *error_sum_q32, float *error_max, void *stream);
+
 /* ---- Gradients for the camera: dL/dviewmatrix [4,4], dL/dprojmatrix [4,4], dL/dcampos [3] (additive: every call above keeps its
  * meaning).  Each is the gradient w.r.t. the tensor as the forward consumed it, in the header's row-vector convention; the three
  * are returned separately and the caller chains them to its own pose parametrisation (the library has none).  Column 3 of

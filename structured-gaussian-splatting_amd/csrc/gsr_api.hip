@@ -377,12 +377,40 @@ static int validate_contrib(const gsr_frame_desc *desc, const gsr_contrib_stats 
     return GSR_OK;
 }
 
+// What the _contrib_error calls ask beyond that (err non-NULL; err NULL: nothing, they are the _contrib calls), on the host alone
+static int validate_contrib_error(const gsr_frame_desc *desc, const gsr_contrib_stats *stats, const gsr_contrib_error *err, const char *who)
+{
+    if (!err) return GSR_OK;
+    int rc = validate(desc);
+    if (rc) return rc;
+    if (!stats) {
+        set_error("%s: err without stats: the error-weighted total is taken beside the blend statistics (stats is required)", who);
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    const FrameK f = make_frame(*desc);
+    if (f.ty0 != 0 || f.ty1 != f.Gy) {
+        set_error("%s: the error-weighted statistics are taken over whole images only (tile_row_begin = tile_row_end = 0)", who);
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if (desc->P > 0 && !err->pixel_error) {
+        set_error("%s: err->pixel_error is required ([H*W])", who);
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if (desc->P > 0 && !err->error_frame_q32) {
+        set_error("%s: err->error_frame_q32 is required ([P])", who);
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    return GSR_OK;
+}
+
 static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *binning_ws,
                                void *image_ws, gsr_frame_plan *plan, float *out_color, void *stream, const ZeroSegs *fill, bool *fill_done,
-                               const gsr_aux_outputs *aux_out = nullptr, const gsr_contrib_stats *stats = nullptr)
+                               const gsr_aux_outputs *aux_out = nullptr, const gsr_contrib_stats *stats = nullptr,
+                               const gsr_contrib_error *err = nullptr)
 {
-    int rc = validate_contrib(desc, stats, "gsr_forward_render_contrib");
+    int rc = validate_contrib_error(desc, stats, err, "gsr_forward_render_contrib_error");
     if (rc) return rc;
+    if ((rc = validate_contrib(desc, stats, err ? "gsr_forward_render_contrib_error" : "gsr_forward_render_contrib"))) return rc;
     if ((rc = validate_inputs(desc, cam, g))) return rc;
     if (!cam || !cam->bg || !image_ws || !out_color || !plan || plan->num_rendered < 0 ||
         (desc->P > 0 && !geom_ws) || (plan->num_rendered > 0 && !binning_ws)) {
@@ -407,6 +435,8 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
         if ((rc = launch_binning_init(f, gw0, iw, dbg, s))) return rc;
         AuxWS ax0 = carve_aux(nullptr, 0, f);          // (no list entries: the checkpoints are never touched)
         if (aux_out) { ax0.depth = aux_out->depth; ax0.alpha = aux_out->alpha; ax0.ckpt = ax0.ckpt_start = nullptr; }
+        // (err is not handed on: nothing is blended, every error total is zero, and with P == 0 the caller may have passed no map -
+        // the error kernel would load it at tile start whatever the ranges hold)
         if ((rc = launch_render_fwd(f, *cam, 0, true, 0, gw0, bw0, iw, out_color, dbg, s, false, aux_out ? &ax0 : nullptr, stats))) return rc;
         plan->chunks_run = 1;
         return GSR_OK;
@@ -492,7 +522,7 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
         // small splats (fewer than 4.5 tiles per Gaussian on average; filtered chunks bin a small, unknown part of their bound):
         // the blend forward with one 16-lane group per quadrant
         const bool small_splats = kFwdGroups >= 0 ? kFwdGroups != 0 : (!((plan->chunks_filtered >> c) & 1) && chunk_n > 0 && chunk_max * 2 < chunk_n * 9);
-        if ((rc = launch_render_fwd(f, *cam, c, last, sort_result, gw, bw, iw, out_color, dbg, s, small_splats, aux_out ? &ax : nullptr, stats))) return rc;
+        if ((rc = launch_render_fwd(f, *cam, c, last, sort_result, gw, bw, iw, out_color, dbg, s, small_splats, aux_out ? &ax : nullptr, stats, err))) return rc;
         plan->chunks_run = c + 1;
         plan->instances_emitted = -1;                 // the last chunk's count stays on the device
         if (last) break;
@@ -525,10 +555,11 @@ int gsr_forward_render(const gsr_frame_desc *desc, const gsr_camera *cam, const 
 
 static int forward_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *image_ws, int32_t *radii,
                         gsr_frame_plan *plan, void *binning_ws, int64_t binning_capacity, float *out_color, gsr_grads *early_fill, void *stream,
-                        const gsr_aux_outputs *aux, const gsr_contrib_stats *stats = nullptr)
+                        const gsr_aux_outputs *aux, const gsr_contrib_stats *stats = nullptr, const gsr_contrib_error *err = nullptr)
 {
-    int rc = validate_contrib(desc, stats, "gsr_forward_contrib");      // (before stage 1: a refused call launches nothing)
+    int rc = validate_contrib_error(desc, stats, err, "gsr_forward_contrib_error");      // (before stage 1: a refused call launches nothing)
     if (rc) return rc;
+    if ((rc = validate_contrib(desc, stats, err ? "gsr_forward_contrib_error" : "gsr_forward_contrib"))) return rc;
     if ((rc = gsr_forward_preprocess(desc, cam, g, geom_ws, image_ws, radii, plan, stream))) return rc;
     int64_t need = 0;
     if ((rc = gsr_binning_first_chunk_capacity(plan, &need))) return rc;
@@ -558,7 +589,7 @@ static int forward_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const
         fill = zero_segments(f, *g, nullptr, *early_fill, bw.row_valid, row_flag_bytes(cap));
     }
     if ((rc = forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, fill.n > 0 ? &fill : nullptr, &filled,
-                                  aux, stats)))
+                                  aux, stats, err)))
         return rc;
     if (fill_wanted && plan->chunks_run > 0 && effective_binned_ranks(*plan) * 4 < (long long)desc->P) {
         if (!filled) {
@@ -604,6 +635,35 @@ int gsr_forward_render_contrib(const gsr_frame_desc *desc, const gsr_camera *cam
 {
     bool unused = false;
     return forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, nullptr, &unused, nullptr, stats);
+}
+
+int gsr_forward_contrib_error(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *image_ws,
+                              int32_t *radii, gsr_frame_plan *plan, void *binning_ws, int64_t binning_capacity, float *out_color,
+                              gsr_grads *early_fill, const gsr_contrib_stats *stats, const gsr_contrib_error *err, void *stream)
+{
+    return forward_impl(desc, cam, g, geom_ws, image_ws, radii, plan, binning_ws, binning_capacity, out_color, early_fill, stream, nullptr, stats, err);
+}
+
+int gsr_forward_render_contrib_error(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *binning_ws,
+                                     void *image_ws, gsr_frame_plan *plan, float *out_color, const gsr_contrib_stats *stats,
+                                     const gsr_contrib_error *err, void *stream)
+{
+    bool unused = false;
+    return forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, nullptr, &unused, nullptr, stats, err);
+}
+
+int gsr_contrib_error_fold(int64_t P, uint64_t *error_frame_q32, uint64_t *error_sum_q32, float *error_max, void *stream)
+{
+    if (P < 0) {
+        set_error("gsr_contrib_error_fold: P = %lld", (long long)P);
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if (P == 0) return GSR_OK;
+    if (!error_frame_q32 || !error_sum_q32 || !error_max) {
+        set_error("gsr_contrib_error_fold: error_frame_q32, error_sum_q32 and error_max are required ([P] each)");
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    return launch_contrib_error_fold((long long)P, error_frame_q32, error_sum_q32, error_max, false, (hipStream_t)stream);
 }
 
 int gsr_aux_workspace_size(const gsr_frame_desc *desc, int64_t binning_capacity, size_t *bytes)

@@ -271,7 +271,10 @@ ZeroSegs zero_segments(const FrameK &f, const gsr_gaussians &g, float *screen, c
 // whatever `groups` says)
 int launch_render_fwd(const FrameK &f, const gsr_camera &cam, int c, bool last_chunk, int sort_result, const GeomWS &gw, const BinningWS &bw,
                       ImageWS &iw, float *out_color, bool debug, hipStream_t s, bool groups = false, const AuxWS *aux = nullptr,
-                      const gsr_contrib_stats *stats = nullptr);
+                      const gsr_contrib_stats *stats = nullptr, const gsr_contrib_error *err = nullptr);
+// err (optional, with stats): also add the chunk's error-weighted totals to err->error_frame_q32 (k_render_fwd_contrib_error);
+// launch_contrib_error_fold folds a finished frame's totals into the running sum and maximum and clears them (P <= 0: no launch)
+int launch_contrib_error_fold(long long P, uint64_t *frame_q32, uint64_t *sum_q32, float *error_max, bool debug, hipStream_t s);
 // rows_upper: bound of the instances the chunks that ran emitted (sizes the launch: the unit count lives on the device)
 // aux (optional): the aux backward - dL_dcolor, dL_ddepth, dL_dalpha may each be NULL (zero); rows get slot 9 = sum of w dL/ddepth
 // (dL/dz of the splat).  abs (without aux): the abs backward - rows get slots 10, 11 = the per-pixel absolute sums of d/dmean2D

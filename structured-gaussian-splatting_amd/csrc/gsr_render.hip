@@ -372,15 +372,33 @@ struct ContribK {
     unsigned long long *sum_q32;       // [P] += (uint64)(s 2^32): s < 256, the product is below 2^40 and exact but for what lies under 2^-32
     uint32_t *max_bits;                // [P] = max(., bits of m): w >= 0, so the bit patterns order like the values
 };
-template <class Map, bool kAux, bool kStats = false>
+// kErr (gsr_forward_render_contrib_error; with kStats): a fourth total per blended splat, e = the sum over the wave's 256 pixels of
+// w E(pixel), with E the caller's per-pixel error map.  Each lane loads the error of its four pixels once per launch (load_px's
+// addressing; 0 outside the image; clamped to [0, 1] on load, which also reads a NaN as 0) and keeps them in registers for the walk.
+// The lane's four products are added in the association of `s` (err_dot4), so that E = 1 gives the bits of `s`; lane j
+// keeps e beside n, s, m and the batch's fourth atomic is a 64-bit integer add in units of 2^-32 (E <= 1: the bound of sum_q32).
+struct ErrK {
+    const float *pixel_error;          // [H, W]
+    unsigned long long *frame_q32;     // [P] += (uint64)(e 2^32): this frame's total, folded and cleared by k_contrib_error_fold
+};
+// ((a0 e0 + a1 e1) + a2 e2) + a3 e3 with every product and sum rounded on its own: the file is built with -ffp-contract=fast, which
+// would fuse three of the products into the adds.  The association is what makes E = 1 reproduce `s` (a product with 1 is exact, fused
+// or not); the pragma only fixes which roundings a general E sees, so that they do not move with the compiler's choice.
+__device__ __forceinline__ float err_dot4(float a0, float a1, float a2, float a3, float e0, float e1, float e2, float e3)
+{
+#pragma clang fp contract(off)
+    return ((a0 * e0 + a1 * e1) + a2 * e2) + a3 * e3;
+}
+template <class Map, bool kAux, bool kStats = false, bool kErr = false>
 __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, const uint2 *__restrict__ ranges_c, uint32_t *__restrict__ open,
                                            const uint32_t *__restrict__ sorted_gid, const float4 *__restrict__ records,
                                            const float *__restrict__ bg, float *__restrict__ out_color, float *__restrict__ T_state,
                                            int32_t *__restrict__ last_enc, uint32_t *__restrict__ tile_walk_c, float *__restrict__ ckpt,
                                            float *__restrict__ ckpt_start_c, const UnitLists &units, uint32_t *__restrict__ unit_count,
-                                           const AuxFwdK &ax, const ContribK &cs = ContribK{})
+                                           const AuxFwdK &ax, const ContribK &cs = ContribK{}, const ErrK &er = ErrK{})
 {
     static_assert(!kStats || (Map::kLockStep && !kAux), "the statistics are built for the lock-step colour kernel");
+    static_assert(!kErr || kStats, "the error-weighted total rides on the statistics");
     __shared__ float4 sh_rec[kWave * 3];
 #ifdef GSR_FWD_TRACE
     TraceEnd trace_end{(unsigned long long)wall_clock64(), (int)blockIdx.x};
@@ -417,6 +435,15 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
         P0.T = v2f{t0, t1}; P0.Cr = v2f{r0, r1}; P0.Cg = v2f{g0, g1}; P0.Cb = v2f{b0, b1};
         load_px(2, t0, r0, g0, b0, P1.last0); load_px(3, t1, r1, g1, b1, P1.last1);
         P1.T = v2f{t0, t1}; P1.Cr = v2f{r0, r1}; P1.Cg = v2f{g0, g1}; P1.Cb = v2f{b0, b1};
+    }
+    float e00 = 0.f, e01 = 0.f, e10 = 0.f, e11 = 0.f;      // kErr: the error of the lane's four pixels (P0's two, P1's two)
+    if constexpr (kErr) {
+        auto load_e = [&](int e) {
+            const int px = px0 + map.ex(e), py = py0 + map.ey(e);
+            const float x = (px < f.W && py < f.H) ? er.pixel_error[(size_t)py * f.W + px] : 0.f;
+            return fminf(fmaxf(x, 0.f), 1.f);               // (fmaxf(NaN, 0) = 0)
+        };
+        e00 = load_e(0); e01 = load_e(1); e10 = load_e(2); e11 = load_e(3);
     }
     v2f Z0 = {0.f, 0.f}, Z1 = {0.f, 0.f};                  // kAux: the depth so far of the two pairs
     if constexpr (kAux) {
@@ -475,7 +502,7 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
         __syncthreads();
         uint32_t entry = 0;                                // kStats: the lane's list entry, and its totals over the wave's pixels
         uint32_t st_n = 0;
-        float st_s = 0.f, st_m = 0.f;
+        float st_s = 0.f, st_m = 0.f, st_e = 0.f;
         const unsigned mymask = stage_batch(sh_rec, lane, n, sorted_gid, rng.x + base, records, kStats ? &entry : nullptr);
         __syncthreads();
         // every 8 blended splats (passes, with groups) the live mask is refreshed: quadrants (and tiles) that saturate mid-batch stop there
@@ -494,6 +521,10 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
                         const float sum = wave_sum(((sw0[0] + sw0[1]) + sw1[0]) + sw1[1]);
                         const float top = wave_max(fmaxf(fmaxf(sw0[0], sw0[1]), fmaxf(sw1[0], sw1[1])));
                         if (lane == j) { st_n = cnt; st_s = sum; st_m = top; }      // an entry is blended at most once
+                        if constexpr (kErr) {
+                            const float err = wave_sum(err_dot4(sw0[0], sw0[1], sw1[0], sw1[1], e00, e01, e10, e11));
+                            if (lane == j) st_e = err;
+                        }
                     }
                 }
                 if (++since_refresh == 8) {
@@ -522,6 +553,7 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
                 atomicAdd(cs.count + gid, (unsigned long long)st_n);
                 atomicAdd(cs.sum_q32 + gid, (unsigned long long)(st_s * 4294967296.f));
                 atomicMax(cs.max_bits + gid, __float_as_uint(st_m));
+                if constexpr (kErr) atomicAdd(er.frame_q32 + gid, (unsigned long long)(st_e * 4294967296.f));
             }
         }
     }
@@ -619,12 +651,61 @@ __global__ __launch_bounds__(kWave, 4) void k_render_fwd_contrib(FrameK f, int n
                                            unit_count, AuxFwdK{}, cs);
 }
 
+// the statistics instantiation that also takes the error-weighted total (gsr_forward_render_contrib_error)
+__global__ __launch_bounds__(kWave, 4) void k_render_fwd_contrib_error(FrameK f, int n_tiles, int c, int finalize_all,
+                                                                       const uint2 *__restrict__ ranges_c, uint32_t *__restrict__ open,
+                                                                       const uint32_t *__restrict__ sorted_gid,
+                                                                       const float4 *__restrict__ records, const float *__restrict__ bg,
+                                                                       float *__restrict__ out_color, float *__restrict__ T_state,
+                                                                       int32_t *__restrict__ last_enc, uint32_t *__restrict__ tile_walk_c,
+                                                                       float *__restrict__ ckpt, float *__restrict__ ckpt_start_c,
+                                                                       UnitLists units, uint32_t *__restrict__ unit_count, ContribK cs, ErrK er)
+{
+    render_fwd<QuadrantLanes, false, true, true>(f, c, finalize_all, ranges_c, open, sorted_gid, records, bg, out_color, T_state, last_enc, tile_walk_c, ckpt, ckpt_start_c,
+                                                 units, unit_count, AuxFwdK{}, cs, er);
+}
+
+// Behind a frame's last chunk: fold the frame's error totals into the running sum and the running maximum, and clear them for the next
+// frame.  One thread per Gaussian; no row is touched by two threads.
+__global__ __launch_bounds__(256) void k_contrib_error_fold(long long P, unsigned long long *__restrict__ frame_q32,
+                                                            unsigned long long *__restrict__ sum_q32, float *__restrict__ error_max)
+{
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= P) return;
+    const unsigned long long q = frame_q32[g];
+    sum_q32[g] += q;
+    error_max[g] = fmaxf(error_max[g], (float)((double)q * 0x1p-32));
+    frame_q32[g] = 0ull;
+}
+
+int launch_contrib_error_fold(long long P, uint64_t *frame_q32, uint64_t *sum_q32, float *error_max, bool debug, hipStream_t s)
+{
+    if (P <= 0) return GSR_OK;
+    ProfileScope prof("contrib_error_fold", s);
+    hipLaunchKernelGGL(k_contrib_error_fold, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, P, (unsigned long long *)frame_q32,
+                       (unsigned long long *)sum_q32, error_max);
+    GSR_LAUNCH_CHECK("contrib_error_fold", debug, s);
+    return GSR_OK;
+}
+
 int launch_render_fwd(const FrameK &f, const gsr_camera &cam, int c, bool last_chunk, int sort_result, const GeomWS &gw, const BinningWS &bw,
-                      ImageWS &iw, float *out_color, bool debug, hipStream_t s, bool groups, const AuxWS *aux, const gsr_contrib_stats *stats)
+                      ImageWS &iw, float *out_color, bool debug, hipStream_t s, bool groups, const AuxWS *aux, const gsr_contrib_stats *stats,
+                      const gsr_contrib_error *err)
 {
     const int n_tiles = (f.ty1 - f.ty0) * f.Gx;
     if (n_tiles <= 0) return GSR_OK;
     const size_t Tn = (size_t)f.Gx * f.Gy;
+    if (stats && err) {
+        ProfileScope prof("render_fwd_contrib_error", s);
+        const ContribK cs{(unsigned long long *)stats->count, (unsigned long long *)stats->weight_sum_q32, stats->weight_max_bits};
+        const ErrK er{err->pixel_error, (unsigned long long *)err->error_frame_q32};
+        hipLaunchKernelGGL(k_render_fwd_contrib_error, dim3(n_tiles), dim3(kWave), 0, s, f, n_tiles, c, last_chunk ? 1 : 0,
+                           iw.ranges + (size_t)c * Tn, iw.open, bw.gids[1], gw.records, cam.bg, out_color, iw.T_state,
+                           iw.last_enc, iw.tile_walk + (size_t)c * Tn, bw.ckpt,
+                           c > 0 ? iw.ckpt_start + (size_t)(c - 1) * Tn * kCkptFloats : nullptr, bw.units, iw.unit_count, cs, er);
+        GSR_LAUNCH_CHECK("render_fwd_contrib_error", debug, s);
+        return GSR_OK;
+    }
     if (stats) {
         ProfileScope prof("render_fwd_contrib", s);
         const ContribK cs{(unsigned long long *)stats->count, (unsigned long long *)stats->weight_sum_q32, stats->weight_max_bits};

@@ -39,6 +39,13 @@ without it, bit for bit; with antialiasing the compensated opacity is what gets 
 with a ValueError: a `stats` of another P or device, depth_alpha=True, absgrad=True, tile_rows / ShardedRenderer, and grad mode on
 with an input that requires grad (render under torch.no_grad()).  Off (the default): no extra launch, the same bits.
 
+Extension: GaussianRasterizer(raster_settings, contributions=stats, pixel_error=E) with a contrib.ErrorStats and a float32 error map E
+([H,W] or [1,H,W], read clamped to [0, 1]) also scores every Gaussian by the image error it is responsible for in the frame,
+E_g = sum over the pixels of w E: a fourth total of the same blend kernel, folded behind the frame's last chunk into stats.error_sum_q32
+and stats.error_max (module contrib).  The frame is the plain frame and the three statistics are the statistics
+frame's, bit for bit.  Refused with a ValueError: pixel_error without contributions, contributions that is not an ErrorStats, a map of
+another shape, dtype or device, and everything a statistics frame refuses.  pixel_error=None: a plain statistics frame.
+
 Autograd contract (train.py:106, scene/gaussian_model.py:415-417): gradients for
 (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, None) in that order;
 `means2D.grad[:, :2]` is dL/d(NDC position) with the W/2, H/2 pixel scale folded in, `[:, 2] = 0`.
@@ -173,13 +180,18 @@ def _aux_outputs(fr: "_Frame", capacity: int):
 
 def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                       rs: GaussianRasterizationSettings, tile_rows=None, out_color=None, sh_rest=None, raw=False,
-                      prepare_needs=None, aux=False, contrib=None):
+                      prepare_needs=None, aux=False, contrib=None, pixel_error=None, pixel_error_checked=False):
     """Stage 1 + stage 2 of the native forward.  Returns (color, radii, frame).
     aux=True: the same blend also renders frame.depth and frame.alpha ([1,H,W] each; whole images only).
     contrib (a contrib.ContributionStats of this P and device; whole images, no aux): the blend also adds the frame's per-Gaussian
     statistics into it.  Such a frame runs the two stages as two calls: a stage 2 that stops for want of room in a later chunk has
     already added its earlier chunks, so a frame that can stop that way (several chunks planned, a workspace for fewer than all
     num_rendered instances) first copies the three accumulators, and the re-run starts from the copies.
+    pixel_error (with a contrib.ErrorStats as `contrib`; float32 [H,W] or [1,H,W] on the inputs' device): the blend also adds the
+    frame's error-weighted totals into contrib.error_frame_q32 (copied and put back with the three), and the fold into error_sum_q32
+    and error_max follows the last chunk on the same stream.  pixel_error_checked: the map is what contrib.check_pixel_error
+    returned for this frame and `contrib` (GaussianRasterizer checks before anything runs, once).  A frame that raises leaves
+    contrib.error_frame_q32 as it found it: zero.
     raw=True: the tensors are the parameter store's RAW values (sh = _features_dc, sh_rest = _features_rest,
     opacities = logits, scales = log-scales, rotations = unnormalised) and the activations run in the kernels.
     prepare_needs: which gradients a backward will want (as rasterize_backward_geom's `needs`), when one will follow: the
@@ -194,6 +206,9 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
     if contrib is not None:
         from .contrib import check_inputs
         check_inputs(contrib, (means3D,), "rasterize_forward")
+    if pixel_error is not None and not pixel_error_checked:
+        from .contrib import check_pixel_error
+        pixel_error = check_pixel_error(contrib, pixel_error, int(rs.image_height), int(rs.image_width), device, "rasterize_forward")
     if device.type != "cuda":
         raise RuntimeError("diff_gaussian_rasterization (MI355X build) needs tensors on a HIP device; "
                            "there is no CPU path")
@@ -279,7 +294,10 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
             if binning is not None and capacity <= guess and contrib is None:
                 capacity = R                                   # the guessed workspace covered the first chunk, a later one did not fit
         # a statistics frame that may stop in a later chunk: what the accumulators held before it
-        saved = [t.clone() for t in (contrib.count, contrib.weight_sum_q32, contrib.weight_max)] if contrib is not None and capacity < R else None
+        accumulators = () if contrib is None else (contrib.count, contrib.weight_sum_q32, contrib.weight_max)
+        if pixel_error is not None:
+            accumulators += (contrib.error_frame_q32,)
+        saved = [t.clone() for t in accumulators] if contrib is not None and capacity < R else None
         while not done:
             need = _binning_bytes(capacity, tiles)
             if binning is None or binning.numel() < need:
@@ -289,16 +307,21 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
             try:
                 N.forward_render(fr.desc, fr.cam, fr.gauss, fr.geom_ws, binning, fr.image_ws, plan, color, device,
                                  aux=_aux_outputs(fr, capacity) if aux else None,
-                                 contrib=contrib.native() if contrib is not None else None)
+                                 contrib=contrib.native() if contrib is not None else None,
+                                 err=contrib.native_error(pixel_error) if pixel_error is not None else None)
+                if pixel_error is not None:
+                    contrib.fold()
                 if contrib is not None:
                     contrib.frames += 1
                 break
             except N.GsrError as e:
                 if e.status != N.ERR_WORKSPACE or capacity >= R:
+                    if pixel_error is not None:                # no fold follows: the chunks that ran must not reach the next frame's
+                        contrib.error_frame_q32.zero_()
                     raise
                 capacity, binning = R, None
                 if saved is not None:                          # (behind the chunks that ran, on the same stream)
-                    for t, t0 in zip((contrib.count, contrib.weight_sum_q32, contrib.weight_max), saved):
+                    for t, t0 in zip(accumulators, saved):
                         t.copy_(t0)
         _binning_guess[guess_key] = capacity
         if len(_binning_guess) > 64:
@@ -726,9 +749,11 @@ def _match_getters(means3D, opacities, shs, scales, rotations):
 
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings: GaussianRasterizationSettings, depth_alpha: bool = False, antialiasing: bool = False,
-                 absgrad: bool = False, contributions=None):
+                 absgrad: bool = False, contributions=None, pixel_error=None):
         """contributions (a contrib.ContributionStats, extension): every frame is also added into it (module docstring); the frame has
         no backward; not with depth_alpha or absgrad.
+        pixel_error (float32 [H,W] or [1,H,W], extension; with a contrib.ErrorStats as contributions): every frame also adds its
+        error-weighted totals and folds them into the running sum and maximum (module docstring).
         absgrad=True (gsplat's flag): backward() also assigns means2D.absgrad [P,3] (module docstring); not with depth_alpha.
         depth_alpha=True (extension): forward / forward_raw also return the depth and alpha maps [1,H,W] (module docstring).
         antialiasing=True (upstream's flag): the opacities are compensated for the 0.3 px^2 dilation first (module docstring)."""
@@ -746,12 +771,23 @@ class GaussianRasterizer(nn.Module):
                 raise ValueError(f"contributions must be a ContributionStats, got {type(contributions).__name__}")
             if self.depth_alpha or self.absgrad:
                 raise ValueError(_CONTRIB_PLAIN_ONLY)
+        self.pixel_error = pixel_error
+        if pixel_error is not None:
+            from .contrib import check_error_stats
+            check_error_stats(contributions, "GaussianRasterizer")
 
-    def _contrib_frame(self, *args, **kw):
-        """A statistics frame (its inputs checked by the caller): the native forward itself - no autograd node, nothing can follow
-        it - and the plain call's (color, radii)."""
+    def _checked_error_map(self, rs, device, what):
+        """The frame's error map, checked against the frame (None without one): once per frame, before anything runs."""
+        if self.pixel_error is None:
+            return None
+        from .contrib import check_pixel_error
+        return check_pixel_error(self.contributions, self.pixel_error, int(rs.image_height), int(rs.image_width), device, what)
+
+    def _contrib_frame(self, error_map, *args, **kw):
+        """A statistics frame (its inputs and its error map checked by the caller): the native forward itself - no autograd node,
+        nothing can follow it - and the plain call's (color, radii)."""
         with torch.no_grad():
-            color, radii, _ = rasterize_forward(*args, contrib=self.contributions, **kw)
+            color, radii, _ = rasterize_forward(*args, contrib=self.contributions, pixel_error=error_map, pixel_error_checked=True, **kw)
             if self.raster_settings.debug:
                 torch.cuda.synchronize(radii.device)
         return color, radii
@@ -775,6 +811,7 @@ class GaussianRasterizer(nn.Module):
             from .contrib import check_inputs
             check_inputs(self.contributions, (means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp,
                                               rs.viewmatrix, rs.projmatrix, rs.campos), "GaussianRasterizer.forward")
+            error_map = self._checked_error_map(rs, means3D.device, "GaussianRasterizer.forward")
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -795,7 +832,7 @@ class GaussianRasterizer(nn.Module):
         rs = rs._replace(sh_degree=int(rs.sh_degree), image_height=int(rs.image_height),
                          image_width=int(rs.image_width))
         if self.contributions is not None:
-            return self._contrib_frame(means3D, shs, colors_precomp, opacities, scales, rotations,
+            return self._contrib_frame(error_map, means3D, shs, colors_precomp, opacities, scales, rotations,
                                        cov3D_precomp, rs)
         if FUSE_GETTERS and torch.is_grad_enabled() and not rs.debug and shs.numel() and scales.numel() and rotations.numel():
             leaves = _match_getters(means3D, opacities, shs, scales, rotations)
@@ -817,6 +854,7 @@ class GaussianRasterizer(nn.Module):
             from .contrib import check_inputs
             check_inputs(self.contributions, (xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations,
                                               rs.viewmatrix, rs.projmatrix, rs.campos), "GaussianRasterizer.forward_raw")
+            error_map = self._checked_error_map(rs, xyz.device, "GaussianRasterizer.forward_raw")
         if self.antialiasing:
             from .antialias import compensate_opacity
             opacity_logits = compensate_opacity(opacity_logits, xyz, log_scales, raw_rotations, rs, raw=True)
@@ -824,7 +862,7 @@ class GaussianRasterizer(nn.Module):
         if not packed and (features_rest is None or features_rest.numel() == 0):
             features_rest = torch.empty(0, dtype=torch.float32, device=xyz.device)
         if self.contributions is not None:
-            return self._contrib_frame(xyz, features_dc, None, opacity_logits, log_scales, raw_rotations,
+            return self._contrib_frame(error_map, xyz, features_dc, None, opacity_logits, log_scales, raw_rotations,
                                        None, rs, sh_rest=features_rest, raw=2 if features_rest is None else 1)
         return _apply(_RasterizeGaussiansRaw, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations, rs,
                       self.depth_alpha, *_camera_args(rs), absgrad_to=means2D if self.absgrad else None)

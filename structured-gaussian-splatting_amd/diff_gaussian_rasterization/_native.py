@@ -54,6 +54,11 @@ class ContribStats(C.Structure):
     _fields_ = [("count", C.c_void_p), ("weight_sum_q32", C.c_void_p), ("weight_max_bits", C.c_void_p)]
 
 
+class ContribError(C.Structure):
+    """gsr_contrib_error: the per-pixel error map [H*W] (read only) and the frame's per-Gaussian error totals [P] (64-bit, units of 2^-32)."""
+    _fields_ = [("pixel_error", _f32p), ("error_frame_q32", C.c_void_p)]
+
+
 class CameraGrads(C.Structure):
     """gsr_camera_grads: dL/dviewmatrix [16], dL/dprojmatrix [16], dL/dcampos [3]; any may be NULL."""
     _fields_ = [("viewmatrix", _f32p), ("projmatrix", _f32p), ("campos", _f32p)]
@@ -133,7 +138,8 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_workspace_sizes", "gsr_binning_
            "gsr_bilagrid_workspace_size", "gsr_bilagrid_forward", "gsr_bilagrid_backward", "gsr_bilagrid_tv_forward", "gsr_bilagrid_tv_backward",
            "gsr_vq_workspace_size", "gsr_vq_assign", "gsr_vq_update",
            "gsr_filter3d_workspace_size", "gsr_filter3d_compute", "gsr_filter3d_apply_forward", "gsr_filter3d_apply_backward",
-           "gsr_forward_contrib", "gsr_forward_render_contrib")
+           "gsr_forward_contrib", "gsr_forward_render_contrib",
+           "gsr_forward_contrib_error", "gsr_forward_render_contrib_error", "gsr_contrib_error_fold")
 
 _lib = None
 
@@ -224,8 +230,10 @@ def forward_preprocess(desc, cam: Camera, g: Gaussians, geom_ws, radii, device, 
 
 
 def forward_both(desc, cam: Camera, g: Gaussians, geom_ws, image_ws, radii, binning_ws, binning_capacity, out_color, device,
-                 early_fill: Optional[Grads] = None, aux: Optional[AuxOutputs] = None, contrib: Optional[ContribStats] = None):
-    """gsr_forward (gsr_forward_aux with `aux`, gsr_forward_contrib with `contrib`; not both): both stages in one call.  Returns
+                 early_fill: Optional[Grads] = None, aux: Optional[AuxOutputs] = None, contrib: Optional[ContribStats] = None,
+                 err: Optional[ContribError] = None):
+    """gsr_forward (gsr_forward_aux with `aux`, gsr_forward_contrib with `contrib`; not both; gsr_forward_contrib_error with `contrib`
+    and `err`): both stages in one call.  Returns
     (plan, done): done = False when the binning workspace was too small for the first chunk (nothing of stage 2 ran: allocate and
     call forward_render) - or, when the plan has more than one chunk, for a later one: a statistics frame has then already added
     its earlier chunks (include/gsrast.h), so its caller sizes the workspace for num_rendered."""
@@ -234,7 +242,11 @@ def forward_both(desc, cam: Camera, g: Gaussians, geom_ws, image_ws, radii, binn
             _ptr(binning_ws), C.c_int64(int(binning_capacity)), _ptr(out_color), None if early_fill is None else C.byref(early_fill))
     if aux is not None and contrib is not None:
         raise ValueError("forward_both: aux and contrib together (that kernel is not built)")
-    if contrib is not None:
+    if err is not None:
+        if contrib is None:
+            raise ValueError("forward_both: err without contrib")
+        rc = load().gsr_forward_contrib_error(*args, C.byref(contrib), C.byref(err), _stream(device))
+    elif contrib is not None:
         rc = load().gsr_forward_contrib(*args, C.byref(contrib), _stream(device))
     elif aux is None:
         rc = load().gsr_forward(*args, _stream(device))
@@ -247,16 +259,27 @@ def forward_both(desc, cam: Camera, g: Gaussians, geom_ws, image_ws, radii, binn
 
 
 def forward_render(desc, cam: Camera, g: Gaussians, geom_ws, binning_ws, image_ws, plan: FramePlan, out_color, device,
-                   aux: Optional[AuxOutputs] = None, contrib: Optional[ContribStats] = None):
+                   aux: Optional[AuxOutputs] = None, contrib: Optional[ContribStats] = None, err: Optional[ContribError] = None):
     args = (C.byref(desc), C.byref(cam), C.byref(g), _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws), C.byref(plan), _ptr(out_color))
     if aux is not None and contrib is not None:
         raise ValueError("forward_render: aux and contrib together (that kernel is not built)")
-    if contrib is not None:
+    if err is not None:
+        if contrib is None:
+            raise ValueError("forward_render: err without contrib")
+        _check(load().gsr_forward_render_contrib_error(*args, C.byref(contrib), C.byref(err), _stream(device)),
+               "gsr_forward_render_contrib_error")
+    elif contrib is not None:
         _check(load().gsr_forward_render_contrib(*args, C.byref(contrib), _stream(device)), "gsr_forward_render_contrib")
     elif aux is None:
         _check(load().gsr_forward_render(*args, _stream(device)), "gsr_forward_render")
     else:
         _check(load().gsr_forward_render_aux(*args, C.byref(aux), _stream(device)), "gsr_forward_render_aux")
+
+
+def contrib_error_fold(error_frame_q32, error_sum_q32, error_max, device):
+    """gsr_contrib_error_fold on the device's current stream: the frame's error totals into the running sum and maximum, then cleared."""
+    _check(load().gsr_contrib_error_fold(C.c_int64(int(error_frame_q32.shape[0])), _ptr(error_frame_q32), _ptr(error_sum_q32),
+                                         _ptr(error_max), _stream(device)), "gsr_contrib_error_fold")
 
 
 def aux_workspace_size(desc: FrameDesc, binning_capacity: int) -> int:

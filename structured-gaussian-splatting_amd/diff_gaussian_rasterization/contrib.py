@@ -17,7 +17,18 @@ tiles, depth chunks or frames arrive: the same frames give the same bits.
 The fixed-point sum holds 2^32 units of weight per Gaussian (a full-screen opaque splat over about 2 000 views at 1920x1080)
 before it wraps; every (tile, Gaussian) total is truncated below 2^-32.
 
-Statistics frames are rendered without a backward: under torch.no_grad(), or from inputs none of which requires grad."""
+Statistics frames are rendered without a backward: under torch.no_grad(), or from inputs none of which requires grad.
+
+Error-weighted statistics.  An ErrorStats is a ContributionStats that also scores every Gaussian by the image
+error it is responsible for: with a per-pixel error map E in [0, 1] (l1_error_map), E_g = sum over the pixels of w_g E per view.
+GaussianRasterizer(settings, contributions=stats, pixel_error=E) takes the fourth total in the same blend kernel and folds the frame
+behind its last chunk:
+
+    error_frame_q32 int64   [P]   the running frame's E_g, in units of 2^-32; zero between frames (also behind a frame that raised)
+    error_sum_q32   int64   [P]   the sum of E_g over the frames (error_sum: the same as float64) - Taming-3DGS's score
+    error_max       float32 [P]   the largest single frame's E_g - the score of "Revising Densification in Gaussian Splatting"
+
+E is read clamped to [0, 1] (a NaN as 0).  A frame without pixel_error leaves the three error tensors alone."""
 from __future__ import annotations
 
 import torch
@@ -56,6 +67,67 @@ class ContributionStats:
 
     def __repr__(self):
         return f"ContributionStats(P={self.P}, device={self.device}, frames={self.frames})"
+
+
+class ErrorStats(ContributionStats):
+    def __init__(self, P: int, device):
+        super().__init__(P, device)
+        self.error_frame_q32 = torch.zeros(self.P, dtype=torch.int64, device=self.device)
+        self.error_sum_q32 = torch.zeros(self.P, dtype=torch.int64, device=self.device)
+        self.error_max = torch.zeros(self.P, dtype=torch.float32, device=self.device)
+
+    @property
+    def error_sum(self) -> torch.Tensor:
+        """float64 [P]: exact, as weight_sum."""
+        return self.error_sum_q32.double() * Q32
+
+    def reset(self) -> None:
+        super().reset()
+        self.error_frame_q32.zero_()
+        self.error_sum_q32.zero_()
+        self.error_max.zero_()
+
+    def native_error(self, pixel_error: torch.Tensor) -> N.ContribError:
+        """The gsr_contrib_error of a checked map (check_pixel_error) and this object's frame accumulator."""
+        return N.ContribError(N._ptr(pixel_error), N._ptr(self.error_frame_q32))
+
+    def fold(self) -> None:
+        """Close a frame on the current stream: error_sum_q32 += error_frame_q32, error_max = max(., its float), error_frame_q32 = 0."""
+        with torch.cuda.device(self.device):
+            N.contrib_error_fold(self.error_frame_q32, self.error_sum_q32, self.error_max, self.device)
+
+    def __repr__(self):
+        return f"ErrorStats(P={self.P}, device={self.device}, frames={self.frames})"
+
+
+def l1_error_map(image: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """[H,W]: the per-pixel error map of an image against its target ([C,H,W] each) - the mean absolute difference over the channels,
+    clamped to [0, 1].  Plain torch ops on detached values: the map is a weight, never differentiated."""
+    with torch.no_grad():
+        return (image.detach() - target.detach()).abs().mean(0).clamp(0, 1)
+
+
+def check_error_stats(stats, what: str) -> None:
+    """What a pixel_error asks of `contributions`: that there is one, and that it is an ErrorStats."""
+    if stats is None:
+        raise ValueError(f"{what}: pixel_error without contributions: the error-weighted total is taken beside the blend statistics "
+                         f"(pass an ErrorStats as contributions)")
+    if not isinstance(stats, ErrorStats):
+        raise ValueError(f"{what}: pixel_error needs contributions to be an ErrorStats, got {type(stats).__name__}")
+
+
+def check_pixel_error(stats, pixel_error, height: int, width: int, device, what: str) -> torch.Tensor:
+    """The refusals of an error frame that need no device -> the map as a contiguous [H,W] tensor."""
+    check_error_stats(stats, what)
+    if not isinstance(pixel_error, torch.Tensor):
+        raise ValueError(f"{what}: pixel_error must be a tensor, got {type(pixel_error).__name__}")
+    if pixel_error.dtype != torch.float32:
+        raise ValueError(f"{what}: pixel_error must be float32, got {pixel_error.dtype}")
+    if tuple(pixel_error.shape) not in ((height, width), (1, height, width)):
+        raise ValueError(f"{what}: pixel_error has shape {tuple(pixel_error.shape)}, the frame wants [{height}, {width}] or [1, {height}, {width}]")
+    if pixel_error.device != torch.device(device):
+        raise ValueError(f"{what}: pixel_error lives on {pixel_error.device}, the inputs on {device}")
+    return pixel_error.detach().reshape(height, width).contiguous()
 
 
 def check_inputs(stats: "ContributionStats", tensors, what: str) -> None:

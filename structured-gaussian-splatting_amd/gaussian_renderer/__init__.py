@@ -27,6 +27,9 @@ whatever `pipe.fused_activations` says: fusing the activations into the kernels 
 frame does not have, and the two paths round the activations differently in the last bit - so the statistics are the model's and
 the camera's, the same bits under either setting of that switch (the image is the one the getter path renders).  The rasterizer
 itself takes `contributions` on forward and forward_raw alike.  Not together with depth_alpha=True or pipe.absgrad (ValueError).
+
+`pixel_error` (float32 [H,W] or [1,H,W]; None: off; with a contrib.ErrorStats as `contributions`): the frame also adds every
+Gaussian's error-weighted blend total into the ErrorStats and folds it (diff_gaussian_rasterization, "pixel_error"); passed through.
 """
 import math
 
@@ -74,18 +77,19 @@ def _zero_points(like: torch.Tensor) -> torch.Tensor:
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, depth_alpha=False,
-           contributions=None):
+           contributions=None, pixel_error=None):
     """Render the scene.  Background tensor (bg_color) must be on the GPU.
     depth_alpha=True (extension): the dict also holds "depth" and "alpha" [1,H,W], differentiable (diff_gaussian_rasterization).
     contributions (extension): a ContributionStats the frame's blend statistics are added into; rendered under torch.no_grad(),
-    through the getters whatever pipe.fused_activations says (module docstring)."""
+    through the getters whatever pipe.fused_activations says (module docstring).
+    pixel_error (extension; with an ErrorStats as contributions): the error map of this view, passed to the rasterizer."""
     if contributions is not None:
         with torch.no_grad():
-            return _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, depth_alpha, contributions)
-    return _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, depth_alpha, None)
+            return _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, depth_alpha, contributions, pixel_error)
+    return _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, depth_alpha, None, pixel_error)
 
 
-def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, depth_alpha, contributions):
+def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, depth_alpha, contributions, pixel_error=None):
     xyz = pc.get_xyz
     # (the reference builds this as zeros_like(...) + 0 and retain_grad()s the non-leaf result; a leaf with requires_grad keeps
     # its .grad by itself.  Its VALUES are never read, by the rasterizer or by the training loop, only its .grad: every frame
@@ -100,7 +104,7 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
         campos=viewpoint_camera.camera_center, prefiltered=False, debug=pipe.debug)
     rasterizer = GaussianRasterizer(raster_settings=raster_settings, depth_alpha=depth_alpha,
                                     antialiasing=getattr(pipe, "antialiasing", False), absgrad=getattr(pipe, "absgrad", False),
-                                    contributions=contributions)
+                                    contributions=contributions, pixel_error=pixel_error)
 
     def result(out):
         d = {"render": out[0], "viewspace_points": screenspace_points, "visibility_filter": out[1] > 0, "radii": out[1]}

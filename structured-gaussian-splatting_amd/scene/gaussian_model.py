@@ -84,6 +84,9 @@ class OptimizationDefaults:
     significance_prune_fraction: float = 0.6      # the fraction of the Gaussians the first listed iteration removes (LightGaussian's 60 %)
     significance_prune_decay: float = 0.6         # the k-th removes fraction * decay ** k
     significance_prune_score: str = "volume_weighted"     # GaussianModel.significance's `score`
+    densify_error_views: int = 0                  # > 0: refine by image error, scored over that many sampled cameras (train_loop.train); untuned
+    densify_error_growth: float = 0.05            # the budget of a refinement: ceil(growth * P) Gaussians are cloned or split; untuned
+    densify_error_score: str = "max"              # "max": the largest single view's error (Revising Densification); "sum": over the views (Taming-3DGS)
 
 
 def expon_lr(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1_000_000):
@@ -389,6 +392,12 @@ class GaussianModel:
         grads[grads.isnan()] = 0.0
         big = torch.max(self.get_scaling.detach(), dim=1).values > self.percent_dense * extent
         hot = torch.norm(grads, dim=-1) >= max_grad
+        self._densify_hot_and_prune(hot, big, min_opacity, extent, max_screen_size)
+
+    def _densify_hot_and_prune(self, hot, big, min_opacity, extent, max_screen_size):
+        """Clone the small and split the large Gaussians of the mask `hot` [P], then prune (densify_and_prune's body, whatever chose
+        `hot`)."""
+        n_before = hot.shape[0]
         # clone: small Gaussians with a large view-space gradient are duplicated in place
         sel = hot & ~big
         self._rebuild(extra={k: self._t[k].detach()[sel] for k in TABLE})
@@ -397,7 +406,7 @@ class GaussianModel:
         # split: large ones are replaced by N = 2 samples from themselves, 1.6x smaller
         N = 2
         sel = torch.zeros(n_after_clone, dtype=torch.bool, device=self.device)
-        sel[:grads.shape[0]] = hot & big
+        sel[:n_before] = hot & big
         scale_sel = self.get_scaling.detach()[sel].repeat(N, 1)
         offs = torch.normal(mean=torch.zeros_like(scale_sel), std=scale_sel)
         R = quat_to_rotmat(self._rotation.detach()[sel]).repeat(N, 1, 1)
@@ -412,6 +421,56 @@ class GaussianModel:
         if max_screen_size:
             drop = drop | (self.max_radii2D > max_screen_size) | (self.get_scaling.detach().max(dim=1).values > 0.1 * extent)
         self.prune_points(drop)
+
+    # ---- error-based densification (diff_gaussian_rasterization/contrib.py) ----------------------------
+    DENSIFY_ERROR_SCORES = ("max", "sum")
+
+    def error_stats(self, cameras, targets, pipe=None, bg=None, views=None, correct=None):
+        """The error-weighted blend statistics of this model (an ErrorStats): per chosen camera, under torch.no_grad(), a plain render,
+        E = l1_error_map(image, target), and a statistics frame with pixel_error=E.  views: the indices of the cameras to use (None:
+        all).  correct(image, idx): what stands between render() and the loss in training (a bilateral grid), applied to the image
+        before it is compared.  pipe: default Pipe(); bg: default black."""
+        from diff_gaussian_rasterization.contrib import ErrorStats, l1_error_map
+        from gaussian_renderer import render
+        if len(cameras) != len(targets):
+            raise ValueError(f"error_stats: {len(cameras)} cameras, {len(targets)} targets")
+        if pipe is None:
+            from gaussian_params import Pipe
+            pipe = Pipe()
+        if bg is None:
+            bg = torch.zeros(3, device=self.device)
+        views = range(len(cameras)) if views is None else [int(i) for i in views]
+        stats = ErrorStats(self._xyz.shape[0], self.device)
+        absgrad = getattr(pipe, "absgrad", False)            # (as contribution_stats: these frames have no backward)
+        if absgrad:
+            pipe.absgrad = False
+        try:
+            with torch.no_grad():
+                for idx in views:
+                    image = render(cameras[idx], self, pipe, bg)["render"]
+                    if correct is not None:
+                        image = correct(image, idx)
+                    render(cameras[idx], self, pipe, bg, contributions=stats, pixel_error=l1_error_map(image, targets[idx]))
+        finally:
+            if absgrad:
+                pipe.absgrad = absgrad
+        return stats
+
+    def densify_and_prune_by_score(self, scores, count, min_opacity, extent, max_screen_size):
+        """densify_and_prune with a budget: the `count` Gaussians of the highest positive score are cloned (small) or split (large),
+        then the prune runs as there.  Ties go to the lower index (a stable descending sort: deterministic); a score of 0 (or less) is
+        never selected, so fewer than `count` may be."""
+        P = self._xyz.shape[0]
+        scores = torch.as_tensor(scores).reshape(-1)
+        if scores.shape[0] != P:
+            raise ValueError(f"densify_and_prune_by_score: {scores.shape[0]} scores for {P} Gaussians")
+        scores = scores.to(self.device)
+        scores = torch.where(scores > 0, scores, torch.zeros_like(scores))        # (a NaN would sort in front of every number)
+        n = min(max(int(count), 0), int((scores > 0).sum()))
+        hot = torch.zeros(P, dtype=torch.bool, device=self.device)
+        hot[torch.sort(scores, stable=True, descending=True).indices[:n]] = True
+        big = torch.max(self.get_scaling.detach(), dim=1).values > self.percent_dense * extent
+        self._densify_hot_and_prune(hot, big, min_opacity, extent, max_screen_size)
 
     # ---- significance pruning (diff_gaussian_rasterization/contrib.py, DESIGN section 21) ---------------------------------
     SIGNIFICANCE_SCORES = ("weight_sum", "weight_max", "volume_weighted")

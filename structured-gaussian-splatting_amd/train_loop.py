@@ -7,7 +7,13 @@ opt.filter_3d keeps the model's 3D smoothing filter current:
 every edit that changes or moves the Gaussians, and every 100 iterations after densification; off, the loop is as before.
 opt.significance_prune_iterations lists iterations at which the model is pruned by significance: behind the
 optimizer step, the blend statistics of all `cameras` are collected and the least significant fraction removed; empty (the default),
-the loop is as before."""
+the loop is as before.
+opt.densify_error_views > 0 replaces the refinement's criterion: at a refinement iteration that many cameras are
+drawn, the model's error-weighted blend statistics are taken over them (GaussianModel.error_stats; with opt.bilateral_grid the image is
+corrected by the camera's grid first), and the ceil(opt.densify_error_growth * P) Gaussians responsible for the most image error
+(opt.densify_error_score: "max" over the views, or "sum") are cloned or split in place of those over the gradient threshold; the
+prune is unchanged.  0 (the default): the loop is as before.  The defaults of the two numbers are not tuned on captured scenes."""
+import math
 import random
 
 import torch
@@ -40,6 +46,15 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
     if prune_at and mcmc:
         raise ValueError("significance_prune_iterations with densify_strategy = \"mcmc\": the MCMC strategy keeps its tables at a fixed "
                          "size (relocation and growth to a cap), pruning by significance shrinks them")
+    error_views = int(getattr(opt, "densify_error_views", 0))
+    if error_views > 0:
+        if mcmc:
+            raise ValueError("densify_error_views with densify_strategy = \"mcmc\": the MCMC strategy has its own relocation and growth rule")
+        if getattr(opt, "densify_absgrad", False):
+            raise ValueError("densify_error_views with densify_absgrad: the error score replaces the gradient criterion that absgrad feeds")
+        if opt.densify_error_score not in gaussians.DENSIFY_ERROR_SCORES:
+            raise ValueError(f"densify_error_score = {opt.densify_error_score!r}: one of "
+                             f"{', '.join(repr(n) for n in gaussians.DENSIFY_ERROR_SCORES)}")
     if filter_3d:
         gaussians.compute_3D_filter(cameras)
     for it in range(first_iter, iterations + 1):
@@ -67,7 +82,14 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
                 gaussians.update_densification_stats(vsp, radii)       # train.py:127-130, one native pass
                 if it > opt.densify_from_iter and it % opt.densification_interval == 0:
                     size_threshold = 20 if it > opt.opacity_reset_interval else None
-                    gaussians.densify_and_prune(opt.densify_grad_threshold, 0.005, scene_extent, size_threshold)
+                    if error_views > 0:
+                        views = random.sample(range(len(cameras)), min(error_views, len(cameras)))
+                        stats = gaussians.error_stats(cameras, targets, pipe, bg, views=views, correct=bilagrid if use_bilagrid else None)
+                        scores = stats.error_max if opt.densify_error_score == "max" else stats.error_sum
+                        gaussians.densify_and_prune_by_score(scores, math.ceil(opt.densify_error_growth * gaussians.get_xyz.shape[0]),
+                                                             0.005, scene_extent, size_threshold)
+                    else:
+                        gaussians.densify_and_prune(opt.densify_grad_threshold, 0.005, scene_extent, size_threshold)
                     if filter_3d:
                         gaussians.compute_3D_filter(cameras)
                 if it % opt.opacity_reset_interval == 0 or (white_background and it == opt.densify_from_iter):
