@@ -518,32 +518,77 @@ __global__ __launch_bounds__(kBinBlock) void k_bin_chunk(FrameK f, int c, int r0
 // scan_n > 0 (chunks of up to kRankScanMax Gaussians): the same block first scans the chunk's per-rank counts (offs_open, the chunk's
 // emitted total and the next chunk's base), which saves the launch of a one-block scan in front of this one.
 constexpr int kRankScanMax = 16384;
+// Both scans of the kernel run in rounds of 1024 kTrPer = 8192 elements (a 1920x1080 frame has 8160 tiles): global memory is read and
+// written COALESCED (thread t holds elements t, t + 1024, ...: with consecutive elements per thread every load and store of a wave
+// touched 64 cache lines, and the one CU's address path, not the scan, was the kernel's time), the block scan wants consecutive
+// elements per thread, and a padded LDS array (one spare word per kTrPer: conflict-free both ways) turns one layout into the other.
+constexpr int kTrPer = 8, kTrRound = 1024 * kTrPer;
+__device__ __forceinline__ int tr_pad(int i) { return i + i / kTrPer; }
+// cv[k]: element k * 1024 + threadIdx.x of the round (0 beyond its end) -> ex[k]: carry + the sum of the round's elements in front of
+// it; total: the round's sum.  (its first barrier: every read of buf and sh_wave by the previous round is behind it)
+__device__ __forceinline__ void tr_round_scan(const uint32_t (&cv)[kTrPer], uint32_t (&ex)[kTrPer], uint32_t carry, uint32_t &total,
+                                              uint32_t *buf, uint32_t *sh_wave)
+{
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kTrPer; ++k) buf[tr_pad(k * 1024 + (int)threadIdx.x)] = cv[k];
+    __syncthreads();
+    uint32_t v[kTrPer], mine = 0;
+#pragma unroll
+    for (int k = 0; k < kTrPer; ++k) { v[k] = buf[tr_pad((int)threadIdx.x * kTrPer + k)]; mine += v[k]; }
+    uint32_t run = carry + block_incl_scan<16>(mine, sh_wave, total) - mine;
+#pragma unroll
+    for (int k = 0; k < kTrPer; ++k) { buf[tr_pad((int)threadIdx.x * kTrPer + k)] = run; run += v[k]; }      // (the thread's own words)
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kTrPer; ++k) ex[k] = buf[tr_pad(k * 1024 + (int)threadIdx.x)];
+}
+
 __global__ __launch_bounds__(1024) void k_tile_ranges(FrameK f, int c, Ctrl *__restrict__ ctrl, uint32_t *__restrict__ tile_cnt,
                                                       uint2 *__restrict__ ranges_c, int scan_n, const uint32_t *__restrict__ cnt_open,
                                                       uint32_t *__restrict__ offs_open)
 {
     __shared__ uint32_t sh_wave[16];
+    __shared__ uint32_t buf[kTrRound + kTrRound / kTrPer];
     const int t_begin = f.ty0 * f.Gx, t_end = f.ty1 * f.Gx;
+    // every load of the two scans' first rounds is issued here, ahead of the first barrier: the block waits for memory once
+    const uint32_t base = ctrl->chunk_base[c];                   // (thread 0 stores chunk_base[c + 1] below: another word)
+    uint32_t cr[kTrPer], ct[kTrPer], ex[kTrPer];
+#pragma unroll
+    for (int k = 0; k < kTrPer; ++k) { const int r = k * 1024 + (int)threadIdx.x; cr[k] = r < scan_n ? cnt_open[r] : 0u; }
+#pragma unroll
+    for (int k = 0; k < kTrPer; ++k) { const int t = t_begin + k * 1024 + (int)threadIdx.x; ct[k] = t < t_end ? tile_cnt[t] : 0u; }
     if (scan_n > 0) {
-        constexpr int kPer = kRankScanMax / 1024;                // 16 consecutive ranks per thread
-        uint32_t v[kPer], mine = 0;
+        uint32_t done = 0;
+        for (int q0 = 0; q0 < scan_n; q0 += kTrRound) {
+            uint32_t total;
+            if (q0) {
 #pragma unroll
-        for (int i = 0; i < kPer; ++i) { const int r = (int)threadIdx.x * kPer + i; v[i] = r < scan_n ? cnt_open[r] : 0u; mine += v[i]; }
-        uint32_t total;
-        uint32_t run = block_incl_scan<16>(mine, sh_wave, total) - mine;
+                for (int k = 0; k < kTrPer; ++k) { const int r = q0 + k * 1024 + (int)threadIdx.x; cr[k] = r < scan_n ? cnt_open[r] : 0u; }
+            }
+            tr_round_scan(cr, ex, done, total, buf, sh_wave);
 #pragma unroll
-        for (int i = 0; i < kPer; ++i) { const int r = (int)threadIdx.x * kPer + i; run += v[i]; if (r < scan_n) offs_open[r] = run; }
-        if (threadIdx.x == 0) { ctrl->chunk_R[c] = total; ctrl->chunk_base[c + 1] = ctrl->chunk_base[c] + total; }
+            for (int k = 0; k < kTrPer; ++k) { const int r = q0 + k * 1024 + (int)threadIdx.x; if (r < scan_n) offs_open[r] = ex[k] + cr[k]; }
+            done += total;
+        }
+        if (threadIdx.x == 0) { ctrl->chunk_R[c] = done; ctrl->chunk_base[c + 1] = base + done; }
     }
-    uint32_t carry = ctrl->chunk_base[c];
-    for (int t0 = t_begin; t0 < t_end; t0 += 1024) {
-        const int t = t0 + (int)threadIdx.x;
-        const uint32_t v = t < t_end ? tile_cnt[t] : 0u;
-        if (v) tile_cnt[t] = 0u;                               // ready for the next chunk / frame
+    uint32_t carry = base;
+    for (int t0 = t_begin; t0 < t_end; t0 += kTrRound) {
         uint32_t wtot;
-        __syncthreads();                                       // sh_wave: the rank scan above, then the previous round, read it
-        const uint32_t inc = block_incl_scan<16>(v, sh_wave, wtot);
-        if (v) { const uint32_t b = carry + inc - v; ranges_c[t] = make_uint2(b, b + v); }
+        if (t0 != t_begin) {
+#pragma unroll
+            for (int k = 0; k < kTrPer; ++k) { const int t = t0 + k * 1024 + (int)threadIdx.x; ct[k] = t < t_end ? tile_cnt[t] : 0u; }
+        }
+        tr_round_scan(ct, ex, carry, wtot, buf, sh_wave);
+#pragma unroll
+        for (int k = 0; k < kTrPer; ++k) {
+            const int t = t0 + k * 1024 + (int)threadIdx.x;
+            if (ct[k]) {
+                tile_cnt[t] = 0u;                              // ready for the next chunk / frame
+                ranges_c[t] = make_uint2(ex[k], ex[k] + ct[k]);
+            }
+        }
         carry += wtot;
     }
 }

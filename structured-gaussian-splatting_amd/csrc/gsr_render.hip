@@ -1082,7 +1082,7 @@ __global__ __launch_bounds__(kRedBlock) void k_reduce_rows(int r_begin, int n_ra
                                                            const uint32_t *__restrict__ row_begin,
                                                            const uint8_t *__restrict__ row_valid,
                                                            const float4 *__restrict__ grad_rows, float4 *__restrict__ screen,
-                                                           int write_empty)
+                                                           int write_empty, int plain)
 {
     const int sub = threadIdx.x & (kRedGroup - 1);
     const int r = r_begin + (blockIdx.x * kRedBlock + threadIdx.x) / kRedGroup;
@@ -1091,7 +1091,55 @@ __global__ __launch_bounds__(kRedBlock) void k_reduce_rows(int r_begin, int n_ra
     const uint32_t cnt = live ? cnt_open[r] : 0u, begin = live ? row_begin[r] : 0u, g = live ? order[r] : 0u;
     float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
     float a8 = 0.f, a9 = 0.f, a10 = 0.f, a11 = 0.f;
-    if (cnt) {
+    bool batched = false;
+    if constexpr (kRedGroup >= 64) batched = !plain;
+    if (cnt && batched) {
+        // Wide groups, kRedBatch trips of a lane at a time: the rows of the batch's valid trips are loaded together, and with them
+        // the valid bytes of the NEXT batch (clamped to the lane's last row, masked after), then the rows are added in ascending
+        // row order - the adds of the plain loop below in its order, so the same bits, with ceil(trips / kRedBatch) + 1 dependent
+        // round trips on a lane's chain instead of 2 trips
+        constexpr int kRedBatch = 8;
+        const size_t end = (size_t)begin + cnt, first = (size_t)begin + (size_t)sub;
+        uint32_t ok[kRedBatch], nx[kRedBatch];
+        if (first < end) {
+#pragma unroll
+            for (int u = 0; u < kRedBatch; ++u) {
+                const size_t su = first + (size_t)(u * kRedGroup);
+                ok[u] = row_valid[su < end ? su : first];
+                if (su >= end) ok[u] = 0u;
+            }
+        }
+        for (size_t sl = first; sl < end; sl += kRedBatch * kRedGroup) {
+            float4 r0[kRedBatch], r1[kRedBatch], r2[kRedBatch];
+            const size_t sn = sl + kRedBatch * kRedGroup;
+#pragma unroll
+            for (int u = 0; u < kRedBatch; ++u) {
+                const size_t su = sn + (size_t)(u * kRedGroup);
+                nx[u] = row_valid[su < end ? su : sl];
+                if (su >= end) nx[u] = 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < kRedBatch; ++u) {
+                const size_t su = sl + (size_t)(u * kRedGroup);
+                if (ok[u]) {
+                    r0[u] = grad_rows[3 * su]; r1[u] = grad_rows[3 * su + 1];
+                    if constexpr (kAux || kAbs) r2[u] = grad_rows[3 * su + 2];
+                    else r2[u].x = grad_rows[3 * su + 2].x;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kRedBatch; ++u) {
+                if (ok[u]) {
+                    a0.x += r0[u].x; a0.y += r0[u].y; a0.z += r0[u].z; a0.w += r0[u].w;
+                    a1.x += r1[u].x; a1.y += r1[u].y; a1.z += r1[u].z; a1.w += r1[u].w;
+                    a8 += r2[u].x;
+                    if constexpr (kAux) a9 += r2[u].y;
+                    if constexpr (kAbs) { a10 += r2[u].z; a11 += r2[u].w; }
+                }
+                ok[u] = nx[u];
+            }
+        }
+    } else if (cnt) {
         for (uint32_t sl = begin + sub; sl < begin + cnt; sl += kRedGroup) {
             // a clear valid byte: nobody walked that far into the tile's list, or no pixel accepted the splat — the row was never
             // written.  Wide groups (big splats: most rows of a saturating frame are invalid) test the byte first; narrow ones (small
@@ -1142,6 +1190,7 @@ int launch_reduce_rows(const FrameK &f, const gsr_frame_plan &plan, const GeomWS
     ProfileScope prof(aux ? "reduce_rows_aux" : abs ? "reduce_rows_abs" : "reduce_rows", s);
     if (prezeroed == 0) GSR_HIP_CHECK(hipMemsetAsync(screen_grads, 0, (size_t)f.P * kRowFloats * sizeof(float), s));
     const int write_empty = prezeroed == 2 ? 1 : 0;
+    const int plain = getenv("GSR_REDUCE_ROWS_PLAIN") ? 1 : 0;                   // test hook (tests set it per case): the wide groups' one-trip-at-a-time loop
     const int chunks = (plan.num_rendered > 0 && plan.chunks_run > 0) ? plan.chunks_run : 0;
     for (int c = 0; c < chunks && c < GSR_MAX_CHUNKS; ++c) {
         const int r0 = plan.chunk_rank_begin[c], r1 = plan.chunk_rank_begin[c + 1];
@@ -1155,7 +1204,7 @@ int launch_reduce_rows(const FrameK &f, const gsr_frame_plan &plan, const GeomWS
         hipLaunchKernelGGL((aux ? (wide ? k_reduce_rows<64, true> : k_reduce_rows<8, true>)
                                 : abs ? (wide ? k_reduce_rows<64, false, true> : k_reduce_rows<8, false, true>)
                                       : (wide ? k_reduce_rows<64> : k_reduce_rows<8>)), grid, dim3(kRedBlock), 0, s, r0, r1, gw.order, gw.cnt_open, gw.row_begin,
-                           bw.row_valid, reinterpret_cast<const float4 *>(bw.grad_rows), reinterpret_cast<float4 *>(screen_grads), write_empty);
+                           bw.row_valid, reinterpret_cast<const float4 *>(bw.grad_rows), reinterpret_cast<float4 *>(screen_grads), write_empty, plain);
     }
     GSR_LAUNCH_CHECK("reduce_rows", debug, s);
     return GSR_OK;

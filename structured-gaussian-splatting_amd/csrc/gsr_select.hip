@@ -12,8 +12,8 @@
 //   2. a stable partition by chunk (one pass: 8-way, so per-wave ballots instead of digit histograms) puts chunk c's
 //      Gaussians at order[bnd[c] .. bnd[c+1]) in index order;
 //   3. a chunk is sorted by (depth, index) only when it is about to be binned: its keys are gathered relative to the
-//      chunk's lowest key and sorted in LDS by one block (chunks up to 16 K Gaussians: the nearest chunk of a
-//      saturating frame) or by the library's radix sort on the bits that actually vary inside the chunk.
+//      chunk's lowest key and ranked against one another by a grid of blocks (chunks up to 16 K Gaussians: the nearest
+//      chunk of a saturating frame) or sorted by the library's radix sort on the bits that actually vary inside the chunk.
 // Equal keys always share a chunk and keep index order inside it, so the (depth, index) order of the binned prefix
 // is exactly the stable full sort's; the image does not depend on where chunks end.
 #include "gsr_internal.h"
@@ -21,6 +21,7 @@
 namespace gsr {
 
 constexpr int kSelThreads = 512;
+constexpr int kSmallSortMax = 16384;                          // chunks of up to this many Gaussians are ordered by one launch (3. below)
 constexpr int kSelHistBlocks = 256;
 constexpr int kSelWaves = kSelThreads / kWave;
 
@@ -283,16 +284,22 @@ __host__ __device__ __forceinline__ uint32_t sel_key_base(uint32_t prev_end, boo
 __global__ __launch_bounds__(kSelThreads) void k_part_scatter(int P, const uint32_t *__restrict__ keys, const uint2 *__restrict__ tiles_mass,
                                                               const Ctrl *__restrict__ ctrl, const SelState *__restrict__ st,
                                                               uint32_t *__restrict__ order, uint32_t *__restrict__ pos_key,
-                                                              uint32_t *__restrict__ pos_tiles, uint4 *__restrict__ clear16, int clear16_n)
+                                                              uint32_t *__restrict__ pos_tiles, uint32_t *__restrict__ pos_gid,
+                                                              uint4 *__restrict__ clear16, int clear16_n)
 {
     // on the side: the frame's per-chunk tile ranges and per-tile counters start at zero (no memset launch of their own)
     for (int z = (int)(blockIdx.x * kSelThreads + threadIdx.x); z < clear16_n; z += (int)gridDim.x * kSelThreads)
         clear16[z] = make_uint4(0u, 0u, 0u, 0u);
     __shared__ uint32_t ends[GSR_MAX_CHUNKS];
+    __shared__ bool small[GSR_MAX_CHUNKS];
     __shared__ __align__(16) PartitionLds<GSR_MAX_CHUNKS, kSelWaves> sh;      // way k = chunk k
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int n = (int)ctrl->num_chunks;
-    if (threadIdx.x < GSR_MAX_CHUNKS) ends[threadIdx.x] = ctrl->key_end[threadIdx.x];
+    if (threadIdx.x < GSR_MAX_CHUNKS) {
+        ends[threadIdx.x] = ctrl->key_end[threadIdx.x];
+        // a chunk that k_chunk_rank may order: its Gaussians by position a second time, where no block of that kernel writes
+        small[threadIdx.x] = (int)threadIdx.x < n && ctrl->bnd[threadIdx.x + 1] - ctrl->bnd[threadIdx.x] <= (uint32_t)kSmallSortMax;
+    }
     if (wv < n) {                                                // wave k: chunk k's Gaussians in the blocks before this one
         const uint32_t s = wave_sum_counters(st->blk_cnt[wv], 0, (int)blockIdx.x);
         if (lane == 0) sh.run[wv] = ctrl->bnd[wv] + s;
@@ -308,6 +315,7 @@ __global__ __launch_bounds__(kSelThreads) void k_part_scatter(int P, const uint3
         if (c >= 0) {
             const uint32_t base = sel_key_base(c > 0 ? ends[c - 1] : 0u, c == 0);
             order[pos] = (uint32_t)i;
+            if (small[c]) pos_gid[pos] = (uint32_t)i;
             pos_key[pos] = key > base ? key - base : 0u;
             pos_tiles[pos] = tiles_mass[i].x;
         }
@@ -335,8 +343,10 @@ int launch_depth_select(const FrameK &f, GeomWS &ws, bool debug, hipStream_t s, 
     {
         ProfileScope prof("depth_partition", s);
         hipLaunchKernelGGL(k_part_count, dim3(blocks), dim3(kSelThreads), 0, s, f.P, ws.sort_keys[0], first_mass, ws.ctrl, ws.sel);
+        // (pos_gid = cnt_open: a chunk's by-rank arrays are scratch until its binning starts - the live filter and the radix sort of
+        // a large chunk use them the same way - and the count pass of the chunk writes its range before anybody reads it)
         hipLaunchKernelGGL(k_part_scatter, dim3(blocks), dim3(kSelThreads), 0, s, f.P, ws.sort_keys[0], ws.tiles_mass, ws.ctrl, ws.sel, ws.order,
-                           ws.sort_keys[1], ws.sort_vals[1], reinterpret_cast<uint4 *>(clear16), (int)clear16_n);
+                           ws.sort_keys[1], ws.sort_vals[1], ws.cnt_open, reinterpret_cast<uint4 *>(clear16), (int)clear16_n);
         GSR_LAUNCH_CHECK("depth_partition", debug, s);
     }
     return GSR_OK;
@@ -429,14 +439,15 @@ int launch_rows_scatter(int n_rows, int P, const int32_t *rows, const float *pac
 // Gaussians in index order (the partition above); output: the same range in depth order and, beside it, the inclusive
 // scan of their tile counts (offs_full, relative to the chunk's first rank).
 //
-// Small chunks (the nearest chunk of a saturating frame: 5 K Gaussians at cfg3) are sorted by ONE block in LDS.  One CU
+// Small chunks (the nearest chunk of a saturating frame: 5 K Gaussians at cfg3) are ranked by k_chunk_rank below; the kernel
+// here, ONE block sorting in LDS, did it before and stays as that kernel's twin (GSR_SORT_FORCE_RADIX).  One CU
 // issues about one wave instruction per SIMD every four cycles, so instructions are what counts: the keys are dealt into
 // 4096 buckets by their top bits (one LDS atomic each), the bucket sizes are scanned, and the keys are rank-sorted inside their
 // buckets (1.3 keys per bucket on average at cfg3, 3.8 at cfg2's 15 k) by (key, position in the partition = Gaussian index
 // order).  The result does not depend on the order the atomics landed in.  Keys that crowd into one bucket (> kBucketMax:
 // equal depths) take the 4-bit radix passes below instead (stable, any distribution, ~8x slower).
-constexpr int kSmallSortMax = 16384;                          // two instantiations: 8192 keys (8 per thread) and 16384 (16 per thread,
-constexpr int kSmallThreads = 1024;                           // some of them spilled: only chunks that need it take that one)
+constexpr int kSmallThreads = 1024;                           // two instantiations: 8192 keys (8 per thread) and 16384 (16 per thread,
+                                                              // some of them spilled: only chunks that need it take that one)
 constexpr int kBuckets = 4096;
 constexpr int kBucketsPer = kBuckets / kSmallThreads;
 constexpr int kBucketBits = 12;
@@ -641,6 +652,85 @@ __global__ __launch_bounds__(kSmallThreads) void k_chunk_sort_small(int n, uint3
     }
 }
 
+// The same result by RANKING, on as many CUs as the chunk has groups of elements: the element at position e goes to rank
+// #{j : (key_j, j) < (key_e, e)} and its entry of the tile scan is the tiles of those j plus its own - integer sums, so the result
+// does not depend on their order, and equal keys keep position order whatever the key distribution.  kRankLanes lanes share an
+// element (lane l takes j = l, l + kRankLanes, ...); every block stages (key, tiles) of all positions in LDS, kRankSlab at a time,
+// padded to whole rounds of the unrolled walk with keys that rank behind everything.  No block waits for another: the Gaussians are
+// read from pos_gid (k_part_scatter's second copy of the positions), which no block writes, order[] is only written.
+constexpr int kRankLanes = 16, kRankBlock = 256, kRankUnroll = 8, kRankStage = 32, kRankSlab = 8192;
+static_assert(kRankSlab % (kRankLanes * kRankUnroll) == 0 && kRankSlab * sizeof(uint2) <= 65536, "slab: whole rounds, within the static LDS limit");
+__global__ __launch_bounds__(kRankBlock) void k_chunk_rank(int n, uint32_t r0, const uint32_t *__restrict__ pos_key,
+                                                           const uint32_t *__restrict__ pos_tiles, const uint32_t *__restrict__ pos_gid,
+                                                           uint32_t *__restrict__ order, uint32_t *__restrict__ offs_full)
+{
+    __shared__ uint2 sh[kRankSlab];
+    const int l = threadIdx.x & (kRankLanes - 1);
+    const int e = (int)blockIdx.x * (kRankBlock / kRankLanes) + (int)(threadIdx.x / kRankLanes);
+    const bool mine = e < n;
+    const uint32_t key_e = mine ? pos_key[r0 + e] : 0u, tiles_e = mine ? pos_tiles[r0 + e] : 0u, gid_e = mine ? pos_gid[r0 + e] : 0u;
+    uint32_t rank = 0, pre = 0;
+    for (int s0 = 0; s0 < n; s0 += kRankSlab) {
+        const int m = n - s0 < kRankSlab ? n - s0 : kRankSlab;
+        const int m_pad = (m + kRankLanes * kRankUnroll - 1) / (kRankLanes * kRankUnroll) * (kRankLanes * kRankUnroll);      // <= kRankSlab
+        if (s0) __syncthreads();                                 // the previous slab has been read
+        for (int j0 = 0; j0 < m_pad; j0 += kRankBlock * kRankStage) {          // kRankStage loads in flight per thread (clamped, never past m - 1)
+            uint2 t[kRankStage];
+#pragma unroll
+            for (int u = 0; u < kRankStage; ++u) {
+                const int j = j0 + (int)threadIdx.x + u * kRankBlock, jc = j < m ? j : m - 1;
+                t[u] = make_uint2(pos_key[r0 + s0 + jc], pos_tiles[r0 + s0 + jc]);
+                if (j >= m) t[u] = make_uint2(0xFFFFFFFFu, 0u);
+            }
+#pragma unroll
+            for (int u = 0; u < kRankStage; ++u) {
+                const int j = j0 + (int)threadIdx.x + u * kRankBlock;
+                if (j < m_pad) sh[j] = t[u];
+            }
+        }
+        __syncthreads();
+        // Position jj = s0 + j is before e when key_jj < key_e + (jj < e) (relative keys stay below 0xFFFFFFFF: the sum does not wrap, and
+        // the padding is never before).  A round is kRankLanes kRankUnroll consecutive positions, the same for every lane group of the
+        // wave, and the wave's elements are consecutive: the rounds in front of all of them compare with key_e + 1, the rounds behind
+        // all of them with key_e, and only the one or two in between decide per position - three loops with wave-uniform bounds.
+        constexpr int kRound = kRankLanes * kRankUnroll, kPerWave = kWave / kRankLanes;
+        const int rel = __builtin_amdgcn_readfirstlane(e) - s0;   // the wave's first element (its lanes 0 .. kRankLanes - 1), slab-relative
+        int ja = rel >= kRound ? rel / kRound * kRound : 0;       // rounds [0, ja): every position < every element of the wave
+        ja = ja < m_pad ? ja : m_pad;
+        int jb = rel + kPerWave - 1 > 0 ? (rel + kPerWave - 1 + kRound - 1) / kRound * kRound : 0;      // rounds [jb, m_pad): every position >= every element
+        jb = jb < m_pad ? jb : m_pad;
+        jb = jb > ja ? jb : ja;
+        auto round_flat = [&](int jr, uint32_t thr) {
+            uint2 kt[kRankUnroll];
+#pragma unroll
+            for (int u = 0; u < kRankUnroll; ++u) kt[u] = sh[jr + l + u * kRankLanes];
+#pragma unroll
+            for (int u = 0; u < kRankUnroll; ++u) {
+                const bool before = kt[u].x < thr;
+                rank += before ? 1u : 0u;
+                pre += before ? kt[u].y : 0u;
+            }
+        };
+        for (int jr = 0; jr < ja; jr += kRound) round_flat(jr, key_e + 1u);
+        for (int jr = ja; jr < jb; jr += kRound) {
+            uint2 kt[kRankUnroll];
+#pragma unroll
+            for (int u = 0; u < kRankUnroll; ++u) kt[u] = sh[jr + l + u * kRankLanes];
+#pragma unroll
+            for (int u = 0; u < kRankUnroll; ++u) {
+                const bool before = kt[u].x < key_e + (s0 + jr + l + u * kRankLanes < e ? 1u : 0u);
+                rank += before ? 1u : 0u;
+                pre += before ? kt[u].y : 0u;
+            }
+        }
+        for (int jr = jb; jr < m_pad; jr += kRound) round_flat(jr, key_e);
+    }
+    if (!mine) { rank = 0; pre = 0; }                            // (groups past the chunk's end walked the slab with a zero key)
+#pragma unroll
+    for (int off = kRankLanes / 2; off >= 1; off >>= 1) { rank += __shfl_xor(rank, off); pre += __shfl_xor(pre, off); }
+    if (mine && l == 0) { order[r0 + rank] = gid_e; offs_full[r0 + rank] = pre + tiles_e; }
+}
+
 // live_count (device): only the first *live_count Gaussians of the range need sorting (launch_live_filter put the ones that
 // can still reach an open tile in front); the rest keep their place behind them
 int launch_chunk_order(const FrameK &f, int r0, int r1, uint32_t key_lo, uint32_t key_hi, bool first, GeomWS &ws, bool debug, hipStream_t s,
@@ -654,9 +744,12 @@ int launch_chunk_order(const FrameK &f, int r0, int r1, uint32_t key_lo, uint32_
     int bits = bit_width(key_hi > base ? key_hi - base : 0u);
     if (bits < 1) bits = 1;
     if (n <= kSmallSortMax && !live_count) {
-        const int force_radix = getenv("GSR_SORT_FORCE_RADIX") ? 1 : 0;               // test hook (tests set it per case): the fallback path of the LDS sort
+        const int force_radix = getenv("GSR_SORT_FORCE_RADIX") ? 1 : 0;               // test hook (tests set it per case): the one-block LDS sort, on its radix path, instead of the ranking kernel
         ProfileScope prof("chunk_sort", s);
-        if (n <= kSmallSortMax / 2)
+        if (!force_radix)
+            hipLaunchKernelGGL(k_chunk_rank, dim3((unsigned)((n + kRankBlock / kRankLanes - 1) / (kRankBlock / kRankLanes))), dim3(kRankBlock), 0, s, n,
+                               (uint32_t)r0, ws.sort_keys[1], ws.sort_vals[1], ws.cnt_open, ws.order, ws.offs_full);
+        else if (n <= kSmallSortMax / 2)
             hipLaunchKernelGGL(k_chunk_sort_small<kSmallSortMax / 2>, dim3(1), dim3(kSmallThreads), 0, s, n, (uint32_t)r0, bits, force_radix,
                                ws.sort_keys[1], ws.sort_vals[1], ws.order, ws.offs_full);
         else
