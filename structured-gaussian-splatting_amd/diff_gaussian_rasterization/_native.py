@@ -19,62 +19,72 @@ SCREEN_GRAD_STRIDE = 12
 
 _f32p = C.c_void_p
 
+MIRRORS = {}          # typedef of include/gsrast.h -> its ctypes mirror (tests/test_abi.py checks every layout against gcc's)
 
-class FrameDesc(C.Structure):
+
+class _Mirror(C.Structure):
+    """Base of the mirrors: `class X(_Mirror, c="gsr_x")` records the header typedef(s) X mirrors, as X.c_names and in MIRRORS."""
+    def __init_subclass__(cls, c=(), **kw):
+        super().__init_subclass__(**kw)
+        cls.c_names = (c,) if isinstance(c, str) else tuple(c)
+        MIRRORS.update((n, cls) for n in cls.c_names)
+
+
+class FrameDesc(_Mirror, c="gsr_frame_desc"):
     _fields_ = [("P", C.c_int32), ("sh_degree", C.c_int32), ("sh_coeffs", C.c_int32), ("width", C.c_int32),
                 ("height", C.c_int32), ("tanfovx", C.c_float), ("tanfovy", C.c_float), ("scale_modifier", C.c_float),
                 ("prefiltered", C.c_int32), ("debug", C.c_int32), ("tile_row_begin", C.c_int32),
                 ("tile_row_end", C.c_int32)]
 
 
-class Camera(C.Structure):
+class Camera(_Mirror, c="gsr_camera"):
     _fields_ = [("bg", _f32p), ("viewmatrix", _f32p), ("projmatrix", _f32p), ("campos", _f32p)]
 
 
-class Gaussians(C.Structure):
+class Gaussians(_Mirror, c="gsr_gaussians"):
     _fields_ = [("means3D", _f32p), ("shs", _f32p), ("colors_precomp", _f32p), ("opacities", _f32p),
                 ("scales", _f32p), ("rotations", _f32p), ("cov3D_precomp", _f32p),
                 ("shs_rest", _f32p), ("raw", C.c_int32)]      # raw-parameter mode (a14): see include/gsrast.h
 
 
-class Grads(C.Structure):
+class Grads(_Mirror, c="gsr_grads"):
     _fields_ = [("means3D", _f32p), ("means2D", _f32p), ("shs", _f32p), ("colors_precomp", _f32p),
                 ("opacities", _f32p), ("scales", _f32p), ("rotations", _f32p), ("cov3D_precomp", _f32p),
                 ("shs_rest", _f32p), ("prezeroed", C.c_int32)]
 
 
-class AuxOutputs(C.Structure):
+class AuxOutputs(_Mirror, c="gsr_aux_outputs"):
     """gsr_aux_outputs: the depth and alpha maps [H,W] and their checkpoint workspace (gsr_aux_workspace_size)."""
     _fields_ = [("depth", _f32p), ("alpha", _f32p), ("ckpt_ws", C.c_void_p)]
 
 
-class ContribStats(C.Structure):
+class ContribStats(_Mirror, c="gsr_contrib_stats"):
     """gsr_contrib_stats: the per-Gaussian accumulators of the blend statistics, [P] each (count and weight_sum_q32 64-bit, weight_max_bits
     the bits of a float)."""
     _fields_ = [("count", C.c_void_p), ("weight_sum_q32", C.c_void_p), ("weight_max_bits", C.c_void_p)]
 
 
-class ContribError(C.Structure):
+class ContribError(_Mirror, c="gsr_contrib_error"):
     """gsr_contrib_error: the per-pixel error map [H*W] (read only) and the frame's per-Gaussian error totals [P] (64-bit, units of 2^-32)."""
     _fields_ = [("pixel_error", _f32p), ("error_frame_q32", C.c_void_p)]
 
 
-class CameraGrads(C.Structure):
+class CameraGrads(_Mirror, c="gsr_camera_grads"):
     """gsr_camera_grads: dL/dviewmatrix [16], dL/dprojmatrix [16], dL/dcampos [3]; any may be NULL."""
     _fields_ = [("viewmatrix", _f32p), ("projmatrix", _f32p), ("campos", _f32p)]
 
 
-class StructuredDesc(C.Structure):
+class StructuredDesc(_Mirror, c="gsr_structured_desc"):
     """gsr_structured_desc: B structures of K children with sh_coeffs SH coefficients per channel each."""
     _fields_ = [("B", C.c_int32), ("K", C.c_int32), ("sh_coeffs", C.c_int32)]
 
 
-class Structures(C.Structure):
+class Structures(_Mirror, c="gsr_structures"):
     """gsr_structures: means [B,3], opacities [B], scales [B,3], rotations [B,4]."""
     _fields_ = [("means", _f32p), ("opacities", _f32p), ("scales", _f32p), ("rotations", _f32p)]
 
 
-class Children(C.Structure):
+class Children(_Mirror, c=("gsr_children", "gsr_children_grads")):
     """gsr_children (the composed tensors) and gsr_children_grads (their incoming gradients, NULL = zero): one layout."""
     _fields_ = [("xyz", _f32p), ("opacity", _f32p), ("scaling", _f32p), ("rotation", _f32p), ("features", _f32p)]
 
@@ -82,32 +92,39 @@ class Children(C.Structure):
 ChildrenGrads = Children
 
 
-class StructuredGrads(C.Structure):
+class StructuredGrads(_Mirror, c="gsr_structured_grads"):
     """gsr_structured_grads: dL/ddecoded [B, K D] and the structure gradients; NULL = not wanted."""
     _fields_ = [("decoded", _f32p), ("means", _f32p), ("opacities", _f32p), ("scales", _f32p), ("rotations", _f32p)]
 
 
-class DecoderDesc(C.Structure):
+class DecoderDesc(_Mirror, c="gsr_decoder_desc"):
     """gsr_decoder_desc: B structures, an input row of in_size = positional dims + latent_size floats, out_size outputs."""
     _fields_ = [("B", C.c_int32), ("in_size", C.c_int32), ("latent_size", C.c_int32), ("hidden_size", C.c_int32),
                 ("out_size", C.c_int32)]
 
 
-class DecoderParams(C.Structure):
+class DecoderParams(_Mirror, c="gsr_decoder_params"):
     """gsr_decoder_params: nn.Linear layouts, w [out, in]."""
     _fields_ = [("w0", _f32p), ("b0", _f32p), ("w1", _f32p), ("b1", _f32p), ("w2", _f32p), ("b2", _f32p)]
 
 
-class DecoderGrads(C.Structure):
+class DecoderGrads(_Mirror, c="gsr_decoder_grads"):
     """gsr_decoder_grads: NULL = not wanted."""
     _fields_ = [("latents", _f32p), ("w0", _f32p), ("b0", _f32p), ("w1", _f32p), ("b1", _f32p), ("w2", _f32p), ("b2", _f32p)]
 
 
+# constants of the header, mirrored by hand (tests/test_abi.py compares them with its #defines and enum)
 MAX_CHUNKS = 8
 LAST_SHIFT = 26
+ERR_WORKSPACE = -4
+ADAM_MAX_TENSORS = 8
+ADAM_STEP_UNCORRECTED = 2 ** 63 - 1        # GSR_ADAM_STEP_UNCORRECTED: a `step` that applies no bias correction
+MCMC_MAX_TENSORS = 8
+MCMC_ROLES = {"copy": 0, "opacity": 1, "scaling": 2}
+PROFILE_NAME_LEN = 32
 
 
-class FramePlan(C.Structure):
+class FramePlan(_Mirror, c="gsr_frame_plan"):
     _fields_ = [("num_rendered", C.c_int64), ("num_visible", C.c_int32), ("num_chunks", C.c_int32),
                 ("chunk_rank_begin", C.c_int32 * (MAX_CHUNKS + 1)), ("chunk_instances_max", C.c_int64 * MAX_CHUNKS),
                 ("chunks_run", C.c_int32), ("sort_result", C.c_int32), ("instances_emitted", C.c_int64),
@@ -116,30 +133,115 @@ class FramePlan(C.Structure):
                 ("tile_order_ready", C.c_int32), ("key_max", C.c_uint32)]
 
 
-class DebugViews(C.Structure):
+class DebugViews(_Mirror, c="gsr_debug_views"):
     _fields_ = [("splat_records", C.c_void_p), ("tiles_touched", C.c_void_p), ("depth_order", C.c_void_p),
                 ("point_offsets", C.c_void_p), ("clamped", C.c_void_p), ("sorted_gaussian", C.c_void_p),
                 ("ranges", C.c_void_p), ("final_T", C.c_void_p), ("n_contrib", C.c_void_p), ("tile_walk", C.c_void_p),
                 ("bwd_units", C.c_void_p), ("bwd_unit_count", C.c_void_p), ("bwd_unit_cap_full", C.c_uint32), ("bwd_unit_cap_part", C.c_uint32)]
 
 
-EXPORTS = ("gsr_version", "gsr_last_error", "gsr_workspace_sizes", "gsr_binning_size", "gsr_binning_first_chunk_capacity", "gsr_forward_preprocess", "gsr_forward",
-           "gsr_forward_render", "gsr_bwd_segment_entries", "gsr_backward_rows_size", "gsr_backward_prepare", "gsr_backward_render", "gsr_backward_geom", "gsr_backward_geom_rows", "gsr_frame_arrays", "gsr_exchange_rows_gather", "gsr_exchange_rows_scatter", "gsr_mark_visible", "gsr_debug_get_views", "gsr_profile_enable",
-           "gsr_profile_read", "gsr_loss_workspace_size", "gsr_loss_l1_ssim_forward", "gsr_loss_l1_ssim_backward", "gsr_loss_l1_ssim_forward_rows", "gsr_loss_l1_ssim_backward_rows", "gsr_loss_l1_backward",
-           "gsr_debug_sort_temp_bytes", "gsr_debug_sort_pairs", "gsr_debug_sort_pairs_ex", "gsr_dist2_workspace_size", "gsr_dist2_knn3", "gsr_adam_step", "gsr_adam_step_split", "gsr_adam_step_multi", "gsr_adam_step_sparse_multi", "gsr_densify_stats",
-           "gsr_activations_forward", "gsr_activations_backward",
-           "gsr_aux_workspace_size", "gsr_forward_aux", "gsr_forward_render_aux", "gsr_backward_render_aux", "gsr_backward_geom_aux",
-           "gsr_camera_grad_workspace_size", "gsr_backward_camera",
-           "gsr_backward_render_abs", "gsr_screen_absgrad",
-           "gsr_structured_compose_forward", "gsr_structured_compose_backward",
-           "gsr_opacity_compensation_forward", "gsr_opacity_compensation_backward",
-           "gsr_decoder_workspace_size", "gsr_decoder_forward", "gsr_decoder_backward",
-           "gsr_mcmc_relocation_workspace_size", "gsr_mcmc_relocation", "gsr_mcmc_relocate_rows", "gsr_mcmc_inject_noise", "gsr_mcmc_reg_grads",
-           "gsr_bilagrid_workspace_size", "gsr_bilagrid_forward", "gsr_bilagrid_backward", "gsr_bilagrid_tv_forward", "gsr_bilagrid_tv_backward",
-           "gsr_vq_workspace_size", "gsr_vq_assign", "gsr_vq_update",
-           "gsr_filter3d_workspace_size", "gsr_filter3d_compute", "gsr_filter3d_apply_forward", "gsr_filter3d_apply_backward",
-           "gsr_forward_contrib", "gsr_forward_render_contrib",
-           "gsr_forward_contrib_error", "gsr_forward_render_contrib_error", "gsr_contrib_error_fold")
+class AdamTensor(_Mirror, c="gsr_adam_tensor"):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("n", C.c_int64),
+                ("lr", C.c_float), ("lr_tail", C.c_float), ("step", C.c_int64), ("row_len", C.c_int32), ("split", C.c_int32)]
+
+
+class McmcTensor(_Mirror, c="gsr_mcmc_tensor"):
+    """gsr_mcmc_tensor: a [P, width] tensor, its Adam moments (both or neither None) and its role."""
+    _fields_ = [("param", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("width", C.c_int32), ("role", C.c_int32)]
+
+
+# ---- The C ABI's signatures, once: every function include/gsrast.h declares -> (restype, argtypes in header order).  load() applies
+# them, so a wrong arity or a mirror of the wrong struct is a TypeError / ArgumentError; tests/test_abi.py holds the table to the
+# header's prototypes.  A struct parameter is POINTER(its mirror) and takes the instance bare (or None); a host out-parameter is
+# POINTER(scalar) and takes the scalar object bare; _dev is everything else behind a pointer (device memory, the stream, the host
+# arrays of gsr_profile_read) and takes a plain int address, a ctypes object or None.
+_int, _i32, _i64, _u32, _f32, _size, _dev, _P = C.c_int, C.c_int32, C.c_int64, C.c_uint32, C.c_float, C.c_size_t, C.c_void_p, C.POINTER
+_desc, _cam, _gs, _plan, _grads, _aux = _P(FrameDesc), _P(Camera), _P(Gaussians), _P(FramePlan), _P(Grads), _P(AuxOutputs)
+_stats, _err = _P(ContribStats), _P(ContribError)
+_forward = (_desc, _cam, _gs, _dev, _dev, _dev, _plan, _dev, _i64, _dev, _grads)          # gsr_forward's arguments in front of the stream
+_forward_render = (_desc, _cam, _gs, _dev, _dev, _dev, _plan, _dev)                       # gsr_forward_render's
+_backward_render = (_desc, _cam, _dev, _dev, _dev, _dev, _plan, _dev)                     # gsr_backward_render's, up to out_color
+_backward_geom = (_desc, _cam, _gs, _dev, _dev, _dev, _i32, _i32, _i32, _plan, _grads, _dev)
+SIGNATURES = {
+    "gsr_version": (_int, ()),
+    "gsr_last_error": (C.c_char_p, ()),
+    "gsr_workspace_sizes": (_int, (_desc, _P(_size), _P(_size))),
+    "gsr_binning_size": (_int, (_desc, _i64, _P(_size))),
+    "gsr_binning_first_chunk_capacity": (_int, (_plan, _P(_i64))),
+    "gsr_forward_preprocess": (_int, (_desc, _cam, _gs, _dev, _dev, _dev, _plan, _dev)),
+    "gsr_forward_render": (_int, _forward_render + (_dev,)),
+    "gsr_forward": (_int, _forward + (_dev,)),
+    "gsr_backward_rows_size": (_int, (_desc, _plan, _P(_size))),
+    "gsr_backward_prepare": (_int, (_desc, _gs, _plan, _dev, _grads, _dev)),
+    "gsr_backward_render": (_int, _backward_render + (_dev, _dev, _dev)),
+    "gsr_bwd_segment_entries": (_int, ()),
+    "gsr_backward_geom": (_int, _backward_geom),
+    "gsr_backward_geom_rows": (_int, (_desc, _cam, _gs, _dev, _dev, _dev, _dev, _i32, _grads, _dev)),
+    "gsr_aux_workspace_size": (_int, (_desc, _i64, _P(_size))),
+    "gsr_forward_render_aux": (_int, _forward_render + (_aux, _dev)),
+    "gsr_forward_aux": (_int, _forward + (_aux, _dev)),
+    "gsr_backward_render_aux": (_int, _backward_render + (_aux, _dev, _dev, _dev, _dev, _dev)),
+    "gsr_backward_geom_aux": (_int, _backward_geom),
+    "gsr_forward_render_contrib": (_int, _forward_render + (_stats, _dev)),
+    "gsr_forward_contrib": (_int, _forward + (_stats, _dev)),
+    "gsr_forward_render_contrib_error": (_int, _forward_render + (_stats, _err, _dev)),
+    "gsr_forward_contrib_error": (_int, _forward + (_stats, _err, _dev)),
+    "gsr_contrib_error_fold": (_int, (_i64, _dev, _dev, _dev, _dev)),
+    "gsr_camera_grad_workspace_size": (_int, (_desc, _P(_size))),
+    "gsr_backward_camera": (_int, (_desc, _cam, _gs, _dev, _dev, _dev, _i32, _plan, _i32, _dev, _P(CameraGrads), _dev)),
+    "gsr_backward_render_abs": (_int, _backward_render + (_dev, _dev, _dev)),
+    "gsr_screen_absgrad": (_int, (_desc, _dev, _dev, _dev, _i32, _plan, _dev, _dev)),
+    "gsr_frame_arrays": (_int, (_desc, _dev, _P(_dev), _P(_dev))),
+    "gsr_exchange_rows_gather": (_int, (_desc, _dev, _u32, _dev, _i32, _dev, _dev, _dev)),
+    "gsr_exchange_rows_scatter": (_int, (_desc, _i32, _dev, _dev, _dev, _dev)),
+    "gsr_mark_visible": (_int, (_i32, _dev, _dev, _dev, _dev, _dev)),
+    "gsr_debug_get_views": (_int, (_desc, _dev, _dev, _dev, _plan, _P(DebugViews))),
+    "gsr_loss_workspace_size": (_int, (_i32, _i32, _i32, _P(_size))),
+    "gsr_loss_l1_ssim_forward": (_int, (_i32, _i32, _i32, _f32, _dev, _dev, _dev, _dev, _dev)),
+    "gsr_loss_l1_ssim_backward": (_int, (_i32, _i32, _i32, _f32, _dev, _dev, _dev, _dev, _dev, _dev)),
+    "gsr_loss_l1_backward": (_int, (_i64, _dev, _dev, _dev, _dev, _dev)),
+    "gsr_loss_l1_ssim_forward_rows": (_int, (_i32, _i32, _i32, _dev, _dev, _dev, _dev, _i32, _i32, _dev)),
+    "gsr_loss_l1_ssim_backward_rows": (_int, (_i32, _i32, _i32, _f32, _dev, _dev, _dev, _dev, _dev, _i32, _i32, _dev)),
+    "gsr_dist2_workspace_size": (_int, (_i32, _P(_size))),
+    "gsr_dist2_knn3": (_int, (_i32, _dev, _dev, _dev, _dev)),
+    "gsr_adam_step": (_int, (_i64, _dev, _dev, _dev, _dev, _f32, _f32, _f32, _f32, _i64, _dev)),
+    "gsr_adam_step_split": (_int, (_i64, _i32, _i32, _dev, _dev, _dev, _dev, _f32, _f32, _f32, _f32, _f32, _i64, _dev)),
+    "gsr_adam_step_multi": (_int, (_i32, _P(AdamTensor), _f32, _f32, _f32, _dev)),
+    "gsr_adam_step_sparse_multi": (_int, (_i32, _P(AdamTensor), _i64, _dev, _i32, _f32, _f32, _f32, _dev)),
+    "gsr_activations_forward": (_int, (_i64,) + (_dev,) * 7),
+    "gsr_activations_backward": (_int, (_i64,) + (_dev,) * 10),
+    "gsr_structured_compose_forward": (_int, (_P(StructuredDesc), _dev, _P(Structures), _P(Children), _dev)),
+    "gsr_structured_compose_backward": (_int, (_P(StructuredDesc), _dev, _P(Structures), _P(ChildrenGrads), _P(StructuredGrads), _dev)),
+    "gsr_opacity_compensation_forward": (_int, (_desc, _cam, _gs, _dev, _dev)),
+    "gsr_opacity_compensation_backward": (_int, (_desc, _cam, _gs, _dev, _grads, _dev)),
+    "gsr_decoder_workspace_size": (_int, (_P(DecoderDesc), _P(_size))),
+    "gsr_decoder_forward": (_int, (_P(DecoderDesc), _dev, _dev, _P(DecoderParams), _dev, _dev)),
+    "gsr_decoder_backward": (_int, (_P(DecoderDesc), _dev, _dev, _P(DecoderParams), _dev, _P(DecoderGrads), _dev, _size, _dev)),
+    "gsr_mcmc_relocation_workspace_size": (_int, (_i64, _P(_size))),
+    "gsr_mcmc_relocation": (_int, (_i64, _i64, _dev, _dev, _dev, _f32, _dev, _dev, _dev, _dev)),
+    "gsr_mcmc_relocate_rows": (_int, (_i32, _P(McmcTensor), _i64, _i64, _dev, _dev, _dev, _dev, _dev)),
+    "gsr_mcmc_inject_noise": (_int, (_i64, _dev, _dev, _dev, _dev, _dev, _f32, _dev)),
+    "gsr_mcmc_reg_grads": (_int, (_i64, _dev, _dev, _f32, _f32, _dev, _dev, _dev)),
+    "gsr_bilagrid_workspace_size": (_int, (_i32, _i32, _i32, _i32, _i32, _P(_size), _P(_size))),
+    "gsr_bilagrid_forward": (_int, (_i32,) * 7 + (_dev,) * 4),
+    "gsr_bilagrid_backward": (_int, (_i32,) * 7 + (_dev,) * 6 + (_size, _dev)),
+    "gsr_bilagrid_tv_forward": (_int, (_i32, _i32, _i32, _i32, _dev, _dev, _dev, _dev)),
+    "gsr_bilagrid_tv_backward": (_int, (_i32, _i32, _i32, _i32, _dev, _dev, _dev, _dev)),
+    "gsr_vq_workspace_size": (_int, (_i64, _i32, _i32, _P(_size))),
+    "gsr_vq_assign": (_int, (_i64, _i32, _i32, _dev, _dev, _dev, _dev, _dev, _size, _dev)),
+    "gsr_vq_update": (_int, (_i64, _i32, _i32, _dev, _dev, _dev, _dev, _dev, _dev, _size, _dev)),
+    "gsr_filter3d_workspace_size": (_int, (_i64, _P(_size))),
+    "gsr_filter3d_compute": (_int, (_i64, _i32, _dev, _f32, _dev, _dev, _dev, _size, _P(_i32), _dev)),
+    "gsr_filter3d_apply_forward": (_int, (_i64, _i32, _dev, _dev, _dev, _dev, _dev, _dev)),
+    "gsr_filter3d_apply_backward": (_int, (_i64, _i32) + (_dev,) * 8),
+    "gsr_densify_stats": (_int, (_i32, _dev, _dev, _dev, _dev, _dev, _dev)),
+    "gsr_debug_sort_temp_bytes": (_int, (_P(_size),)),
+    "gsr_debug_sort_pairs": (_int, (_dev, _dev, _dev, _dev, _i64, _i32, _i32, _dev, _P(_i32), _dev)),
+    "gsr_debug_sort_pairs_ex": (_int, (_dev,) * 6 + (_i64, _i64, _i64, _i32, _i32, _dev, _P(_i32), _dev)),
+    "gsr_profile_enable": (_int, (_int,)),
+    "gsr_profile_read": (_int, (_int, _dev, _dev, _dev)),
+}
+EXPORTS = tuple(SIGNATURES)
 
 _lib = None
 
@@ -157,6 +259,7 @@ def build(force: bool = False) -> str:
 
 
 def load():
+    """The CDLL with SIGNATURES applied: its functions return the status (or value) as it is."""
     global _lib
     if _lib is None:
         if not os.path.exists(_LIB_PATH):
@@ -164,10 +267,11 @@ def load():
                 f"libgsrast.so not found at {_LIB_PATH}: the HIP extension is required (no CPU fallback exists). "
                 f"Build it with `make -C {_CSRC}` or `python -c 'import __graft_entry__ as g; g.build()'`.")
         lib = C.CDLL(_LIB_PATH)
-        lib.gsr_last_error.restype = C.c_char_p
-        for name in EXPORTS:
+        for name, (restype, argtypes) in SIGNATURES.items():
             if not hasattr(lib, name):
                 raise RuntimeError(f"libgsrast.so does not export {name}")
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
     return _lib
 
@@ -176,21 +280,50 @@ class GsrError(RuntimeError):
     status = 0
 
 
-ERR_WORKSPACE = -4
-
-
-def _check(rc: int, what: str):
+def _errcheck(rc, fn, args=None):
+    """ctypes' errcheck of the checked functions: a non-zero status raises GsrError under the function's own name."""
     if rc != 0:
-        msg = load().gsr_last_error().decode("utf-8", "replace")
-        e = GsrError(f"{what} failed (status {rc}): {msg}")
+        e = GsrError(f"{fn.__name__} failed (status {rc}): {load().gsr_last_error().decode('utf-8', 'replace')}")
         e.status = rc
         raise e
+    return rc
+
+
+class _Checked:
+    """_gsr.gsr_x(...): the typed gsr_x of load() that raises GsrError on a non-zero status (only for the functions that return one:
+    gsr_version, gsr_last_error, gsr_bwd_segment_entries and gsr_profile_read return a value and are called through load())."""
+
+    def __getattr__(self, name):                  # once per name: the function then sits in the instance's __dict__
+        if name not in SIGNATURES:
+            raise AttributeError(name)
+        fn = load()[name]                         # a function object of its own: load()'s keep returning the status
+        fn.restype, fn.argtypes = SIGNATURES[name]
+        fn.errcheck = _errcheck
+        self.__dict__[name] = fn
+        return fn
+
+
+_gsr = _Checked()
+
+
+def _size(fn, *args) -> int:
+    """A size query: fn(*args, size_t *bytes) -> bytes."""
+    b = C.c_size_t()
+    fn(*args, b)
+    return b.value
+
+
+def _size2(fn, *args):
+    """A size query with two results: fn(*args, size_t *a, size_t *b) -> (a, b).  (Apart from _size: a general one costs 0.5 us a call.)"""
+    a, b = C.c_size_t(), C.c_size_t()
+    fn(*args, a, b)
+    return a.value, b.value
 
 
 def _ptr(t: Optional[torch.Tensor]):
     if t is None or t.numel() == 0:
         return None
-    return C.c_void_p(t.data_ptr())
+    return t.data_ptr()
 
 
 def _stream(device) -> C.c_void_p:
@@ -205,27 +338,22 @@ def make_desc(P, sh_degree, sh_coeffs, width, height, tanfovx, tanfovy, scale_mo
 
 
 def workspace_sizes(desc: FrameDesc):
-    g, i = C.c_size_t(0), C.c_size_t(0)
-    _check(load().gsr_workspace_sizes(C.byref(desc), C.byref(g), C.byref(i)), "gsr_workspace_sizes")
-    return g.value, i.value
+    return _size2(_gsr.gsr_workspace_sizes, desc)
 
 
 def binning_size(desc: FrameDesc, R: int) -> int:
-    b = C.c_size_t(0)
-    _check(load().gsr_binning_size(C.byref(desc), C.c_int64(R), C.byref(b)), "gsr_binning_size")
-    return b.value
+    return _size(_gsr.gsr_binning_size, desc, R)
 
 
 def binning_first_chunk_capacity(plan: FramePlan) -> int:
     n = C.c_int64(0)
-    _check(load().gsr_binning_first_chunk_capacity(C.byref(plan), C.byref(n)), "gsr_binning_first_chunk_capacity")
+    _gsr.gsr_binning_first_chunk_capacity(plan, n)
     return n.value
 
 
 def forward_preprocess(desc, cam: Camera, g: Gaussians, geom_ws, radii, device, image_ws=None) -> FramePlan:
     plan = FramePlan()
-    _check(load().gsr_forward_preprocess(C.byref(desc), C.byref(cam), C.byref(g), _ptr(geom_ws), _ptr(image_ws), _ptr(radii),
-                                         C.byref(plan), _stream(device)), "gsr_forward_preprocess")
+    _gsr.gsr_forward_preprocess(desc, cam, g, _ptr(geom_ws), _ptr(image_ws), _ptr(radii), plan, _stream(device))
     return plan
 
 
@@ -238,88 +366,81 @@ def forward_both(desc, cam: Camera, g: Gaussians, geom_ws, image_ws, radii, binn
     call forward_render) - or, when the plan has more than one chunk, for a later one: a statistics frame has then already added
     its earlier chunks (include/gsrast.h), so its caller sizes the workspace for num_rendered."""
     plan = FramePlan()
-    args = (C.byref(desc), C.byref(cam), C.byref(g), _ptr(geom_ws), _ptr(image_ws), _ptr(radii), C.byref(plan),
-            _ptr(binning_ws), C.c_int64(int(binning_capacity)), _ptr(out_color), None if early_fill is None else C.byref(early_fill))
+    lib = load()                      # the plain functions: GSR_ERR_WORKSPACE is an answer here, not an error
+    args = (desc, cam, g, _ptr(geom_ws), _ptr(image_ws), _ptr(radii), plan, _ptr(binning_ws), int(binning_capacity), _ptr(out_color),
+            early_fill)
     if aux is not None and contrib is not None:
         raise ValueError("forward_both: aux and contrib together (that kernel is not built)")
     if err is not None:
         if contrib is None:
             raise ValueError("forward_both: err without contrib")
-        rc = load().gsr_forward_contrib_error(*args, C.byref(contrib), C.byref(err), _stream(device))
+        fn, more = lib.gsr_forward_contrib_error, (contrib, err)
     elif contrib is not None:
-        rc = load().gsr_forward_contrib(*args, C.byref(contrib), _stream(device))
+        fn, more = lib.gsr_forward_contrib, (contrib,)
     elif aux is None:
-        rc = load().gsr_forward(*args, _stream(device))
+        fn, more = lib.gsr_forward, ()
     else:
-        rc = load().gsr_forward_aux(*args, C.byref(aux), _stream(device))
+        fn, more = lib.gsr_forward_aux, (aux,)
+    rc = fn(*args, *more, _stream(device))
     if rc == ERR_WORKSPACE:           # the guessed workspace did not do (for the first chunk, or for a later one)
         return plan, False
-    _check(rc, "gsr_forward")
+    _errcheck(rc, fn)
     return plan, True
 
 
 def forward_render(desc, cam: Camera, g: Gaussians, geom_ws, binning_ws, image_ws, plan: FramePlan, out_color, device,
                    aux: Optional[AuxOutputs] = None, contrib: Optional[ContribStats] = None, err: Optional[ContribError] = None):
-    args = (C.byref(desc), C.byref(cam), C.byref(g), _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws), C.byref(plan), _ptr(out_color))
+    args = (desc, cam, g, _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws), plan, _ptr(out_color))
     if aux is not None and contrib is not None:
         raise ValueError("forward_render: aux and contrib together (that kernel is not built)")
     if err is not None:
         if contrib is None:
             raise ValueError("forward_render: err without contrib")
-        _check(load().gsr_forward_render_contrib_error(*args, C.byref(contrib), C.byref(err), _stream(device)),
-               "gsr_forward_render_contrib_error")
+        _gsr.gsr_forward_render_contrib_error(*args, contrib, err, _stream(device))
     elif contrib is not None:
-        _check(load().gsr_forward_render_contrib(*args, C.byref(contrib), _stream(device)), "gsr_forward_render_contrib")
+        _gsr.gsr_forward_render_contrib(*args, contrib, _stream(device))
     elif aux is None:
-        _check(load().gsr_forward_render(*args, _stream(device)), "gsr_forward_render")
+        _gsr.gsr_forward_render(*args, _stream(device))
     else:
-        _check(load().gsr_forward_render_aux(*args, C.byref(aux), _stream(device)), "gsr_forward_render_aux")
+        _gsr.gsr_forward_render_aux(*args, aux, _stream(device))
 
 
 def contrib_error_fold(error_frame_q32, error_sum_q32, error_max, device):
     """gsr_contrib_error_fold on the device's current stream: the frame's error totals into the running sum and maximum, then cleared."""
-    _check(load().gsr_contrib_error_fold(C.c_int64(int(error_frame_q32.shape[0])), _ptr(error_frame_q32), _ptr(error_sum_q32),
-                                         _ptr(error_max), _stream(device)), "gsr_contrib_error_fold")
+    _gsr.gsr_contrib_error_fold(int(error_frame_q32.shape[0]), _ptr(error_frame_q32), _ptr(error_sum_q32), _ptr(error_max), _stream(device))
 
 
 def aux_workspace_size(desc: FrameDesc, binning_capacity: int) -> int:
     """gsr_aux_workspace_size: bytes of the depth checkpoints of an aux frame whose binning workspace holds that many instances."""
-    b = C.c_size_t(0)
-    _check(load().gsr_aux_workspace_size(C.byref(desc), C.c_int64(int(binning_capacity)), C.byref(b)), "gsr_aux_workspace_size")
-    return b.value
+    return _size(_gsr.gsr_aux_workspace_size, desc, int(binning_capacity))
 
 
 def backward_rows_size(desc: FrameDesc, plan: FramePlan) -> int:
-    b = C.c_size_t(0)
-    _check(load().gsr_backward_rows_size(C.byref(desc), C.byref(plan), C.byref(b)), "gsr_backward_rows_size")
-    return b.value
+    return _size(_gsr.gsr_backward_rows_size, desc, plan)
 
 
 def backward_prepare(desc, g: Gaussians, plan: FramePlan, screen_grads, grads: Grads, device):
-    _check(load().gsr_backward_prepare(C.byref(desc), C.byref(g), C.byref(plan), _ptr(screen_grads), C.byref(grads),
-                                       _stream(device)), "gsr_backward_prepare")
+    _gsr.gsr_backward_prepare(desc, g, plan, _ptr(screen_grads), grads, _stream(device))
 
 
 def backward_render(desc, cam: Camera, geom_ws, binning_ws, image_ws, rows_ws, plan: FramePlan, out_color, dL_dcolor, screen_grads,
                     device, absgrad: bool = False):
     """absgrad: gsr_backward_render_abs - screen_grads slots 10, 11 also receive the per-pixel absolute sums of d/dmean2D."""
-    fn, name = (load().gsr_backward_render_abs, "gsr_backward_render_abs") if absgrad else (load().gsr_backward_render, "gsr_backward_render")
-    _check(fn(C.byref(desc), C.byref(cam), _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws),
-              _ptr(rows_ws), C.byref(plan), _ptr(out_color), _ptr(dL_dcolor), _ptr(screen_grads), _stream(device)), name)
+    fn = _gsr.gsr_backward_render_abs if absgrad else _gsr.gsr_backward_render
+    fn(desc, cam, _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws), _ptr(rows_ws), plan, _ptr(out_color), _ptr(dL_dcolor), _ptr(screen_grads),
+       _stream(device))
 
 
 def screen_absgrad(desc, radii, geom_ws, screen_grads, out, device, binned_ranks: int = -1, own_plan: Optional[FramePlan] = None):
     """gsr_screen_absgrad, behind backward_geom of the same arguments: out [P,3] = (slot 10, slot 11, 0) of the rows it visits."""
-    _check(load().gsr_screen_absgrad(C.byref(desc), _ptr(radii), _ptr(geom_ws), _ptr(screen_grads), C.c_int32(binned_ranks),
-                                     None if own_plan is None else C.byref(own_plan), _ptr(out), _stream(device)), "gsr_screen_absgrad")
+    _gsr.gsr_screen_absgrad(desc, _ptr(radii), _ptr(geom_ws), _ptr(screen_grads), binned_ranks, own_plan, _ptr(out), _stream(device))
 
 
 def backward_render_aux(desc, cam: Camera, geom_ws, binning_ws, image_ws, rows_ws, plan: FramePlan, out_color, aux: AuxOutputs,
                         dL_dcolor, dL_ddepth, dL_dalpha, screen_grads, device):
     """gsr_backward_render_aux: any of the three upstream gradients may be None (zero); screen_grads slot 9 receives dL/dz."""
-    _check(load().gsr_backward_render_aux(C.byref(desc), C.byref(cam), _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws), _ptr(rows_ws),
-                                          C.byref(plan), _ptr(out_color), C.byref(aux), _ptr(dL_dcolor), _ptr(dL_ddepth), _ptr(dL_dalpha),
-                                          _ptr(screen_grads), _stream(device)), "gsr_backward_render_aux")
+    _gsr.gsr_backward_render_aux(desc, cam, _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws), _ptr(rows_ws), plan, _ptr(out_color), aux,
+                                 _ptr(dL_dcolor), _ptr(dL_ddepth), _ptr(dL_dalpha), _ptr(screen_grads), _stream(device))
 
 
 _SEG = [0]
@@ -336,27 +457,20 @@ def backward_geom(desc, cam: Camera, g: Gaussians, radii, geom_ws, screen_grads,
                   binned_ranks: int = -1, own_plan: Optional[FramePlan] = None, depth_chain: bool = False):
     """own_plan: the frame's plan when screen_grads are this very frame's (gsr_backward_render of the same plan), else None.
     depth_chain: screen_grads slot 9 holds dL/dz (gsr_backward_render_aux): gsr_backward_geom_aux adds its chain to means3D."""
-    fn = load().gsr_backward_geom_aux if depth_chain else load().gsr_backward_geom
-    _check(fn(C.byref(desc), C.byref(cam), C.byref(g), _ptr(radii), _ptr(geom_ws),
-              _ptr(screen_grads), C.c_int32(g0), C.c_int32(g1), C.c_int32(binned_ranks),
-              None if own_plan is None else C.byref(own_plan), C.byref(grads), _stream(device)),
-           "gsr_backward_geom_aux" if depth_chain else "gsr_backward_geom")
+    fn = _gsr.gsr_backward_geom_aux if depth_chain else _gsr.gsr_backward_geom
+    fn(desc, cam, g, _ptr(radii), _ptr(geom_ws), _ptr(screen_grads), g0, g1, binned_ranks, own_plan, grads, _stream(device))
 
 
 def camera_grad_workspace_size(desc: FrameDesc) -> int:
     """gsr_camera_grad_workspace_size: bytes of the per-block partial sums of gsr_backward_camera."""
-    b = C.c_size_t(0)
-    _check(load().gsr_camera_grad_workspace_size(C.byref(desc), C.byref(b)), "gsr_camera_grad_workspace_size")
-    return b.value
+    return _size(_gsr.gsr_camera_grad_workspace_size, desc)
 
 
 def backward_camera(desc, cam: Camera, g: Gaussians, radii, geom_ws, screen_grads, workspace, out: CameraGrads, device,
                     binned_ranks: int = -1, own_plan: Optional[FramePlan] = None, depth_chain: bool = False):
     """gsr_backward_camera, behind backward_geom of the same arguments (binned_ranks / own_plan / depth_chain as there)."""
-    _check(load().gsr_backward_camera(C.byref(desc), C.byref(cam), C.byref(g), _ptr(radii), _ptr(geom_ws), _ptr(screen_grads),
-                                      C.c_int32(binned_ranks), None if own_plan is None else C.byref(own_plan),
-                                      C.c_int32(int(bool(depth_chain))), _ptr(workspace), C.byref(out), _stream(device)),
-           "gsr_backward_camera")
+    _gsr.gsr_backward_camera(desc, cam, g, _ptr(radii), _ptr(geom_ws), _ptr(screen_grads), binned_ranks, own_plan, int(bool(depth_chain)),
+                             _ptr(workspace), out, _stream(device))
 
 
 def binned_prefix(plan: FramePlan) -> int:
@@ -374,8 +488,7 @@ def effective_binned_ranks(plan: FramePlan) -> int:
 
 def backward_geom_rows(desc, cam: Camera, g: Gaussians, radii, geom_ws, screen_grads, rows, grads: Grads, device):
     """Sparse geometry backward over the Gaussians listed in `rows` (int32 device tensor)."""
-    _check(load().gsr_backward_geom_rows(C.byref(desc), C.byref(cam), C.byref(g), _ptr(radii), _ptr(geom_ws), _ptr(screen_grads),
-                                         _ptr(rows), C.c_int32(rows.numel()), C.byref(grads), _stream(device)), "gsr_backward_geom_rows")
+    _gsr.gsr_backward_geom_rows(desc, cam, g, _ptr(radii), _ptr(geom_ws), _ptr(screen_grads), _ptr(rows), rows.numel(), grads, _stream(device))
 
 
 _frame_offsets = {}
@@ -387,7 +500,7 @@ def frame_arrays(desc, geom_ws):
     offs = _frame_offsets.get(P)
     if offs is None:
         k, o = C.c_void_p(), C.c_void_p()
-        _check(load().gsr_frame_arrays(C.byref(desc), _ptr(geom_ws), C.byref(k), C.byref(o)), "gsr_frame_arrays")
+        _gsr.gsr_frame_arrays(desc, _ptr(geom_ws), k, o)
         base = geom_ws.data_ptr()
         offs = _frame_offsets[P] = (int(k.value) - base, int(o.value) - base)
     return tuple(geom_ws[o:o + 4 * P].view(torch.int32) for o in offs)
@@ -400,26 +513,23 @@ def exchange_rows_gather(desc, geom_ws, key_max: int, screen, n_rows: int):
     # the sparse geometry backward; their packed rows are zero), not whatever the allocator left there
     rows = torch.full((n_rows,), -1, dtype=torch.int32, device=screen.device)
     packed = torch.zeros(n_rows, SCREEN_GRAD_STRIDE, dtype=torch.float32, device=screen.device)
-    _check(load().gsr_exchange_rows_gather(C.byref(desc), _ptr(geom_ws), C.c_uint32(int(key_max) & 0xFFFFFFFF), _ptr(screen), C.c_int32(n_rows),
-                                           _ptr(rows), _ptr(packed), _stream(screen.device)), "gsr_exchange_rows_gather")
+    _gsr.gsr_exchange_rows_gather(desc, _ptr(geom_ws), int(key_max) & 0xFFFFFFFF, _ptr(screen), n_rows, _ptr(rows), _ptr(packed),
+                                  _stream(screen.device))
     return rows, packed
 
 
 def exchange_rows_scatter(desc, rows, packed, screen):
-    _check(load().gsr_exchange_rows_scatter(C.byref(desc), C.c_int32(rows.numel()), _ptr(rows), _ptr(packed), _ptr(screen),
-                                            _stream(screen.device)), "gsr_exchange_rows_scatter")
+    _gsr.gsr_exchange_rows_scatter(desc, rows.numel(), _ptr(rows), _ptr(packed), _ptr(screen), _stream(screen.device))
 
 
 def mark_visible(means3D, viewmatrix, projmatrix, present):
-    _check(load().gsr_mark_visible(C.c_int32(means3D.shape[0]), _ptr(means3D), _ptr(viewmatrix), _ptr(projmatrix),
-                                   _ptr(present), _stream(means3D.device)), "gsr_mark_visible")
+    _gsr.gsr_mark_visible(means3D.shape[0], _ptr(means3D), _ptr(viewmatrix), _ptr(projmatrix), _ptr(present), _stream(means3D.device))
 
 
 def debug_views(desc, geom_ws, binning_ws, image_ws, plan: FramePlan) -> dict:
     """Intermediate arrays as torch views INTO the workspaces (tests / profiling)."""
     v = DebugViews()
-    _check(load().gsr_debug_get_views(C.byref(desc), _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws), C.byref(plan),
-                                      C.byref(v)), "gsr_debug_get_views")
+    _gsr.gsr_debug_get_views(desc, _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws), plan, v)
     P, N, R = desc.P, desc.width * desc.height, int(plan.binning_capacity or plan.num_rendered)
     Tn = ((desc.width + 15) // 16) * ((desc.height + 15) // 16)
 
@@ -451,12 +561,12 @@ def debug_views(desc, geom_ws, binning_ws, image_ws, plan: FramePlan) -> dict:
 
 def profile_enable(on: bool):
     """Per-kernel hipEvent timing inside the library (thread-local; resets the accumulators)."""
-    _check(load().gsr_profile_enable(C.c_int(int(on))), "gsr_profile_enable")
+    _gsr.gsr_profile_enable(int(on))
 
 
 def profile_read(n_max: int = 32) -> dict:
     """{kernel name: (total_ms, launches)} since profile_enable(True), up to n_max names; synchronises the recorded events."""
-    names = ((C.c_char * 32) * n_max)()
+    names = ((C.c_char * PROFILE_NAME_LEN) * n_max)()
     ms = (C.c_float * n_max)()
     cnt = (C.c_int32 * n_max)()
     n = load().gsr_profile_read(n_max, names, ms, cnt)
@@ -464,42 +574,32 @@ def profile_read(n_max: int = 32) -> dict:
 
 
 def loss_workspace_size(C_, H, W) -> int:
-    b = C.c_size_t(0)
-    _check(load().gsr_loss_workspace_size(C.c_int32(C_), C.c_int32(H), C.c_int32(W), C.byref(b)), "gsr_loss_workspace_size")
-    return b.value
+    return _size(_gsr.gsr_loss_workspace_size, C_, H, W)
 
 
 def loss_forward(image, target, lam, workspace, out3):
     Cn, H, W = image.shape
-    _check(load().gsr_loss_l1_ssim_forward(C.c_int32(Cn), C.c_int32(H), C.c_int32(W), C.c_float(lam), _ptr(image), _ptr(target),
-                                           _ptr(workspace), _ptr(out3), _stream(image.device)), "gsr_loss_l1_ssim_forward")
+    _gsr.gsr_loss_l1_ssim_forward(Cn, H, W, lam, _ptr(image), _ptr(target), _ptr(workspace), _ptr(out3), _stream(image.device))
 
 
 def loss_backward(image, target, lam, upstream, workspace, grad_image):
     Cn, H, W = image.shape
-    _check(load().gsr_loss_l1_ssim_backward(C.c_int32(Cn), C.c_int32(H), C.c_int32(W), C.c_float(lam), _ptr(upstream),
-                                            _ptr(image), _ptr(target), _ptr(workspace), _ptr(grad_image),
-                                            _stream(image.device)), "gsr_loss_l1_ssim_backward")
+    _gsr.gsr_loss_l1_ssim_backward(Cn, H, W, lam, _ptr(upstream), _ptr(image), _ptr(target), _ptr(workspace), _ptr(grad_image), _stream(image.device))
 
 
 def loss_l1_backward(image, target, upstream, grad_image):
-    _check(load().gsr_loss_l1_backward(C.c_int64(image.numel()), _ptr(upstream), _ptr(image), _ptr(target), _ptr(grad_image),
-                                       _stream(image.device)), "gsr_loss_l1_backward")
+    _gsr.gsr_loss_l1_backward(image.numel(), _ptr(upstream), _ptr(image), _ptr(target), _ptr(grad_image), _stream(image.device))
 
 
 def loss_forward_rows(image, target, workspace, out2, row_begin, row_end):
     Cn, H, W = image.shape
-    _check(load().gsr_loss_l1_ssim_forward_rows(C.c_int32(Cn), C.c_int32(H), C.c_int32(W), _ptr(image), _ptr(target),
-                                                _ptr(workspace), _ptr(out2), C.c_int32(row_begin), C.c_int32(row_end),
-                                                _stream(image.device)), "gsr_loss_l1_ssim_forward_rows")
+    _gsr.gsr_loss_l1_ssim_forward_rows(Cn, H, W, _ptr(image), _ptr(target), _ptr(workspace), _ptr(out2), row_begin, row_end, _stream(image.device))
 
 
 def loss_backward_rows(image, target, lam, upstream, workspace, grad_image, row_begin, row_end):
     Cn, H, W = image.shape
-    _check(load().gsr_loss_l1_ssim_backward_rows(C.c_int32(Cn), C.c_int32(H), C.c_int32(W), C.c_float(lam), _ptr(upstream),
-                                                 _ptr(image), _ptr(target), _ptr(workspace), _ptr(grad_image),
-                                                 C.c_int32(row_begin), C.c_int32(row_end), _stream(image.device)),
-           "gsr_loss_l1_ssim_backward_rows")
+    _gsr.gsr_loss_l1_ssim_backward_rows(Cn, H, W, lam, _ptr(upstream), _ptr(image), _ptr(target), _ptr(workspace), _ptr(grad_image),
+                                        row_begin, row_end, _stream(image.device))
 
 
 def debug_sort_pairs(keys: torch.Tensor, vals: torch.Tensor, end_bit: int, count_on_device: bool = False):
@@ -507,15 +607,11 @@ def debug_sort_pairs(keys: torch.Tensor, vals: torch.Tensor, end_bit: int, count
     n = keys.numel()
     k = [keys.contiguous().clone(), torch.empty_like(keys)]
     v = [vals.contiguous().clone(), torch.empty_like(vals)]
-    b = C.c_size_t(0)
-    _check(load().gsr_debug_sort_temp_bytes(C.byref(b)), "gsr_debug_sort_temp_bytes")
-    temp = torch.empty(b.value, dtype=torch.uint8, device=keys.device)
+    temp = torch.empty(_size(_gsr.gsr_debug_sort_temp_bytes), dtype=torch.uint8, device=keys.device)
     res = C.c_int32(0)
     with torch.cuda.device(keys.device):
-        _check(load().gsr_debug_sort_pairs(_ptr(k[0]) or C.c_void_p(temp.data_ptr()), _ptr(k[1]) or C.c_void_p(temp.data_ptr()),
-                                           _ptr(v[0]) or C.c_void_p(temp.data_ptr()), _ptr(v[1]) or C.c_void_p(temp.data_ptr()),
-                                           C.c_int64(n), C.c_int32(end_bit), C.c_int32(int(count_on_device)), _ptr(temp),
-                                           C.byref(res), _stream(keys.device)), "gsr_debug_sort_pairs")
+        _gsr.gsr_debug_sort_pairs(_ptr(k[0]) or temp.data_ptr(), _ptr(k[1]) or temp.data_ptr(), _ptr(v[0]) or temp.data_ptr(),
+                                  _ptr(v[1]) or temp.data_ptr(), n, end_bit, int(count_on_device), _ptr(temp), res, _stream(keys.device))
     return k[res.value], v[res.value]
 
 
@@ -536,14 +632,11 @@ def debug_sort_pairs_ex(keys: torch.Tensor, vals: torch.Tensor, end_bit: int, n_
         return [a, torch.full_like(a, -1)]
     k, v = pair(keys), pair(vals)
     v2 = pair(vals2) if vals2 is not None else [None, None]
-    b = C.c_size_t(0)
-    _check(load().gsr_debug_sort_temp_bytes(C.byref(b)), "gsr_debug_sort_temp_bytes")
-    temp = torch.empty(b.value, dtype=torch.uint8, device=keys.device)
+    temp = torch.empty(_size(_gsr.gsr_debug_sort_temp_bytes), dtype=torch.uint8, device=keys.device)
     res = C.c_int32(0)
     with torch.cuda.device(keys.device):
-        _check(load().gsr_debug_sort_pairs_ex(_ptr(k[0]), _ptr(k[1]), _ptr(v[0]), _ptr(v[1]), _ptr(v2[0]), _ptr(v2[1]), C.c_int64(n),
-                                              C.c_int64(n_max), C.c_int64(base), C.c_int32(end_bit), C.c_int32(int(even_passes)),
-                                              _ptr(temp), C.byref(res), _stream(keys.device)), "gsr_debug_sort_pairs_ex")
+        _gsr.gsr_debug_sort_pairs_ex(_ptr(k[0]), _ptr(k[1]), _ptr(v[0]), _ptr(v[1]), _ptr(v2[0]), _ptr(v2[1]), n, n_max, base, end_bit,
+                                     int(even_passes), _ptr(temp), res, _stream(keys.device))
     r = res.value
     out = lambda bufs: None if bufs[r] is None else bufs[r][base:base + n]
     return out(k), out(v), out(v2), r
@@ -556,35 +649,23 @@ def dist2_knn3(xyz: torch.Tensor) -> torch.Tensor:
     out = torch.zeros(P, dtype=torch.float32, device=pts.device)
     if P == 0:
         return out
-    b = C.c_size_t(0)
-    _check(load().gsr_dist2_workspace_size(C.c_int32(P), C.byref(b)), "gsr_dist2_workspace_size")
-    ws = torch.empty(b.value, dtype=torch.uint8, device=pts.device)
+    ws = torch.empty(_size(_gsr.gsr_dist2_workspace_size, P), dtype=torch.uint8, device=pts.device)
     with torch.cuda.device(pts.device):
-        _check(load().gsr_dist2_knn3(C.c_int32(P), _ptr(pts), _ptr(out), _ptr(ws), _stream(pts.device)), "gsr_dist2_knn3")
+        _gsr.gsr_dist2_knn3(P, _ptr(pts), _ptr(out), _ptr(ws), _stream(pts.device))
     return out
 
 
 def adam_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step):
-    _check(load().gsr_adam_step(C.c_int64(param.numel()), _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), C.c_float(lr),
-                                C.c_float(beta1), C.c_float(beta2), C.c_float(eps), C.c_int64(int(step)),
-                                _stream(param.device)), "gsr_adam_step")
+    _gsr.gsr_adam_step(param.numel(), _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), lr, beta1, beta2, eps, int(step),
+                       _stream(param.device))
 
 
 def adam_step_split(param, grad, exp_avg, exp_avg_sq, split, lr_head, lr_tail, beta1, beta2, eps, step):
     """param [rows, ...] contiguous; the first `split` elements of every row step with lr_head, the rest with lr_tail."""
     rows = param.shape[0]
     row_len = param.numel() // max(rows, 1)
-    _check(load().gsr_adam_step_split(C.c_int64(rows), C.c_int32(row_len), C.c_int32(int(split)), _ptr(param), _ptr(grad), _ptr(exp_avg),
-                                      _ptr(exp_avg_sq), C.c_float(lr_head), C.c_float(lr_tail), C.c_float(beta1), C.c_float(beta2),
-                                      C.c_float(eps), C.c_int64(int(step)), _stream(param.device)), "gsr_adam_step_split")
-
-
-class AdamTensor(C.Structure):
-    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("n", C.c_int64),
-                ("lr", C.c_float), ("lr_tail", C.c_float), ("step", C.c_int64), ("row_len", C.c_int32), ("split", C.c_int32)]
-
-
-ADAM_MAX_TENSORS = 8
+    _gsr.gsr_adam_step_split(rows, row_len, int(split), _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), lr_head, lr_tail, beta1,
+                             beta2, eps, int(step), _stream(param.device))
 
 
 def _adam_tensors(items):
@@ -594,16 +675,12 @@ def _adam_tensors(items):
     for a, (p, g, m, v, lr, lr_tail, step, row_len, split) in zip(arr, items):
         a.param, a.grad, a.exp_avg, a.exp_avg_sq, a.n = _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel()
         a.lr, a.lr_tail, a.step, a.row_len, a.split = float(lr), float(lr_tail), int(step), int(row_len), int(split)
-    return C.c_int32(len(items)), arr
+    return len(items), arr
 
 
 def adam_step_multi(items, beta1, beta2, eps):
     """The whole optimizer step in one launch; items: see _adam_tensors."""
-    _check(load().gsr_adam_step_multi(*_adam_tensors(items), C.c_float(beta1), C.c_float(beta2), C.c_float(eps),
-                                      _stream(items[0][0].device)), "gsr_adam_step_multi")
-
-
-ADAM_STEP_UNCORRECTED = 2 ** 63 - 1        # GSR_ADAM_STEP_UNCORRECTED: a `step` that applies no bias correction
+    _gsr.gsr_adam_step_multi(*_adam_tensors(items), beta1, beta2, eps, _stream(items[0][0].device))
 
 
 def adam_step_sparse_multi(items, visible, beta1, beta2, eps):
@@ -614,9 +691,8 @@ def adam_step_sparse_multi(items, visible, beta1, beta2, eps):
     if visible.device != items[0][0].device:
         raise ValueError(f"adam_step_sparse_multi: visible is on {visible.device}, the tensors on {items[0][0].device}")
     visible = visible.contiguous()
-    _check(load().gsr_adam_step_sparse_multi(*_adam_tensors(items), C.c_int64(visible.shape[0]), _ptr(visible),
-                                             C.c_int32(visible.element_size()), C.c_float(beta1), C.c_float(beta2), C.c_float(eps),
-                                             _stream(items[0][0].device)), "gsr_adam_step_sparse_multi")
+    _gsr.gsr_adam_step_sparse_multi(*_adam_tensors(items), visible.shape[0], _ptr(visible), visible.element_size(), beta1, beta2, eps,
+                                    _stream(items[0][0].device))
 
 
 def activations_forward(scaling_raw, rotation_raw, opacity_raw):
@@ -625,8 +701,8 @@ def activations_forward(scaling_raw, rotation_raw, opacity_raw):
     P = some.shape[0]
     outs = [None if t is None else torch.empty_like(t) for t in (scaling_raw, rotation_raw, opacity_raw)]
     with torch.cuda.device(some.device):
-        _check(load().gsr_activations_forward(C.c_int64(P), _ptr(scaling_raw), _ptr(rotation_raw), _ptr(opacity_raw), _ptr(outs[0]),
-                                              _ptr(outs[1]), _ptr(outs[2]), _stream(some.device)), "gsr_activations_forward")
+        _gsr.gsr_activations_forward(P, _ptr(scaling_raw), _ptr(rotation_raw), _ptr(opacity_raw), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
+                                     _stream(some.device))
     return tuple(outs)
 
 
@@ -636,15 +712,14 @@ def activations_backward(scales, rotation_raw, opacities, g_scales, g_rotations,
     P = some.shape[0]
     outs = [None if g is None else torch.empty_like(g) for g in (g_scales, g_rotations, g_opacities)]
     with torch.cuda.device(some.device):
-        _check(load().gsr_activations_backward(C.c_int64(P), _ptr(scales), _ptr(rotation_raw), _ptr(opacities), _ptr(g_scales),
-                                               _ptr(g_rotations), _ptr(g_opacities), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
-                                               _stream(some.device)), "gsr_activations_backward")
+        _gsr.gsr_activations_backward(P, _ptr(scales), _ptr(rotation_raw), _ptr(opacities), _ptr(g_scales), _ptr(g_rotations),
+                                      _ptr(g_opacities), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _stream(some.device))
     return tuple(outs)
 
 
 def densify_stats(radii, viewspace_grad, max_radii2D, xyz_gradient_accum, denom):
-    _check(load().gsr_densify_stats(C.c_int32(radii.shape[0]), _ptr(radii), _ptr(viewspace_grad), _ptr(max_radii2D),
-                                    _ptr(xyz_gradient_accum), _ptr(denom), _stream(radii.device)), "gsr_densify_stats")
+    _gsr.gsr_densify_stats(radii.shape[0], _ptr(radii), _ptr(viewspace_grad), _ptr(max_radii2D), _ptr(xyz_gradient_accum), _ptr(denom),
+                           _stream(radii.device))
 
 
 def structured_compose_forward(decoded, means, opacities, scales, rotations, K: int, sh_coeffs: int):
@@ -658,8 +733,7 @@ def structured_compose_forward(decoded, means, opacities, scales, rotations, K: 
     st = Structures(_ptr(means), _ptr(opacities), _ptr(scales), _ptr(rotations))
     ch = Children(*(_ptr(t) for t in outs))
     with torch.cuda.device(decoded.device):
-        _check(load().gsr_structured_compose_forward(C.byref(desc), _ptr(decoded), C.byref(st), C.byref(ch), _stream(decoded.device)),
-               "gsr_structured_compose_forward")
+        _gsr.gsr_structured_compose_forward(desc, _ptr(decoded), st, ch, _stream(decoded.device))
     return outs
 
 
@@ -674,8 +748,7 @@ def structured_compose_backward(decoded, means, opacities, scales, rotations, K:
     gin = ChildrenGrads(*(_ptr(g) for g in grads_in))
     gout = StructuredGrads(*(_ptr(t) for t in outs))
     with torch.cuda.device(decoded.device):
-        _check(load().gsr_structured_compose_backward(C.byref(desc), _ptr(decoded), C.byref(st), C.byref(gin), C.byref(gout),
-                                                      _stream(decoded.device)), "gsr_structured_compose_backward")
+        _gsr.gsr_structured_compose_backward(desc, _ptr(decoded), st, gin, gout, _stream(decoded.device))
     return tuple(outs)
 
 
@@ -688,8 +761,7 @@ def opacity_compensation_forward(desc: FrameDesc, viewmatrix, means3D, opacities
     cam = Camera(None, _ptr(viewmatrix), None, None)
     g = Gaussians(_ptr(means3D), None, None, _ptr(opacities), _ptr(scales), _ptr(rotations), None, None, 2 if raw else 0)
     with torch.cuda.device(means3D.device):
-        _check(load().gsr_opacity_compensation_forward(C.byref(desc), C.byref(cam), C.byref(g), _ptr(out), _stream(means3D.device)),
-               "gsr_opacity_compensation_forward")
+        _gsr.gsr_opacity_compensation_forward(desc, cam, g, _ptr(out), _stream(means3D.device))
     return out
 
 
@@ -703,8 +775,7 @@ def opacity_compensation_backward(desc: FrameDesc, viewmatrix, means3D, opacitie
     g = Gaussians(_ptr(means3D), None, None, _ptr(opacities), _ptr(scales), _ptr(rotations), None, None, 2 if raw else 0)
     grads = Grads(_ptr(outs[1]), None, None, None, _ptr(outs[0]), _ptr(outs[2]), _ptr(outs[3]), None, None, 0)
     with torch.cuda.device(means3D.device):
-        _check(load().gsr_opacity_compensation_backward(C.byref(desc), C.byref(cam), C.byref(g), _ptr(grad_out), C.byref(grads),
-                                                        _stream(means3D.device)), "gsr_opacity_compensation_backward")
+        _gsr.gsr_opacity_compensation_backward(desc, cam, g, _ptr(grad_out), grads, _stream(means3D.device))
     return tuple(outs)
 
 
@@ -714,9 +785,7 @@ def decoder_desc(latents, w0, w2) -> DecoderDesc:
 
 
 def decoder_workspace_size(desc: DecoderDesc) -> int:
-    b = C.c_size_t(0)
-    _check(load().gsr_decoder_workspace_size(C.byref(desc), C.byref(b)), "gsr_decoder_workspace_size")
-    return b.value
+    return _size(_gsr.gsr_decoder_workspace_size, desc)
 
 
 def decoder_forward(pos_emb, latents, params):
@@ -726,8 +795,7 @@ def decoder_forward(pos_emb, latents, params):
     decoded = torch.empty(desc.B, desc.out_size, dtype=torch.float32, device=latents.device)
     pr = DecoderParams(*(_ptr(t) for t in params))
     with torch.cuda.device(latents.device):
-        _check(load().gsr_decoder_forward(C.byref(desc), _ptr(pos_emb), _ptr(latents), C.byref(pr), _ptr(decoded),
-                                          _stream(latents.device)), "gsr_decoder_forward")
+        _gsr.gsr_decoder_forward(desc, _ptr(pos_emb), _ptr(latents), pr, _ptr(decoded), _stream(latents.device))
     return decoded
 
 
@@ -747,18 +815,8 @@ def decoder_backward(pos_emb, latents, params, d_decoded, want):
     pr = DecoderParams(*(_ptr(t) for t in params))
     gr = DecoderGrads(*(_ptr(t) for t in outs))
     with torch.cuda.device(latents.device):
-        _check(load().gsr_decoder_backward(C.byref(desc), _ptr(pos_emb), _ptr(latents), C.byref(pr), _ptr(d_decoded), C.byref(gr),
-                                           _ptr(ws), C.c_size_t(nbytes), _stream(latents.device)), "gsr_decoder_backward")
+        _gsr.gsr_decoder_backward(desc, _ptr(pos_emb), _ptr(latents), pr, _ptr(d_decoded), gr, _ptr(ws), nbytes, _stream(latents.device))
     return tuple(outs)
-
-
-class McmcTensor(C.Structure):
-    """gsr_mcmc_tensor: a [P, width] tensor, its Adam moments (both or neither None) and its role."""
-    _fields_ = [("param", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("width", C.c_int32), ("role", C.c_int32)]
-
-
-MCMC_MAX_TENSORS = 8
-MCMC_ROLES = {"copy": 0, "opacity": 1, "scaling": 2}
 
 
 def mcmc_relocation(opacity_raw, scaling_raw, sampled, min_opacity: float):
@@ -767,15 +825,13 @@ def mcmc_relocation(opacity_raw, scaling_raw, sampled, min_opacity: float):
     P, n = int(opacity_raw.shape[0]), int(sampled.shape[0])
     new_o = torch.empty(n, dtype=torch.float32, device=opacity_raw.device)
     new_s = torch.empty(n, 3, dtype=torch.float32, device=opacity_raw.device)
-    b = C.c_size_t(0)
-    _check(load().gsr_mcmc_relocation_workspace_size(C.c_int64(P), C.byref(b)), "gsr_mcmc_relocation_workspace_size")
+    nbytes = _size(_gsr.gsr_mcmc_relocation_workspace_size, P)
     if P == 0 or n == 0:
         return new_o, new_s
-    ws = torch.empty(b.value, dtype=torch.uint8, device=opacity_raw.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=opacity_raw.device)
     with torch.cuda.device(opacity_raw.device):
-        _check(load().gsr_mcmc_relocation(C.c_int64(P), C.c_int64(n), _ptr(opacity_raw), _ptr(scaling_raw), _ptr(sampled),
-                                          C.c_float(min_opacity), _ptr(ws), _ptr(new_o), _ptr(new_s), _stream(opacity_raw.device)),
-               "gsr_mcmc_relocation")
+        _gsr.gsr_mcmc_relocation(P, n, _ptr(opacity_raw), _ptr(scaling_raw), _ptr(sampled), min_opacity, _ptr(ws), _ptr(new_o), _ptr(new_s),
+                                 _stream(opacity_raw.device))
     return new_o, new_s
 
 
@@ -788,15 +844,15 @@ def mcmc_relocate_rows(items, P: int, sampled, dead, new_opacity_raw, new_scalin
         a.width, a.role = p.numel() // max(int(p.shape[0]), 1), MCMC_ROLES[role]
     dev = sampled.device
     with torch.cuda.device(dev):
-        _check(load().gsr_mcmc_relocate_rows(C.c_int32(len(items)), arr, C.c_int64(int(P)), C.c_int64(int(sampled.shape[0])), _ptr(sampled),
-                                             _ptr(dead), _ptr(new_opacity_raw), _ptr(new_scaling_raw), _stream(dev)), "gsr_mcmc_relocate_rows")
+        _gsr.gsr_mcmc_relocate_rows(len(items), arr, int(P), int(sampled.shape[0]), _ptr(sampled), _ptr(dead), _ptr(new_opacity_raw),
+                                    _ptr(new_scaling_raw), _stream(dev))
 
 
 def mcmc_inject_noise(xyz, scaling_raw, rotation_raw, opacity_raw, noise, c: float):
     """gsr_mcmc_inject_noise: in place on xyz [P,3]; all tensors contiguous fp32 on one device."""
     with torch.cuda.device(xyz.device):
-        _check(load().gsr_mcmc_inject_noise(C.c_int64(int(xyz.shape[0])), _ptr(xyz), _ptr(scaling_raw), _ptr(rotation_raw), _ptr(opacity_raw),
-                                            _ptr(noise), C.c_float(c), _stream(xyz.device)), "gsr_mcmc_inject_noise")
+        _gsr.gsr_mcmc_inject_noise(int(xyz.shape[0]), _ptr(xyz), _ptr(scaling_raw), _ptr(rotation_raw), _ptr(opacity_raw), _ptr(noise), c,
+                                   _stream(xyz.device))
 
 
 def mcmc_reg_grads(opacity_raw, scaling_raw, lambda_opacity: float, lambda_scale: float, grad_opacity, grad_scaling):
@@ -806,8 +862,8 @@ def mcmc_reg_grads(opacity_raw, scaling_raw, lambda_opacity: float, lambda_scale
         return
     P = int(some.shape[0])
     with torch.cuda.device(some.device):
-        _check(load().gsr_mcmc_reg_grads(C.c_int64(P), _ptr(opacity_raw), _ptr(scaling_raw), C.c_float(lambda_opacity), C.c_float(lambda_scale),
-                                         _ptr(grad_opacity), _ptr(grad_scaling), _stream(some.device)), "gsr_mcmc_reg_grads")
+        _gsr.gsr_mcmc_reg_grads(P, _ptr(opacity_raw), _ptr(scaling_raw), lambda_opacity, lambda_scale, _ptr(grad_opacity), _ptr(grad_scaling),
+                                _stream(some.device))
 
 
 def _bilagrid_dims(grids):
@@ -819,10 +875,7 @@ def _bilagrid_dims(grids):
 
 def bilagrid_workspace_sizes(H: int, W: int, L: int, Gy: int, Gx: int):
     """gsr_bilagrid_workspace_size -> (bytes of the backward's per-block partial sums, bytes of the TV workspace)."""
-    b, t = C.c_size_t(0), C.c_size_t(0)
-    _check(load().gsr_bilagrid_workspace_size(C.c_int32(H), C.c_int32(W), C.c_int32(L), C.c_int32(Gy), C.c_int32(Gx), C.byref(b), C.byref(t)),
-           "gsr_bilagrid_workspace_size")
-    return b.value, t.value
+    return _size2(_gsr.gsr_bilagrid_workspace_size, H, W, L, Gy, Gx)
 
 
 def bilagrid_forward(grids, image, idx: int):
@@ -831,8 +884,7 @@ def bilagrid_forward(grids, image, idx: int):
     H, W = int(image.shape[1]), int(image.shape[2])
     out = torch.empty_like(image)
     with torch.cuda.device(image.device):
-        _check(load().gsr_bilagrid_forward(C.c_int32(N), C.c_int32(L), C.c_int32(Gy), C.c_int32(Gx), C.c_int32(H), C.c_int32(W), C.c_int32(int(idx)),
-                                           _ptr(grids), _ptr(image), _ptr(out), _stream(image.device)), "gsr_bilagrid_forward")
+        _gsr.gsr_bilagrid_forward(N, L, Gy, Gx, H, W, int(idx), _ptr(grids), _ptr(image), _ptr(out), _stream(image.device))
     return out
 
 
@@ -850,9 +902,8 @@ def bilagrid_backward(grids, image, idx: int, grad_out, want_grids: bool, want_i
         nbytes = bilagrid_workspace_sizes(H, W, L, Gy, Gx)[0]
         ws = torch.empty(nbytes, dtype=torch.uint8, device=image.device)
     with torch.cuda.device(image.device):
-        _check(load().gsr_bilagrid_backward(C.c_int32(N), C.c_int32(L), C.c_int32(Gy), C.c_int32(Gx), C.c_int32(H), C.c_int32(W), C.c_int32(int(idx)),
-                                            _ptr(grids), _ptr(image), _ptr(grad_out), _ptr(dgrids), _ptr(dimage), _ptr(ws), C.c_size_t(nbytes),
-                                            _stream(image.device)), "gsr_bilagrid_backward")
+        _gsr.gsr_bilagrid_backward(N, L, Gy, Gx, H, W, int(idx), _ptr(grids), _ptr(image), _ptr(grad_out), _ptr(dgrids), _ptr(dimage), _ptr(ws),
+                                   nbytes, _stream(image.device))
     return dgrids, dimage
 
 
@@ -874,8 +925,7 @@ def bilagrid_tv_forward(grids):
     out = torch.empty(1, dtype=torch.float32, device=grids.device)
     ws = _bilagrid_tv_workspace(grids.device)
     with torch.cuda.device(grids.device):
-        _check(load().gsr_bilagrid_tv_forward(C.c_int32(N), C.c_int32(L), C.c_int32(Gy), C.c_int32(Gx), _ptr(grids), _ptr(ws), _ptr(out),
-                                              _stream(grids.device)), "gsr_bilagrid_tv_forward")
+        _gsr.gsr_bilagrid_tv_forward(N, L, Gy, Gx, _ptr(grids), _ptr(ws), _ptr(out), _stream(grids.device))
     return out.reshape(())
 
 
@@ -884,16 +934,13 @@ def bilagrid_tv_backward(grids, grad_out):
     N, L, Gy, Gx = _bilagrid_dims(grids)
     dgrids = torch.empty_like(grids)
     with torch.cuda.device(grids.device):
-        _check(load().gsr_bilagrid_tv_backward(C.c_int32(N), C.c_int32(L), C.c_int32(Gy), C.c_int32(Gx), _ptr(grids), _ptr(grad_out), _ptr(dgrids),
-                                               _stream(grids.device)), "gsr_bilagrid_tv_backward")
+        _gsr.gsr_bilagrid_tv_backward(N, L, Gy, Gx, _ptr(grids), _ptr(grad_out), _ptr(dgrids), _stream(grids.device))
     return dgrids
 
 
 def vq_workspace_size(P: int, K: int, D: int) -> int:
     """gsr_vq_workspace_size: bytes of scratch gsr_vq_assign and gsr_vq_update need (one size serves both)."""
-    b = C.c_size_t(0)
-    _check(load().gsr_vq_workspace_size(C.c_int64(int(P)), C.c_int32(int(K)), C.c_int32(int(D)), C.byref(b)), "gsr_vq_workspace_size")
-    return b.value
+    return _size(_gsr.gsr_vq_workspace_size, int(P), int(K), int(D))
 
 
 def vq_assign(x, codebook):
@@ -907,8 +954,7 @@ def vq_assign(x, codebook):
         return idx, dist2
     with torch.cuda.device(x.device):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        _check(load().gsr_vq_assign(C.c_int64(P), C.c_int32(K), C.c_int32(D), _ptr(x), _ptr(codebook), _ptr(idx), _ptr(dist2), _ptr(ws),
-                                    C.c_size_t(nbytes), _stream(x.device)), "gsr_vq_assign")
+        _gsr.gsr_vq_assign(P, K, D, _ptr(x), _ptr(codebook), _ptr(idx), _ptr(dist2), _ptr(ws), nbytes, _stream(x.device))
     return idx, dist2
 
 
@@ -921,8 +967,7 @@ def vq_update(x, idx, codebook):
     counts = torch.empty(K, dtype=torch.int32, device=codebook.device)
     with torch.cuda.device(codebook.device):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=codebook.device)
-        _check(load().gsr_vq_update(C.c_int64(P), C.c_int32(K), C.c_int32(D), _ptr(x), _ptr(idx), _ptr(codebook), _ptr(out), _ptr(counts),
-                                    _ptr(ws), C.c_size_t(nbytes), _stream(codebook.device)), "gsr_vq_update")
+        _gsr.gsr_vq_update(P, K, D, _ptr(x), _ptr(idx), _ptr(codebook), _ptr(out), _ptr(counts), _ptr(ws), nbytes, _stream(codebook.device))
     return out, counts
 
 
@@ -932,13 +977,11 @@ def filter3d_compute(xyz, cameras, focal_max: float):
     synchronisation."""
     P, Cn = int(xyz.shape[0]), int(cameras.shape[0])
     out = torch.empty(P, 1, dtype=torch.float32, device=xyz.device)
-    b = C.c_size_t(0)
-    _check(load().gsr_filter3d_workspace_size(C.c_int64(P), C.byref(b)), "gsr_filter3d_workspace_size")
+    nbytes = _size(_gsr.gsr_filter3d_workspace_size, P)
     seen = C.c_int32(0)
     with torch.cuda.device(xyz.device):
-        ws = torch.empty(b.value, dtype=torch.uint8, device=xyz.device)
-        _check(load().gsr_filter3d_compute(C.c_int64(P), C.c_int32(Cn), _ptr(cameras), C.c_float(focal_max), _ptr(xyz), _ptr(out), _ptr(ws),
-                                           C.c_size_t(b.value), C.byref(seen), _stream(xyz.device)), "gsr_filter3d_compute")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=xyz.device)
+        _gsr.gsr_filter3d_compute(P, Cn, _ptr(cameras), focal_max, _ptr(xyz), _ptr(out), _ptr(ws), nbytes, seen, _stream(xyz.device))
     return out, bool(seen.value)
 
 
@@ -948,8 +991,8 @@ def filter3d_apply_forward(opacities, scales, filter_3D, raw: bool):
     P = int(scales.shape[0])
     o_out, s_out = torch.empty_like(opacities), torch.empty_like(scales)
     with torch.cuda.device(scales.device):
-        _check(load().gsr_filter3d_apply_forward(C.c_int64(P), C.c_int32(int(bool(raw))), _ptr(opacities), _ptr(scales), _ptr(filter_3D),
-                                                 _ptr(o_out), _ptr(s_out), _stream(scales.device)), "gsr_filter3d_apply_forward")
+        _gsr.gsr_filter3d_apply_forward(P, int(bool(raw)), _ptr(opacities), _ptr(scales), _ptr(filter_3D), _ptr(o_out), _ptr(s_out),
+                                        _stream(scales.device))
     return o_out, s_out
 
 
@@ -961,7 +1004,6 @@ def filter3d_apply_backward(opacities, scales, filter_3D, raw: bool, grad_opacit
     if P == 0 or not any(want):
         return tuple(outs)
     with torch.cuda.device(scales.device):
-        _check(load().gsr_filter3d_apply_backward(C.c_int64(P), C.c_int32(int(bool(raw))), _ptr(opacities), _ptr(scales), _ptr(filter_3D),
-                                                  _ptr(grad_opacities_out), _ptr(grad_scales_out), _ptr(outs[0]), _ptr(outs[1]),
-                                                  _stream(scales.device)), "gsr_filter3d_apply_backward")
+        _gsr.gsr_filter3d_apply_backward(P, int(bool(raw)), _ptr(opacities), _ptr(scales), _ptr(filter_3D), _ptr(grad_opacities_out),
+                                         _ptr(grad_scales_out), _ptr(outs[0]), _ptr(outs[1]), _stream(scales.device))
     return tuple(outs)

@@ -392,12 +392,12 @@ def test_native_binding_passes_the_tensors_stream_to_every_call():
 def test_selfcheck_native_binding_violations_are_reported():
     with open(NATIVE_PY) as f:
         text = f.read()
-    one = "_ptr(out), _ptr(ws), _stream(pts.device)), \"gsr_dist2_knn3\")"
+    one = "_gsr.gsr_dist2_knn3(P, _ptr(pts), _ptr(out), _ptr(ws), _stream(pts.device))"
     assert text.count(one) == 1
-    for new in ("_ptr(out), _ptr(ws), None), \"gsr_dist2_knn3\")",
-                "_ptr(out), _ptr(ws), _stream(None)), \"gsr_dist2_knn3\")",
-                "_ptr(out), _ptr(ws), _stream(torch.device('cuda:0'))), \"gsr_dist2_knn3\")",
-                "_ptr(out), _ptr(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream)), \"gsr_dist2_knn3\")"):
+    for new in ("_gsr.gsr_dist2_knn3(P, _ptr(pts), _ptr(out), _ptr(ws), None)",
+                "_gsr.gsr_dist2_knn3(P, _ptr(pts), _ptr(out), _ptr(ws), _stream(None))",
+                "_gsr.gsr_dist2_knn3(P, _ptr(pts), _ptr(out), _ptr(ws), _stream(torch.device('cuda:0')))",
+                "_gsr.gsr_dist2_knn3(P, _ptr(pts), _ptr(out), _ptr(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream))"):
         bad, _ = check_native_py(text.replace(one, new))
         assert bad and any("gsr_dist2_knn3" in b or "current_stream" in b for b in bad), (new, bad)
 
