@@ -20,7 +20,7 @@ from collections import defaultdict
 
 # kernel-name prefix (demangled, as rocprofv3 prints it) -> key used in bench.py's "kernels" table
 NAMES = {
-    "gsr::k_render_bwd": "render_bwd", "gsr::k_render_fwd": "render_fwd", "void gsr::k_geom_bwd<": "geom_bwd",
+    "void gsr::k_render_bwd<": "render_bwd", "void gsr::k_render_fwd<": "render_fwd", "void gsr::k_geom_bwd<": "geom_bwd",
     "void gsr::k_geom_bwd_sparse<": "geom_bwd", "void gsr::k_preprocess<": "preprocess",
     "void gsr::k_reduce_rows<": "reduce_rows", "void gsr::k_loss_fwd<": "loss_fwd", "void gsr::k_loss_bwd<": "loss_bwd",
     "void gsr::k_emit_team<": "emit", "void gsr::k_count_team<": "count_open", "void gsr::k_bin_chunk<false>": "count_open",

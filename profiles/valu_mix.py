@@ -22,7 +22,7 @@ import re
 import sys
 from collections import defaultdict
 
-KERNELS = {"gsr::k_render_bwd": "render_bwd", "gsr::k_render_fwd": "render_fwd"}
+KERNELS = {"void gsr::k_render_bwd<": "render_bwd", "void gsr::k_render_fwd<": "render_fwd"}
 WORKLOAD = "cfg3"
 SKIP_FIRST = 3
 

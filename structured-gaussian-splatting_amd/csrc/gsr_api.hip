@@ -356,61 +356,58 @@ int gsr_forward_preprocess(const gsr_frame_desc *desc, const gsr_camera *cam, co
     return GSR_OK;
 }
 
-// fill (optional): a zero fill to enqueue behind the FIRST chunk's blend and readback kernels, ahead of the wait for that readback
-// (gsr_forward's early fill); *fill_done reports whether it was enqueued
-// aux (optional): the depth / alpha outputs (gsr_forward_render_aux)
-// stats (optional, without aux): the per-Gaussian blend statistics (gsr_forward_render_contrib), added by every chunk's blend
-// What gsr_forward_render_contrib / gsr_forward_contrib ask of their arguments beyond the plain calls, checked on the host alone
-static int validate_contrib(const gsr_frame_desc *desc, const gsr_contrib_stats *stats, const char *who)
+// What the _contrib and _contrib_error calls ask of their arguments beyond the plain calls (stats and err NULL: nothing), checked on the
+// host alone.  who: the _contrib entry point; with err it is the _contrib_error one
+static int validate_contrib(const gsr_frame_desc *desc, const gsr_contrib_stats *stats, const gsr_contrib_error *err, const char *who)
 {
     int rc = validate(desc);
-    if (rc || !stats) return rc;
+    if (rc || (!stats && !err)) return rc;
+    const char *sfx = err ? "_error" : "";
+    if (!stats) {
+        set_error("%s%s: err without stats: the error-weighted total is taken beside the blend statistics (stats is required)", who, sfx);
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
     const FrameK f = make_frame(*desc);
     if (f.ty0 != 0 || f.ty1 != f.Gy) {
-        set_error("%s: the blend statistics are taken over whole images only (tile_row_begin = tile_row_end = 0)", who);
+        set_error("%s%s: the %s statistics are taken over whole images only (tile_row_begin = tile_row_end = 0)", who, sfx,
+                  err ? "error-weighted" : "blend");
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if (desc->P > 0 && err && !err->pixel_error) {
+        set_error("%s%s: err->pixel_error is required ([H*W])", who, sfx);
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    if (desc->P > 0 && err && !err->error_frame_q32) {
+        set_error("%s%s: err->error_frame_q32 is required ([P])", who, sfx);
         return GSR_ERR_INVALID_ARGUMENT;
     }
     if (desc->P > 0 && (!stats->count || !stats->weight_sum_q32 || !stats->weight_max_bits)) {
-        set_error("%s: stats->count, ->weight_sum_q32 and ->weight_max_bits are required ([P] each)", who);
+        set_error("%s%s: stats->count, ->weight_sum_q32 and ->weight_max_bits are required ([P] each)", who, sfx);
         return GSR_ERR_INVALID_ARGUMENT;
     }
     return GSR_OK;
 }
 
-// What the _contrib_error calls ask beyond that (err non-NULL; err NULL: nothing, they are the _contrib calls), on the host alone
-static int validate_contrib_error(const gsr_frame_desc *desc, const gsr_contrib_stats *stats, const gsr_contrib_error *err, const char *who)
+// The aux workspace of a frame: the caller's maps, and the checkpoints carved from its ckpt_ws (binned = false: the frame has no list
+// entries, the checkpoints are never touched)
+static AuxWS aux_workspace(const gsr_aux_outputs *aux_out, bool binned, int64_t capacity, const FrameK &f)
 {
-    if (!err) return GSR_OK;
-    int rc = validate(desc);
-    if (rc) return rc;
-    if (!stats) {
-        set_error("%s: err without stats: the error-weighted total is taken beside the blend statistics (stats is required)", who);
-        return GSR_ERR_INVALID_ARGUMENT;
-    }
-    const FrameK f = make_frame(*desc);
-    if (f.ty0 != 0 || f.ty1 != f.Gy) {
-        set_error("%s: the error-weighted statistics are taken over whole images only (tile_row_begin = tile_row_end = 0)", who);
-        return GSR_ERR_INVALID_ARGUMENT;
-    }
-    if (desc->P > 0 && !err->pixel_error) {
-        set_error("%s: err->pixel_error is required ([H*W])", who);
-        return GSR_ERR_INVALID_ARGUMENT;
-    }
-    if (desc->P > 0 && !err->error_frame_q32) {
-        set_error("%s: err->error_frame_q32 is required ([P])", who);
-        return GSR_ERR_INVALID_ARGUMENT;
-    }
-    return GSR_OK;
+    AuxWS ax = carve_aux(aux_out && binned ? aux_out->ckpt_ws : nullptr, capacity, f);
+    if (aux_out) { ax.depth = aux_out->depth; ax.alpha = aux_out->alpha; }
+    return ax;
 }
 
+// The variant of a frame as the _aux, _contrib and _contrib_error entry points receive it (FwdVariant once the aux workspace is carved)
+struct FwdArgs { const gsr_aux_outputs *aux = nullptr; const gsr_contrib_stats *stats = nullptr; const gsr_contrib_error *err = nullptr; };
+
+// fill (optional): a zero fill to enqueue behind the FIRST chunk's blend and readback kernels, ahead of the wait for that readback
+// (gsr_forward's early fill); *fill_done reports whether it was enqueued
 static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *binning_ws,
                                void *image_ws, gsr_frame_plan *plan, float *out_color, void *stream, const ZeroSegs *fill, bool *fill_done,
-                               const gsr_aux_outputs *aux_out = nullptr, const gsr_contrib_stats *stats = nullptr,
-                               const gsr_contrib_error *err = nullptr)
+                               const FwdArgs &v)
 {
-    int rc = validate_contrib_error(desc, stats, err, "gsr_forward_render_contrib_error");
+    int rc = validate_contrib(desc, v.stats, v.err, "gsr_forward_render_contrib");
     if (rc) return rc;
-    if ((rc = validate_contrib(desc, stats, err ? "gsr_forward_render_contrib_error" : "gsr_forward_render_contrib"))) return rc;
     if ((rc = validate_inputs(desc, cam, g))) return rc;
     if (!cam || !cam->bg || !image_ws || !out_color || !plan || plan->num_rendered < 0 ||
         (desc->P > 0 && !geom_ws) || (plan->num_rendered > 0 && !binning_ws)) {
@@ -422,7 +419,7 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
     const bool dbg = desc->debug != 0;
     const FrameK f = make_frame(*desc);
     ImageWS iw = carve_image(image_ws, f);
-    if (aux_out && (!aux_out->depth || !aux_out->alpha || (plan->num_rendered > 0 && !aux_out->ckpt_ws) || f.ty0 != 0 || f.ty1 != f.Gy)) {
+    if (v.aux && (!v.aux->depth || !v.aux->alpha || (plan->num_rendered > 0 && !v.aux->ckpt_ws) || f.ty0 != 0 || f.ty1 != f.Gy)) {
         set_error("gsr_forward_render_aux: depth, alpha and (for a frame that bins anything) ckpt_ws are required; whole images only");
         return GSR_ERR_INVALID_ARGUMENT;
     }
@@ -433,11 +430,10 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
         BinningWS bw0 = carve_binning(binning_ws, 0, f);
         if (f.P == 0 || !geom_ws) gw0.ctrl = iw.ctrl_scratch;   // no geometry workspace at all
         if ((rc = launch_binning_init(f, gw0, iw, dbg, s))) return rc;
-        AuxWS ax0 = carve_aux(nullptr, 0, f);          // (no list entries: the checkpoints are never touched)
-        if (aux_out) { ax0.depth = aux_out->depth; ax0.alpha = aux_out->alpha; ax0.ckpt = ax0.ckpt_start = nullptr; }
+        const AuxWS ax0 = aux_workspace(v.aux, false, 0, f);
         // (err is not handed on: nothing is blended, every error total is zero, and with P == 0 the caller may have passed no map -
         // the error kernel would load it at tile start whatever the ranges hold)
-        if ((rc = launch_render_fwd(f, *cam, 0, true, 0, gw0, bw0, iw, out_color, dbg, s, false, aux_out ? &ax0 : nullptr, stats))) return rc;
+        if ((rc = launch_render_fwd(f, *cam, 0, true, 0, gw0, bw0, iw, out_color, dbg, s, false, {v.aux ? &ax0 : nullptr, v.stats, nullptr}))) return rc;
         plan->chunks_run = 1;
         return GSR_OK;
     }
@@ -448,8 +444,8 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
     // GSR_ERR_WORKSPACE before anything of that chunk is written (re-run this stage with a workspace for R instances).
     const int64_t capacity = plan_capacity(plan);
     BinningWS bw = carve_binning(binning_ws, capacity, f);
-    AuxWS ax = carve_aux(aux_out ? aux_out->ckpt_ws : nullptr, capacity, f);
-    if (aux_out) { ax.depth = aux_out->depth; ax.alpha = aux_out->alpha; }
+    const AuxWS ax = aux_workspace(v.aux, true, capacity, f);
+    const FwdVariant variant{v.aux ? &ax : nullptr, v.stats, v.err};
     if (!plan->binning_initialised && (rc = launch_binning_init(f, gw, iw, dbg, s))) return rc;
     plan->binning_initialised = 0;                  // a re-run of this stage must reset the tile ranges / open flags itself
     int sort_result = 0;
@@ -522,7 +518,7 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
         // small splats (fewer than 4.5 tiles per Gaussian on average; filtered chunks bin a small, unknown part of their bound):
         // the blend forward with one 16-lane group per quadrant
         const bool small_splats = kFwdGroups >= 0 ? kFwdGroups != 0 : (!((plan->chunks_filtered >> c) & 1) && chunk_n > 0 && chunk_max * 2 < chunk_n * 9);
-        if ((rc = launch_render_fwd(f, *cam, c, last, sort_result, gw, bw, iw, out_color, dbg, s, small_splats, aux_out ? &ax : nullptr, stats, err))) return rc;
+        if ((rc = launch_render_fwd(f, *cam, c, last, sort_result, gw, bw, iw, out_color, dbg, s, small_splats, variant))) return rc;
         plan->chunks_run = c + 1;
         plan->instances_emitted = -1;                 // the last chunk's count stays on the device
         if (last) break;
@@ -549,17 +545,15 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
 int gsr_forward_render(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *binning_ws,
                        void *image_ws, gsr_frame_plan *plan, float *out_color, void *stream)
 {
-    bool unused = false;
-    return forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, nullptr, &unused);
+    return forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, nullptr, nullptr, {});
 }
 
 static int forward_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *image_ws, int32_t *radii,
                         gsr_frame_plan *plan, void *binning_ws, int64_t binning_capacity, float *out_color, gsr_grads *early_fill, void *stream,
-                        const gsr_aux_outputs *aux, const gsr_contrib_stats *stats = nullptr, const gsr_contrib_error *err = nullptr)
+                        const FwdArgs &v)
 {
-    int rc = validate_contrib_error(desc, stats, err, "gsr_forward_contrib_error");      // (before stage 1: a refused call launches nothing)
+    int rc = validate_contrib(desc, v.stats, v.err, "gsr_forward_contrib");      // (before stage 1: a refused call launches nothing)
     if (rc) return rc;
-    if ((rc = validate_contrib(desc, stats, err ? "gsr_forward_contrib_error" : "gsr_forward_contrib"))) return rc;
     if ((rc = gsr_forward_preprocess(desc, cam, g, geom_ws, image_ws, radii, plan, stream))) return rc;
     int64_t need = 0;
     if ((rc = gsr_binning_first_chunk_capacity(plan, &need))) return rc;
@@ -588,8 +582,7 @@ static int forward_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const
         const BinningWS bw = carve_binning(binning_ws, cap, f);
         fill = zero_segments(f, *g, nullptr, *early_fill, bw.row_valid, row_flag_bytes(cap));
     }
-    if ((rc = forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, fill.n > 0 ? &fill : nullptr, &filled,
-                                  aux, stats, err)))
+    if ((rc = forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, fill.n > 0 ? &fill : nullptr, &filled, v)))
         return rc;
     if (fill_wanted && plan->chunks_run > 0 && effective_binned_ranks(*plan) * 4 < (long long)desc->P) {
         if (!filled) {
@@ -606,50 +599,47 @@ static int forward_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const
 int gsr_forward(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *image_ws, int32_t *radii,
                 gsr_frame_plan *plan, void *binning_ws, int64_t binning_capacity, float *out_color, gsr_grads *early_fill, void *stream)
 {
-    return forward_impl(desc, cam, g, geom_ws, image_ws, radii, plan, binning_ws, binning_capacity, out_color, early_fill, stream, nullptr);
+    return forward_impl(desc, cam, g, geom_ws, image_ws, radii, plan, binning_ws, binning_capacity, out_color, early_fill, stream, {});
 }
 
 int gsr_forward_aux(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *image_ws, int32_t *radii,
                     gsr_frame_plan *plan, void *binning_ws, int64_t binning_capacity, float *out_color, gsr_grads *early_fill,
                     const gsr_aux_outputs *aux, void *stream)
 {
-    return forward_impl(desc, cam, g, geom_ws, image_ws, radii, plan, binning_ws, binning_capacity, out_color, early_fill, stream, aux);
+    return forward_impl(desc, cam, g, geom_ws, image_ws, radii, plan, binning_ws, binning_capacity, out_color, early_fill, stream, {aux});
 }
 
 int gsr_forward_render_aux(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *binning_ws,
                            void *image_ws, gsr_frame_plan *plan, float *out_color, const gsr_aux_outputs *aux, void *stream)
 {
-    bool unused = false;
-    return forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, nullptr, &unused, aux);
+    return forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, nullptr, nullptr, {aux});
 }
 
 int gsr_forward_contrib(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *image_ws, int32_t *radii,
                         gsr_frame_plan *plan, void *binning_ws, int64_t binning_capacity, float *out_color, gsr_grads *early_fill,
                         const gsr_contrib_stats *stats, void *stream)
 {
-    return forward_impl(desc, cam, g, geom_ws, image_ws, radii, plan, binning_ws, binning_capacity, out_color, early_fill, stream, nullptr, stats);
+    return forward_impl(desc, cam, g, geom_ws, image_ws, radii, plan, binning_ws, binning_capacity, out_color, early_fill, stream, {nullptr, stats});
 }
 
 int gsr_forward_render_contrib(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *binning_ws,
                                void *image_ws, gsr_frame_plan *plan, float *out_color, const gsr_contrib_stats *stats, void *stream)
 {
-    bool unused = false;
-    return forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, nullptr, &unused, nullptr, stats);
+    return forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, nullptr, nullptr, {nullptr, stats});
 }
 
 int gsr_forward_contrib_error(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *image_ws,
                               int32_t *radii, gsr_frame_plan *plan, void *binning_ws, int64_t binning_capacity, float *out_color,
                               gsr_grads *early_fill, const gsr_contrib_stats *stats, const gsr_contrib_error *err, void *stream)
 {
-    return forward_impl(desc, cam, g, geom_ws, image_ws, radii, plan, binning_ws, binning_capacity, out_color, early_fill, stream, nullptr, stats, err);
+    return forward_impl(desc, cam, g, geom_ws, image_ws, radii, plan, binning_ws, binning_capacity, out_color, early_fill, stream, {nullptr, stats, err});
 }
 
 int gsr_forward_render_contrib_error(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *binning_ws,
                                      void *image_ws, gsr_frame_plan *plan, float *out_color, const gsr_contrib_stats *stats,
                                      const gsr_contrib_error *err, void *stream)
 {
-    bool unused = false;
-    return forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, nullptr, &unused, nullptr, stats, err);
+    return forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, nullptr, nullptr, {nullptr, stats, err});
 }
 
 int gsr_contrib_error_fold(int64_t P, uint64_t *error_frame_q32, uint64_t *error_sum_q32, float *error_max, void *stream)
@@ -704,11 +694,11 @@ int gsr_bwd_segment_entries(void) { return kSeg; }
 static int backward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const void *geom_ws, void *binning_ws,
                                 const void *image_ws, void *rows_ws, const gsr_frame_plan *plan, const float *out_color,
                                 const gsr_aux_outputs *aux_out, const float *dL_dcolor, const float *dL_ddepth, const float *dL_dalpha,
-                                float *screen_grads, void *stream, bool abs = false)
+                                float *screen_grads, void *stream, BwdKind kind)
 {
     int rc = validate(desc);
     if (rc) return rc;
-    if (abs && (desc->tile_row_begin != 0 || desc->tile_row_end > 0)) {
+    if (kind == BwdKind::kAbs && (desc->tile_row_begin != 0 || desc->tile_row_end > 0)) {
         set_error("gsr_backward_render_abs: whole images only (tile_row_begin = tile_row_end = 0)");
         return GSR_ERR_INVALID_ARGUMENT;
     }
@@ -734,15 +724,13 @@ static int backward_render_impl(const gsr_frame_desc *desc, const gsr_camera *ca
     if (plan->num_rendered > 0) {
         if (!plan->tile_order_ready) GSR_HIP_CHECK(hipMemsetAsync(bw.row_valid, 0, valid_bytes(plan), s));
         const long long rows_n = plan->instances_emitted >= 0 ? (long long)plan->instances_emitted : rows_upper;
-        AuxWS ax = carve_aux(aux_out ? aux_out->ckpt_ws : nullptr, plan_capacity(plan), f);
-        if (aux_out) { ax.depth = aux_out->depth; ax.alpha = aux_out->alpha; }
+        const AuxWS ax = aux_workspace(aux_out, true, plan_capacity(plan), f);
         if ((rc = launch_render_bwd(f, plan->chunks_run, plan->sort_result, rows_n, gw, bw, iw, out_color, dL_dcolor, dbg, s,
-                                    aux_out ? &ax : nullptr, dL_ddepth, dL_dalpha, abs)))
+                                    {kind, &ax, dL_ddepth, dL_dalpha})))
             return rc;
     }
     // only the depth ranks of chunks that ran can own gradient rows
-    if ((rc = launch_reduce_rows(f, *plan, gw, bw, screen_grads, plan->screen_prezeroed, dbg, s, aux_out != nullptr, abs))) return rc;
-    return GSR_OK;
+    return launch_reduce_rows(f, *plan, gw, bw, screen_grads, plan->screen_prezeroed, dbg, s, kind);
 }
 
 int gsr_backward_render(const gsr_frame_desc *desc, const gsr_camera *cam, const void *geom_ws, void *binning_ws,
@@ -750,7 +738,7 @@ int gsr_backward_render(const gsr_frame_desc *desc, const gsr_camera *cam, const
                         float *screen_grads, void *stream)
 {
     return backward_render_impl(desc, cam, geom_ws, binning_ws, image_ws, rows_ws, plan, out_color, nullptr, dL_dcolor, nullptr, nullptr,
-                                screen_grads, stream);
+                                screen_grads, stream, BwdKind::kPlain);
 }
 
 int gsr_backward_render_abs(const gsr_frame_desc *desc, const gsr_camera *cam, const void *geom_ws, void *binning_ws,
@@ -758,7 +746,7 @@ int gsr_backward_render_abs(const gsr_frame_desc *desc, const gsr_camera *cam, c
                             float *screen_grads, void *stream)
 {
     return backward_render_impl(desc, cam, geom_ws, binning_ws, image_ws, rows_ws, plan, out_color, nullptr, dL_dcolor, nullptr, nullptr,
-                                screen_grads, stream, true);
+                                screen_grads, stream, BwdKind::kAbs);
 }
 
 int gsr_screen_absgrad(const gsr_frame_desc *desc, const int32_t *radii, const void *geom_ws, const float *screen_grads,
@@ -784,8 +772,8 @@ int gsr_backward_render_aux(const gsr_frame_desc *desc, const gsr_camera *cam, c
                             const gsr_aux_outputs *aux, const float *dL_dcolor, const float *dL_ddepth, const float *dL_dalpha,
                             float *screen_grads, void *stream)
 {
-    return backward_render_impl(desc, cam, geom_ws, binning_ws, image_ws, rows_ws, plan, out_color, aux, dL_dcolor, aux ? dL_ddepth : nullptr,
-                                aux ? dL_dalpha : nullptr, screen_grads, stream);
+    return backward_render_impl(desc, cam, geom_ws, binning_ws, image_ws, rows_ws, plan, out_color, aux, dL_dcolor, dL_ddepth, dL_dalpha,
+                                screen_grads, stream, aux ? BwdKind::kAux : BwdKind::kPlain);      // aux NULL: gsr_backward_render
 }
 
 static int backward_geom_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, const int32_t *radii,

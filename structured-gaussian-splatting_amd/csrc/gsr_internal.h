@@ -265,29 +265,28 @@ struct ZeroSegs {
 };
 ZeroSegs zero_segments(const FrameK &f, const gsr_gaussians &g, float *screen, const gsr_grads &out, uint8_t *row_valid = nullptr,
                        size_t valid_bytes = 0);
-// groups: the chunk's splats are small (fewer than 4.5 tiles per Gaussian): the quadrant-group kernel (gsr_render.hip)
-// aux (optional): also render the depth and alpha maps (the aux kernels)
-// stats (optional, without aux): also add the chunk's per-Gaussian blend statistics to the caller's accumulators (k_render_fwd_contrib,
-// whatever `groups` says)
+// What a blend forward does beside the colour image (each optional).  aux: the depth and alpha maps.  stats (without aux; lock step
+// whatever `groups` says): the chunk's per-Gaussian blend statistics, added to the caller's accumulators.  err (with stats): its
+// error-weighted totals, added to err->error_frame_q32
+struct FwdVariant { const AuxWS *aux; const gsr_contrib_stats *stats; const gsr_contrib_error *err; };
+// groups: the chunk's splats are small (fewer than 4.5 tiles per Gaussian): the quadrant-group mapping (gsr_render.hip)
 int launch_render_fwd(const FrameK &f, const gsr_camera &cam, int c, bool last_chunk, int sort_result, const GeomWS &gw, const BinningWS &bw,
-                      ImageWS &iw, float *out_color, bool debug, hipStream_t s, bool groups = false, const AuxWS *aux = nullptr,
-                      const gsr_contrib_stats *stats = nullptr, const gsr_contrib_error *err = nullptr);
-// err (optional, with stats): also add the chunk's error-weighted totals to err->error_frame_q32 (k_render_fwd_contrib_error);
-// launch_contrib_error_fold folds a finished frame's totals into the running sum and maximum and clears them (P <= 0: no launch)
+                      ImageWS &iw, float *out_color, bool debug, hipStream_t s, bool groups, const FwdVariant &v);
+// folds a finished frame's totals into the running sum and maximum and clears them (P <= 0: no launch)
 int launch_contrib_error_fold(long long P, uint64_t *frame_q32, uint64_t *sum_q32, float *error_max, bool debug, hipStream_t s);
+// The blend backward's kind.  kAux: dL_dcolor, dL_ddepth, dL_dalpha may each be NULL (zero); rows get slot 9 = dL/dz of the splat (the sum
+// of w dL/ddepth).  kAbs: rows get slots 10, 11 = the per-pixel absolute sums of d/dmean2D.  launch_reduce_rows sums the kind's slots too
+enum class BwdKind { kPlain, kAux, kAbs };
+struct BwdVariant { BwdKind kind; const AuxWS *aux; const float *dL_ddepth, *dL_dalpha; };      // the pointers: kAux only
 // rows_upper: bound of the instances the chunks that ran emitted (sizes the launch: the unit count lives on the device)
-// aux (optional): the aux backward - dL_dcolor, dL_ddepth, dL_dalpha may each be NULL (zero); rows get slot 9 = sum of w dL/ddepth
-// (dL/dz of the splat).  abs (without aux): the abs backward - rows get slots 10, 11 = the per-pixel absolute sums of d/dmean2D
 int launch_render_bwd(const FrameK &f, int chunks_run, int sort_result, long long rows_upper, const GeomWS &gw, BinningWS &bw,
-                      const ImageWS &iw, const float *out_color, const float *dL_dcolor, bool debug, hipStream_t s, const AuxWS *aux = nullptr,
-                      const float *dL_ddepth = nullptr, const float *dL_dalpha = nullptr, bool abs = false);
+                      const ImageWS &iw, const float *out_color, const float *dL_dcolor, bool debug, hipStream_t s, const BwdVariant &v);
 // row_valid / valid_bytes: also clear that many bytes of the blend backward's row-valid flags
 int launch_zero_segments(const ZeroSegs &z, hipStream_t s);
 int launch_zero_outputs(const FrameK &f, const gsr_gaussians &g, float *screen, const gsr_grads &out, hipStream_t s,
                         uint8_t *row_valid = nullptr, size_t valid_bytes = 0);
-// aux: the rows come from the aux backward - slot 9 (dL/dz) is carried into screen_grads too
 int launch_reduce_rows(const FrameK &f, const gsr_frame_plan &plan, const GeomWS &gw, const BinningWS &bw, float *screen_grads,
-                       int prezeroed, bool debug, hipStream_t s, bool aux = false, bool abs = false);
+                       int prezeroed, bool debug, hipStream_t s, BwdKind kind);
 // gsr_screen_absgrad: out [P,3] = (slot 10, slot 11, 0) of the rows launch_geom_bwd visits (same arguments), zeros elsewhere
 int launch_screen_absgrad(const FrameK &f, const int32_t *radii, const float *screen_grads, int n_ranks, const uint32_t *rows,
                           const uint32_t *cnt_open, bool sparse, float *out, bool debug, hipStream_t s);

@@ -2,10 +2,10 @@
 // per-Gaussian reduction of the backward's instance rows.  Spec: SURVEY A.8 / A.9.
 //
 // MI355X mapping ("one wave, one tile"):
-//   * forward: a 16x16 binning tile is blended by ONE wave64.  Chunks of large splats (k_render_fwd): lane l owns the pixel
+//   * forward: a 16x16 binning tile is blended by ONE wave64.  Chunks of large splats (k_render_fwd<QuadrantLanes>): lane l owns the pixel
 //     (l & 7, l >> 3) of each of the tile's four 8x8 QUADRANTS, so "can this splat reach quadrant k at all" is wave-uniform and
 //     clear quadrants are skipped with scalar branches (sub-tile culling); early termination is a wave ballot per quadrant.
-//     Chunks of small splats (k_render_fwd_groups): the backward's mapping, one 16-lane group per quadrant, each walking its own
+//     Chunks of small splats (k_render_fwd<GroupLanes>): the backward's mapping, one 16-lane group per quadrant, each walking its own
 //     entries.  Both kernels are one body (render_fwd) over the pixel mapping (QuadrantLanes, GroupLanes), so they render the same
 //     bits and leave the checkpoints in one layout (ckpt_word).  No workgroup barrier exists anywhere in the blend loops.
 //   * splat records (48 B: xy, conic, opacity, rgb) are gathered 64 at a time, one per lane, staged in
@@ -184,7 +184,7 @@ struct FwdPair {             // state of a lane's two pixels in one pair (elemen
 // One register per pixel carries both "live transmittance" and "final transmittance of a done pixel": for a done pixel
 // test_T = T (1 - alpha) is negative, so the stop test fires by itself, nothing is composited and T keeps its value.
 // ONE definition for both forward kernels (active: the lane's group has a splat in this pass - always, in the lock-step kernel).
-// Returns the pair's blend weights w = alpha T (0 where nothing was composited): the aux kernels blend the depth with them.
+// Returns the pair's blend weights w = alpha T (0 where nothing was composited): the aux instantiations blend the depth with them.
 __device__ __forceinline__ v2f fwd_pair(bool active, v2f lp, float lop, float cr, float cg, float cb, int contributor, FwdPair &P)
 {
     const bool keep0 = active && !(lp[0] > lop) && !(lp[0] < kLog2AlphaMin);      // power > 0  <=>  lp > lop;  alpha < 1/255  <=>  lp < log2(1/255)
@@ -223,7 +223,7 @@ template <int P> struct LanePairs {
     __device__ static int ey(int e) { return (e >> 1) * kPair; }
 };
 
-// k_render_fwd ("one wave, one tile", QUADRANT-major): lane l owns the pixel (l & 7, l >> 3) of each of the tile's four 8x8 quadrants
+// k_render_fwd<QuadrantLanes> ("one wave, one tile", QUADRANT-major): lane l owns the pixel (l & 7, l >> 3) of each of the tile's four 8x8 quadrants
 // (element e = quadrant e).  Whether a splat can reach a quadrant at all (quadrant_mask_q: the exact alpha >= 1/255 bound on the 8x8
 // pixel rectangle) is then WAVE-UNIFORM: the 4-bit mask travels with the tile list's entry, and the blend loop skips clear quadrants
 // with scalar branches.  A 2-3 px splat reaches one or two quadrants of a tile, not four.
@@ -247,7 +247,7 @@ struct QuadrantLanes : LanePairs<8> {
     }
 };
 
-// k_render_bwd and k_render_fwd_groups: the wave is four GROUPS of 16 lanes, one per quadrant; lane l belongs to quadrant g = l >> 4
+// k_render_bwd and k_render_fwd<GroupLanes>: the wave is four GROUPS of 16 lanes, one per quadrant; lane l belongs to quadrant g = l >> 4
 // and owns the pixels (i & 3 [+ 4], i >> 2 [+ 4]), i = l & 15, of it.  Each group walks its own entries (GroupWalk).
 struct GroupLanes : LanePairs<4> {
     static constexpr bool kLockStep = false;
@@ -597,72 +597,24 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
     fwd_tile_epilogue(t, tile, c, lane, closing, stuck, walked, open, tile_walk_c, units, unit_count);
 }
 
-__global__ __launch_bounds__(kWave, kFwdWaves) void k_render_fwd(FrameK f, int n_tiles, int c, int finalize_all,
-                                                   const uint2 *__restrict__ ranges_c, uint32_t *__restrict__ open,
-                                                   const uint32_t *__restrict__ sorted_gid,
-                                                   const float4 *__restrict__ records, const float *__restrict__ bg,
-                                                   float *__restrict__ out_color, float *__restrict__ T_state,
-                                                   int32_t *__restrict__ last_enc, uint32_t *__restrict__ tile_walk_c,
-                                                   float *__restrict__ ckpt, float *__restrict__ ckpt_start_c,
-                                                   UnitLists units, uint32_t *__restrict__ unit_count)
-{
-    render_fwd<QuadrantLanes, false>(f, c, finalize_all, ranges_c, open, sorted_gid, records, bg, out_color, T_state, last_enc, tile_walk_c, ckpt, ckpt_start_c, units, unit_count,
-                                     AuxFwdK{});
-}
-
-__global__ __launch_bounds__(kWave, kFwdWaves) void k_render_fwd_groups(FrameK f, int n_tiles, int c, int finalize_all,
-                                                          const uint2 *__restrict__ ranges_c, uint32_t *__restrict__ open,
-                                                          const uint32_t *__restrict__ sorted_gid,
-                                                          const float4 *__restrict__ records, const float *__restrict__ bg,
-                                                          float *__restrict__ out_color, float *__restrict__ T_state,
-                                                          int32_t *__restrict__ last_enc, uint32_t *__restrict__ tile_walk_c,
-                                                          float *__restrict__ ckpt, float *__restrict__ ckpt_start_c,
-                                                          UnitLists units, uint32_t *__restrict__ unit_count)
-{
-    render_fwd<GroupLanes, false>(f, c, finalize_all, ranges_c, open, sorted_gid, records, bg, out_color, T_state, last_enc, tile_walk_c, ckpt, ckpt_start_c, units, unit_count,
-                                  AuxFwdK{});
-}
-
-// the aux instantiations of both pixel mappings: colour, radii and every array above as the plain kernels, plus depth and alpha
-template <class Map>
-__global__ __launch_bounds__(kWave, 4) void k_render_fwd_aux(FrameK f, int n_tiles, int c, int finalize_all,
-                                                             const uint2 *__restrict__ ranges_c, uint32_t *__restrict__ open,
-                                                             const uint32_t *__restrict__ sorted_gid,
-                                                             const float4 *__restrict__ records, const float *__restrict__ bg,
-                                                             float *__restrict__ out_color, float *__restrict__ T_state,
-                                                             int32_t *__restrict__ last_enc, uint32_t *__restrict__ tile_walk_c,
-                                                             float *__restrict__ ckpt, float *__restrict__ ckpt_start_c,
-                                                             UnitLists units, uint32_t *__restrict__ unit_count, AuxFwdK ax)
-{
-    render_fwd<Map, true>(f, c, finalize_all, ranges_c, open, sorted_gid, records, bg, out_color, T_state, last_enc, tile_walk_c, ckpt, ckpt_start_c, units, unit_count, ax);
-}
-
-// the statistics instantiation (lock step, whatever the chunk's splats are like: both mappings render the same bits)
-__global__ __launch_bounds__(kWave, 4) void k_render_fwd_contrib(FrameK f, int n_tiles, int c, int finalize_all,
+// Every variant of the blend forward is an instantiation of this one kernel.  X: the variant's own kernel arguments - AuxFwdK for the aux
+// instantiations of both pixel mappings (colour, radii and every array as the plain kernels, plus depth and alpha); ContribK, then
+// ErrK, for the statistics instantiations (lock step, whatever the chunk's splats are like: both mappings render the same bits)
+template <class Map, bool kAux, bool kStats, bool kErr, int kMinWaves, class... X>
+__global__ __launch_bounds__(kWave, kMinWaves) void k_render_fwd(FrameK f, int n_tiles, int c, int finalize_all,
                                                                  const uint2 *__restrict__ ranges_c, uint32_t *__restrict__ open,
                                                                  const uint32_t *__restrict__ sorted_gid,
                                                                  const float4 *__restrict__ records, const float *__restrict__ bg,
                                                                  float *__restrict__ out_color, float *__restrict__ T_state,
                                                                  int32_t *__restrict__ last_enc, uint32_t *__restrict__ tile_walk_c,
                                                                  float *__restrict__ ckpt, float *__restrict__ ckpt_start_c,
-                                                                 UnitLists units, uint32_t *__restrict__ unit_count, ContribK cs)
+                                                                 UnitLists units, uint32_t *__restrict__ unit_count, X... x)
 {
-    render_fwd<QuadrantLanes, false, true>(f, c, finalize_all, ranges_c, open, sorted_gid, records, bg, out_color, T_state, last_enc, tile_walk_c, ckpt, ckpt_start_c, units,
-                                           unit_count, AuxFwdK{}, cs);
-}
-
-// the statistics instantiation that also takes the error-weighted total (gsr_forward_render_contrib_error)
-__global__ __launch_bounds__(kWave, 4) void k_render_fwd_contrib_error(FrameK f, int n_tiles, int c, int finalize_all,
-                                                                       const uint2 *__restrict__ ranges_c, uint32_t *__restrict__ open,
-                                                                       const uint32_t *__restrict__ sorted_gid,
-                                                                       const float4 *__restrict__ records, const float *__restrict__ bg,
-                                                                       float *__restrict__ out_color, float *__restrict__ T_state,
-                                                                       int32_t *__restrict__ last_enc, uint32_t *__restrict__ tile_walk_c,
-                                                                       float *__restrict__ ckpt, float *__restrict__ ckpt_start_c,
-                                                                       UnitLists units, uint32_t *__restrict__ unit_count, ContribK cs, ErrK er)
-{
-    render_fwd<QuadrantLanes, false, true, true>(f, c, finalize_all, ranges_c, open, sorted_gid, records, bg, out_color, T_state, last_enc, tile_walk_c, ckpt, ckpt_start_c,
-                                                 units, unit_count, AuxFwdK{}, cs, er);
+    if constexpr (kAux)
+        render_fwd<Map, true>(f, c, finalize_all, ranges_c, open, sorted_gid, records, bg, out_color, T_state, last_enc, tile_walk_c, ckpt, ckpt_start_c, units, unit_count, x...);
+    else
+        render_fwd<Map, false, kStats, kErr>(f, c, finalize_all, ranges_c, open, sorted_gid, records, bg, out_color, T_state, last_enc, tile_walk_c, ckpt, ckpt_start_c, units,
+                                             unit_count, AuxFwdK{}, x...);
 }
 
 // Behind a frame's last chunk: fold the frame's error totals into the running sum and the running maximum, and clear them for the next
@@ -689,50 +641,32 @@ int launch_contrib_error_fold(long long P, uint64_t *frame_q32, uint64_t *sum_q3
 }
 
 int launch_render_fwd(const FrameK &f, const gsr_camera &cam, int c, bool last_chunk, int sort_result, const GeomWS &gw, const BinningWS &bw,
-                      ImageWS &iw, float *out_color, bool debug, hipStream_t s, bool groups, const AuxWS *aux, const gsr_contrib_stats *stats,
-                      const gsr_contrib_error *err)
+                      ImageWS &iw, float *out_color, bool debug, hipStream_t s, bool groups, const FwdVariant &v)
 {
     const int n_tiles = (f.ty1 - f.ty0) * f.Gx;
     if (n_tiles <= 0) return GSR_OK;
     const size_t Tn = (size_t)f.Gx * f.Gy;
-    if (stats && err) {
-        ProfileScope prof("render_fwd_contrib_error", s);
-        const ContribK cs{(unsigned long long *)stats->count, (unsigned long long *)stats->weight_sum_q32, stats->weight_max_bits};
-        const ErrK er{err->pixel_error, (unsigned long long *)err->error_frame_q32};
-        hipLaunchKernelGGL(k_render_fwd_contrib_error, dim3(n_tiles), dim3(kWave), 0, s, f, n_tiles, c, last_chunk ? 1 : 0,
-                           iw.ranges + (size_t)c * Tn, iw.open, bw.gids[1], gw.records, cam.bg, out_color, iw.T_state,
-                           iw.last_enc, iw.tile_walk + (size_t)c * Tn, bw.ckpt,
-                           c > 0 ? iw.ckpt_start + (size_t)(c - 1) * Tn * kCkptFloats : nullptr, bw.units, iw.unit_count, cs, er);
-        GSR_LAUNCH_CHECK("render_fwd_contrib_error", debug, s);
+    const auto launch = [&](auto kernel, const char *name, auto... x) -> int {
+        ProfileScope prof(name, s);
+        hipLaunchKernelGGL(kernel, dim3(n_tiles), dim3(kWave), 0, s, f, n_tiles, c, last_chunk ? 1 : 0, iw.ranges + (size_t)c * Tn, iw.open,
+                           bw.gids[1], gw.records, cam.bg, out_color, iw.T_state, iw.last_enc, iw.tile_walk + (size_t)c * Tn, bw.ckpt,
+                           c > 0 ? iw.ckpt_start + (size_t)(c - 1) * Tn * kCkptFloats : nullptr, bw.units, iw.unit_count, x...);
+        GSR_LAUNCH_CHECK(name, debug, s);
         return GSR_OK;
+    };
+    if (v.stats) {
+        const ContribK cs{(unsigned long long *)v.stats->count, (unsigned long long *)v.stats->weight_sum_q32, v.stats->weight_max_bits};
+        if (!v.err) return launch(k_render_fwd<QuadrantLanes, false, true, false, 4, ContribK>, "render_fwd_contrib", cs);
+        const ErrK er{v.err->pixel_error, (unsigned long long *)v.err->error_frame_q32};
+        return launch(k_render_fwd<QuadrantLanes, false, true, true, 4, ContribK, ErrK>, "render_fwd_contrib_error", cs, er);
     }
-    if (stats) {
-        ProfileScope prof("render_fwd_contrib", s);
-        const ContribK cs{(unsigned long long *)stats->count, (unsigned long long *)stats->weight_sum_q32, stats->weight_max_bits};
-        hipLaunchKernelGGL(k_render_fwd_contrib, dim3(n_tiles), dim3(kWave), 0, s, f, n_tiles, c, last_chunk ? 1 : 0,
-                           iw.ranges + (size_t)c * Tn, iw.open, bw.gids[1], gw.records, cam.bg, out_color, iw.T_state,
-                           iw.last_enc, iw.tile_walk + (size_t)c * Tn, bw.ckpt,
-                           c > 0 ? iw.ckpt_start + (size_t)(c - 1) * Tn * kCkptFloats : nullptr, bw.units, iw.unit_count, cs);
-        GSR_LAUNCH_CHECK("render_fwd_contrib", debug, s);
-        return GSR_OK;
+    if (v.aux) {
+        const AuxFwdK ax{v.aux->depth, v.aux->alpha, v.aux->ckpt, c > 0 ? v.aux->ckpt_start + (size_t)(c - 1) * Tn * kAuxCkptFloats : nullptr};
+        return launch(groups ? k_render_fwd<GroupLanes, true, false, false, 4, AuxFwdK> : k_render_fwd<QuadrantLanes, true, false, false, 4, AuxFwdK>,
+                      "render_fwd_aux", ax);
     }
-    if (aux) {
-        ProfileScope prof("render_fwd_aux", s);
-        const AuxFwdK ax{aux->depth, aux->alpha, aux->ckpt, c > 0 ? aux->ckpt_start + (size_t)(c - 1) * Tn * kAuxCkptFloats : nullptr};
-        hipLaunchKernelGGL(groups ? k_render_fwd_aux<GroupLanes> : k_render_fwd_aux<QuadrantLanes>, dim3(n_tiles), dim3(kWave), 0, s, f, n_tiles, c,
-                           last_chunk ? 1 : 0, iw.ranges + (size_t)c * Tn, iw.open, bw.gids[1], gw.records, cam.bg, out_color, iw.T_state,
-                           iw.last_enc, iw.tile_walk + (size_t)c * Tn, bw.ckpt,
-                           c > 0 ? iw.ckpt_start + (size_t)(c - 1) * Tn * kCkptFloats : nullptr, bw.units, iw.unit_count, ax);
-        GSR_LAUNCH_CHECK("render_fwd_aux", debug, s);
-        return GSR_OK;
-    }
-    ProfileScope prof("render_fwd", s);
-    hipLaunchKernelGGL(groups ? k_render_fwd_groups : k_render_fwd, dim3(n_tiles), dim3(kWave), 0, s, f, n_tiles, c, last_chunk ? 1 : 0,
-                       iw.ranges + (size_t)c * Tn, iw.open, bw.gids[1], gw.records, cam.bg, out_color, iw.T_state,
-                       iw.last_enc, iw.tile_walk + (size_t)c * Tn, bw.ckpt,
-                       c > 0 ? iw.ckpt_start + (size_t)(c - 1) * Tn * kCkptFloats : nullptr, bw.units, iw.unit_count);
-    GSR_LAUNCH_CHECK("render_fwd", debug, s);
-    return GSR_OK;
+    return launch(groups ? k_render_fwd<GroupLanes, false, false, false, kFwdWaves> : k_render_fwd<QuadrantLanes, false, false, false, kFwdWaves>,
+                  "render_fwd");
 }
 
 // ------------------------------------------------------------------------------------------- K7
@@ -1047,8 +981,7 @@ __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const
 }
 
 int launch_render_bwd(const FrameK &f, int chunks_run, int sort_result, long long rows_upper, const GeomWS &gw, BinningWS &bw,
-                      const ImageWS &iw, const float *out_color, const float *dL_dcolor, bool debug, hipStream_t s, const AuxWS *aux,
-                      const float *dL_ddepth, const float *dL_dalpha, bool abs)
+                      const ImageWS &iw, const float *out_color, const float *dL_dcolor, bool debug, hipStream_t s, const BwdVariant &v)
 {
     const int n_tiles = (f.ty1 - f.ty0) * f.Gx;
     if (n_tiles <= 0 || chunks_run <= 0) return GSR_OK;
@@ -1057,11 +990,13 @@ int launch_render_bwd(const FrameK &f, int chunks_run, int sort_result, long lon
     long long per_shard = (rows_upper / kSeg + (long long)n_tiles * chunks_run) / kUnitShards + 1;
     if (per_shard > (long long)bw.units.shard_stride()) per_shard = (long long)bw.units.shard_stride();
     if (per_shard > (1 << 13)) per_shard = 1 << 13;
-    // the two instantiations take the same arguments; the colour-only one ignores the aux block
-    const char *name = aux ? "render_bwd_aux" : abs ? "render_bwd_abs" : "render_bwd";
-    const AuxBwdK ax = aux ? AuxBwdK{aux->depth, dL_ddepth, dL_dalpha, aux->ckpt, aux->ckpt_start} : AuxBwdK{};
+    // by BwdKind: the instantiations take the same arguments; only the aux one reads the aux block
+    static const decltype(&k_render_bwd<false, false>) kernels[] = {k_render_bwd<false, false>, k_render_bwd<true, false>, k_render_bwd<false, true>};
+    static const char *const names[] = {"render_bwd", "render_bwd_aux", "render_bwd_abs"};
+    const char *name = names[(int)v.kind];
+    const AuxBwdK ax = v.kind == BwdKind::kAux ? AuxBwdK{v.aux->depth, v.dL_ddepth, v.dL_dalpha, v.aux->ckpt, v.aux->ckpt_start} : AuxBwdK{};
     ProfileScope prof(name, s);
-    hipLaunchKernelGGL((aux ? k_render_bwd<true, false> : abs ? k_render_bwd<false, true> : k_render_bwd<false, false>), dim3((unsigned)(per_shard * kUnitShards)), dim3(kWave), 0, s, f,
+    hipLaunchKernelGGL(kernels[(int)v.kind], dim3((unsigned)(per_shard * kUnitShards)), dim3(kWave), 0, s, f,
                        iw.ranges, iw.tile_walk, bw.gids[1], bw.vals[sort_result], gw.records, out_color, iw.T_state, iw.last_enc, dL_dcolor,
                        bw.ckpt, iw.ckpt_start, reinterpret_cast<float4 *>(bw.grad_rows), bw.row_valid, bw.units, iw.unit_count, ax);
     GSR_LAUNCH_CHECK(name, debug, s);
@@ -1182,12 +1117,17 @@ __global__ __launch_bounds__(kRedBlock) void k_reduce_rows(int r_begin, int n_ra
 // through the live filter, whose instance bound says nothing about what it emitted (a training frame's last chunk is most of the
 // scene with a bound of tens of millions: 64 lanes for each of its 1e6 ranks was 100 us of idle threads).
 int launch_reduce_rows(const FrameK &f, const gsr_frame_plan &plan, const GeomWS &gw, const BinningWS &bw, float *screen_grads,
-                       int prezeroed, bool debug, hipStream_t s, bool aux, bool abs)
+                       int prezeroed, bool debug, hipStream_t s, BwdKind kind)
 {
     // prezeroed: 0 = clear the whole tensor first; 1 = the caller already has; 2 = only the rows of the binned prefix will ever
     // be read (the sparse geometry backward of the same frame): every prefix row is written, zeros included, nothing else
     if (f.P == 0) return GSR_OK;
-    ProfileScope prof(aux ? "reduce_rows_aux" : abs ? "reduce_rows_abs" : "reduce_rows", s);
+    // by BwdKind, then narrow / wide groups
+    static const decltype(&k_reduce_rows<8>) kernels[][2] = {{k_reduce_rows<8>, k_reduce_rows<64>},
+                                                             {k_reduce_rows<8, true>, k_reduce_rows<64, true>},
+                                                             {k_reduce_rows<8, false, true>, k_reduce_rows<64, false, true>}};
+    static const char *const names[] = {"reduce_rows", "reduce_rows_aux", "reduce_rows_abs"};
+    ProfileScope prof(names[(int)kind], s);
     if (prezeroed == 0) GSR_HIP_CHECK(hipMemsetAsync(screen_grads, 0, (size_t)f.P * kRowFloats * sizeof(float), s));
     const int write_empty = prezeroed == 2 ? 1 : 0;
     const int plain = getenv("GSR_REDUCE_ROWS_PLAIN") ? 1 : 0;                   // test hook (tests set it per case): the wide groups' one-trip-at-a-time loop
@@ -1201,9 +1141,7 @@ int launch_reduce_rows(const FrameK &f, const gsr_frame_plan &plan, const GeomWS
         // (two lanes per Gaussian for small splats, measured: 89 us against 81 at cfg3n, 352 against 374 at cfg5n — not kept)
         const long long threads = (long long)(r1 - r0) * (wide ? 64 : 8);
         const dim3 grid((unsigned)((threads + kRedBlock - 1) / kRedBlock));
-        hipLaunchKernelGGL((aux ? (wide ? k_reduce_rows<64, true> : k_reduce_rows<8, true>)
-                                : abs ? (wide ? k_reduce_rows<64, false, true> : k_reduce_rows<8, false, true>)
-                                      : (wide ? k_reduce_rows<64> : k_reduce_rows<8>)), grid, dim3(kRedBlock), 0, s, r0, r1, gw.order, gw.cnt_open, gw.row_begin,
+        hipLaunchKernelGGL(kernels[(int)kind][wide], grid, dim3(kRedBlock), 0, s, r0, r1, gw.order, gw.cnt_open, gw.row_begin,
                            bw.row_valid, reinterpret_cast<const float4 *>(bw.grad_rows), reinterpret_cast<float4 *>(screen_grads), write_empty, plain);
     }
     GSR_LAUNCH_CHECK("reduce_rows", debug, s);

@@ -545,6 +545,34 @@ def _restash_frame(fr):
     fr.plan.screen_prezeroed = 0
 
 
+def _finish_forward(ctx, frame, color, radii, aux, means2D, opacities):
+    """The tail of both Functions' forward(): the frame into autograd's slots, what backward() needs on ctx, the return tuple."""
+    maps = (frame.depth, frame.alpha)
+    _stash_frame(ctx, frame)
+    ctx.absgrad_to = getattr(_tls, "absgrad_to", None)
+    ctx.shapes = (means2D.shape, opacities.shape)
+    ctx.mark_non_differentiable(radii)
+    ctx.set_materialize_grads(False)         # radii's "gradient" would arrive as a zero-filled int32 [P] tensor: one launch per step
+    return (color, radii) + (maps if aux else ())
+
+
+def _backward_core(ctx, fr, needs, grad_out_color, grad_depth, grad_alpha):
+    """The core of both Functions' backward(): (rasterize_backward_geom's gradients for `needs`, means2D's and the opacities' in
+    their inputs' shapes; the camera gradients).  The frame goes back to its stashed state."""
+    # no depth / alpha gradient: the colour-only kernels, bit for bit the plain frame's gradients
+    with_aux = grad_depth is not None or grad_alpha is not None
+    screen = rasterize_backward_screen(fr, grad_out_color, only_for_own_geom=True, grad_depth=grad_depth, grad_alpha=grad_alpha,
+                                       absgrad=ctx.absgrad_to is not None)
+    g = list(rasterize_backward_geom(fr, screen, needs, depth_chain=with_aux))
+    g_cam = _camera_backward(ctx, fr, screen, with_aux)
+    _assign_absgrad(ctx, fr, screen)
+    for i, shape in ((1, ctx.shapes[0]), (4, ctx.shapes[1])):         # means2D, opacities
+        if g[i] is not None:
+            g[i] = g[i].view(shape)
+    _restash_frame(fr)
+    return g, g_cam
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -566,48 +594,27 @@ class _RasterizeGaussians(torch.autograd.Function):
         else:
             color, radii, frame = rasterize_forward(*args, rs, prepare_needs=tuple(ctx.needs_input_grad[:8]), aux=aux)
             prepare_backward(frame, tuple(ctx.needs_input_grad[:8]), screen_prefix_only=True)
-        maps = (frame.depth, frame.alpha)
-        _stash_frame(ctx, frame)
         ctx.raster_settings = rs
-        ctx.absgrad_to = getattr(_tls, "absgrad_to", None)
-        ctx.shapes = (means2D.shape, opacities.shape)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)         # radii's "gradient" would arrive as a zero-filled int32 [P] tensor: one launch per step
-        return (color, radii) + (maps if aux else ())
+        return _finish_forward(ctx, frame, color, radii, aux, means2D, opacities)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None):
         fr, rs = _unstash_frame(ctx), ctx.raster_settings
-        needs = tuple(ctx.needs_input_grad[:8])
         # input order: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp
-        order = (needs[0], needs[1], needs[2], needs[3], needs[4], needs[5], needs[6], needs[7])
-        # no depth / alpha gradient: the colour-only kernels, bit for bit the plain frame's gradients
-        with_aux = grad_depth is not None or grad_alpha is not None
-
-        def run():
-            screen = rasterize_backward_screen(fr, grad_out_color, only_for_own_geom=True, grad_depth=grad_depth, grad_alpha=grad_alpha,
-                                               absgrad=ctx.absgrad_to is not None)
-            out = rasterize_backward_geom(fr, screen, order, depth_chain=with_aux) + (_camera_backward(ctx, fr, screen, with_aux),)
-            _assign_absgrad(ctx, fr, screen)
-            return out
+        needs = tuple(ctx.needs_input_grad[:8])
         if rs.debug:
+            kept = fr.keep[1:]                 # (the frame lets go of them once its gradients are enqueued)
             try:
-                out = run()
+                g, g_cam = _backward_core(ctx, fr, needs, grad_out_color, grad_depth, grad_alpha)
                 torch.cuda.synchronize(fr.device)
             except Exception:
-                _dump("snapshot_bw.dump", (tuple(None if k is None else k.detach().cpu() for k in fr.keep[1:]),
+                _dump("snapshot_bw.dump", (tuple(None if k is None else k.detach().cpu() for k in kept),
                                            None if grad_out_color is None else grad_out_color.detach().cpu(), tuple(rs)))
                 print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
                 raise
         else:
-            out = run()
-        g_means3D, g_means2D, g_sh, g_col, g_op, g_sc, g_rot, g_cov, g_cam = out
-        if g_op is not None:
-            g_op = g_op.view(ctx.shapes[1])
-        if g_means2D is not None:
-            g_means2D = g_means2D.view(ctx.shapes[0])
-        _restash_frame(fr)
-        return (g_means3D, g_means2D, g_sh, g_col, g_op, g_sc, g_rot, g_cov, None, None) + g_cam
+            g, g_cam = _backward_core(ctx, fr, needs, grad_out_color, grad_depth, grad_alpha)
+        return (*g, None, None) + g_cam
 
 
 class _RasterizeGaussiansRaw(torch.autograd.Function):
@@ -629,30 +636,14 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         if rs.debug:
             torch.cuda.synchronize(xyz.device)
         prepare_backward(frame, needs, screen_prefix_only=True)
-        maps = (frame.depth, frame.alpha)
-        _stash_frame(ctx, frame)
-        ctx.absgrad_to = getattr(_tls, "absgrad_to", None)
-        ctx.shapes = (means2D.shape, opacity_logits.shape)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)         # radii's "gradient" would arrive as a zero-filled int32 [P] tensor: one launch per step
-        return (color, radii) + (maps if aux else ())
+        return _finish_forward(ctx, frame, color, radii, aux, means2D, opacity_logits)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None):
-        fr = _unstash_frame(ctx)
         n = ctx.needs_input_grad       # xyz, means2D, f_dc, f_rest, opacity, scales, rotations
         needs = (n[0], n[1], n[2], False, n[4], n[5], n[6], False, n[3])
-        with_aux = grad_depth is not None or grad_alpha is not None
-        screen = rasterize_backward_screen(fr, grad_out_color, only_for_own_geom=True, grad_depth=grad_depth, grad_alpha=grad_alpha,
-                                           absgrad=ctx.absgrad_to is not None)
-        g_xyz, g_means2D, g_dc, _, g_op, g_sc, g_rot, _, g_rest = rasterize_backward_geom(fr, screen, needs, depth_chain=with_aux)
-        g_cam = _camera_backward(ctx, fr, screen, with_aux)
-        _assign_absgrad(ctx, fr, screen)
-        if g_op is not None:
-            g_op = g_op.view(ctx.shapes[1])
-        if g_means2D is not None:
-            g_means2D = g_means2D.view(ctx.shapes[0])
-        _restash_frame(fr)
+        g, g_cam = _backward_core(ctx, _unstash_frame(ctx), needs, grad_out_color, grad_depth, grad_alpha)
+        g_xyz, g_means2D, g_dc, _, g_op, g_sc, g_rot, _, g_rest = g
         return (g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None, None) + g_cam
 
 

@@ -357,6 +357,18 @@ def forward_preprocess(desc, cam: Camera, g: Gaussians, geom_ws, radii, device, 
     return plan
 
 
+def _variant(who: str, aux, contrib, err):
+    """(i, more) of a frame's variant: i picks among a wrapper's (plain, _aux, _contrib, _contrib_error) entry points, `more` are the
+    arguments that one takes in front of the stream."""
+    if aux is not None and contrib is not None:
+        raise ValueError(f"{who}: aux and contrib together (that kernel is not built)")
+    if err is not None and contrib is None:
+        raise ValueError(f"{who}: err without contrib")
+    if contrib is not None:
+        return (2, (contrib,)) if err is None else (3, (contrib, err))
+    return (0, ()) if aux is None else (1, (aux,))
+
+
 def forward_both(desc, cam: Camera, g: Gaussians, geom_ws, image_ws, radii, binning_ws, binning_capacity, out_color, device,
                  early_fill: Optional[Grads] = None, aux: Optional[AuxOutputs] = None, contrib: Optional[ContribStats] = None,
                  err: Optional[ContribError] = None):
@@ -367,21 +379,10 @@ def forward_both(desc, cam: Camera, g: Gaussians, geom_ws, image_ws, radii, binn
     its earlier chunks (include/gsrast.h), so its caller sizes the workspace for num_rendered."""
     plan = FramePlan()
     lib = load()                      # the plain functions: GSR_ERR_WORKSPACE is an answer here, not an error
-    args = (desc, cam, g, _ptr(geom_ws), _ptr(image_ws), _ptr(radii), plan, _ptr(binning_ws), int(binning_capacity), _ptr(out_color),
-            early_fill)
-    if aux is not None and contrib is not None:
-        raise ValueError("forward_both: aux and contrib together (that kernel is not built)")
-    if err is not None:
-        if contrib is None:
-            raise ValueError("forward_both: err without contrib")
-        fn, more = lib.gsr_forward_contrib_error, (contrib, err)
-    elif contrib is not None:
-        fn, more = lib.gsr_forward_contrib, (contrib,)
-    elif aux is None:
-        fn, more = lib.gsr_forward, ()
-    else:
-        fn, more = lib.gsr_forward_aux, (aux,)
-    rc = fn(*args, *more, _stream(device))
+    i, more = _variant("forward_both", aux, contrib, err)
+    fn = (lib.gsr_forward, lib.gsr_forward_aux, lib.gsr_forward_contrib, lib.gsr_forward_contrib_error)[i]
+    rc = fn(desc, cam, g, _ptr(geom_ws), _ptr(image_ws), _ptr(radii), plan, _ptr(binning_ws), int(binning_capacity), _ptr(out_color),
+            early_fill, *more, _stream(device))
     if rc == ERR_WORKSPACE:           # the guessed workspace did not do (for the first chunk, or for a later one)
         return plan, False
     _errcheck(rc, fn)
@@ -390,19 +391,9 @@ def forward_both(desc, cam: Camera, g: Gaussians, geom_ws, image_ws, radii, binn
 
 def forward_render(desc, cam: Camera, g: Gaussians, geom_ws, binning_ws, image_ws, plan: FramePlan, out_color, device,
                    aux: Optional[AuxOutputs] = None, contrib: Optional[ContribStats] = None, err: Optional[ContribError] = None):
-    args = (desc, cam, g, _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws), plan, _ptr(out_color))
-    if aux is not None and contrib is not None:
-        raise ValueError("forward_render: aux and contrib together (that kernel is not built)")
-    if err is not None:
-        if contrib is None:
-            raise ValueError("forward_render: err without contrib")
-        _gsr.gsr_forward_render_contrib_error(*args, contrib, err, _stream(device))
-    elif contrib is not None:
-        _gsr.gsr_forward_render_contrib(*args, contrib, _stream(device))
-    elif aux is None:
-        _gsr.gsr_forward_render(*args, _stream(device))
-    else:
-        _gsr.gsr_forward_render_aux(*args, aux, _stream(device))
+    i, more = _variant("forward_render", aux, contrib, err)
+    fn = (_gsr.gsr_forward_render, _gsr.gsr_forward_render_aux, _gsr.gsr_forward_render_contrib, _gsr.gsr_forward_render_contrib_error)[i]
+    fn(desc, cam, g, _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws), plan, _ptr(out_color), *more, _stream(device))
 
 
 def contrib_error_fold(error_frame_q32, error_sum_q32, error_max, device):
