@@ -741,6 +741,10 @@ int gsr_debug_sort_pairs_ex(uint32_t *keys0, uint32_t *keys1, uint32_t *vals0, u
 int gsr_profile_enable(int enable);
 int gsr_profile_read(int max_entries, char (*names)[GSR_PROFILE_NAME_LEN], float *total_ms, int32_t *launches);
 
+/* Normal maps for surface regularisation (per-Gaussian normals, depth normals, the normal-consistency loss): the entry points are
+ * part of this ABI and of libgsrast.so, declared in a header of their own that this one brings in. */
+#include "gsrast_normals.h"
+
 #ifdef __cplusplus
 }
 #endif

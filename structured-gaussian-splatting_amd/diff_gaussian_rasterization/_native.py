@@ -243,6 +243,20 @@ SIGNATURES = {
 }
 EXPORTS = tuple(SIGNATURES)
 
+# The normal-map entry points, declared in include/gsrast_normals.h (which gsrast.h includes): the same rules, a table per header, so
+# that each table is held to the prototypes of its own file (tests/test_abi.py, tests/test_normals_ref.py).
+_image = (_i32, _i32, _f32, _f32, _f32)                                                    # H, W, tanfovx, tanfovy, alpha_min
+NORMALS_SIGNATURES = {
+    "gsr_gaussian_normals_forward": (_int, (_i64,) + (_dev,) * 7),
+    "gsr_gaussian_normals_backward": (_int, (_i64,) + (_dev,) * 8),
+    "gsr_depth_normal_forward": (_int, _image + (_dev,) * 4),
+    "gsr_depth_normal_backward": (_int, _image + (_dev,) * 6),
+    "gsr_normal_consistency_workspace_size": (_int, (_i32, _i32, _P(_size))),
+    "gsr_normal_consistency_forward": (_int, _image + (_dev,) * 4 + (_size, _dev, _dev)),
+    "gsr_normal_consistency_backward": (_int, _image + (_dev,) * 8),
+}
+_ALL_SIGNATURES = {**SIGNATURES, **NORMALS_SIGNATURES}
+
 _lib = None
 
 
@@ -267,7 +281,7 @@ def load():
                 f"libgsrast.so not found at {_LIB_PATH}: the HIP extension is required (no CPU fallback exists). "
                 f"Build it with `make -C {_CSRC}` or `python -c 'import __graft_entry__ as g; g.build()'`.")
         lib = C.CDLL(_LIB_PATH)
-        for name, (restype, argtypes) in SIGNATURES.items():
+        for name, (restype, argtypes) in _ALL_SIGNATURES.items():
             if not hasattr(lib, name):
                 raise RuntimeError(f"libgsrast.so does not export {name}")
             fn = getattr(lib, name)
@@ -294,10 +308,10 @@ class _Checked:
     gsr_version, gsr_last_error, gsr_bwd_segment_entries and gsr_profile_read return a value and are called through load())."""
 
     def __getattr__(self, name):                  # once per name: the function then sits in the instance's __dict__
-        if name not in SIGNATURES:
+        if name not in _ALL_SIGNATURES:
             raise AttributeError(name)
         fn = load()[name]                         # a function object of its own: load()'s keep returning the status
-        fn.restype, fn.argtypes = SIGNATURES[name]
+        fn.restype, fn.argtypes = _ALL_SIGNATURES[name]
         fn.errcheck = _errcheck
         self.__dict__[name] = fn
         return fn
@@ -997,4 +1011,84 @@ def filter3d_apply_backward(opacities, scales, filter_3D, raw: bool, grad_opacit
     with torch.cuda.device(scales.device):
         _gsr.gsr_filter3d_apply_backward(P, int(bool(raw)), _ptr(opacities), _ptr(scales), _ptr(filter_3D), _ptr(grad_opacities_out),
                                          _ptr(grad_scales_out), _ptr(outs[0]), _ptr(outs[1]), _stream(scales.device))
+    return tuple(outs)
+
+
+def gaussian_normals_forward(scales, rotations, means3D, viewmatrix, campos):
+    """gsr_gaussian_normals_forward: scales [P,3], rotations [P,4], means3D [P,3], viewmatrix [4,4], campos [3], contiguous fp32 on one
+    device -> the view-space normals [P,3]."""
+    P = int(scales.shape[0])
+    out = torch.empty(P, 3, dtype=torch.float32, device=scales.device)
+    with torch.cuda.device(scales.device):
+        _gsr.gsr_gaussian_normals_forward(P, _ptr(scales), _ptr(rotations), _ptr(means3D), _ptr(viewmatrix), _ptr(campos), _ptr(out),
+                                          _stream(scales.device))
+    return out
+
+
+def gaussian_normals_backward(scales, rotations, means3D, viewmatrix, campos, grad_out):
+    """gsr_gaussian_normals_backward: grad_out [P,3] contiguous -> dL/drotations [P,4]."""
+    P = int(scales.shape[0])
+    out = torch.empty(P, 4, dtype=torch.float32, device=scales.device)
+    with torch.cuda.device(scales.device):
+        _gsr.gsr_gaussian_normals_backward(P, _ptr(scales), _ptr(rotations), _ptr(means3D), _ptr(viewmatrix), _ptr(campos), _ptr(grad_out),
+                                           _ptr(out), _stream(scales.device))
+    return out
+
+
+def depth_normal_forward(depth, alpha, tanfovx, tanfovy, alpha_min):
+    """gsr_depth_normal_forward: depth, alpha [H,W] contiguous fp32 on one device -> the normal map [3,H,W]."""
+    H, W = int(depth.shape[-2]), int(depth.shape[-1])
+    out = torch.empty(3, H, W, dtype=torch.float32, device=depth.device)
+    with torch.cuda.device(depth.device):
+        _gsr.gsr_depth_normal_forward(H, W, tanfovx, tanfovy, alpha_min, _ptr(depth), _ptr(alpha), _ptr(out), _stream(depth.device))
+    return out
+
+
+def depth_normal_backward(depth, alpha, tanfovx, tanfovy, alpha_min, grad_out, want):
+    """gsr_depth_normal_backward.  grad_out [3,H,W] contiguous; want: two booleans for (depth, alpha).  Returns the two gradients, shaped
+    like the inputs, None where not wanted."""
+    H, W = int(depth.shape[-2]), int(depth.shape[-1])
+    outs = [torch.empty_like(t) if w else None for t, w in zip((depth, alpha), want)]
+    if H * W == 0 or not any(want):
+        return tuple(outs)
+    with torch.cuda.device(depth.device):
+        _gsr.gsr_depth_normal_backward(H, W, tanfovx, tanfovy, alpha_min, _ptr(depth), _ptr(alpha), _ptr(grad_out), _ptr(outs[0]), _ptr(outs[1]),
+                                       _stream(depth.device))
+    return tuple(outs)
+
+
+_nrm_ws = {}
+
+
+def _normal_consistency_workspace(device, H, W):
+    """The loss forward's workspace of a (device, stream): cleared when made (or grown), every call leaves its ticket at zero."""
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    need = _size(_gsr.gsr_normal_consistency_workspace_size, H, W)
+    ws = _nrm_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _nrm_ws[key] = torch.zeros(need, dtype=torch.uint8, device=device)
+    return ws
+
+
+def normal_consistency_forward(normal_map, depth, alpha, tanfovx, tanfovy, alpha_min):
+    """gsr_normal_consistency_forward: normal_map [3,H,W], depth, alpha [H,W] contiguous fp32 on one device -> the loss, a 0-dim tensor."""
+    H, W = int(depth.shape[-2]), int(depth.shape[-1])
+    out = torch.empty(1, dtype=torch.float32, device=depth.device)
+    with torch.cuda.device(depth.device):
+        ws = _normal_consistency_workspace(depth.device, H, W)
+        _gsr.gsr_normal_consistency_forward(H, W, tanfovx, tanfovy, alpha_min, _ptr(normal_map), _ptr(depth), _ptr(alpha), _ptr(ws), ws.numel(),
+                                            _ptr(out), _stream(depth.device))
+    return out.reshape(())
+
+
+def normal_consistency_backward(normal_map, depth, alpha, tanfovx, tanfovy, alpha_min, grad_loss, want):
+    """gsr_normal_consistency_backward.  grad_loss: a one-element fp32 device tensor; want: three booleans for (normal_map, depth, alpha).
+    Returns the three gradients, shaped like the inputs, None where not wanted."""
+    H, W = int(depth.shape[-2]), int(depth.shape[-1])
+    outs = [torch.empty_like(t) if w else None for t, w in zip((normal_map, depth, alpha), want)]
+    if not any(want):
+        return tuple(outs)
+    with torch.cuda.device(depth.device):
+        _gsr.gsr_normal_consistency_backward(H, W, tanfovx, tanfovy, alpha_min, _ptr(normal_map), _ptr(depth), _ptr(alpha), _ptr(grad_loss),
+                                             _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _stream(depth.device))
     return tuple(outs)

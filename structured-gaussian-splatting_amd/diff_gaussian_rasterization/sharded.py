@@ -372,13 +372,18 @@ _NO_CONTRIBUTIONS = ("contributions is not supported by ShardedRenderer: the ble
                      "renders a slab of tile rows (render the statistics frames unsharded)")
 
 
+_NO_NORMALS = ("lambda_normal / render_normals is not supported by ShardedRenderer: the depth normals read every pixel's four neighbours "
+               "and the loss is a mean over the whole image, a rank holds a slab of rows and renders no depth or alpha map (train "
+               "unsharded, or leave lambda_normal at 0)")
+
+
 class ShardedRenderer:
     """render()-shaped front end for world_size > 1 (same arguments and returned dict as
     gaussian_renderer.render, reference gaussian_renderer/__init__.py:18-100)."""
 
     def __init__(self, dist, world: int, rank: int, backend=None, group=None, row_weights=None,
                  backward_mode: str = "allreduce_screen", balance_every: int = 0, async_gather: bool = True,
-                 bilateral_grid: bool = False):
+                 bilateral_grid: bool = False, lambda_normal: float = 0.0):
         """row_weights: fixed per-tile-row weights for the slab boundaries (None = equal rows).  balance_every = k > 0:
         SURVEY 7 "slab load balance" — every k-th frame the ranks' measured per-tile-row work (instances binned) rides
         on the all-gather and the next frames' slabs are cut at equal cumulative work.  async_gather=False: the slabs'
@@ -389,6 +394,8 @@ class ShardedRenderer:
         if bilateral_grid:
             raise ValueError("bilateral_grid is not supported by ShardedRenderer: the slice reads whole images and sums the grid's gradient "
                              "over all of an image's pixels, a rank holds a slab of rows (train unsharded, or turn it off)")
+        if lambda_normal:
+            raise ValueError(_NO_NORMALS)
         self.balance_every, self._frames, self._pending = int(balance_every), 0, None
         self.comm = _Comm(dist, world, rank, group, async_gather=async_gather)
         self.backend = NativeBackend() if backend is None else backend
@@ -458,6 +465,9 @@ class ShardedRenderer:
                       e if colors_precomp is None else colors_precomp, opacities,
                       e if scales is None else scales, e if rotations is None else rotations,
                       e if cov3D_precomp is None else cov3D_precomp, rs, self)
+
+    def render_normals(self, viewpoint_camera, pc, pipe, scaling_modifier=1.0):
+        raise ValueError(_NO_NORMALS)
 
     def render(self, viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, contributions=None):
         import math

@@ -30,6 +30,10 @@ itself takes `contributions` on forward and forward_raw alike.  Not together wit
 
 `pixel_error` (float32 [H,W] or [1,H,W]; None: off; with a contrib.ErrorStats as `contributions`): the frame also adds every
 Gaussian's error-weighted blend total into the ErrorStats and folds it (diff_gaussian_rasterization, "pixel_error"); passed through.
+
+render_normals() (extension) is a frame of its own for the normal-consistency term (diff_gaussian_rasterization.normals): the
+Gaussians' view-space normals as precomputed colours, with the depth and alpha maps and the normal map the depth implies.  render()
+neither gains nor loses anything by it.
 """
 import math
 
@@ -65,6 +69,31 @@ def eval_sh(deg: int, sh: torch.Tensor, dirs: torch.Tensor) -> torch.Tensor:
 
 
 _ZERO_POINTS = {}
+_ZERO_BG = {}
+
+
+def render_normals(viewpoint_camera, pc, pipe, scaling_modifier=1.0):
+    """The maps of the normal-consistency term (extension; diff_gaussian_rasterization.normals), one frame: the Gaussians' view-space
+    normals (the shortest axis, turned to the camera) rendered as precomputed colours over a zero background with depth_alpha=True.
+    -> {"normal" [3,H,W] (alpha-weighted, not normalised), "depth", "alpha" [1,H,W], "depth_normal" [3,H,W] (depth_to_normal of the two),
+    "viewspace_points", "radii", "visibility_filter"}.  The model's getters are used; a model with a 3D filter renders its filtered
+    scales, as render() does, and the same scales choose the axis.  pipe.absgrad raises (depth_alpha=True refuses it)."""
+    from diff_gaussian_rasterization.normals import depth_to_normal, gaussian_normals
+    if getattr(pipe, "absgrad", False):
+        raise ValueError("render_normals: the frame is rendered with depth_alpha=True, which pipe.absgrad is not supported with (the abs "
+                         "blend backward does not carry the depth and alpha gradients): turn pipe.absgrad off for this frame")
+    filtered = getattr(pc, "filter_3D", None) is not None
+    xyz = pc.get_xyz
+    normals = gaussian_normals(pc.get_scaling_with_3D_filter if filtered else pc.get_scaling, pc.get_rotation, xyz,
+                               viewpoint_camera.world_view_transform, viewpoint_camera.camera_center)
+    key = (xyz.device.type, xyz.device.index)
+    bg = _ZERO_BG.get(key)
+    if bg is None:
+        bg = _ZERO_BG[key] = torch.zeros(3, dtype=torch.float32, device=xyz.device)
+    pkg = render(viewpoint_camera, pc, pipe, bg, scaling_modifier, override_color=normals, depth_alpha=True)
+    depth_normal = depth_to_normal(pkg["depth"], pkg["alpha"], math.tan(viewpoint_camera.FoVx * 0.5), math.tan(viewpoint_camera.FoVy * 0.5))
+    return {"normal": pkg["render"], "depth": pkg["depth"], "alpha": pkg["alpha"], "depth_normal": depth_normal,
+            "viewspace_points": pkg["viewspace_points"], "radii": pkg["radii"], "visibility_filter": pkg["visibility_filter"]}
 
 
 def _zero_points(like: torch.Tensor) -> torch.Tensor:

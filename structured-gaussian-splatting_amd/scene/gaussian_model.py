@@ -87,6 +87,8 @@ class OptimizationDefaults:
     densify_error_views: int = 0                  # > 0: refine by image error, scored over that many sampled cameras (train_loop.train); untuned
     densify_error_growth: float = 0.05            # the budget of a refinement: ceil(growth * P) Gaussians are cloned or split; untuned
     densify_error_score: str = "max"              # "max": the largest single view's error (Revising Densification); "sum": over the views (Taming-3DGS)
+    lambda_normal: float = 0.0                    # > 0: weight of the normal-consistency loss, one render_normals frame per iteration (train_loop.train); untuned
+    normal_from_iter: int = 7000                  # the first iteration that adds it (2DGS's value, not tuned here)
 
 
 def expon_lr(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1_000_000):

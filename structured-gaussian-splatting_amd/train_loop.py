@@ -12,7 +12,11 @@ opt.densify_error_views > 0 replaces the refinement's criterion (DESIGN section 
 drawn, the model's error-weighted blend statistics are taken over them (GaussianModel.error_stats; with opt.bilateral_grid the image is
 corrected by the camera's grid first), and the ceil(opt.densify_error_growth * P) Gaussians responsible for the most image error
 (opt.densify_error_score: "max" over the views, or "sum") are cloned or split in place of those over the gradient threshold; the
-prune is unchanged.  0 (the default): the loop is as before.  The defaults of the two numbers are not tuned on captured scenes."""
+prune is unchanged.  0 (the default): the loop is as before.  The defaults of the two numbers are not tuned on captured scenes.
+opt.lambda_normal > 0 adds the normal-consistency loss from iteration opt.normal_from_iter on: one
+gaussian_renderer.render_normals frame of the same camera beside the colour frame, opt.lambda_normal * normal_consistency_loss(...)
+added to the loss in front of backward(); on_iteration still receives the image loss alone.  It composes with every strategy above (the
+normals frame is rendered without pipe.absgrad).  0 (the default): the loop is as before.  Neither number is tuned on captured scenes."""
 import math
 import random
 
@@ -55,6 +59,12 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
         if opt.densify_error_score not in gaussians.DENSIFY_ERROR_SCORES:
             raise ValueError(f"densify_error_score = {opt.densify_error_score!r}: one of "
                              f"{', '.join(repr(n) for n in gaussians.DENSIFY_ERROR_SCORES)}")
+    lambda_normal = float(getattr(opt, "lambda_normal", 0.0))
+    if lambda_normal < 0:
+        raise ValueError(f"lambda_normal = {lambda_normal}: a weight of at least 0 expected")
+    if lambda_normal > 0:
+        from diff_gaussian_rasterization.normals import normal_consistency_loss
+        from gaussian_renderer import render_normals
     if filter_3d:
         gaussians.compute_3D_filter(cameras)
     for it in range(first_iter, iterations + 1):
@@ -74,7 +84,17 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
         loss = training_loss(image, targets[idx], opt.lambda_dssim)
         if use_bilagrid:
             loss = loss + opt.bilateral_grid_tv * total_variation_loss(bilagrid.grids)
-        loss.backward()
+        if lambda_normal > 0 and it >= opt.normal_from_iter:
+            cam, absgrad = cameras[idx], getattr(pipe, "absgrad", False)
+            if absgrad:                                            # the normals frame carries depth and alpha: rendered without it
+                pipe.absgrad = False
+            maps = render_normals(cam, gaussians, pipe)
+            if absgrad:
+                pipe.absgrad = absgrad
+            normal_loss = normal_consistency_loss(maps["normal"], maps["depth"], maps["alpha"], math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5))
+            (loss + lambda_normal * normal_loss).backward()
+        else:
+            loss.backward()
         with torch.no_grad():
             if mcmc:
                 gaussians.mcmc_add_regularizer_grads(opt.mcmc_opacity_reg, opt.mcmc_scale_reg)
