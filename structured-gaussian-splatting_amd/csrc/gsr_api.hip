@@ -9,9 +9,6 @@
 #include <vector>
 
 #include "gsr_internal.h"
-#ifndef GSR_FILL_BEFORE_WAIT
-#define GSR_FILL_BEFORE_WAIT 1
-#endif
 
 namespace gsr {
 
@@ -152,10 +149,18 @@ static int validate_inputs(const gsr_frame_desc *d, const gsr_camera *c, const g
 // the copy is a 5 us kernel of its own and the event another packet, both on the critical path of a 0.8 ms step.)  A frame
 // whose geometry workspace is absent, or a stream that drains without the word arriving, falls back to the copy.
 constexpr double kReadbackTimeoutS = 30.0;
-// experiment switches (tools/): read ONCE, when the library is loaded — a re-run of gsr_forward_render after GSR_ERR_WORKSPACE must
-// take the decisions of the first run, whatever the environment does in between
-static const bool kNoLiveFilter = getenv("GSR_NO_LIVE_FILTER") != nullptr, kNoChunkMerge = getenv("GSR_NO_CHUNK_MERGE") != nullptr;
-static const int kFwdGroups = getenv("GSR_FWD_GROUPS") ? atoi(getenv("GSR_FWD_GROUPS")) : -1;       // 0 / 1: force the blend forward's kernel
+
+// the one reader of the environment (gsr_internal.h Switches): the experiments when the library is loaded, the test hooks per call
+static const Switches g_loaded = {getenv("GSR_NO_LIVE_FILTER") != nullptr, getenv("GSR_NO_CHUNK_MERGE") != nullptr,
+                                  getenv("GSR_NO_GATHER") != nullptr, getenv("GSR_FWD_GROUPS") ? atoi(getenv("GSR_FWD_GROUPS")) : -1,
+                                  false, false};
+Switches switches()
+{
+    Switches sw = g_loaded;
+    sw.sort_force_radix = getenv("GSR_SORT_FORCE_RADIX") != nullptr;
+    sw.reduce_rows_plain = getenv("GSR_REDUCE_ROWS_PLAIN") != nullptr;
+    return sw;
+}
 
 static inline void cpu_pause()
 {
@@ -245,29 +250,6 @@ static int wait_ctrl(const Ctrl *dev, Ctrl *out, hipStream_t s)
     return GSR_OK;
 }
 
-// Instances the backward's scratch must hold: exact when the forward stopped early (the count was read back with the open-tile
-// count); when the LAST chunk ran its count stayed on the device and the bound is what the chunks that ran could have emitted.
-static long long rows_bound(const gsr_frame_plan *plan)
-{
-    long long n = plan->instances_emitted;
-    if (n < 0) {
-        n = 0;
-        for (int c = 0; c < plan->chunks_run && c < GSR_MAX_CHUNKS; ++c) n += plan->chunk_instances_max[c];
-    }
-    return n < 1 ? 1 : n;
-}
-
-// bytes of the row-valid flags of n instances: one byte each, rounded up to whole 16-byte words of their padded block
-static size_t row_flag_bytes(long long n) { return ((size_t)(n < 1 ? 1 : n) + 15) & ~(size_t)15; }
-
-// row-valid flags to clear ahead of the blend backward: those of the instances the chunks that ran can have emitted (never more
-// than the binning workspace holds)
-static size_t valid_bytes(const gsr_frame_plan *plan)
-{
-    const long long n = rows_bound(plan), cap = plan_capacity(plan);
-    return row_flag_bytes(n > cap ? cap : n);
-}
-
 }  // namespace gsr
 
 using namespace gsr;
@@ -300,10 +282,7 @@ int gsr_binning_size(const gsr_frame_desc *desc, int64_t num_rendered, size_t *b
 int gsr_binning_first_chunk_capacity(const gsr_frame_plan *plan, int64_t *instances)
 {
     if (!plan || !instances) { set_error("gsr_binning_first_chunk_capacity: NULL argument"); return GSR_ERR_INVALID_ARGUMENT; }
-    // what the first depth chunk can emit at most, plus headroom for a small straggler chunk; never more than R
-    int64_t n = plan->num_chunks > 1 ? plan->chunk_instances_max[0] + plan->chunk_instances_max[0] / 4 + (1 << 20) : plan->num_rendered;
-    if (n > plan->num_rendered) n = plan->num_rendered;
-    *instances = n;
+    *instances = first_chunk_capacity(*plan);
     return GSR_OK;
 }
 
@@ -449,58 +428,35 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
     if (!plan->binning_initialised && (rc = launch_binning_init(f, gw, iw, dbg, s))) return rc;
     plan->binning_initialised = 0;                  // a re-run of this stage must reset the tile ranges / open flags itself
     int sort_result = 0;
-    uint64_t emitted_before = 0;                    // instances earlier chunks emitted (exact: read back with the open-tile count)
-    uint32_t open_now = 0xFFFFFFFFu, stuck_now = 0; // tiles still open before the current chunk, and those nothing covers yet (known from chunk 1 on)
-    constexpr int kLiveFilterMin = 1 << 16;         // the filter's launches pay off from this many Gaussians on
+    const Switches sw = switches();
+    const long long slab_tiles = (long long)(f.ty1 - f.ty0) * f.Gx;
+    Progress now;                                   // what the chunks so far left behind (each readback below)
     // Early stop: one control-block readback per chunk (~10 us of stream idle, measured); the chunk plan keeps
-    // the number of chunks at three or fewer.
+    // the number of chunks at three or fewer.  Which path each step takes: gsr_dispatch.h.
     for (int c = 0; c < plan->num_chunks; ++c) {
-        // A frame that is not going to close (an uncovered corner: some open tile still has a pixel that nothing has covered after
-        // the chunks so far, k_render_fwd marks those): every further chunk costs its fixed ~250 us for little.  All remaining chunks then become ONE, which goes
-        // through the live filter below (its Gaussians' relative keys are re-based there).
-        LiveParts parts{1, {0}, {0}};
-        const long long slab_tiles_now = (long long)(f.ty1 - f.ty0) * f.Gx;
-        if (c > 0 && c >= plan->chunks_sorted && c < plan->num_chunks - 1 && stuck_now > 0 && (long long)open_now * 2 < slab_tiles_now &&
-            !kNoLiveFilter && !kNoChunkMerge) {
-            const int last_c = plan->num_chunks - 1;
-            uint64_t m_max = 0;
-            for (int j = c; j <= last_c; ++j) m_max += (uint64_t)plan->chunk_instances_max[j];
-            const uint64_t m_n = (uint64_t)(plan->chunk_rank_begin[last_c + 1] - plan->chunk_rank_begin[c]);
-            if (m_n >= (uint64_t)kLiveFilterMin && m_max / 32 + 2 * m_n + 4 <= m_max && m_max <= 0xFFFFFFFFull) {
-                if (emitted_before + m_max > (uint64_t)capacity) {          // (before the plan is touched: the re-run decides the same)
-                    set_error("binning workspace holds %lld instances, the remaining depth chunks may need %llu: re-run "
-                              "gsr_forward_render with binning_capacity = num_rendered (%lld)", (long long)capacity,
-                              (unsigned long long)(emitted_before + m_max), (long long)plan->num_rendered);
-                    return GSR_ERR_WORKSPACE;
-                }
-                auto base_of = [&](int j) { const uint32_t e = plan->chunk_key_end[j - 1]; return e < 0x3E4CCCCDu ? 0x3E4CCCCDu : e; };
-                parts.n = last_c - c + 1;
-                for (int j = c; j <= last_c; ++j) {
-                    parts.end[j - c] = (uint32_t)(plan->chunk_rank_begin[j + 1] - plan->chunk_rank_begin[c]);
-                    parts.delta[j - c] = base_of(j) - base_of(c);
-                }
-                plan->chunk_rank_begin[c + 1] = plan->chunk_rank_begin[last_c + 1];
-                plan->chunk_key_end[c] = plan->chunk_key_end[last_c];
-                plan->chunk_instances_max[c] = (int64_t)m_max;
-                plan->num_chunks = c + 1;
-            }
+        // plan step: a frame that is not going to close runs all remaining chunks as one
+        LiveParts parts;
+        uint64_t need = 0;
+        if (merge_rest(plan, c, now, slab_tiles, capacity, !sw.no_live_filter && !sw.no_chunk_merge, &parts, &need) == Merge::kShort) {
+            set_error("binning workspace holds %lld instances, the remaining depth chunks may need %llu: re-run "
+                      "gsr_forward_render with binning_capacity = num_rendered (%lld)", (long long)capacity,
+                      (unsigned long long)need, (long long)plan->num_rendered);
+            return GSR_ERR_WORKSPACE;
         }
         const bool last = c == plan->num_chunks - 1;
         const int r0 = plan->chunk_rank_begin[c], r1 = plan->chunk_rank_begin[c + 1];
-        if (emitted_before + (uint64_t)plan->chunk_instances_max[c] > (uint64_t)capacity) {
+        const uint64_t chunk_n = (uint64_t)(r1 - r0), chunk_max = (uint64_t)plan->chunk_instances_max[c];
+        // capacity check
+        if (capacity_short(now.emitted, chunk_max, capacity)) {
             set_error("binning workspace holds %lld instances, depth chunk %d may need %llu: re-run gsr_forward_render with "
                       "binning_capacity = num_rendered (%lld)", (long long)capacity, c,
-                      (unsigned long long)(emitted_before + (uint64_t)plan->chunk_instances_max[c]), (long long)plan->num_rendered);
+                      (unsigned long long)(now.emitted + chunk_max), (long long)plan->num_rendered);
             return GSR_ERR_WORKSPACE;
         }
-        // the chunk's Gaussians were selected by depth; now that it is needed, put them in (depth, index) order
+        // filter, order: the chunk's Gaussians were selected by depth; now that it is needed, put them in (depth, index) order - a
+        // late, large chunk only those that can still reach an open tile
         // (once: a re-run of this stage after GSR_ERR_WORKSPACE finds the earlier chunks sorted, and the sort's inputs consumed)
-        // A late, large chunk with most tiles closed (a frame with a corner no splat covers runs every chunk, and the last one is
-        // most of the scene): first move the Gaussians whose rectangle still holds an open tile to the front of its range
-        // (launch_live_filter) — only those get sorted and binned, one wave each.
-        const uint64_t chunk_n = (uint64_t)(r1 - r0), chunk_max = (uint64_t)plan->chunk_instances_max[c];
-        const bool filtered = c > 0 && r1 - r0 >= kLiveFilterMin && (long long)open_now * 2 < (long long)(f.ty1 - f.ty0) * f.Gx &&
-                              chunk_max / 32 + 2 * chunk_n + 4 <= chunk_max && !kNoLiveFilter;
+        const bool filtered = chunk_filtered(c, r1 - r0, chunk_max, now, slab_tiles, sw.no_live_filter);
         if (filtered) plan->chunks_filtered |= 1 << c;
         if (c >= plan->chunks_sorted) {
             if (filtered && (rc = launch_live_filter(f, c, r0, r1, parts, gw, iw, dbg, s))) return rc;
@@ -511,17 +467,17 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
                 return rc;
             plan->chunks_sorted = c + 1;
         }
-        if ((rc = launch_chunk_binning(f, c, r0, r1, chunk_max, emitted_before, gw, bw, iw, &sort_result, dbg, s,
-                                       (plan->chunks_filtered >> c) & 1)))
-            return rc;
+        // bin, colours, blend.  From here on the PLAN's filtered bit decides, not the local one: a re-run of this stage after
+        // GSR_ERR_WORKSPACE must take the decisions of the first run
+        const bool plan_filtered = (plan->chunks_filtered >> c) & 1;
+        if ((rc = launch_chunk_binning(f, c, r0, r1, chunk_max, now.emitted, gw, bw, iw, &sort_result, dbg, s, plan_filtered))) return rc;
         if ((rc = launch_chunk_colors(f, *cam, *g, r0, r1, plan->num_visible, gw, dbg, s))) return rc;      // A.6 for this chunk's Gaussians only
-        // small splats (fewer than 4.5 tiles per Gaussian on average; filtered chunks bin a small, unknown part of their bound):
-        // the blend forward with one 16-lane group per quadrant
-        const bool small_splats = kFwdGroups >= 0 ? kFwdGroups != 0 : (!((plan->chunks_filtered >> c) & 1) && chunk_n > 0 && chunk_max * 2 < chunk_n * 9);
-        if ((rc = launch_render_fwd(f, *cam, c, last, sort_result, gw, bw, iw, out_color, dbg, s, small_splats, variant))) return rc;
+        const bool groups = sw.fwd_groups >= 0 ? sw.fwd_groups != 0 : small_splats(chunk_n, chunk_max, plan_filtered);
+        if ((rc = launch_render_fwd(f, *cam, c, last, sort_result, gw, bw, iw, out_color, dbg, s, groups, variant))) return rc;
         plan->chunks_run = c + 1;
         plan->instances_emitted = -1;                 // the last chunk's count stays on the device
         if (last) break;
+        // readback
         CtrlMirror mirror;
         if ((rc = next_mirror(&mirror))) return rc;
         if ((rc = launch_open_update(f, gw, iw, dbg, s, mirror))) return rc;
@@ -533,9 +489,7 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
         Ctrl h;
         if ((rc = wait_ctrl(gw.ctrl, &h, s))) return rc;
         plan->instances_emitted = (int64_t)h.chunk_base[c + 1];
-        emitted_before = (uint64_t)h.chunk_base[c + 1];
-        open_now = h.open_count;
-        stuck_now = h.open_stuck;
+        now = Progress{(uint64_t)h.chunk_base[c + 1], h.open_count, h.open_stuck};
         if (h.open_count == 0) break;
     }
     plan->sort_result = sort_result;
@@ -555,8 +509,7 @@ static int forward_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const
     int rc = validate_contrib(desc, v.stats, v.err, "gsr_forward_contrib");      // (before stage 1: a refused call launches nothing)
     if (rc) return rc;
     if ((rc = gsr_forward_preprocess(desc, cam, g, geom_ws, image_ws, radii, plan, stream))) return rc;
-    int64_t need = 0;
-    if ((rc = gsr_binning_first_chunk_capacity(plan, &need))) return rc;
+    const int64_t need = first_chunk_capacity(*plan);
     if (plan->num_rendered > 0 && (!binning_ws || binning_capacity < need)) {
         set_error("gsr_forward: the binning workspace holds %lld instances, the first depth chunk may need %lld: allocate and call "
                   "gsr_forward_render", (long long)binning_capacity, (long long)need);
@@ -567,9 +520,7 @@ static int forward_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const
     // The early fill: the zeros of a depth-complex frame's gradient tensors + the blend backward's row flags, 50 us of HBM writes at
     // 1M Gaussians.  It is enqueued behind the first chunk's blend and the kernel that posts its readback, BEFORE the host waits, so that it
     // runs while the host is idle in the wait and then busy getting back to its caller and on to the next launch (~60 us in which the
-    // GPU has nothing else to do).  Whether the frame ends up sparse is only known after the readback: the fill is enqueued when the
-    // first planned chunk alone is sparse - a frame whose first chunk holds a quarter of the Gaussians takes the dense path whatever
-    // follows - and is wasted bandwidth, nothing more, when later chunks make the frame dense after all.  (Measured and dropped: the
+    // GPU has nothing else to do).  For which frames: gsr_dispatch.h early_fill_before_wait; the others fill late, below.  (Measured and dropped: the
     // fill on a side stream beside the blend - the cross-queue waits cost more than it hid; the fill as the first job of every wave
     // of the blend forward - 17 us there instead of 47, but the gap after the readback was empty again: 0.694 ms per step, not 0.678.)
     const bool fill_wanted = early_fill && !early_fill->prezeroed && desc->P > 0 && plan->num_rendered > 0;
@@ -577,7 +528,7 @@ static int forward_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const
     ZeroSegs fill;
     fill.n = 0;
     bool filled = false;
-    if (GSR_FILL_BEFORE_WAIT && fill_wanted && plan->num_chunks > 1 && (long long)plan->chunk_rank_begin[1] * 4 < (long long)desc->P) {
+    if (fill_wanted && early_fill_before_wait(*plan, desc->P)) {
         const long long cap = plan_capacity(plan);
         const BinningWS bw = carve_binning(binning_ws, cap, f);
         fill = zero_segments(f, *g, nullptr, *early_fill, bw.row_valid, row_flag_bytes(cap));
@@ -762,9 +713,8 @@ int gsr_screen_absgrad(const gsr_frame_desc *desc, const int32_t *radii, const v
     if (!radii || !geom_ws || !screen_grads || !out) { set_error("gsr_screen_absgrad: NULL argument"); return GSR_ERR_INVALID_ARGUMENT; }
     const FrameK f = make_frame(*desc);
     GeomWS gw = carve_geom(const_cast<void *>(geom_ws), f.P);
-    const GeomRows rows = geom_rows(f, 0, f.P, binned_ranks, own_plan);          // the rows gsr_backward_geom visits
-    return launch_screen_absgrad(f, radii, screen_grads, rows.n_ranks, gw.order, rows.own_sparse ? gw.cnt_open : nullptr, rows.sparse, out,
-                                 desc->debug != 0, (hipStream_t)stream);
+    const GeomRows rows = geom_rows(f, 0, f.P, binned_ranks, own_plan, gw.order, gw.cnt_open);          // the rows gsr_backward_geom visits
+    return launch_screen_absgrad(f, radii, screen_grads, rows, out, desc->debug != 0, (hipStream_t)stream);
 }
 
 int gsr_backward_render_aux(const gsr_frame_desc *desc, const gsr_camera *cam, const void *geom_ws, void *binning_ws,
@@ -789,13 +739,10 @@ static int backward_geom_impl(const gsr_frame_desc *desc, const gsr_camera *cam,
     if (!radii || !geom_ws || !screen_grads) { set_error("gsr_backward_geom: NULL argument"); return GSR_ERR_INVALID_ARGUMENT; }
     const FrameK f = make_frame(*desc);
     GeomWS gw = carve_geom(const_cast<void *>(geom_ws), f.P);
-    const GeomRows rows = geom_rows(f, g_begin, g_end, binned_ranks, own_plan);
-    if ((rc = launch_geom_bwd(f, *cam, *g, radii, gw, screen_grads, g_begin, g_end, rows.n_ranks, *out, desc->debug != 0,
-                              (hipStream_t)stream, nullptr, rows.own_sparse)))
-        return rc;
+    const GeomRows rows = geom_rows(f, g_begin, g_end, binned_ranks, own_plan, gw.order, gw.cnt_open);
+    if ((rc = launch_geom_bwd(f, *cam, *g, radii, gw, screen_grads, rows, *out, desc->debug != 0, (hipStream_t)stream))) return rc;
     if (!depth_chain) return GSR_OK;
-    return launch_geom_bwd_depth(f, *cam, radii, screen_grads, g_begin, g_end, rows.n_ranks, gw.order, rows.own_sparse ? gw.cnt_open : nullptr,
-                                 rows.sparse, out->means3D, desc->debug != 0, (hipStream_t)stream);
+    return launch_geom_bwd_depth(f, *cam, radii, screen_grads, rows, out->means3D, desc->debug != 0, (hipStream_t)stream);
 }
 
 int gsr_backward_geom(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, const int32_t *radii,
@@ -836,9 +783,9 @@ int gsr_backward_camera(const gsr_frame_desc *desc, const gsr_camera *cam, const
     if (desc->P > 0 && (!radii || !geom_ws || !screen_grads)) { set_error("gsr_backward_camera: NULL argument"); return GSR_ERR_INVALID_ARGUMENT; }
     const FrameK f = make_frame(*desc);
     GeomWS gw = carve_geom(const_cast<void *>(geom_ws), f.P);
-    const GeomRows rows = geom_rows(f, 0, f.P, binned_ranks, own_plan);          // the rows gsr_backward_geom visits
-    return launch_camera_bwd(f, *cam, *g, radii, gw, screen_grads, rows.n_ranks, rows.sparse, rows.own_sparse, depth_chain != 0,
-                             (float *)workspace, *out, desc->debug != 0, (hipStream_t)stream);
+    const GeomRows rows = geom_rows(f, 0, f.P, binned_ranks, own_plan, gw.order, gw.cnt_open);          // the rows gsr_backward_geom visits
+    return launch_camera_bwd(f, *cam, *g, radii, gw, screen_grads, rows, depth_chain != 0, (float *)workspace, *out, desc->debug != 0,
+                             (hipStream_t)stream);
 }
 
 int gsr_backward_geom_rows(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, const int32_t *radii,
@@ -853,8 +800,9 @@ int gsr_backward_geom_rows(const gsr_frame_desc *desc, const gsr_camera *cam, co
     if (!radii || !geom_ws || !screen_grads) { set_error("gsr_backward_geom_rows: NULL argument"); return GSR_ERR_INVALID_ARGUMENT; }
     const FrameK f = make_frame(*desc);
     GeomWS gw = carve_geom(const_cast<void *>(geom_ws), f.P);
-    return launch_geom_bwd(f, *cam, *g, radii, gw, screen_grads, 0, f.P, n_rows, *out, desc->debug != 0, (hipStream_t)stream,
-                           reinterpret_cast<const uint32_t *>(rows));
+    // the caller's list: sparse below P / 4 rows, else the dense kernel over every Gaussian
+    const GeomRows visit = geom_rows(f, 0, f.P, n_rows, nullptr, reinterpret_cast<const uint32_t *>(rows), nullptr);
+    return launch_geom_bwd(f, *cam, *g, radii, gw, screen_grads, visit, *out, desc->debug != 0, (hipStream_t)stream);
 }
 
 int gsr_frame_arrays(const gsr_frame_desc *desc, const void *geom_ws, const uint32_t **depth_keys, const uint32_t **depth_order)

@@ -517,7 +517,6 @@ __global__ __launch_bounds__(kBinBlock) void k_bin_chunk(FrameK f, int c, int r0
 // bit tests (44 M for cfg3's first chunk) instead of a 2 M-key radix sort.
 // scan_n > 0 (chunks of up to kRankScanMax Gaussians): the same block first scans the chunk's per-rank counts (offs_open, the chunk's
 // emitted total and the next chunk's base), which saves the launch of a one-block scan in front of this one.
-constexpr int kRankScanMax = 16384;
 // Both scans of the kernel run in rounds of 1024 kTrPer = 8192 elements (a 1920x1080 frame has 8160 tiles): global memory is read and
 // written COALESCED (thread t holds elements t, t + 1024, ...: with consecutive elements per thread every load and store of a wave
 // touched 64 cache lines, and the one CU's address path, not the scan, was the kernel's time), the block scan wants consecutive
@@ -857,38 +856,22 @@ int launch_chunk_binning(const FrameK &f, int c, int r0, int r1, uint64_t n_max,
     const int n = r1 - r0;
     if (n <= 0) return GSR_OK;
     const size_t Tn = (size_t)f.Gx * f.Gy;
-    // variant B packs the (Gaussian, tile) candidates of 64 Gaussians into full wave steps: right when rectangles are
-    // small; chunks of few large splats (the nearest ones) get a team of 1, 4 or 16 waves per Gaussian (variant A)
-    const uint64_t avg = n_max / (uint64_t)n;
-    // a chunk the live filter went through: few survivors, every one of them with work -> one wave per Gaussian whatever the
-    // rectangle size (64 ranks per wave would leave a handful of long-running waves); its mask scratch fits (the caller checked)
-    const bool flat = avg < 24 && !filtered;
-    const int team = filtered ? 1 : avg >= 1024 ? 16 : avg >= 96 ? 4 : 1;
+    const uint64_t slab_tiles = (uint64_t)(f.ty1 - f.ty0) * (uint64_t)f.Gx;
+    const BinPath path = bin_path(n, n_max, filtered, slab_tiles, Tn, switches().no_gather);      // every choice below is made there
+    const bool flat = path.flat, gather = path.gather, carry_gid = path.carry_gid;
+    const int team = path.team, team_grid = path.team_grid;
     const int bin_blocks = (n + kBinBlock - 1) / kBinBlock;      // B: 64 depth ranks per wave, 4 waves per block
     // A's mask scratch: the idle half of the radix double buffer beyond everything earlier chunks have written (their exact
     // emitted count; ceil(n_max / 64) + n words of 8 bytes fit in the n_max slots the caller has checked are there: a team
-    // chunk averages >= 24 tiles per Gaussian)
+    // chunk averages >= 24 tiles per Gaussian, a filtered one passed live_filter_pays)
     unsigned long long *masks = reinterpret_cast<unsigned long long *>(bw.keys[1] + ((emitted_before + 1) & ~(uint64_t)1));
-    // A' (gather instead of emit + sort) when the ranks x tiles bit tests are cheaper than sorting the instances; its
-    // scratch (mask prefixes, rank metadata: n_max / 64 + 9 n + 4 words) sits in the other idle key buffer
-    const uint64_t slab_tiles = (uint64_t)(f.ty1 - f.ty0) * (uint64_t)f.Gx;
-    const uint64_t scratch_words = n_max / 64 + 1 + 9 * (uint64_t)n + 4;
-    static const bool no_gather = getenv("GSR_NO_GATHER") != nullptr;      // experiment switch, read once
-    const bool gather = !flat && !filtered && !no_gather && n < (1 << 26) && (uint64_t)n * slab_tiles <= 24 * n_max + (1ull << 22) &&
-                        scratch_words <= n_max;
+    // the gather's scratch (mask prefixes, rank metadata) sits in the other idle key buffer
     uint32_t *scratch = bw.keys[0] + ((emitted_before + 3) & ~(uint64_t)3);
     uint4 *meta_a = reinterpret_cast<uint4 *>(scratch);
     float4 *meta_b = reinterpret_cast<float4 *>(scratch + 4 * (size_t)n);
     uint32_t *wprefix = scratch + 8 * (size_t)n;
-    const int tile_bits = bit_width((uint32_t)(Tn ? Tn - 1 : 0));
-    // The blend kernels find a sorted entry's Gaussian (| quadrant mask) in gids[1], always.  Large sorts carry the word through the
-    // radix passes (the emit kernels then write it into the buffer the passes leave in [1]); small ones gather it behind the sort.
-    const int sort_passes = ((tile_bits > 0 ? tile_bits : 1) + 7) / 8;
-    const bool carry_gid = n_max >= (4ull << 20);
-    uint32_t *const gid_emit = bw.gids[carry_gid && !(sort_passes & 1) ? 1 : 0];
-    uint32_t *const gid_pingpong[2] = {gid_emit, gid_emit == bw.gids[0] ? bw.gids[1] : bw.gids[0]};
-    // a filtered chunk: a fixed grid walks the live front part; everybody else's count is zero from the start
-    const int team_grid = filtered ? (n < 65536 ? n : 65536) : n;      // (4 k: +35 us per launch, 256 k: +20 us; measured)
+    uint32_t *const gid_emit = bw.gids[path.gid_emit];
+    uint32_t *const gid_pingpong[2] = {gid_emit, bw.gids[path.gid_emit ^ 1]};
     if (filtered) GSR_HIP_CHECK(hipMemsetAsync(gw.cnt_open + r0, 0, (size_t)n * sizeof(uint32_t), s));
     {
         ProfileScope prof("count_open", s);
@@ -904,13 +887,12 @@ int launch_chunk_binning(const FrameK &f, int c, int r0, int r1, uint64_t n_max,
 #undef GSR_CT
         GSR_LAUNCH_CHECK("count_open", debug, s);
     }
-    const bool fused_scan = gather && n <= kRankScanMax;         // the rank scan rides in k_tile_ranges
+    const bool fused_scan = path.fused_scan;
     if (!fused_scan && (rc = launch_scan_inclusive(gw.cnt_open + r0, gw.offs_open + r0, n, gw.scan_temp, &gw.ctrl->chunk_R[c],
                                                    &gw.ctrl->chunk_base[c], &gw.ctrl->chunk_base[c + 1], "scan_open", debug, s)))
         return rc;
     if (gather) {
-        // the list ends where the radix passes would have left it, so that all chunks of a frame agree on the buffer
-        const int res = (((tile_bits > 0 ? tile_bits : 1) + 7) / 8) & 1;
+        const int res = path.result;
         *sort_result = res;
         {
             ProfileScope prof("tile_ranges", s);
@@ -942,7 +924,7 @@ int launch_chunk_binning(const FrameK &f, int c, int r0, int r1, uint64_t n_max,
         GSR_LAUNCH_CHECK("emit", debug, s);
     }
     if ((rc = launch_radix_sort<uint32_t>(bw.keys, bw.vals, &gw.ctrl->chunk_R[c], 0, n_max, &gw.ctrl->chunk_base[c], 0,
-                                          tile_bits > 0 ? tile_bits : 1, gw.radix_temp, sort_result, "tile_sort", debug, s, false,
+                                          path.tile_bits, gw.radix_temp, sort_result, "tile_sort", debug, s, false,
                                           carry_gid ? gid_pingpong : nullptr)))
         return rc;
     {

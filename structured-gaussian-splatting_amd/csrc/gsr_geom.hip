@@ -318,8 +318,7 @@ int launch_chunk_colors(const FrameK &f, const gsr_camera &cam, const gsr_gaussi
 {
     if (!g.shs || r1 <= r0) return GSR_OK;           // precomputed colours went into the records in the preprocess
     ProfileScope prof("chunk_colors", s);
-    if (r0 == 0 && r1 >= num_visible && (long long)num_visible * 2 >= (long long)f.P) {
-        // the chunk is every visible Gaussian and most Gaussians are visible: walk the tensor in index order
+    if (colors_in_index_order(r0, r1, num_visible, f.P)) {
         const int grid_all = (f.P + kGeomBlock - 1) / kGeomBlock;
         // (no activations in these kernels: RAW only names the SH layout)
         dispatch_deg_raw<2>(f.D, raw_split_sh(g) ? 1 : 0, [&](auto deg, auto raw) {
@@ -766,18 +765,17 @@ size_t camera_grad_workspace_bytes(int P)
 }
 
 int launch_camera_bwd(const FrameK &f, const gsr_camera &cam, const gsr_gaussians &g, const int32_t *radii, const GeomWS &gw,
-                      const float *screen_grads, int n_ranks, bool sparse, bool own_frame_sparse, bool depth_chain, float *partials,
-                      const gsr_camera_grads &out, bool debug, hipStream_t s)
+                      const float *screen_grads, const GeomRows &rows, bool depth_chain, float *partials, const gsr_camera_grads &out,
+                      bool debug, hipStream_t s)
 {
-    const int n = sparse ? (n_ranks > 0 ? n_ranks : 0) : f.P;
+    const int n = rows.count();
     const int grid = min((n + kGeomBlock - 1) / kGeomBlock, kCamMaxBlocks);
     if (grid > 0) {
         ProfileScope prof("camera_bwd", s);
-        const uint32_t *cnt_open = sparse && own_frame_sparse ? gw.cnt_open : nullptr;
         dispatch_deg_raw<3>(f.D, raw_mode(g), [&](auto deg, auto raw) {
-            auto *kernel = sparse ? k_camera_bwd<decltype(deg)::value, decltype(raw)::value, true>
-                                  : k_camera_bwd<decltype(deg)::value, decltype(raw)::value, false>;
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kGeomBlock), 0, s, f, n, sparse ? gw.order : nullptr, cnt_open, cam.viewmatrix,
+            auto *kernel = rows.sparse ? k_camera_bwd<decltype(deg)::value, decltype(raw)::value, true>
+                                       : k_camera_bwd<decltype(deg)::value, decltype(raw)::value, false>;
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kGeomBlock), 0, s, f, n, rows.rows, rows.cnt_open, cam.viewmatrix,
                                cam.projmatrix, cam.campos, g.means3D, g.scales, g.rotations, g.cov3D_precomp, g.opacities, g.shs,
                                g.shs_rest, g.colors_precomp ? 1 : 0, radii, gw.clamped, reinterpret_cast<const float4 *>(screen_grads),
                                depth_chain ? 1 : 0, partials);
@@ -850,44 +848,43 @@ int launch_zero_segments(const ZeroSegs &z, hipStream_t s)
 }
 
 // the aux backward's z chain (k_geom_bwd_depth), behind launch_geom_bwd of the same arguments: over the rows it visited
-int launch_geom_bwd_depth(const FrameK &f, const gsr_camera &cam, const int32_t *radii, const float *screen_grads, int g0, int g1,
-                          int n_ranks, const uint32_t *rows, const uint32_t *cnt_open, bool sparse, float *dmeans, bool debug, hipStream_t s)
+int launch_geom_bwd_depth(const FrameK &f, const gsr_camera &cam, const int32_t *radii, const float *screen_grads, const GeomRows &rows,
+                          float *dmeans, bool debug, hipStream_t s)
 {
-    const int n = sparse ? n_ranks : g1 - g0;
+    const int n = rows.count();
     if (!dmeans || n <= 0) return GSR_OK;
     ProfileScope prof("geom_bwd_depth", s);
     const dim3 grid((unsigned)((n + kGeomBlock - 1) / kGeomBlock));
     const float4 *screen = reinterpret_cast<const float4 *>(screen_grads);
-    hipLaunchKernelGGL(sparse ? k_geom_bwd_depth<true> : k_geom_bwd_depth<false>, grid, dim3(kGeomBlock), 0, s, sparse ? 0 : g0, n, f.P,
-                       sparse ? rows : nullptr, sparse ? cnt_open : nullptr, cam.viewmatrix, radii, screen, dmeans);
+    hipLaunchKernelGGL(rows.sparse ? k_geom_bwd_depth<true> : k_geom_bwd_depth<false>, grid, dim3(kGeomBlock), 0, s, rows.sparse ? 0 : rows.g0,
+                       n, f.P, rows.rows, rows.cnt_open, cam.viewmatrix, radii, screen, dmeans);
     GSR_LAUNCH_CHECK("geom_bwd_depth", debug, s);
     return GSR_OK;
 }
 
-int launch_screen_absgrad(const FrameK &f, const int32_t *radii, const float *screen_grads, int n_ranks, const uint32_t *rows,
-                          const uint32_t *cnt_open, bool sparse, float *out, bool debug, hipStream_t s)
+int launch_screen_absgrad(const FrameK &f, const int32_t *radii, const float *screen_grads, const GeomRows &rows, float *out, bool debug,
+                          hipStream_t s)
 {
     if (f.P <= 0) return GSR_OK;
     ProfileScope prof("screen_absgrad", s);
-    if (sparse) GSR_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)f.P * 3 * sizeof(float), s));
-    const int n = sparse ? n_ranks : f.P;
+    if (rows.sparse) GSR_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)f.P * 3 * sizeof(float), s));
+    const int n = rows.count();
     if (n > 0) {
         const dim3 grid((unsigned)((n + kGeomBlock - 1) / kGeomBlock));
         const float4 *screen = reinterpret_cast<const float4 *>(screen_grads);
-        hipLaunchKernelGGL(sparse ? k_screen_absgrad<true> : k_screen_absgrad<false>, grid, dim3(kGeomBlock), 0, s, n, f.P,
-                           sparse ? rows : nullptr, sparse ? cnt_open : nullptr, radii, screen, out);
+        hipLaunchKernelGGL(rows.sparse ? k_screen_absgrad<true> : k_screen_absgrad<false>, grid, dim3(kGeomBlock), 0, s, n, f.P, rows.rows,
+                           rows.cnt_open, radii, screen, out);
     }
     GSR_LAUNCH_CHECK("screen_absgrad", debug, s);
     return GSR_OK;
 }
 
 int launch_geom_bwd(const FrameK &f, const gsr_camera &cam, const gsr_gaussians &g, const int32_t *radii, const GeomWS &gw,
-                    const float *screen_grads, int g0, int g1, int n_ranks, const gsr_grads &out, bool debug, hipStream_t s,
-                    const uint32_t *rows, bool own_frame_sparse)
+                    const float *screen_grads, const GeomRows &rows, const gsr_grads &out, bool debug, hipStream_t s)
 {
+    const int g0 = rows.g0, g1 = rows.g1, n_ranks = rows.n_ranks;
     if (g1 <= g0) return GSR_OK;
-    if (!rows) rows = gw.order;                  // the frame's own binned prefix
-    if (geom_bwd_sparse(f, g0, g1, n_ranks, own_frame_sparse)) {
+    if (rows.sparse) {
         // depth-complex frame: almost every gradient row is zero -> memset the outputs, then visit the binned prefix only
         ProfileScope prof("geom_bwd", s);
         int rc0;
@@ -896,9 +893,9 @@ int launch_geom_bwd(const FrameK &f, const gsr_camera &cam, const gsr_gaussians 
             const int sgrid = (n_ranks + kGeomBlock - 1) / kGeomBlock;
             dispatch_deg_raw<3>(f.D, raw_mode(g), [&](auto deg, auto raw) {
                 hipLaunchKernelGGL((k_geom_bwd_sparse<decltype(deg)::value, decltype(raw)::value>), dim3(sgrid), dim3(kGeomBlock), 0, s, f,
-                                   n_ranks, rows, cam.viewmatrix, cam.projmatrix, cam.campos, g.means3D, g.scales, g.rotations,
+                                   n_ranks, rows.rows, cam.viewmatrix, cam.projmatrix, cam.campos, g.means3D, g.scales, g.rotations,
                                    g.cov3D_precomp, g.opacities, g.shs, g.shs_rest, g.colors_precomp ? 1 : 0, radii, gw.clamped,
-                                   reinterpret_cast<const float4 *>(screen_grads), out, own_frame_sparse ? gw.cnt_open : nullptr);
+                                   reinterpret_cast<const float4 *>(screen_grads), out, rows.cnt_open);
             });
         }
         GSR_LAUNCH_CHECK("geom_bwd_sparse", debug, s);

@@ -7,6 +7,7 @@
 #include <stdio.h>
 
 #include "../../include/gsrast.h"
+#include "gsr_dispatch.h"
 #include "gsr_math.h"
 #include "gsr_wave.h"
 
@@ -38,6 +39,18 @@ void set_error(const char *fmt, ...);     // thread-local message behind gsr_las
         }                                                                                         \
     } while (0)
 
+// ---- environment switches: one struct, one reader (gsr_api.hip).  The path rules of gsr_dispatch.h take them as booleans.
+struct Switches {
+    // experiments (tools/, child processes of the tests): read ONCE, when the library is loaded - a re-run of gsr_forward_render after
+    // GSR_ERR_WORKSPACE must take the decisions of the first run, whatever the environment does in between
+    bool no_live_filter, no_chunk_merge, no_gather;      // GSR_NO_LIVE_FILTER, GSR_NO_CHUNK_MERGE, GSR_NO_GATHER
+    int fwd_groups;                                      // GSR_FWD_GROUPS: 0 / 1 force the blend forward's kernel, -1 (unset): small_splats()
+    // test hooks: read again on every call (tests set them per case, in-process)
+    bool sort_force_radix;                               // GSR_SORT_FORCE_RADIX: the one-block LDS sort, on its radix path, instead of the ranking kernel
+    bool reduce_rows_plain;                              // GSR_REDUCE_ROWS_PLAIN: the wide row reduction's one-trip-at-a-time loop
+};
+Switches switches();
+
 // ---- optional per-kernel timing (gsr_profile_enable / gsr_profile_read)
 bool profile_on();
 int profile_begin(const char *name, hipStream_t s);
@@ -49,12 +62,6 @@ struct ProfileScope {
 };
 
 inline size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
-inline int bit_width(uint32_t v)          // bits needed to write v: 0 for 0, else 1 + the position of its highest set bit
-{
-    int b = 0;
-    while (v) { ++b; v >>= 1; }
-    return b;
-}
 
 inline FrameK make_frame(const gsr_frame_desc &d)
 {
@@ -236,10 +243,9 @@ int launch_depth_select(const FrameK &f, GeomWS &ws, bool debug, hipStream_t s, 
 int launch_rows_gather(const FrameK &f, GeomWS &ws, uint32_t key_max, const float *screen, int n_rows, int32_t *rows, float *packed,
                        bool debug, hipStream_t s);
 int launch_rows_scatter(int n_rows, int P, const int32_t *rows, const float *packed, float *screen, bool debug, hipStream_t s);
+// live_count (device, a filtered chunk's): only the first *live_count Gaussians of the range need sorting
 int launch_chunk_order(const FrameK &f, int r0, int r1, uint32_t key_lo, uint32_t key_hi, bool first, GeomWS &ws, bool debug, hipStream_t s,
                        const uint32_t *live_count = nullptr);
-// parts: the range may span several planned chunks (merged by the caller); their relative keys are re-based to the first one's
-struct LiveParts { int n; uint32_t end[GSR_MAX_CHUNKS]; uint32_t delta[GSR_MAX_CHUNKS]; };      // end: position in the range; delta: added to the key
 int launch_live_filter(const FrameK &f, int c, int r0, int r1, const LiveParts &parts, GeomWS &gw, ImageWS &iw, bool debug, hipStream_t s);
 size_t binning_clear_bytes(const ImageWS &iw);      // ranges + tile counters: a multiple of 16
 // Where k_open_count publishes the control block for the host: sizeof(Ctrl) / 4 words of host-coherent pinned memory (device
@@ -250,8 +256,7 @@ int launch_binning_init(const FrameK &f, GeomWS &gw, ImageWS &iw, bool debug, hi
 int launch_chunk_colors(const FrameK &f, const gsr_camera &cam, const gsr_gaussians &g, int r0, int r1, int num_visible, GeomWS &ws,
                         bool debug, hipStream_t s);
 int launch_chunk_binning(const FrameK &f, int c, int r0, int r1, uint64_t n_max, uint64_t emitted_before, GeomWS &gw, BinningWS &bw,
-                         ImageWS &iw,
-                         int *sort_result, bool debug, hipStream_t s, bool filtered = false);
+                         ImageWS &iw, int *sort_result, bool debug, hipStream_t s, bool filtered);
 // init: (re)initialise the open flags for the slab instead of reading them (launch_binning_init's call)
 int launch_open_update(const FrameK &f, GeomWS &gw, ImageWS &iw, bool debug, hipStream_t s, CtrlMirror mirror = CtrlMirror(),
                        bool init = false);
@@ -287,56 +292,22 @@ int launch_zero_outputs(const FrameK &f, const gsr_gaussians &g, float *screen, 
                         uint8_t *row_valid = nullptr, size_t valid_bytes = 0);
 int launch_reduce_rows(const FrameK &f, const gsr_frame_plan &plan, const GeomWS &gw, const BinningWS &bw, float *screen_grads,
                        int prezeroed, bool debug, hipStream_t s, BwdKind kind);
-// gsr_screen_absgrad: out [P,3] = (slot 10, slot 11, 0) of the rows launch_geom_bwd visits (same arguments), zeros elsewhere
-int launch_screen_absgrad(const FrameK &f, const int32_t *radii, const float *screen_grads, int n_ranks, const uint32_t *rows,
-                          const uint32_t *cnt_open, bool sparse, float *out, bool debug, hipStream_t s);
-// Depth ranks that can own a gradient, as far as the host knows: the chunks that ran, a chunk that went through the live filter
-// counted as nothing (only the Gaussians that still reached an open tile were binned: few, and how few is the device's knowledge).
-// Decides "sparse geometry backward + zero fill" against "dense geometry backward" (sparse below P / 4).
-inline long long effective_binned_ranks(const gsr_frame_plan &plan)
-{
-    long long n = 0;
-    const int chunks = (plan.num_rendered > 0 && plan.chunks_run > 0) ? plan.chunks_run : 0;
-    for (int c = 0; c < chunks && c < GSR_MAX_CHUNKS; ++c)
-        if (!((plan.chunks_filtered >> c) & 1)) n += plan.chunk_rank_begin[c + 1] - plan.chunk_rank_begin[c];
-    return n;
-}
-// own_frame_sparse: the gradients are this frame's own (gsr_backward_render of the same plan) and the sparse path was chosen from
-// effective_binned_ranks: ranks that emitted no instance (GeomWS::cnt_open) are skipped before anything of theirs is read
+// The geometry backward over `rows` (gsr_dispatch.h geom_rows: the Gaussians or ranks to visit, and the sparse choice, made once).
+// Sparse: zero-fills the outputs (unless out.prezeroed) and visits the listed ranks only.
 int launch_geom_bwd(const FrameK &f, const gsr_camera &cam, const gsr_gaussians &g, const int32_t *radii, const GeomWS &gw,
-                    const float *screen_grads, int g0, int g1, int n_ranks, const gsr_grads &out, bool debug, hipStream_t s,
-                    const uint32_t *rows = nullptr, bool own_frame_sparse = false);
-// launch_geom_bwd visits the ranks [0, n_ranks) of `rows` (sparse) instead of the Gaussians [g0, g1)
-inline bool geom_bwd_sparse(const FrameK &f, int g0, int g1, int n_ranks, bool own_frame_sparse)
-{
-    return n_ranks >= 0 && g0 == 0 && g1 == f.P && (own_frame_sparse || (long long)n_ranks * 4 < (long long)f.P);
-}
-// The rows gsr_backward_geom(_aux) and gsr_backward_camera visit.  own_plan (honoured for the whole range [0, P) only): the gradients
-// come from gsr_backward_render of THIS frame: the ranks of the chunks that ran, and among them only those that emitted an instance,
-// can be non-zero; sparse (fill + visit those) unless unfiltered chunks hold P / 4 Gaussians or more.
-struct GeomRows { int n_ranks; bool own_sparse, sparse; };      // launch_geom_bwd's n_ranks and own_frame_sparse; geom_bwd_sparse of them
-inline GeomRows geom_rows(const FrameK &f, int g_begin, int g_end, int binned_ranks, const gsr_frame_plan *own_plan)
-{
-    GeomRows r{binned_ranks, false, false};
-    if (own_plan && g_begin == 0 && g_end == f.P && own_plan->num_rendered > 0 && own_plan->chunks_run > 0) {
-        r.n_ranks = own_plan->chunk_rank_begin[own_plan->chunks_run];
-        r.own_sparse = effective_binned_ranks(*own_plan) * 4 < (long long)f.P;
-    }
-    r.sparse = g_end > g_begin && geom_bwd_sparse(f, g_begin, g_end, r.n_ranks, r.own_sparse);
-    return r;
-}
-// instances the frame's binning workspace holds
-inline long long plan_capacity(const gsr_frame_plan *plan) { return plan->binning_capacity > 0 ? plan->binning_capacity : plan->num_rendered; }
-// The aux backward's z chain behind launch_geom_bwd (same rows, same sparse choice): dmeans3D += dL/dz (view[2], view[6], view[10]),
-// dL/dz = screen_grads slot 9.  cnt_open: as launch_geom_bwd's own_frame_sparse (ranks that emitted nothing are skipped), else NULL.
-int launch_geom_bwd_depth(const FrameK &f, const gsr_camera &cam, const int32_t *radii, const float *screen_grads, int g0, int g1,
-                          int n_ranks, const uint32_t *rows, const uint32_t *cnt_open, bool sparse, float *dmeans, bool debug, hipStream_t s);
-// Camera gradients behind launch_geom_bwd (same rows, same sparse choice): k_camera_bwd writes one kCamTerms-float partial per
-// block into `partials` (camera_grad_workspace_bytes(P) bytes), k_camera_reduce adds them in block order into `out`.
+                    const float *screen_grads, const GeomRows &rows, const gsr_grads &out, bool debug, hipStream_t s);
+// The aux backward's z chain behind launch_geom_bwd (same rows): dmeans3D += dL/dz (view[2], view[6], view[10]), dL/dz = screen_grads slot 9
+int launch_geom_bwd_depth(const FrameK &f, const gsr_camera &cam, const int32_t *radii, const float *screen_grads, const GeomRows &rows,
+                          float *dmeans, bool debug, hipStream_t s);
+// gsr_screen_absgrad: out [P,3] = (slot 10, slot 11, 0) of the rows launch_geom_bwd visits (same rows), zeros elsewhere
+int launch_screen_absgrad(const FrameK &f, const int32_t *radii, const float *screen_grads, const GeomRows &rows, float *out, bool debug,
+                          hipStream_t s);
+// Camera gradients behind launch_geom_bwd (same rows): k_camera_bwd writes one kCamTerms-float partial per block into `partials`
+// (camera_grad_workspace_bytes(P) bytes), k_camera_reduce adds them in block order into `out`.
 size_t camera_grad_workspace_bytes(int P);
 int launch_camera_bwd(const FrameK &f, const gsr_camera &cam, const gsr_gaussians &g, const int32_t *radii, const GeomWS &gw,
-                      const float *screen_grads, int n_ranks, bool sparse, bool own_frame_sparse, bool depth_chain, float *partials,
-                      const gsr_camera_grads &out, bool debug, hipStream_t s);
+                      const float *screen_grads, const GeomRows &rows, bool depth_chain, float *partials, const gsr_camera_grads &out,
+                      bool debug, hipStream_t s);
 int launch_mark_visible(int P, const float *means3D, const float *view, uint8_t *present, hipStream_t s);
 
 }  // namespace gsr

@@ -1112,10 +1112,7 @@ __global__ __launch_bounds__(kRedBlock) void k_reduce_rows(int r_begin, int n_ra
         screen[3 * (size_t)g + sub] = sub == 0 ? a0 : (sub == 1 ? a1 : make_float4(a8, a9, a10, a11));
 }
 
-// One launch per depth chunk that ran, each with its own lanes-per-Gaussian: a whole wave where the chunk's Gaussians own many
-// rows each (the nearest, screen-filling splats: a few thousand rows), eight otherwise — and always eight for a chunk that went
-// through the live filter, whose instance bound says nothing about what it emitted (a training frame's last chunk is most of the
-// scene with a bound of tens of millions: 64 lanes for each of its 1e6 ranks was 100 us of idle threads).
+// One launch per depth chunk that ran, each with its own lanes-per-Gaussian: a whole wave or eight (gsr_dispatch.h reduce_wide)
 int launch_reduce_rows(const FrameK &f, const gsr_frame_plan &plan, const GeomWS &gw, const BinningWS &bw, float *screen_grads,
                        int prezeroed, bool debug, hipStream_t s, BwdKind kind)
 {
@@ -1130,15 +1127,12 @@ int launch_reduce_rows(const FrameK &f, const gsr_frame_plan &plan, const GeomWS
     ProfileScope prof(names[(int)kind], s);
     if (prezeroed == 0) GSR_HIP_CHECK(hipMemsetAsync(screen_grads, 0, (size_t)f.P * kRowFloats * sizeof(float), s));
     const int write_empty = prezeroed == 2 ? 1 : 0;
-    const int plain = getenv("GSR_REDUCE_ROWS_PLAIN") ? 1 : 0;                   // test hook (tests set it per case): the wide groups' one-trip-at-a-time loop
+    const int plain = switches().reduce_rows_plain ? 1 : 0;
     const int chunks = (plan.num_rendered > 0 && plan.chunks_run > 0) ? plan.chunks_run : 0;
     for (int c = 0; c < chunks && c < GSR_MAX_CHUNKS; ++c) {
         const int r0 = plan.chunk_rank_begin[c], r1 = plan.chunk_rank_begin[c + 1];
         if (r1 <= r0) continue;
-        const bool filtered = (plan.chunks_filtered >> c) & 1;
-        const long long avg = plan.chunk_instances_max[c] / (long long)(r1 - r0);
-        const bool wide = !filtered && avg >= 48;
-        // (two lanes per Gaussian for small splats, measured: 89 us against 81 at cfg3n, 352 against 374 at cfg5n — not kept)
+        const bool wide = reduce_wide(r1 - r0, plan.chunk_instances_max[c], (plan.chunks_filtered >> c) & 1);
         const long long threads = (long long)(r1 - r0) * (wide ? 64 : 8);
         const dim3 grid((unsigned)((threads + kRedBlock - 1) / kRedBlock));
         hipLaunchKernelGGL(kernels[(int)kind][wide], grid, dim3(kRedBlock), 0, s, r0, r1, gw.order, gw.cnt_open, gw.row_begin,

@@ -21,7 +21,6 @@
 namespace gsr {
 
 constexpr int kSelThreads = 512;
-constexpr int kSmallSortMax = 16384;                          // chunks of up to this many Gaussians are ordered by one launch (3. below)
 constexpr int kSelHistBlocks = 256;
 constexpr int kSelWaves = kSelThreads / kWave;
 
@@ -278,7 +277,6 @@ __global__ __launch_bounds__(kSelThreads) void k_part_count(int P, const uint32_
 
 // relative key of a Gaussian inside its chunk: the chunk's keys lie in (lower, key_end]; visible depths exceed the near cut,
 // whose bits bound the first chunk from below.  The chunk sort works on these (fewer varying bits = fewer passes).
-constexpr uint32_t kNearBits = 0x3E4CCCCDu;                      // 0.2f (GSR_NEAR_CUT): in_frustum() keeps view depth > 0.2
 __host__ __device__ __forceinline__ uint32_t sel_key_base(uint32_t prev_end, bool first) { return first || prev_end < kNearBits ? kNearBits : prev_end; }
 
 __global__ __launch_bounds__(kSelThreads) void k_part_scatter(int P, const uint32_t *__restrict__ keys, const uint2 *__restrict__ tiles_mass,
@@ -743,8 +741,8 @@ int launch_chunk_order(const FrameK &f, int r0, int r1, uint32_t key_lo, uint32_
     const uint32_t base = sel_key_base(key_lo, first);
     int bits = bit_width(key_hi > base ? key_hi - base : 0u);
     if (bits < 1) bits = 1;
-    if (n <= kSmallSortMax && !live_count) {
-        const int force_radix = getenv("GSR_SORT_FORCE_RADIX") ? 1 : 0;               // test hook (tests set it per case): the one-block LDS sort, on its radix path, instead of the ranking kernel
+    if (order_in_one_launch(n, live_count != nullptr)) {
+        const int force_radix = switches().sort_force_radix ? 1 : 0;
         ProfileScope prof("chunk_sort", s);
         if (!force_radix)
             hipLaunchKernelGGL(k_chunk_rank, dim3((unsigned)((n + kRankBlock / kRankLanes - 1) / (kRankBlock / kRankLanes))), dim3(kRankBlock), 0, s, n,

@@ -288,9 +288,7 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
             capacity = int(plan.binning_capacity) if plan.binning_capacity > 0 else guess
             fr.binning_ws = binning
         else:
-            first = int(plan.chunk_instances_max[0])
-            capacity = min(first + first // 4 + (1 << 20), R) if plan.num_chunks > 1 else R        # = gsr_binning_first_chunk_capacity
-            capacity = max(capacity, min(guess, R))
+            capacity = max(N.first_chunk_capacity(plan), min(guess, R))
             if binning is not None and capacity <= guess and contrib is None:
                 capacity = R                                   # the guessed workspace covered the first chunk, a later one did not fit
         # a statistics frame that may stop in a later chunk: what the accumulators held before it

@@ -479,12 +479,19 @@ def backward_camera(desc, cam: Camera, g: Gaussians, radii, geom_ws, screen_grad
 
 
 def binned_prefix(plan: FramePlan) -> int:
-    """The depth ranks of the chunks that ran: the binned_ranks of a frame's own backward (csrc/gsr_internal.h geom_rows)."""
+    """The depth ranks of the chunks that ran: the binned_ranks of a frame's own backward (csrc/gsr_dispatch.h geom_rows)."""
     return int(plan.chunk_rank_begin[plan.chunks_run]) if plan.num_rendered > 0 and plan.chunks_run > 0 else 0
 
 
+def first_chunk_capacity(plan: FramePlan) -> int:
+    """csrc/gsr_dispatch.h first_chunk_capacity (= gsr_binning_first_chunk_capacity), as plain arithmetic: rasterize_forward sizes the
+    binning workspace between the plan readback and the first launch of stage 2, where the stream idles through every library call."""
+    R, first = int(plan.num_rendered), int(plan.chunk_instances_max[0])
+    return min(first + first // 4 + (1 << 20), R) if plan.num_chunks > 1 else R
+
+
 def effective_binned_ranks(plan: FramePlan) -> int:
-    """csrc/gsr_internal.h effective_binned_ranks: the ranks of the chunks that ran, a live-filtered chunk counted as nothing."""
+    """csrc/gsr_dispatch.h effective_binned_ranks: the ranks of the chunks that ran, a live-filtered chunk counted as nothing."""
     if plan.num_rendered <= 0 or plan.chunks_run <= 0:
         return 0
     return sum(int(plan.chunk_rank_begin[c + 1]) - int(plan.chunk_rank_begin[c]) for c in range(int(plan.chunks_run))
