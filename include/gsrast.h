@@ -745,6 +745,10 @@ int gsr_profile_read(int max_entries, char (*names)[GSR_PROFILE_NAME_LEN], float
  * part of this ABI and of libgsrast.so, declared in a header of their own that this one brings in. */
 #include "gsrast_normals.h"
 
+/* A second colour triple inside the colour frame (three per-Gaussian values blended with the colour's weights, differentiable): the
+ * entry points are part of this ABI and of libgsrast.so, declared in a header of their own that this one brings in. */
+#include "gsrast_extra.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -369,15 +369,34 @@ static int validate_contrib(const gsr_frame_desc *desc, const gsr_contrib_stats 
 
 // The aux workspace of a frame: the caller's maps, and the checkpoints carved from its ckpt_ws (binned = false: the frame has no list
 // entries, the checkpoints are never touched)
-static AuxWS aux_workspace(const gsr_aux_outputs *aux_out, bool binned, int64_t capacity, const FrameK &f)
+static AuxWS aux_workspace(const gsr_aux_outputs *aux_out, bool binned, int64_t capacity, const FrameK &f, int planes = 1)
 {
-    AuxWS ax = carve_aux(aux_out && binned ? aux_out->ckpt_ws : nullptr, capacity, f);
+    AuxWS ax = carve_aux(aux_out && binned ? aux_out->ckpt_ws : nullptr, capacity, f, planes);
     if (aux_out) { ax.depth = aux_out->depth; ax.alpha = aux_out->alpha; }
     return ax;
 }
 
 // The variant of a frame as the _aux, _contrib and _contrib_error entry points receive it (FwdVariant once the aux workspace is carved)
-struct FwdArgs { const gsr_aux_outputs *aux = nullptr; const gsr_contrib_stats *stats = nullptr; const gsr_contrib_error *err = nullptr; };
+// extra / extra_map (gsr_forward_extra: `ext` set, with aux): the table and the map of the three extra channels
+struct FwdArgs {
+    const gsr_aux_outputs *aux = nullptr; const gsr_contrib_stats *stats = nullptr; const gsr_contrib_error *err = nullptr;
+    bool ext = false; const float *extra = nullptr; float *extra_map = nullptr;
+};
+
+// An extra frame's arguments (include/gsrast_extra.h): refused with a message before anything is launched
+static int validate_extra(const gsr_frame_desc *desc, const gsr_aux_outputs *aux, const float *extra, const float *extra_map, const char *who)
+{
+    if (!desc) { set_error("%s: NULL frame description", who); return GSR_ERR_INVALID_ARGUMENT; }
+    if (!aux) { set_error("%s: aux is required (an extra frame is an aux frame: depth, alpha and a four-plane ckpt_ws)", who); return GSR_ERR_INVALID_ARGUMENT; }
+    if (desc->P > 0 && !extra) { set_error("%s: the extra table is NULL ([P] rows of four floats)", who); return GSR_ERR_INVALID_ARGUMENT; }
+    if (((uintptr_t)extra & 15u) != 0) { set_error("%s: the extra table is not 16-byte aligned", who); return GSR_ERR_INVALID_ARGUMENT; }
+    if (!extra_map) { set_error("%s: extra_map is NULL ([3,H,W])", who); return GSR_ERR_INVALID_ARGUMENT; }
+    if (desc->tile_row_begin != 0 || desc->tile_row_end > 0) {
+        set_error("%s: whole images only (tile_row_begin = tile_row_end = 0)", who);
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    return GSR_OK;
+}
 
 // fill (optional): a zero fill to enqueue behind the FIRST chunk's blend and readback kernels, ahead of the wait for that readback
 // (gsr_forward's early fill); *fill_done reports whether it was enqueued
@@ -387,6 +406,7 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
 {
     int rc = validate_contrib(desc, v.stats, v.err, "gsr_forward_render_contrib");
     if (rc) return rc;
+    if (v.ext && (rc = validate_extra(desc, v.aux, v.extra, v.extra_map, "gsr_forward_render_extra"))) return rc;
     if ((rc = validate_inputs(desc, cam, g))) return rc;
     if (!cam || !cam->bg || !image_ws || !out_color || !plan || plan->num_rendered < 0 ||
         (desc->P > 0 && !geom_ws) || (plan->num_rendered > 0 && !binning_ws)) {
@@ -410,9 +430,10 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
         if (f.P == 0 || !geom_ws) gw0.ctrl = iw.ctrl_scratch;   // no geometry workspace at all
         if ((rc = launch_binning_init(f, gw0, iw, dbg, s))) return rc;
         const AuxWS ax0 = aux_workspace(v.aux, false, 0, f);
+        const ExtWS ex0{reinterpret_cast<const float4 *>(v.extra), v.extra_map, nullptr, nullptr, nullptr};
         // (err is not handed on: nothing is blended, every error total is zero, and with P == 0 the caller may have passed no map -
         // the error kernel would load it at tile start whatever the ranges hold)
-        if ((rc = launch_render_fwd(f, *cam, 0, true, 0, gw0, bw0, iw, out_color, dbg, s, false, {v.aux ? &ax0 : nullptr, v.stats, nullptr}))) return rc;
+        if ((rc = launch_render_fwd(f, *cam, 0, true, 0, gw0, bw0, iw, out_color, dbg, s, false, {v.aux ? &ax0 : nullptr, v.stats, nullptr, v.ext ? &ex0 : nullptr}))) return rc;
         plan->chunks_run = 1;
         return GSR_OK;
     }
@@ -423,8 +444,9 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
     // GSR_ERR_WORKSPACE before anything of that chunk is written (re-run this stage with a workspace for R instances).
     const int64_t capacity = plan_capacity(plan);
     BinningWS bw = carve_binning(binning_ws, capacity, f);
-    const AuxWS ax = aux_workspace(v.aux, true, capacity, f);
-    const FwdVariant variant{v.aux ? &ax : nullptr, v.stats, v.err};
+    const AuxWS ax = aux_workspace(v.aux, true, capacity, f, v.ext ? kExtCkptPlanes : 1);
+    const ExtWS ex{reinterpret_cast<const float4 *>(v.extra), v.extra_map, nullptr, nullptr, nullptr};
+    const FwdVariant variant{v.aux ? &ax : nullptr, v.stats, v.err, v.ext ? &ex : nullptr};
     if (!plan->binning_initialised && (rc = launch_binning_init(f, gw, iw, dbg, s))) return rc;
     plan->binning_initialised = 0;                  // a re-run of this stage must reset the tile ranges / open flags itself
     int sort_result = 0;
@@ -508,6 +530,7 @@ static int forward_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const
 {
     int rc = validate_contrib(desc, v.stats, v.err, "gsr_forward_contrib");      // (before stage 1: a refused call launches nothing)
     if (rc) return rc;
+    if (v.ext && (rc = validate_extra(desc, v.aux, v.extra, v.extra_map, "gsr_forward_extra"))) return rc;
     if ((rc = gsr_forward_preprocess(desc, cam, g, geom_ws, image_ws, radii, plan, stream))) return rc;
     const int64_t need = first_chunk_capacity(*plan);
     if (plan->num_rendered > 0 && (!binning_ws || binning_capacity < need)) {
@@ -564,6 +587,31 @@ int gsr_forward_render_aux(const gsr_frame_desc *desc, const gsr_camera *cam, co
                            void *image_ws, gsr_frame_plan *plan, float *out_color, const gsr_aux_outputs *aux, void *stream)
 {
     return forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, nullptr, nullptr, {aux});
+}
+
+int gsr_forward_extra(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *image_ws, int32_t *radii,
+                      gsr_frame_plan *plan, void *binning_ws, int64_t binning_capacity, float *out_color, gsr_grads *early_fill,
+                      const gsr_aux_outputs *aux, const float *extra, float *extra_map, void *stream)
+{
+    return forward_impl(desc, cam, g, geom_ws, image_ws, radii, plan, binning_ws, binning_capacity, out_color, early_fill, stream,
+                        {aux, nullptr, nullptr, true, extra, extra_map});
+}
+
+int gsr_forward_render_extra(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *binning_ws,
+                             void *image_ws, gsr_frame_plan *plan, float *out_color, const gsr_aux_outputs *aux, const float *extra,
+                             float *extra_map, void *stream)
+{
+    return forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, nullptr, nullptr,
+                               {aux, nullptr, nullptr, true, extra, extra_map});
+}
+
+int gsr_extra_workspace_size(const gsr_frame_desc *desc, int64_t binning_capacity, size_t *bytes)
+{
+    int rc = validate(desc);
+    if (rc) return rc;
+    if (binning_capacity < 0 || !bytes) { set_error("gsr_extra_workspace_size: bad binning_capacity / NULL out"); return GSR_ERR_INVALID_ARGUMENT; }
+    *bytes = carve_aux(nullptr, binning_capacity, make_frame(*desc), kExtCkptPlanes).total;
+    return GSR_OK;
 }
 
 int gsr_forward_contrib(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *image_ws, int32_t *radii,
@@ -625,6 +673,15 @@ int gsr_backward_rows_size(const gsr_frame_desc *desc, const gsr_frame_plan *pla
     return GSR_OK;
 }
 
+int gsr_extra_rows_size(const gsr_frame_desc *desc, const gsr_frame_plan *plan, size_t *bytes)
+{
+    int rc = validate(desc);
+    if (rc) return rc;
+    if (!plan || !bytes) { set_error("gsr_extra_rows_size: NULL argument"); return GSR_ERR_INVALID_ARGUMENT; }
+    *bytes = align_up((size_t)rows_bound(plan) * sizeof(float4));
+    return GSR_OK;
+}
+
 int gsr_backward_prepare(const gsr_frame_desc *desc, const gsr_gaussians *g, gsr_frame_plan *plan, float *screen_grads,
                          gsr_grads *grads, void *stream)
 {
@@ -645,10 +702,15 @@ int gsr_bwd_segment_entries(void) { return kSeg; }
 static int backward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const void *geom_ws, void *binning_ws,
                                 const void *image_ws, void *rows_ws, const gsr_frame_plan *plan, const float *out_color,
                                 const gsr_aux_outputs *aux_out, const float *dL_dcolor, const float *dL_ddepth, const float *dL_dalpha,
-                                float *screen_grads, void *stream, BwdKind kind)
+                                float *screen_grads, void *stream, BwdKind kind, const ExtWS *ext = nullptr)
 {
     int rc = validate(desc);
     if (rc) return rc;
+    if (kind == BwdKind::kExt) {
+        if ((rc = validate_extra(desc, aux_out, (const float *)ext->table, ext->map, "gsr_backward_render_extra"))) return rc;
+        if (desc->P > 0 && !ext->dL_dtable) { set_error("gsr_backward_render_extra: dL_dextra is NULL ([P,3])"); return GSR_ERR_INVALID_ARGUMENT; }
+        if (plan && plan->num_rendered > 0 && !ext->rows) { set_error("gsr_backward_render_extra: extra_rows_ws is NULL (gsr_extra_rows_size bytes)"); return GSR_ERR_INVALID_ARGUMENT; }
+    }
     if (kind == BwdKind::kAbs && (desc->tile_row_begin != 0 || desc->tile_row_end > 0)) {
         set_error("gsr_backward_render_abs: whole images only (tile_row_begin = tile_row_end = 0)");
         return GSR_ERR_INVALID_ARGUMENT;
@@ -666,6 +728,8 @@ static int backward_render_impl(const gsr_frame_desc *desc, const gsr_camera *ca
     const bool dbg = desc->debug != 0;
     const FrameK f = make_frame(*desc);
     if (f.P == 0) return GSR_OK;
+    if (kind == BwdKind::kExt && plan->num_rendered <= 0)      // no launch below touches it
+        GSR_HIP_CHECK(hipMemsetAsync(ext->dL_dtable, 0, (size_t)f.P * 3 * sizeof(float), s));
     GeomWS gw = carve_geom(const_cast<void *>(geom_ws), f.P);
     ImageWS iw = carve_image(const_cast<void *>(image_ws), f);
     BinningWS bw = carve_binning(binning_ws, plan_capacity(plan), f);
@@ -675,13 +739,14 @@ static int backward_render_impl(const gsr_frame_desc *desc, const gsr_camera *ca
     if (plan->num_rendered > 0) {
         if (!plan->tile_order_ready) GSR_HIP_CHECK(hipMemsetAsync(bw.row_valid, 0, valid_bytes(plan), s));
         const long long rows_n = plan->instances_emitted >= 0 ? (long long)plan->instances_emitted : rows_upper;
-        const AuxWS ax = aux_workspace(aux_out, true, plan_capacity(plan), f);
+        const AuxWS ax = aux_workspace(aux_out, true, plan_capacity(plan), f, kind == BwdKind::kExt ? kExtCkptPlanes : 1);
         if ((rc = launch_render_bwd(f, plan->chunks_run, plan->sort_result, rows_n, gw, bw, iw, out_color, dL_dcolor, dbg, s,
-                                    {kind, &ax, dL_ddepth, dL_dalpha})))
+                                    {kind, &ax, dL_ddepth, dL_dalpha, ext})))
             return rc;
     }
     // only the depth ranks of chunks that ran can own gradient rows
-    return launch_reduce_rows(f, *plan, gw, bw, screen_grads, plan->screen_prezeroed, dbg, s, kind);
+    if (kind == BwdKind::kExt && plan->num_rendered <= 0) return launch_reduce_rows(f, *plan, gw, bw, screen_grads, plan->screen_prezeroed, dbg, s, BwdKind::kAux);
+    return launch_reduce_rows(f, *plan, gw, bw, screen_grads, plan->screen_prezeroed, dbg, s, kind, ext);
 }
 
 int gsr_backward_render(const gsr_frame_desc *desc, const gsr_camera *cam, const void *geom_ws, void *binning_ws,
@@ -724,6 +789,18 @@ int gsr_backward_render_aux(const gsr_frame_desc *desc, const gsr_camera *cam, c
 {
     return backward_render_impl(desc, cam, geom_ws, binning_ws, image_ws, rows_ws, plan, out_color, aux, dL_dcolor, dL_ddepth, dL_dalpha,
                                 screen_grads, stream, aux ? BwdKind::kAux : BwdKind::kPlain);      // aux NULL: gsr_backward_render
+}
+
+int gsr_backward_render_extra(const gsr_frame_desc *desc, const gsr_camera *cam, const void *geom_ws, void *binning_ws,
+                              const void *image_ws, void *rows_ws, const gsr_frame_plan *plan, const float *out_color,
+                              const gsr_aux_outputs *aux, const float *extra, const float *extra_map, const float *dL_dcolor,
+                              const float *dL_ddepth, const float *dL_dalpha, const float *dL_dextra_map, float *screen_grads,
+                              void *extra_rows_ws, float *dL_dextra, void *stream)
+{
+    const ExtWS ext{reinterpret_cast<const float4 *>(extra), const_cast<float *>(extra_map), dL_dextra_map,
+                    reinterpret_cast<float4 *>(extra_rows_ws), dL_dextra};
+    return backward_render_impl(desc, cam, geom_ws, binning_ws, image_ws, rows_ws, plan, out_color, aux, dL_dcolor, dL_ddepth, dL_dalpha,
+                                screen_grads, stream, BwdKind::kExt, &ext);
 }
 
 static int backward_geom_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, const int32_t *radii,

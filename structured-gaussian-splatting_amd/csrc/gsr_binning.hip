@@ -107,15 +107,15 @@ BinningWS carve_binning(void *base, int64_t R, const FrameK &f)
     return w;
 }
 
-AuxWS carve_aux(void *base, int64_t R, const FrameK &f)
+AuxWS carve_aux(void *base, int64_t R, const FrameK &f, int planes)
 {
     AuxWS w;
     size_t o = 0;
     char *b = (char *)base;
     const size_t Rn = (size_t)(R > 0 ? R : 1), Tn = (size_t)f.Gx * f.Gy;
     w.depth = w.alpha = nullptr;                    // the caller's maps (gsr_aux_outputs)
-    w.ckpt = (float *)(b + o); o += align_up((Rn / kSeg + 2) * (size_t)kAuxCkptFloats * sizeof(float));
-    w.ckpt_start = (float *)(b + o); o += align_up((Tn ? Tn : 1) * (size_t)(GSR_MAX_CHUNKS - 1) * kAuxCkptFloats * sizeof(float));
+    w.ckpt = (float *)(b + o); o += align_up((Rn / kSeg + 2) * (size_t)planes * kAuxCkptFloats * sizeof(float));
+    w.ckpt_start = (float *)(b + o); o += align_up((Tn ? Tn : 1) * (size_t)(GSR_MAX_CHUNKS - 1) * planes * kAuxCkptFloats * sizeof(float));
     w.total = o;
     return w;
 }

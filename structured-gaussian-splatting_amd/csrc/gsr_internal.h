@@ -211,7 +211,19 @@ struct AuxWS {
     float *ckpt_start;          // [GSR_MAX_CHUNKS - 1][Tn][kAuxCkptFloats]
     size_t total;
 };
-AuxWS carve_aux(void *base, int64_t R, const FrameK &f);
+// planes: checkpoint planes per slot - 1 for an aux frame; kExtCkptPlanes for an extra frame (gsr_forward_extra), whose aux checkpoint is
+// [depth, e0, e1, e2][kAuxCkptFloats]
+constexpr int kExtCkptPlanes = 4;
+AuxWS carve_aux(void *base, int64_t R, const FrameK &f, int planes = 1);
+// The three extra channels of an extra frame (include/gsrast_extra.h): the caller's table and map, the upstream gradient of the map, and
+// the backward's second row plane and output.  The checkpoints are planes 1..3 of the frame's AuxWS.
+struct ExtWS {
+    const float4 *table;        // [P] (e0, e1, e2, unused) by Gaussian
+    float *map;                 // [3, H, W]
+    const float *dL_dmap;       // [3, H, W] or NULL (backward)
+    float4 *rows;               // [instances emitted] (sum w g_e0, .. g_e1, .. g_e2, 0) by slot (backward)
+    float *dL_dtable;           // [P, 3] (backward)
+};
 constexpr int kLastShift = 26;  // last_enc = (chunk + 1) << kLastShift | position
 constexpr int kQuadMaskShift = 28;                // BinningWS::gids = quadrant mask << 28 | Gaussian (P < 2^28)
 constexpr uint32_t kGidMask = (1u << kQuadMaskShift) - 1u;
@@ -273,7 +285,8 @@ ZeroSegs zero_segments(const FrameK &f, const gsr_gaussians &g, float *screen, c
 // What a blend forward does beside the colour image (each optional).  aux: the depth and alpha maps.  stats (without aux; lock step
 // whatever `groups` says): the chunk's per-Gaussian blend statistics, added to the caller's accumulators.  err (with stats): its
 // error-weighted totals, added to err->error_frame_q32
-struct FwdVariant { const AuxWS *aux; const gsr_contrib_stats *stats; const gsr_contrib_error *err; };
+// ext (with aux): its three extra channels
+struct FwdVariant { const AuxWS *aux; const gsr_contrib_stats *stats; const gsr_contrib_error *err; const ExtWS *ext = nullptr; };
 // groups: the chunk's splats are small (fewer than 4.5 tiles per Gaussian): the quadrant-group mapping (gsr_render.hip)
 int launch_render_fwd(const FrameK &f, const gsr_camera &cam, int c, bool last_chunk, int sort_result, const GeomWS &gw, const BinningWS &bw,
                       ImageWS &iw, float *out_color, bool debug, hipStream_t s, bool groups, const FwdVariant &v);
@@ -281,8 +294,9 @@ int launch_render_fwd(const FrameK &f, const gsr_camera &cam, int c, bool last_c
 int launch_contrib_error_fold(long long P, uint64_t *frame_q32, uint64_t *sum_q32, float *error_max, bool debug, hipStream_t s);
 // The blend backward's kind.  kAux: dL_dcolor, dL_ddepth, dL_dalpha may each be NULL (zero); rows get slot 9 = dL/dz of the splat (the sum
 // of w dL/ddepth).  kAbs: rows get slots 10, 11 = the per-pixel absolute sums of d/dmean2D.  launch_reduce_rows sums the kind's slots too
-enum class BwdKind { kPlain, kAux, kAbs };
-struct BwdVariant { BwdKind kind; const AuxWS *aux; const float *dL_ddepth, *dL_dalpha; };      // the pointers: kAux only
+// kExt: kAux plus the extra channels - three more sums per entry, into ExtWS::rows; launch_reduce_rows sums them into ExtWS::dL_dtable
+enum class BwdKind { kPlain, kAux, kAbs, kExt };
+struct BwdVariant { BwdKind kind; const AuxWS *aux; const float *dL_ddepth, *dL_dalpha; const ExtWS *ext = nullptr; };      // the pointers: kAux, kExt only
 // rows_upper: bound of the instances the chunks that ran emitted (sizes the launch: the unit count lives on the device)
 int launch_render_bwd(const FrameK &f, int chunks_run, int sort_result, long long rows_upper, const GeomWS &gw, BinningWS &bw,
                       const ImageWS &iw, const float *out_color, const float *dL_dcolor, bool debug, hipStream_t s, const BwdVariant &v);
@@ -291,7 +305,7 @@ int launch_zero_segments(const ZeroSegs &z, hipStream_t s);
 int launch_zero_outputs(const FrameK &f, const gsr_gaussians &g, float *screen, const gsr_grads &out, hipStream_t s,
                         uint8_t *row_valid = nullptr, size_t valid_bytes = 0);
 int launch_reduce_rows(const FrameK &f, const gsr_frame_plan &plan, const GeomWS &gw, const BinningWS &bw, float *screen_grads,
-                       int prezeroed, bool debug, hipStream_t s, BwdKind kind);
+                       int prezeroed, bool debug, hipStream_t s, BwdKind kind, const ExtWS *ext = nullptr);
 // The geometry backward over `rows` (gsr_dispatch.h geom_rows: the Gaussians or ranks to visit, and the sparse choice, made once).
 // Sparse: zero-fills the outputs (unless out.prezeroed) and visits the listed ranks only.
 int launch_geom_bwd(const FrameK &f, const gsr_camera &cam, const gsr_gaussians &g, const int32_t *radii, const GeomWS &gw,

@@ -110,6 +110,25 @@ __device__ __forceinline__ void row_sum11_transpose(float (&a)[11])
 #undef GSR_DPP
 }
 
+// The ext backward's three further values (the sums of w dL/dextra): each reduced over its row of 16 lanes by value 8's four steps, in
+// an asm of their own behind row_sum10_transpose - three adds per step and an s_nop 1 between the steps, so every DPP read is at
+// least two wait states behind the write of its register:   b[0..2]: the row's totals in every lane of the row
+__device__ __forceinline__ void row_sum3_rows(float (&b)[3])
+{
+#define GSR_DPP(d, ctrl) "v_add_f32_dpp %" #d ", %" #d ", %" #d " " ctrl " row_mask:0xf bank_mask:0xf\n\t"
+    asm volatile("s_nop 1\n\t"
+                 GSR_DPP(0, "row_ror:8") GSR_DPP(1, "row_ror:8") GSR_DPP(2, "row_ror:8")
+                 "s_nop 1\n\t"
+                 GSR_DPP(0, "row_half_mirror") GSR_DPP(1, "row_half_mirror") GSR_DPP(2, "row_half_mirror")
+                 "s_nop 1\n\t"
+                 GSR_DPP(0, "quad_perm:[1,0,3,2]") GSR_DPP(1, "quad_perm:[1,0,3,2]") GSR_DPP(2, "quad_perm:[1,0,3,2]")
+                 "s_nop 1\n\t"
+                 GSR_DPP(0, "quad_perm:[2,3,0,1]") GSR_DPP(1, "quad_perm:[2,3,0,1]") GSR_DPP(2, "quad_perm:[2,3,0,1]")
+                 "s_nop 1"
+                 : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]));
+#undef GSR_DPP
+}
+
 __device__ __forceinline__ int wave_max_uniform(int v)
 {
 #pragma unroll
@@ -119,6 +138,7 @@ __device__ __forceinline__ int wave_max_uniform(int v)
 
 constexpr int kFwdWaves = 5;       // resident waves per SIMD the register allocation of the forward kernels aims for
 constexpr int kBwdWaves = 4;       // ... and of k_render_bwd
+constexpr int kFwdExtWaves = 4;    // ... of the ext forward instantiations (the aux ones' value)
 typedef float v2f __attribute__((ext_vector_type(2)));      // packed-fp32 operand: the lane's two pixels of a pair
 
 // lp = log2(opacity exp(power)) of a pair of pixels from the pre-scaled record (qA, qB, qC = a.z, a.w, b.x; log2 opacity = b.y):
@@ -159,6 +179,16 @@ __device__ __forceinline__ unsigned stage_batch(float4 *sh_rec, int lane, int n,
         sh_rec[3 * lane + 1] = r[1];
         sh_rec[3 * lane + 2] = r[2];
     }
+    return m;
+}
+// stage_batch of the ext kernels: the same lanes also gather their Gaussian's row of the extra table, by the entry's index, into a
+// second LDS array beside sh_rec.  (A function of its own: stage_batch, and with it every other instantiation, stays as it is.)
+__device__ __forceinline__ unsigned stage_batch_ext(float4 *sh_rec, float4 *sh_ext, int lane, int n, const uint32_t *__restrict__ sorted_gid,
+                                                    uint32_t first, const float4 *__restrict__ records, const float4 *__restrict__ ext_table)
+{
+    uint32_t entry = 0;
+    const unsigned m = stage_batch(sh_rec, lane, n, sorted_gid, first, records, &entry);
+    if (lane < n) sh_ext[lane] = ext_table[entry & kGidMask];
     return m;
 }
 
@@ -356,9 +386,20 @@ __device__ __forceinline__ void fwd_tile_epilogue(int t, int tile, int c, int la
 // z - and alpha = 1 - |T| when the tile stores its pixels.  Between chunks Z lives in the depth map (as the unfinished colour lives in
 // out_color); in front of every checkpoint it goes into the aux checkpoint plane of the same slot (AuxFwdK).
 struct AuxFwdK {
+    static constexpr int kPlanes = 1;  // planes of kAuxCkptFloats per aux checkpoint
     float *depth, *alpha;              // [H, W]
     float *ckpt;                       // [R / kSeg + 2][kAuxCkptFloats]: Z in front of the checkpoint of the same slot (BinningWS::ckpt)
     float *ckpt_start_c;               // [Tn][kAuxCkptFloats]: Z when this chunk (>= 1) starts on a tile (ImageWS::ckpt_start)
+};
+// kExt (gsr_forward_render_extra; the aux kernels handed an ExtFwdK): the same blend also renders three more linear channels from a
+// per-Gaussian table, staged by stage_batch into a second LDS array beside sh_rec: three more packed accumulators per pair,
+// X = fma(e, w, X) - again the colour channels' own operation on fwd_pair's w, so each is bit for bit a colour channel fed e over a zero
+// background.  Between chunks they live in the map [3, H, W]; in front of every checkpoint they go into planes 1..3 of the aux
+// checkpoint, which has kPlanes = 4 planes in these instantiations (plane 0: Z).
+struct ExtFwdK : AuxFwdK {
+    static constexpr int kPlanes = kExtCkptPlanes;
+    const float4 *table;               // [P] (e0, e1, e2, unused)
+    float *map;                        // [3, H, W]
 };
 // kStats (gsr_forward_render_contrib; lock step only): the same blend also takes, per blended splat, three totals over the wave's 256
 // pixels of the weights w that fwd_pair returns - n = the pixels with w > 0 (ballots: scalar), s = their sum (the lane's four in a
@@ -389,17 +430,25 @@ __device__ __forceinline__ float err_dot4(float a0, float a1, float a2, float a3
 #pragma clang fp contract(off)
     return ((a0 * e0 + a1 * e1) + a2 * e2) + a3 * e3;
 }
-template <class Map, bool kAux, bool kStats = false, bool kErr = false>
+template <class Map, bool kAux, bool kStats = false, bool kErr = false, class AX = AuxFwdK>
 __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, const uint2 *__restrict__ ranges_c, uint32_t *__restrict__ open,
                                            const uint32_t *__restrict__ sorted_gid, const float4 *__restrict__ records,
                                            const float *__restrict__ bg, float *__restrict__ out_color, float *__restrict__ T_state,
                                            int32_t *__restrict__ last_enc, uint32_t *__restrict__ tile_walk_c, float *__restrict__ ckpt,
                                            float *__restrict__ ckpt_start_c, const UnitLists &units, uint32_t *__restrict__ unit_count,
-                                           const AuxFwdK &ax, const ContribK &cs = ContribK{}, const ErrK &er = ErrK{})
+                                           const AX &ax, const ContribK &cs = ContribK{}, const ErrK &er = ErrK{})
 {
+    constexpr bool kExt = AX::kPlanes > 1;
+    constexpr int kAuxStride = AX::kPlanes * kAuxCkptFloats;      // floats per aux checkpoint
+    static_assert(!kExt || kAux, "the extra channels ride on the aux kernels");
     static_assert(!kStats || (Map::kLockStep && !kAux), "the statistics are built for the lock-step colour kernel");
     static_assert(!kErr || kStats, "the error-weighted total rides on the statistics");
     __shared__ float4 sh_rec[kWave * 3];
+    float4 *sh_ext = nullptr;                              // kExt: the batch's rows of the extra table
+    if constexpr (kExt) {
+        __shared__ float4 sh_ext_rows[kWave];
+        sh_ext = sh_ext_rows;
+    }
 #ifdef GSR_FWD_TRACE
     TraceEnd trace_end{(unsigned long long)wall_clock64(), (int)blockIdx.x};
 #endif
@@ -453,6 +502,15 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
         };
         Z0 = v2f{load_z(0), load_z(1)}; Z1 = v2f{load_z(2), load_z(3)};
     }
+    v2f X0[3] = {}, X1[3] = {};                            // kExt: the three extra channels so far of the two pairs
+    if constexpr (kExt) {
+        auto load_x = [&](int e, int k) {
+            const int px = px0 + map.ex(e), py = py0 + map.ey(e);
+            return (c > 0 && px < f.W && py < f.H) ? ax.map[(size_t)k * N + (size_t)py * f.W + px] : 0.f;
+        };
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { X0[k] = v2f{load_x(0, k), load_x(1, k)}; X1[k] = v2f{load_x(2, k), load_x(3, k)}; }
+    }
 
     const int n_total = (int)(rng.y - rng.x);
     const int enc_base = (c + 1) << kLastShift;
@@ -465,6 +523,13 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
         put(0, P0, 0); put(1, P0, 1); put(2, P1, 0); put(3, P1, 1);
         if constexpr (kAux) {
             zdst[map.aux(0)] = Z0[0]; zdst[map.aux(1)] = Z0[1]; zdst[map.aux(2)] = Z1[0]; zdst[map.aux(3)] = Z1[1];
+        }
+        if constexpr (kExt) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                float *xdst = zdst + (k + 1) * kAuxCkptFloats;
+                xdst[map.aux(0)] = X0[k][0]; xdst[map.aux(1)] = X0[k][1]; xdst[map.aux(2)] = X1[k][0]; xdst[map.aux(3)] = X1[k][1];
+            }
         }
     };
     v2f sw0 = {0.f, 0.f}, sw1 = {0.f, 0.f};              // kStats: the weights of the splat blended last (0 for a pair it skipped)
@@ -480,30 +545,44 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
             const float dy = a.y - fy0;
             const v2f w = fwd_pair(active, lp_at(lt, b.x, dy), b.y, b.z, b.w, cbl, contributor, P0);
             if constexpr (kAux) { const float z = sh_rec[3u * j + 2u].y; Z0 = __builtin_elementwise_fma(v2f{z, z}, w, Z0); }
+            if constexpr (kExt) {
+                const float4 x = sh_ext[j];
+                X0[0] = __builtin_elementwise_fma(v2f{x.x, x.x}, w, X0[0]);
+                X0[1] = __builtin_elementwise_fma(v2f{x.y, x.y}, w, X0[1]);
+                X0[2] = __builtin_elementwise_fma(v2f{x.z, x.z}, w, X0[2]);
+            }
             if constexpr (kStats) sw0 = w;
         }
         if (m & 12u) {
             const float dy = a.y - fy1;
             const v2f w = fwd_pair(active, lp_at(lt, b.x, dy), b.y, b.z, b.w, cbl, contributor, P1);
             if constexpr (kAux) { const float z = sh_rec[3u * j + 2u].y; Z1 = __builtin_elementwise_fma(v2f{z, z}, w, Z1); }
+            if constexpr (kExt) {
+                const float4 x = sh_ext[j];
+                X1[0] = __builtin_elementwise_fma(v2f{x.x, x.x}, w, X1[0]);
+                X1[1] = __builtin_elementwise_fma(v2f{x.y, x.y}, w, X1[1]);
+                X1[2] = __builtin_elementwise_fma(v2f{x.z, x.z}, w, X1[2]);
+            }
             if constexpr (kStats) sw1 = w;
         }
     };
     if (c > 0 && n_total > 0)
-        checkpoint(ckpt_start_c + (size_t)tile * kCkptFloats, kAux ? ax.ckpt_start_c + (size_t)tile * kAuxCkptFloats : nullptr);
+        checkpoint(ckpt_start_c + (size_t)tile * kCkptFloats, kAux ? ax.ckpt_start_c + (size_t)tile * kAuxStride : nullptr);
     for (int base = 0; base < n_total; base += kWave) {
         unsigned live = map.live(P0, P1);
         if (live == 0u) break;
         if (base > 0 && base % kSeg == 0) {
             const size_t slot = (rng.x + (uint32_t)base) / kSeg;
-            checkpoint(ckpt + slot * kCkptFloats, kAux ? ax.ckpt + slot * kAuxCkptFloats : nullptr);
+            checkpoint(ckpt + slot * kCkptFloats, kAux ? ax.ckpt + slot * kAuxStride : nullptr);
         }
         const int n = min(kWave, n_total - base);
         __syncthreads();
         uint32_t entry = 0;                                // kStats: the lane's list entry, and its totals over the wave's pixels
         uint32_t st_n = 0;
         float st_s = 0.f, st_m = 0.f, st_e = 0.f;
-        const unsigned mymask = stage_batch(sh_rec, lane, n, sorted_gid, rng.x + base, records, kStats ? &entry : nullptr);
+        unsigned mymask;
+        if constexpr (kExt) mymask = stage_batch_ext(sh_rec, sh_ext, lane, n, sorted_gid, rng.x + base, records, ax.table);
+        else mymask = stage_batch(sh_rec, lane, n, sorted_gid, rng.x + base, records, kStats ? &entry : nullptr);
         __syncthreads();
         // every 8 blended splats (passes, with groups) the live mask is refreshed: quadrants (and tiles) that saturate mid-batch stop there
         int since_refresh = 0;
@@ -587,6 +666,14 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
         };
         store_aux(0, P0.T[0], Z0[0]); store_aux(1, P0.T[1], Z0[1]); store_aux(2, P1.T[0], Z1[0]); store_aux(3, P1.T[1], Z1[1]);
     }
+    if constexpr (kExt) {
+        auto store_x = [&](int e, int k, float x_) {
+            const int px = px0 + map.ex(e), py = py0 + map.ey(e);
+            if (px < f.W && py < f.H) ax.map[(size_t)k * N + (size_t)py * f.W + px] = x_;      // no background term
+        };
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { store_x(0, k, X0[k][0]); store_x(1, k, X0[k][1]); store_x(2, k, X1[k][0]); store_x(3, k, X1[k][1]); }
+    }
     // 2 = open AND some pixel is still more than half transparent after everything so far: a tile no splat has covered yet
     // (the chunk plan merges the remaining chunks when such tiles exist: the frame is not going to close, gsr_api.hip)
     auto clear_px = [&](int e, float t_) { return px0 + map.ex(e) < f.W && py0 + map.ey(e) < f.H && t_ > 0.5f; };
@@ -598,7 +685,8 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
 }
 
 // Every variant of the blend forward is an instantiation of this one kernel.  X: the variant's own kernel arguments - AuxFwdK for the aux
-// instantiations of both pixel mappings (colour, radii and every array as the plain kernels, plus depth and alpha); ContribK, then
+// instantiations of both pixel mappings (colour, radii and every array as the plain kernels, plus depth and alpha), ExtFwdK in its
+// place for the ext instantiations (every array as the aux kernels, plus the extra map); ContribK, then
 // ErrK, for the statistics instantiations (lock step, whatever the chunk's splats are like: both mappings render the same bits)
 template <class Map, bool kAux, bool kStats, bool kErr, int kMinWaves, class... X>
 __global__ __launch_bounds__(kWave, kMinWaves) void k_render_fwd(FrameK f, int n_tiles, int c, int finalize_all,
@@ -660,6 +748,14 @@ int launch_render_fwd(const FrameK &f, const gsr_camera &cam, int c, bool last_c
         const ErrK er{v.err->pixel_error, (unsigned long long *)v.err->error_frame_q32};
         return launch(k_render_fwd<QuadrantLanes, false, true, true, 4, ContribK, ErrK>, "render_fwd_contrib_error", cs, er);
     }
+    if (v.aux && v.ext) {
+        ExtFwdK ex;
+        ex.depth = v.aux->depth; ex.alpha = v.aux->alpha; ex.ckpt = v.aux->ckpt;
+        ex.ckpt_start_c = c > 0 ? v.aux->ckpt_start + (size_t)(c - 1) * Tn * (kExtCkptPlanes * kAuxCkptFloats) : nullptr;
+        ex.table = v.ext->table; ex.map = v.ext->map;
+        return launch(groups ? k_render_fwd<GroupLanes, true, false, false, kFwdExtWaves, ExtFwdK> : k_render_fwd<QuadrantLanes, true, false, false, kFwdExtWaves, ExtFwdK>,
+                      "render_fwd_ext", ex);
+    }
     if (v.aux) {
         const AuxFwdK ax{v.aux->depth, v.aux->alpha, v.aux->ckpt, c > 0 ? v.aux->ckpt_start + (size_t)(c - 1) * Tn * kAuxCkptFloats : nullptr};
         return launch(groups ? k_render_fwd<GroupLanes, true, false, false, 4, AuxFwdK> : k_render_fwd<QuadrantLanes, true, false, false, 4, AuxFwdK>,
@@ -709,6 +805,13 @@ struct BwdPair {             // state of a lane's pair of pixels (4 apart in x, 
 struct BwdPairAux {          // aux: the same pair's dL/ddepth and dL/dalpha T_final
     v2f dpz, GA;
 };
+struct BwdExt {              // ext: the splat's extra triple, and a pair's dL/dextra
+    float e0, e1, e2;
+};
+struct BwdPairExt {
+    v2f dpe0, dpe1, dpe2;
+};
+struct BwdAccExt { v2f S10, S11, S12; };      // ext: the lane's sums of w dL/dextra
 // the lane's partial sums of one splat, per pair element: X = sum tA dx, Y = sum tA dy (dL/dmean2D = ln2 (2 qA X + qB Y, 2 qC Y + qB X):
 // formed once per splat by the lane that stores the row), S2..S4 the conic's, S5 the opacity's, S6..S8 the colour's, S9 (aux) the depth's
 struct BwdAcc { v2f X, Y, S2, S3, S4, S5, S6, S7, S8; };
@@ -723,10 +826,11 @@ __device__ __forceinline__ float add_halves(v2f v)
     return r;
 }
 
-template <bool INIT, bool kAux = false, bool kAbs = false>         // INIT: the splat's first pair, the sums start here (A comes in undefined)
+template <bool INIT, bool kAux = false, bool kAbs = false, bool kExt = false>         // INIT: the splat's first pair, the sums start here (A comes in undefined)
 __device__ __forceinline__ void bwd_pair(const BwdSplat sp, v2f lp, v2f dx, float dy, int pos, BwdPair &P, BwdAcc &A,
                                          const BwdPairAux &PA = BwdPairAux{}, v2f *S9 = nullptr, const BwdAbsQ &Q = BwdAbsQ{},
-                                         BwdAbs *AB = nullptr)
+                                         BwdAbs *AB = nullptr, const BwdExt *se = nullptr, const BwdPairExt *PE = nullptr,
+                                         BwdAccExt *AE = nullptr)
 {
     const bool valid0 = (pos < P.limit0) && !(lp[0] > sp.lop) && !(lp[0] < kLog2AlphaMin);      // power > 0 <=> lp > lop
     const bool valid1 = (pos < P.limit1) && !(lp[1] > sp.lop) && !(lp[1] < kLog2AlphaMin);
@@ -737,6 +841,11 @@ __device__ __forceinline__ void bwd_pair(const BwdSplat sp, v2f lp, v2f dx, floa
     const v2f inv1ma = {fast_rcp(one_m[0]), fast_rcp(one_m[1])};
     v2f cdp = sp.cr * P.dpr + sp.cg * P.dpg + sp.cb * P.dpb;            // <c_i, dL/dpix>
     if constexpr (kAux) cdp = __builtin_elementwise_fma(v2f{sp.z, sp.z}, PA.dpz, cdp);      // + z_i dL/ddepth
+    if constexpr (kExt) {                                                                   // + <e_i, dL/dextra>
+        cdp = __builtin_elementwise_fma(v2f{se->e0, se->e0}, PE->dpe0, cdp);
+        cdp = __builtin_elementwise_fma(v2f{se->e1, se->e1}, PE->dpe1, cdp);
+        cdp = __builtin_elementwise_fma(v2f{se->e2, se->e2}, PE->dpe2, cdp);
+    }
     const v2f w = ae * P.T;                                              // d colour / d rgb
     P.E -= w * cdp;                                                      // this splat's own share leaves the remainder
     v2f dL_dalpha = P.T * cdp - P.E * inv1ma;
@@ -752,6 +861,7 @@ __device__ __forceinline__ void bwd_pair(const BwdSplat sp, v2f lp, v2f dx, floa
         A.S5 = tA;
         A.S6 = w * P.dpr; A.S7 = w * P.dpg; A.S8 = w * P.dpb;
         if constexpr (kAux) *S9 = w * PA.dpz;
+        if constexpr (kExt) { AE->S10 = w * PE->dpe0; AE->S11 = w * PE->dpe1; AE->S12 = w * PE->dpe2; }
         if constexpr (kAbs) {
             AB->AX = __builtin_elementwise_abs(Q.qA2 * tx + Q.qB * ty);
             AB->AY = __builtin_elementwise_abs(Q.qC2 * ty + Q.qB * tx);
@@ -764,6 +874,7 @@ __device__ __forceinline__ void bwd_pair(const BwdSplat sp, v2f lp, v2f dx, floa
         A.S5 += tA;
         A.S6 += w * P.dpr; A.S7 += w * P.dpg; A.S8 += w * P.dpb;
         if constexpr (kAux) *S9 += w * PA.dpz;
+        if constexpr (kExt) { AE->S10 += w * PE->dpe0; AE->S11 += w * PE->dpe1; AE->S12 += w * PE->dpe2; }
         if constexpr (kAbs) {
             AB->AX += __builtin_elementwise_abs(Q.qA2 * tx + Q.qB * ty);
             AB->AY += __builtin_elementwise_abs(Q.qC2 * ty + Q.qB * tx);
@@ -782,13 +893,26 @@ __device__ __forceinline__ void bwd_pair(const BwdSplat sp, v2f lp, v2f dx, floa
 // kAux (k_render_bwd<true>): a tenth sum per entry (dL/dz, row slot 9); the LDS stride goes to 11 words, odd, still conflict-free.
 // kAbs (k_render_bwd<false, true>): eleven sums per entry, the last two the per-pixel absolute sums (BwdAbs) -> row slots 10, 11 with
 // the W/2, H/2 of slots 0, 1; stride 11.  Every other value is computed exactly as in k_render_bwd<false>.
+// kExt (k_render_bwd<true, false, kBwdExtWaves, ExtBwdK>; gsr_backward_render_extra): the aux backward plus the three extra channels
+// of an ext frame, each one more linear channel like the depth: <c_i, dL/dpix> gains <e_i, g_e>, E's starting value
+// <extra_final - extra at the checkpoint, g_e> (planes 1..3 of the four-plane aux checkpoint), and the sums of w g_e are three more
+// per-entry sums - 13 with an LDS stride of 13 words, odd, conflict-free - reduced over the rows by row_sum3_rows and stored to a
+// row plane of their own ([R] float4, by slot): the 48-B rows keep their layout.
 struct AuxBwdK {
     const float *depth;                // [H, W] the forward's depth map (final)
     const float *dL_ddepth, *dL_dalpha;      // [H, W] each, NULL = zero
     const float *ckpt, *ckpt_start;    // the aux checkpoints (AuxWS)
 };
-template <bool kAux, bool kAbs>
-__global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const uint2 *__restrict__ ranges,
+struct ExtBwdK {
+    const float4 *table;               // [P] (e0, e1, e2, unused)
+    const float *map;                  // [3, H, W] the forward's extra map (final)
+    const float *dL_dmap;              // [3, H, W], NULL = zero
+    float4 *rows;                      // [instances emitted] by slot
+};
+constexpr int kBwdExtWaves = 3;        // minimum waves per SIMD of the ext instantiation: at kBwdWaves = 4 (128 VGPRs) it spills three registers
+// X: nothing, or ExtBwdK (the ext instantiation: kAux, and an aux checkpoint of kExtCkptPlanes planes)
+template <bool kAux, bool kAbs, int kMinWaves, class... X>
+__global__ __launch_bounds__(kWave, kMinWaves) void k_render_bwd(FrameK f, const uint2 *__restrict__ ranges,
                                                       const uint32_t *__restrict__ tile_walk,
                                                       const uint32_t *__restrict__ sorted_gid, const uint32_t *__restrict__ sorted_slot,
                                                       const float4 *__restrict__ records, const float *__restrict__ out_color,
@@ -796,12 +920,22 @@ __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const
                                                       const float *__restrict__ dL_dpix, const float *__restrict__ ckpt,
                                                       const float *__restrict__ ckpt_start, float4 *__restrict__ grad_rows,
                                                       uint8_t *__restrict__ row_valid, UnitLists units,
-                                                      const uint32_t *__restrict__ unit_count, AuxBwdK ax)
+                                                      const uint32_t *__restrict__ unit_count, AuxBwdK ax, X... x)
 {
     static_assert(!(kAux && kAbs), "the aux x abs blend backward is not built");
-    constexpr int kSums = kAux ? 10 : kAbs ? 11 : 9;         // per-entry sums
-    constexpr int kAccStride = (kAux || kAbs) ? 11 : 9;
+    constexpr bool kExt = sizeof...(X) == 1;
+    static_assert(sizeof...(X) <= 1 && (!kExt || kAux), "the extra channels ride on the aux backward");
+    constexpr int kSums = kExt ? 13 : kAux ? 10 : kAbs ? 11 : 9;         // per-entry sums
+    constexpr int kAccStride = kExt ? 13 : (kAux || kAbs) ? 11 : 9;
+    constexpr int kAuxStride = (kExt ? kExtCkptPlanes : 1) * kAuxCkptFloats;      // floats per aux checkpoint
     __shared__ float4 sh_rec[kWave * 3];
+    float4 *sh_ext = nullptr;                         // kExt: the batch's rows of the extra table
+    ExtBwdK ex{};
+    if constexpr (kExt) {
+        __shared__ float4 sh_ext_rows[kWave];
+        sh_ext = sh_ext_rows;
+        ex = ExtBwdK{x...};
+    }
     __shared__ float sh_acc[kWave * kAccStride];      // the batch's sums, [entry][value]: stride 9 (11) words, conflict-free by lane
 #ifdef GSR_BWD_TRACE
     TraceEnd trace_end{(unsigned long long)wall_clock64(), (int)blockIdx.x};
@@ -821,9 +955,13 @@ __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const
     const float half_w = 0.5f * (float)f.W, half_h = 0.5f * (float)f.H;
     // where the butterfly leaves this lane's share of a group's totals: which value (of which register), if any
     const int quad = (lane >> 2) & 3, in_quad = lane & 3;
-    const unsigned acc_idx = (unsigned)(in_quad == 0 ? (quad < 2 ? quad : quad + 2) : in_quad == 1 ? (quad < 2 ? quad + 2 : quad + 4) : ((kAux || kAbs) ? 8 + quad : 8));
+    unsigned acc_idx = (unsigned)(in_quad == 0 ? (quad < 2 ? quad : quad + 2) : in_quad == 1 ? (quad < 2 ? quad + 2 : quad + 4) : ((kAux || kAbs) ? 8 + quad : 8));
     const unsigned grp_shift = 8u * (unsigned)map.grp;
-    const bool acc_on = in_quad < 2 || (in_quad == 2 && (kAbs ? quad < 3 : kAux ? quad < 2 : quad == 0));
+    bool acc_on = in_quad < 2 || (in_quad == 2 && (kAbs ? quad < 3 : kAux ? quad < 2 : quad == 0));
+    if constexpr (kExt) {      // values 8 .. 11 with the four quads' third lanes, value 12 with the first quad's fourth
+        if (in_quad == 3) acc_idx = 12u;
+        acc_on = in_quad < 3 || quad == 0;
+    }
 #pragma unroll
     for (int k = 0; k < kSums; ++k) sh_acc[lane * kAccStride + k] = 0.f;
     for (uint32_t u = blockIdx.x / kUnitShards; u < n_units; u += gridDim.x / kUnitShards) {
@@ -876,8 +1014,8 @@ __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const
         BwdPairAux PA0, PA1;
         if constexpr (kAux) {
             // E gains g_z (depth_final - Z in front of the segment); GA = g_a T_final, T_final = |T_state| (frozen at the stop)
-            const float *zchk = (sgm > 0) ? ax.ckpt + (size_t)((rng.x + (uint32_t)seg_begin) / kSeg) * kAuxCkptFloats
-                                          : (c > 0 ? ax.ckpt_start + ((size_t)(c - 1) * Tn + tile) * kAuxCkptFloats : nullptr);
+            const float *zchk = (sgm > 0) ? ax.ckpt + (size_t)((rng.x + (uint32_t)seg_begin) / kSeg) * kAuxStride
+                                          : (c > 0 ? ax.ckpt_start + ((size_t)(c - 1) * Tn + tile) * kAuxStride : nullptr);
             auto load_aux = [&](int e, float &E, float &gz, float &gaT) {
                 const int px = px0 + map.ex(e), py = py0 + map.ey(e);
                 const bool inside = px < f.W && py < f.H;
@@ -892,6 +1030,30 @@ __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const
             P0.E = v2f{E0, E1}; PA0.dpz = v2f{z0, z1}; PA0.GA = v2f{a0, a1};
             P1.E = v2f{E2, E3}; PA1.dpz = v2f{z2, z3}; PA1.GA = v2f{a2, a3};
         }
+        BwdPairExt PE0{}, PE1{};
+        if constexpr (kExt) {
+            // E gains <extra_final - extra in front of the segment, g_e>
+            const float *zchk = (sgm > 0) ? ax.ckpt + (size_t)((rng.x + (uint32_t)seg_begin) / kSeg) * kAuxStride
+                                          : (c > 0 ? ax.ckpt_start + ((size_t)(c - 1) * Tn + tile) * kAuxStride : nullptr);
+            auto load_ext = [&](int e, float &E, float &g0, float &g1, float &g2) {
+                const int px = px0 + map.ex(e), py = py0 + map.ey(e);
+                const bool inside = px < f.W && py < f.H;
+                const size_t pix = inside ? (size_t)py * f.W + px : 0;
+                const bool has = inside && ex.dL_dmap != nullptr;
+                g0 = has ? ex.dL_dmap[pix] : 0.f; g1 = has ? ex.dL_dmap[N + pix] : 0.f; g2 = has ? ex.dL_dmap[2 * N + pix] : 0.f;
+                float d0 = inside ? ex.map[pix] : 0.f, d1 = inside ? ex.map[N + pix] : 0.f, d2 = inside ? ex.map[2 * N + pix] : 0.f;
+                if (zchk) {
+                    const float *q = zchk + map.aux(e);
+                    d0 -= q[kAuxCkptFloats]; d1 -= q[2 * kAuxCkptFloats]; d2 -= q[3 * kAuxCkptFloats];
+                }
+                E += g0 * d0 + g1 * d1 + g2 * d2;
+            };
+            float E0 = P0.E[0], E1 = P0.E[1], E2 = P1.E[0], E3 = P1.E[1], g[4][3];
+            load_ext(0, E0, g[0][0], g[0][1], g[0][2]); load_ext(1, E1, g[1][0], g[1][1], g[1][2]);
+            load_ext(2, E2, g[2][0], g[2][1], g[2][2]); load_ext(3, E3, g[3][0], g[3][1], g[3][2]);
+            P0.E = v2f{E0, E1}; PE0.dpe0 = v2f{g[0][0], g[1][0]}; PE0.dpe1 = v2f{g[0][1], g[1][1]}; PE0.dpe2 = v2f{g[0][2], g[1][2]};
+            P1.E = v2f{E2, E3}; PE1.dpe0 = v2f{g[2][0], g[3][0]}; PE1.dpe1 = v2f{g[2][1], g[3][1]}; PE1.dpe2 = v2f{g[2][2], g[3][2]};
+        }
         // per quadrant (= per group): its last participating contributor
         int gmax = max(max(P0.limit0, P0.limit1), max(P1.limit0, P1.limit1));
 #pragma unroll
@@ -905,7 +1067,9 @@ __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const
             const int n = min(kWave, seg_end - base);
             const uint32_t slot = lane < n ? sorted_slot[rng.x + base + lane] : 0u;
             __syncthreads();
-            unsigned mymask = stage_batch(sh_rec, lane, n, sorted_gid, rng.x + base, records);
+            unsigned mymask;
+            if constexpr (kExt) mymask = stage_batch_ext(sh_rec, sh_ext, lane, n, sorted_gid, rng.x + base, records, ex.table);
+            else mymask = stage_batch(sh_rec, lane, n, sorted_gid, rng.x + base, records);
             __syncthreads();
             const int mypos = base + lane;
             mymask &= (mypos < qmax0 ? 1u : 0u) | (mypos < qmax1 ? 2u : 0u) | (mypos < qmax2 ? 4u : 0u) | (mypos < qmax3 ? 8u : 0u);
@@ -925,20 +1089,40 @@ __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const
                 v2f S9;                                  // aux: the lane's sum of w dL/ddepth
                 BwdAbs AB;                               // abs: the lane's sums of |u|
                 const BwdAbsQ Q{2.f * a.z, a.w, 2.f * b.x};
-                {
-                    const float dy = a.y - fy0;
-                    if constexpr (kAbs) bwd_pair<true, false, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P0, A, PA0, nullptr, Q, &AB);
-                    else if constexpr (kAux) bwd_pair<true, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P0, A, PA0, &S9);
-                    else bwd_pair<true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P0, A);
-                }
-                {
-                    const float dy = a.y - fy1;
-                    if constexpr (kAbs) bwd_pair<false, false, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P1, A, PA1, nullptr, Q, &AB);
-                    else if constexpr (kAux) bwd_pair<false, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P1, A, PA1, &S9);
-                    else bwd_pair<false>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P1, A);
+                BwdAccExt AE;                            // ext: the lane's sums of w dL/dextra
+                if constexpr (kExt) {
+                    const float4 xe = sh_ext[jj];        // the splat's extra triple
+                    float xe1 = xe.y;
+                    // (an opaque copy, no instruction: without it the compiler pairs (e1, e2) out of the 96-bit LDS read as an unaligned
+                    // register pair and legalises that through 16 bytes of scratch)
+                    asm volatile("" : "+v"(xe1));
+                    const BwdExt se{xe.x, xe1, xe.z};
+                    const float dy0 = a.y - fy0, dy1 = a.y - fy1;
+                    bwd_pair<true, true, false, true>(sp, lp_at(lt, b.x, dy0), dx, dy0, (int)j, P0, A, PA0, &S9, Q, nullptr, &se, &PE0, &AE);
+                    bwd_pair<false, true, false, true>(sp, lp_at(lt, b.x, dy1), dx, dy1, (int)j, P1, A, PA1, &S9, Q, nullptr, &se, &PE1, &AE);
+                } else {
+                    {
+                        const float dy = a.y - fy0;
+                        if constexpr (kAbs) bwd_pair<true, false, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P0, A, PA0, nullptr, Q, &AB);
+                        else if constexpr (kAux) bwd_pair<true, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P0, A, PA0, &S9);
+                        else bwd_pair<true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P0, A);
+                    }
+                    {
+                        const float dy = a.y - fy1;
+                        if constexpr (kAbs) bwd_pair<false, false, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P1, A, PA1, nullptr, Q, &AB);
+                        else if constexpr (kAux) bwd_pair<false, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P1, A, PA1, &S9);
+                        else bwd_pair<false>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P1, A);
+                    }
                 }
                 float mine;
-                if constexpr (kAbs) {
+                if constexpr (kExt) {
+                    float s[10] = {add_halves(A.X), add_halves(A.Y), add_halves(A.S2), add_halves(A.S3), add_halves(A.S4), add_halves(A.S5),
+                                   add_halves(A.S6), add_halves(A.S7), add_halves(A.S8), add_halves(S9)};
+                    float t[3] = {add_halves(AE.S10), add_halves(AE.S11), add_halves(AE.S12)};
+                    row_sum10_transpose(s);
+                    row_sum3_rows(t);
+                    mine = in_quad == 0 ? s[0] : in_quad == 1 ? s[2] : in_quad == 3 ? t[2] : (quad == 0 ? s[8] : quad == 1 ? s[9] : quad == 2 ? t[0] : t[1]);
+                } else if constexpr (kAbs) {
                     float s[11] = {add_halves(A.X), add_halves(A.Y), add_halves(A.S2), add_halves(A.S3), add_halves(A.S4), add_halves(A.S5),
                                    add_halves(A.S6), add_halves(A.S7), add_halves(A.S8), add_halves(AB.AX), add_halves(AB.AY)};
                     row_sum11_transpose(s);
@@ -973,7 +1157,8 @@ __global__ __launch_bounds__(kWave, kBwdWaves) void k_render_bwd(FrameK f, const
                 row[0] = make_float4(gx * (0.69314718f * half_w), gy * (0.69314718f * half_h), v[2] * -0.5f, v[3] * -0.5f);
                 row[1] = make_float4(v[4] * -0.5f, v[5] * __builtin_amdgcn_exp2f(-b.y), v[6], v[7]);
                 if constexpr (kAbs) row[2] = make_float4(v[8], 0.f, v[9] * (0.69314718f * half_w), v[10] * (0.69314718f * half_h));
-                else row[2] = make_float4(v[8], kAux ? v[kSums - 1] : 0.f, 0.f, 0.f);
+                else row[2] = make_float4(v[8], kAux ? v[kExt ? 9 : kSums - 1] : 0.f, 0.f, 0.f);
+                if constexpr (kExt) ex.rows[slot] = make_float4(v[10 < kSums ? 10 : 0], v[11 < kSums ? 11 : 0], v[12 < kSums ? 12 : 0], 0.f);
                 row_valid[slot] = 1;
             }
         }
@@ -991,11 +1176,21 @@ int launch_render_bwd(const FrameK &f, int chunks_run, int sort_result, long lon
     if (per_shard > (long long)bw.units.shard_stride()) per_shard = (long long)bw.units.shard_stride();
     if (per_shard > (1 << 13)) per_shard = 1 << 13;
     // by BwdKind: the instantiations take the same arguments; only the aux one reads the aux block
-    static const decltype(&k_render_bwd<false, false>) kernels[] = {k_render_bwd<false, false>, k_render_bwd<true, false>, k_render_bwd<false, true>};
-    static const char *const names[] = {"render_bwd", "render_bwd_aux", "render_bwd_abs"};
+    static const decltype(&k_render_bwd<false, false, kBwdWaves>) kernels[] = {k_render_bwd<false, false, kBwdWaves>, k_render_bwd<true, false, kBwdWaves>,
+                                                                               k_render_bwd<false, true, kBwdWaves>};
+    static const char *const names[] = {"render_bwd", "render_bwd_aux", "render_bwd_abs", "render_bwd_ext"};
     const char *name = names[(int)v.kind];
-    const AuxBwdK ax = v.kind == BwdKind::kAux ? AuxBwdK{v.aux->depth, v.dL_ddepth, v.dL_dalpha, v.aux->ckpt, v.aux->ckpt_start} : AuxBwdK{};
+    const bool with_aux = v.kind == BwdKind::kAux || v.kind == BwdKind::kExt;
+    const AuxBwdK ax = with_aux ? AuxBwdK{v.aux->depth, v.dL_ddepth, v.dL_dalpha, v.aux->ckpt, v.aux->ckpt_start} : AuxBwdK{};
     ProfileScope prof(name, s);
+    if (v.kind == BwdKind::kExt) {
+        const ExtBwdK ex{v.ext->table, v.ext->map, v.ext->dL_dmap, v.ext->rows};
+        hipLaunchKernelGGL((k_render_bwd<true, false, kBwdExtWaves, ExtBwdK>), dim3((unsigned)(per_shard * kUnitShards)), dim3(kWave), 0, s, f,
+                           iw.ranges, iw.tile_walk, bw.gids[1], bw.vals[sort_result], gw.records, out_color, iw.T_state, iw.last_enc, dL_dcolor,
+                           bw.ckpt, iw.ckpt_start, reinterpret_cast<float4 *>(bw.grad_rows), bw.row_valid, bw.units, iw.unit_count, ax, ex);
+        GSR_LAUNCH_CHECK(name, debug, s);
+        return GSR_OK;
+    }
     hipLaunchKernelGGL(kernels[(int)v.kind], dim3((unsigned)(per_shard * kUnitShards)), dim3(kWave), 0, s, f,
                        iw.ranges, iw.tile_walk, bw.gids[1], bw.vals[sort_result], gw.records, out_color, iw.T_state, iw.last_enc, dL_dcolor,
                        bw.ckpt, iw.ckpt_start, reinterpret_cast<float4 *>(bw.grad_rows), bw.row_valid, bw.units, iw.unit_count, ax);
@@ -1010,15 +1205,26 @@ int launch_render_bwd(const FrameK &f, int chunks_run, int sort_result, long lon
 // Only ranks of chunks that actually ran can own rows; every other Gaussian's gradient row is zero (memset).
 // kAux: rows of the aux backward - slot 9 (dL/dz) is summed too, in the same order as the others.
 // kAbs: rows of the abs backward - slots 10, 11 likewise, into screen[3 g + 2].zw.
+// kExt (X = the ext backward's row plane [R] float4 and dL_dextra [P, 3]; with kAux): the plane's three sums are added beside the
+// row's, trip for trip and in the same tree, and the group's fourth lane writes them to dL_dextra[g].
 constexpr int kRedBlock = 256;
-template <int kRedGroup, bool kAux = false, bool kAbs = false>
+template <int kRedGroup, bool kAux = false, bool kAbs = false, class... X>
 __global__ __launch_bounds__(kRedBlock) void k_reduce_rows(int r_begin, int n_ranks, const uint32_t *__restrict__ order,
                                                            const uint32_t *__restrict__ cnt_open,
                                                            const uint32_t *__restrict__ row_begin,
                                                            const uint8_t *__restrict__ row_valid,
                                                            const float4 *__restrict__ grad_rows, float4 *__restrict__ screen,
-                                                           int write_empty, int plain)
+                                                           int write_empty, int plain, X... x)
 {
+    constexpr bool kExt = sizeof...(X) == 2;
+    static_assert(sizeof...(X) == 0 || (kExt && kAux && kRedGroup >= 4), "the ext reduction rides on the aux one");
+    const float4 *ext_rows = nullptr;
+    float *dL_dextra = nullptr;
+    if constexpr (kExt) {
+        auto take = [&](const float4 *r, float *d) { ext_rows = r; dL_dextra = d; };
+        take(x...);
+    }
+    float ax0 = 0.f, ax1 = 0.f, ax2 = 0.f;             // kExt: the three sums
     const int sub = threadIdx.x & (kRedGroup - 1);
     const int r = r_begin + (blockIdx.x * kRedBlock + threadIdx.x) / kRedGroup;
     const bool live = r < n_ranks;
@@ -1046,6 +1252,7 @@ __global__ __launch_bounds__(kRedBlock) void k_reduce_rows(int r_begin, int n_ra
         }
         for (size_t sl = first; sl < end; sl += kRedBatch * kRedGroup) {
             float4 r0[kRedBatch], r1[kRedBatch], r2[kRedBatch];
+            float4 r3[kExt ? kRedBatch : 1];
             const size_t sn = sl + kRedBatch * kRedGroup;
 #pragma unroll
             for (int u = 0; u < kRedBatch; ++u) {
@@ -1060,6 +1267,7 @@ __global__ __launch_bounds__(kRedBlock) void k_reduce_rows(int r_begin, int n_ra
                     r0[u] = grad_rows[3 * su]; r1[u] = grad_rows[3 * su + 1];
                     if constexpr (kAux || kAbs) r2[u] = grad_rows[3 * su + 2];
                     else r2[u].x = grad_rows[3 * su + 2].x;
+                    if constexpr (kExt) r3[u] = ext_rows[su];
                 }
             }
 #pragma unroll
@@ -1069,6 +1277,7 @@ __global__ __launch_bounds__(kRedBlock) void k_reduce_rows(int r_begin, int n_ra
                     a1.x += r1[u].x; a1.y += r1[u].y; a1.z += r1[u].z; a1.w += r1[u].w;
                     a8 += r2[u].x;
                     if constexpr (kAux) a9 += r2[u].y;
+                    if constexpr (kExt) { ax0 += r3[u].x; ax1 += r3[u].y; ax2 += r3[u].z; }
                     if constexpr (kAbs) { a10 += r2[u].z; a11 += r2[u].w; }
                 }
                 ok[u] = nx[u];
@@ -1080,17 +1289,20 @@ __global__ __launch_bounds__(kRedBlock) void k_reduce_rows(int r_begin, int n_ra
             // written.  Wide groups (big splats: most rows of a saturating frame are invalid) test the byte first; narrow ones (small
             // splats, nearly every row valid) load the row beside its byte — one memory round trip instead of two — and drop it after
             float4 r0, r1;
+            float4 r3 = make_float4(0.f, 0.f, 0.f, 0.f);
             float r2, r9 = 0.f, r10 = 0.f, r11 = 0.f;
             if constexpr (kRedGroup >= 64) {
                 if (!row_valid[sl]) continue;
                 r0 = grad_rows[3 * (size_t)sl]; r1 = grad_rows[3 * (size_t)sl + 1]; r2 = grad_rows[3 * (size_t)sl + 2].x;
                 if constexpr (kAux) r9 = grad_rows[3 * (size_t)sl + 2].y;
                 if constexpr (kAbs) { r10 = grad_rows[3 * (size_t)sl + 2].z; r11 = grad_rows[3 * (size_t)sl + 2].w; }
+                if constexpr (kExt) r3 = ext_rows[sl];
             } else {
                 const uint8_t ok = row_valid[sl];
                 r0 = grad_rows[3 * (size_t)sl]; r1 = grad_rows[3 * (size_t)sl + 1]; r2 = grad_rows[3 * (size_t)sl + 2].x;
                 if constexpr (kAux) r9 = grad_rows[3 * (size_t)sl + 2].y;
                 if constexpr (kAbs) { r10 = grad_rows[3 * (size_t)sl + 2].z; r11 = grad_rows[3 * (size_t)sl + 2].w; }
+                if constexpr (kExt) r3 = ext_rows[sl];
                 if (!ok) continue;                      // (whatever the unwritten row holds — NaN patterns included — is never added)
             }
             a0.x += r0.x; a0.y += r0.y; a0.z += r0.z; a0.w += r0.w;
@@ -1098,6 +1310,7 @@ __global__ __launch_bounds__(kRedBlock) void k_reduce_rows(int r_begin, int n_ra
             a8 += r2;
             if constexpr (kAux) a9 += r9;
             if constexpr (kAbs) { a10 += r10; a11 += r11; }
+            if constexpr (kExt) { ax0 += r3.x; ax1 += r3.y; ax2 += r3.z; }
         }
     }
 #pragma unroll
@@ -1107,14 +1320,20 @@ __global__ __launch_bounds__(kRedBlock) void k_reduce_rows(int r_begin, int n_ra
         a8 += __shfl_xor(a8, off);
         if constexpr (kAux) a9 += __shfl_xor(a9, off);
         if constexpr (kAbs) { a10 += __shfl_xor(a10, off); a11 += __shfl_xor(a11, off); }
+        if constexpr (kExt) { ax0 += __shfl_xor(ax0, off); ax1 += __shfl_xor(ax1, off); ax2 += __shfl_xor(ax2, off); }
     }
     if (live && (cnt || write_empty) && sub < 3)
         screen[3 * (size_t)g + sub] = sub == 0 ? a0 : (sub == 1 ? a1 : make_float4(a8, a9, a10, a11));
+    if constexpr (kExt) {
+        if (live && (cnt || write_empty) && sub == 3) {
+            dL_dextra[3 * (size_t)g] = ax0; dL_dextra[3 * (size_t)g + 1] = ax1; dL_dextra[3 * (size_t)g + 2] = ax2;
+        }
+    }
 }
 
 // One launch per depth chunk that ran, each with its own lanes-per-Gaussian: a whole wave or eight (gsr_dispatch.h reduce_wide)
 int launch_reduce_rows(const FrameK &f, const gsr_frame_plan &plan, const GeomWS &gw, const BinningWS &bw, float *screen_grads,
-                       int prezeroed, bool debug, hipStream_t s, BwdKind kind)
+                       int prezeroed, bool debug, hipStream_t s, BwdKind kind, const ExtWS *ext)
 {
     // prezeroed: 0 = clear the whole tensor first; 1 = the caller already has; 2 = only the rows of the binned prefix will ever
     // be read (the sparse geometry backward of the same frame): every prefix row is written, zeros included, nothing else
@@ -1123,8 +1342,10 @@ int launch_reduce_rows(const FrameK &f, const gsr_frame_plan &plan, const GeomWS
     static const decltype(&k_reduce_rows<8>) kernels[][2] = {{k_reduce_rows<8>, k_reduce_rows<64>},
                                                              {k_reduce_rows<8, true>, k_reduce_rows<64, true>},
                                                              {k_reduce_rows<8, false, true>, k_reduce_rows<64, false, true>}};
-    static const char *const names[] = {"reduce_rows", "reduce_rows_aux", "reduce_rows_abs"};
+    static const char *const names[] = {"reduce_rows", "reduce_rows_aux", "reduce_rows_abs", "reduce_rows_ext"};
     ProfileScope prof(names[(int)kind], s);
+    // a Gaussian without a row - outside the chunks that ran, or never emitted - gets exactly 0
+    if (kind == BwdKind::kExt) GSR_HIP_CHECK(hipMemsetAsync(ext->dL_dtable, 0, (size_t)f.P * 3 * sizeof(float), s));
     if (prezeroed == 0) GSR_HIP_CHECK(hipMemsetAsync(screen_grads, 0, (size_t)f.P * kRowFloats * sizeof(float), s));
     const int write_empty = prezeroed == 2 ? 1 : 0;
     const int plain = switches().reduce_rows_plain ? 1 : 0;
@@ -1135,6 +1356,13 @@ int launch_reduce_rows(const FrameK &f, const gsr_frame_plan &plan, const GeomWS
         const bool wide = reduce_wide(r1 - r0, plan.chunk_instances_max[c], (plan.chunks_filtered >> c) & 1);
         const long long threads = (long long)(r1 - r0) * (wide ? 64 : 8);
         const dim3 grid((unsigned)((threads + kRedBlock - 1) / kRedBlock));
+        if (kind == BwdKind::kExt) {
+            const auto kernel = wide ? k_reduce_rows<64, true, false, const float4 *, float *> : k_reduce_rows<8, true, false, const float4 *, float *>;
+            hipLaunchKernelGGL(kernel, grid, dim3(kRedBlock), 0, s, r0, r1, gw.order, gw.cnt_open, gw.row_begin, bw.row_valid,
+                               reinterpret_cast<const float4 *>(bw.grad_rows), reinterpret_cast<float4 *>(screen_grads), write_empty, plain,
+                               (const float4 *)ext->rows, ext->dL_dtable);
+            continue;
+        }
         hipLaunchKernelGGL(kernels[(int)kind][wide], grid, dim3(kRedBlock), 0, s, r0, r1, gw.order, gw.cnt_open, gw.row_begin,
                            bw.row_valid, reinterpret_cast<const float4 *>(bw.grad_rows), reinterpret_cast<float4 *>(screen_grads), write_empty, plain);
     }

@@ -46,6 +46,15 @@ and stats.error_max (module contrib).  The frame is the plain
 frame's, bit for bit.  Refused with a ValueError: pixel_error without contributions, contributions that is not an ErrorStats, a map of
 another shape, dtype or device, and everything a statistics frame refuses.  pixel_error=None: a plain statistics frame.
 
+Extension: GaussianRasterizer(raster_settings, depth_alpha=True)(..., extra_colors=t) with t [P,3] float32 on the frame's device
+returns (color, radii, depth, alpha, extra): extra [3,H,W] = sum_i w_i t_i, three more channels blended inside the colour frame with the
+colour's own weights and no background term - bit for bit the colour of the same geometry rendered with colors_precomp = t over a
+zero background - from one more instantiation of the aux blend kernels.  Differentiable in t and in everything
+the weights depend on; color, radii, depth and alpha are the bits of the call without it.  forward and forward_raw (and
+FUSE_GETTERS) alike, with debug, antialiasing and a model's 3D filter.  Refused with a ValueError: extra_colors without
+depth_alpha=True, another shape, dtype or device, absgrad, contributions, tile_rows / ShardedRenderer, and a viewmatrix / projmatrix /
+campos that requires grad.  extra_colors=None (the default): the calls made without it, the same launches, the same bits.
+
 Autograd contract (train.py:106, scene/gaussian_model.py:415-417): gradients for
 (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, None) in that order;
 `means2D.grad[:, :2]` is dL/d(NDC position) with the W/2, H/2 pixel scale folded in, `[:, 2] = 0`.
@@ -114,7 +123,7 @@ _binning_guess = {}        # (P, W, H, slab, device) -> instances the binning wo
 class _Frame:
     """Native handles of one forward pass, kept alive by autograd's ctx for the backward."""
     __slots__ = ("desc", "cam", "keep", "plan", "geom_ws", "binning_ws", "image_ws", "radii", "color", "gauss", "M", "device", "raw", "pre",
-                 "depth", "alpha", "aux_ws", "aux")
+                 "depth", "alpha", "aux_ws", "aux", "extra_table", "extra_map")
 
     @property
     def R(self):
@@ -173,16 +182,19 @@ def _camera_args(rs: GaussianRasterizationSettings):
 
 def _aux_outputs(fr: "_Frame", capacity: int):
     """gsr_aux_outputs of an aux frame, with a depth-checkpoint workspace for a binning workspace of `capacity` instances."""
-    fr.aux_ws = _workspace(N.aux_workspace_size(fr.desc, capacity), fr.device)
+    size = N.aux_workspace_size if fr.extra_table is None else N.extra_workspace_size          # (an extra frame: four planes)
+    fr.aux_ws = _workspace(size(fr.desc, capacity), fr.device)
     fr.aux = N.AuxOutputs(N._ptr(fr.depth), N._ptr(fr.alpha), N._ptr(fr.aux_ws))
     return fr.aux
 
 
 def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                       rs: GaussianRasterizationSettings, tile_rows=None, out_color=None, sh_rest=None, raw=False,
-                      prepare_needs=None, aux=False, contrib=None, pixel_error=None, pixel_error_checked=False):
+                      prepare_needs=None, aux=False, contrib=None, pixel_error=None, pixel_error_checked=False, extra=None):
     """Stage 1 + stage 2 of the native forward.  Returns (color, radii, frame).
     aux=True: the same blend also renders frame.depth and frame.alpha ([1,H,W] each; whole images only).
+    extra (with aux=True; [P,3] float32 on the inputs' device, whole images, no contrib): the same blend also renders frame.extra_map
+    [3,H,W] from it (check_extra_colors' rules).
     contrib (a contrib.ContributionStats of this P and device; whole images, no aux): the blend also adds the frame's per-Gaussian
     statistics into it.  Such a frame runs the two stages as two calls: a stage 2 that stops for want of room in a later chunk has
     already added its earlier chunks, so a frame that can stop that way (several chunks planned, a workspace for fewer than all
@@ -196,6 +208,8 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
     opacities = logits, scales = log-scales, rotations = unnormalised) and the activations run in the kernels.
     prepare_needs: which gradients a backward will want (as rasterize_backward_geom's `needs`), when one will follow: the
     backward's output tensors are then allocated up front, while the host waits for the plan anyway."""
+    if extra is not None:
+        check_extra_colors(extra, means3D, aux, tile_rows=tile_rows, contributions=contrib, rs=rs)
     if aux and tile_rows is not None:
         raise ValueError("depth / alpha maps are rendered for whole images only: no tile_rows (sharded slabs) with aux=True")
     if contrib is not None and (aux or tile_rows is not None):
@@ -240,7 +254,10 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
     fr.keep = (cam_keep, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, sh_rest)
     fr.raw = raw
     fr.pre = None
-    fr.depth = fr.alpha = fr.aux_ws = fr.aux = None
+    fr.depth = fr.alpha = fr.aux_ws = fr.aux = fr.extra_table = fr.extra_map = None
+    if extra is not None:  # the kernels gather 16-byte rows (e0, e1, e2, unused)
+        fr.extra_table = torch.nn.functional.pad(extra.detach().contiguous(), (0, 1))
+        fr.extra_map = torch.empty(3, H, W, dtype=torch.float32, device=device)
     if aux:                # every pixel is written by the first chunk's blend
         fr.depth = torch.empty(1, H, W, dtype=torch.float32, device=device)
         fr.alpha = torch.empty(1, H, W, dtype=torch.float32, device=device)
@@ -271,7 +288,8 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
         if binning is not None and contrib is None:
             plan, done = N.forward_both(fr.desc, fr.cam, fr.gauss, fr.geom_ws, fr.image_ws, fr.radii, binning, guess, color, device,
                                         early_fill=early[2] if early is not None else None,
-                                        aux=_aux_outputs(fr, guess) if aux else None)
+                                        aux=_aux_outputs(fr, guess) if aux else None,
+                                        extra=None if extra is None else (fr.extra_table, fr.extra_map))
         else:
             plan = N.forward_preprocess(fr.desc, fr.cam, fr.gauss, fr.geom_ws, fr.radii, device, image_ws=fr.image_ws)
         fr.plan = plan
@@ -305,6 +323,7 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
             try:
                 N.forward_render(fr.desc, fr.cam, fr.gauss, fr.geom_ws, binning, fr.image_ws, plan, color, device,
                                  aux=_aux_outputs(fr, capacity) if aux else None,
+                                 extra=None if extra is None else (fr.extra_table, fr.extra_map),
                                  contrib=contrib.native() if contrib is not None else None,
                                  err=contrib.native_error(pixel_error) if pixel_error is not None else None)
                 if pixel_error is not None:
@@ -329,10 +348,12 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
 
 
 def rasterize_backward_screen(fr: "_Frame", grad_color: torch.Tensor, only_for_own_geom: bool = False, grad_depth=None,
-                              grad_alpha=None, absgrad: bool = False) -> torch.Tensor:
+                              grad_alpha=None, absgrad: bool = False, grad_extra=None, extra_out=None) -> torch.Tensor:
     """K7 + deterministic per-Gaussian reduction -> screen-space gradients [P, 12].
     grad_depth / grad_alpha ([1,H,W] or [H,W], an aux frame only; None = zero): when either is given the aux backward runs and slot 9
     holds dL/dz; otherwise the colour-only kernels (the plain frame's bits).
+    grad_extra ([3,H,W], an extra frame only; None = zero) / extra_out ([P,3], required for an extra frame): an extra frame always
+    runs the ext backward - slot 9 as the aux backward leaves it - which also writes the extra table's gradient into extra_out.
     absgrad: the abs instantiation of the colour-only kernels - slots 10, 11 also hold the per-pixel absolute sums of d/dmean2D
     (rasterize_screen_absgrad extracts them); whole images, no aux gradients.
     only_for_own_geom: the tensor goes straight into this frame's geometry backward and nowhere else (the autograd path): rows it
@@ -342,6 +363,11 @@ def rasterize_backward_screen(fr: "_Frame", grad_color: torch.Tensor, only_for_o
     grad_color = _f32c(grad_color, fr.device)
     grad_depth, grad_alpha = _f32c(grad_depth, fr.device), _f32c(grad_alpha, fr.device)
     with_aux = fr.aux is not None and (grad_depth is not None or grad_alpha is not None)
+    with_ext = fr.extra_table is not None
+    grad_extra = _f32c(grad_extra, fr.device) if with_ext else None
+    if with_ext and extra_out is None:
+        raise ValueError("rasterize_backward_screen: an extra frame's backward needs extra_out [P,3]")
+    with_aux = with_aux or (with_ext and grad_extra is not None)
     if absgrad and (fr.aux is not None or fr.desc.tile_row_end > 0 or fr.desc.tile_row_begin != 0):
         raise ValueError("absgrad: the abs blend backward is built for whole colour-only frames: no depth / alpha maps, no tile_rows")
     screen = fr.pre.pop("screen", None) if fr.pre is not None else None        # allocated (and, on sparse frames, zero-filled) by the forward
@@ -350,11 +376,17 @@ def rasterize_backward_screen(fr: "_Frame", grad_color: torch.Tensor, only_for_o
         covered = fr.plan.num_rendered > 0 and fr.plan.chunks_run == fr.plan.num_chunks
         fr.plan.screen_prezeroed = 2 if (only_for_own_geom and covered) else 0            # (1: set only by prepare_backward(), for the very tensor it filled)
     if grad_color is None and not with_aux:
+        if with_ext:
+            extra_out.zero_()
         return screen.zero_()[:P]
     with torch.cuda.device(fr.device):
         # one 48-B gradient row per EMITTED instance: backward-only scratch, returned to the allocator on exit
         rows = _workspace(N.backward_rows_size(fr.desc, fr.plan), fr.device)
-        if with_aux:
+        if with_ext:
+            ext_rows = _workspace(N.extra_rows_size(fr.desc, fr.plan), fr.device)
+            N.backward_render_extra(fr.desc, fr.cam, fr.geom_ws, fr.binning_ws, fr.image_ws, rows, fr.plan, fr.color, fr.aux, fr.extra_table,
+                                    fr.extra_map, grad_color, grad_depth, grad_alpha, grad_extra, screen, ext_rows, extra_out, fr.device)
+        elif with_aux:
             N.backward_render_aux(fr.desc, fr.cam, fr.geom_ws, fr.binning_ws, fr.image_ws, rows, fr.plan, fr.color, fr.aux, grad_color,
                                   grad_depth, grad_alpha, screen, fr.device)
         else:
@@ -512,13 +544,15 @@ def _stash_frame(ctx, frame):
     backward() allowed, under retain_graph=True; a second backward() without it raises autograd's usual error."""
     keep = [t for t in frame.keep[1:] if t is not None]
     aux = (frame.depth, frame.aux_ws) if frame.aux is not None else ()          # an aux frame: its depth map and checkpoints, last
-    ctx.save_for_backward(*(getattr(frame, n) for n in _FRAME_TENSORS), *frame.keep[0], *keep, *aux)
+    ext = (frame.extra_table, frame.extra_map) if frame.extra_table is not None else ()      # an extra frame: its table and map, in front
+    ctx.save_for_backward(*(getattr(frame, n) for n in _FRAME_TENSORS), *frame.keep[0], *keep, *ext, *aux)
     ctx.frame_keep_mask = tuple(t is not None for t in frame.keep[1:])
     ctx.frame_aux = bool(aux)
+    ctx.frame_ext = bool(ext)
     for n in _FRAME_TENSORS:
         setattr(frame, n, None)
     frame.keep = None
-    frame.depth = frame.alpha = frame.aux_ws = None
+    frame.depth = frame.alpha = frame.aux_ws = frame.extra_table = frame.extra_map = None
     ctx.frame = frame
 
 
@@ -529,6 +563,8 @@ def _unstash_frame(ctx):
         setattr(fr, n, t)
     it = iter(saved[9:])
     fr.keep = (tuple(saved[5:9]),) + tuple(next(it) if m else None for m in ctx.frame_keep_mask)
+    if ctx.frame_ext:
+        fr.extra_table, fr.extra_map = next(it), next(it)
     if ctx.frame_aux:
         fr.depth, fr.aux_ws = saved[-2], saved[-1]
         fr.aux = N.AuxOutputs(N._ptr(fr.depth), None, N._ptr(fr.aux_ws))      # (the backward does not read alpha)
@@ -539,13 +575,13 @@ def _restash_frame(fr):
     for n in _FRAME_TENSORS:
         setattr(fr, n, None)
     fr.keep = None
-    fr.depth = fr.aux_ws = None
+    fr.depth = fr.aux_ws = fr.extra_table = fr.extra_map = None
     fr.plan.screen_prezeroed = 0
 
 
 def _finish_forward(ctx, frame, color, radii, aux, means2D, opacities):
     """The tail of both Functions' forward(): the frame into autograd's slots, what backward() needs on ctx, the return tuple."""
-    maps = (frame.depth, frame.alpha)
+    maps = (frame.depth, frame.alpha) + ((frame.extra_map,) if frame.extra_map is not None else ())
     _stash_frame(ctx, frame)
     ctx.absgrad_to = getattr(_tls, "absgrad_to", None)
     ctx.shapes = (means2D.shape, opacities.shape)
@@ -554,15 +590,22 @@ def _finish_forward(ctx, frame, color, radii, aux, means2D, opacities):
     return (color, radii) + (maps if aux else ())
 
 
-def _backward_core(ctx, fr, needs, grad_out_color, grad_depth, grad_alpha):
+def _backward_core(ctx, fr, needs, grad_out_color, grad_depth, grad_alpha, grad_extra=None):
     """The core of both Functions' backward(): (rasterize_backward_geom's gradients for `needs`, means2D's and the opacities' in
-    their inputs' shapes; the camera gradients).  The frame goes back to its stashed state."""
+    their inputs' shapes; the camera gradients - for an extra frame (no camera gradients) the tail of the inputs' gradients instead:
+    three Nones and the extra colours').  The frame goes back to its stashed state."""
     # no depth / alpha gradient: the colour-only kernels, bit for bit the plain frame's gradients
     with_aux = grad_depth is not None or grad_alpha is not None
+    g_extra = None
+    if fr.extra_table is not None:            # an extra frame: the ext backward, which leaves slot 9 as the aux backward does
+        with_aux = True
+        g_extra = torch.empty(fr.desc.P, 3, dtype=torch.float32, device=fr.device)
     screen = rasterize_backward_screen(fr, grad_out_color, only_for_own_geom=True, grad_depth=grad_depth, grad_alpha=grad_alpha,
-                                       absgrad=ctx.absgrad_to is not None)
+                                       absgrad=ctx.absgrad_to is not None, grad_extra=grad_extra, extra_out=g_extra)
     g = list(rasterize_backward_geom(fr, screen, needs, depth_chain=with_aux))
     g_cam = _camera_backward(ctx, fr, screen, with_aux)
+    if g_extra is not None:
+        g_cam = (None, None, None, g_extra if ctx.extra_needs else None)
     _assign_absgrad(ctx, fr, screen)
     for i, shape in ((1, ctx.shapes[0]), (4, ctx.shapes[1])):         # means2D, opacities
         if g[i] is not None:
@@ -574,36 +617,38 @@ def _backward_core(ctx, fr, needs, grad_out_color, grad_depth, grad_alpha):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, aux=False, viewmatrix=None, projmatrix=None, campos=None):
+                raster_settings, aux=False, viewmatrix=None, projmatrix=None, campos=None, extra_colors=None):
         # viewmatrix / projmatrix / campos: raster_settings' own tensors, passed as inputs only when camera gradients are wanted
         # (camera_grads_wanted): the values are read from raster_settings either way
+        # extra_colors: passed only by a call with extra colours (behind three Nones: such a call has no camera gradients)
         rs = raster_settings
         _camera_meta(ctx, (viewmatrix, projmatrix, campos), 10)
+        ctx.extra_needs = extra_colors is not None and ctx.needs_input_grad[13]
         args = (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
         if rs.debug:
             cpu_args = tuple(a.detach().cpu().clone() for a in args)      # README.md:147-150 semantics
             try:
-                color, radii, frame = rasterize_forward(*args, rs, aux=aux)
+                color, radii, frame = rasterize_forward(*args, rs, aux=aux, extra=extra_colors)
                 torch.cuda.synchronize(means3D.device)
             except Exception:
                 _dump("snapshot_fw.dump", (cpu_args, tuple(rs)))
                 print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
                 raise
         else:
-            color, radii, frame = rasterize_forward(*args, rs, prepare_needs=tuple(ctx.needs_input_grad[:8]), aux=aux)
+            color, radii, frame = rasterize_forward(*args, rs, prepare_needs=tuple(ctx.needs_input_grad[:8]), aux=aux, extra=extra_colors)
             prepare_backward(frame, tuple(ctx.needs_input_grad[:8]), screen_prefix_only=True)
         ctx.raster_settings = rs
         return _finish_forward(ctx, frame, color, radii, aux, means2D, opacities)
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None):
+    def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None, grad_extra=None):
         fr, rs = _unstash_frame(ctx), ctx.raster_settings
         # input order: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp
         needs = tuple(ctx.needs_input_grad[:8])
         if rs.debug:
             kept = fr.keep[1:]                 # (the frame lets go of them once its gradients are enqueued)
             try:
-                g, g_cam = _backward_core(ctx, fr, needs, grad_out_color, grad_depth, grad_alpha)
+                g, g_cam = _backward_core(ctx, fr, needs, grad_out_color, grad_depth, grad_alpha, grad_extra)
                 torch.cuda.synchronize(fr.device)
             except Exception:
                 _dump("snapshot_bw.dump", (tuple(None if k is None else k.detach().cpu() for k in kept),
@@ -611,7 +656,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
                 raise
         else:
-            g, g_cam = _backward_core(ctx, fr, needs, grad_out_color, grad_depth, grad_alpha)
+            g, g_cam = _backward_core(ctx, fr, needs, grad_out_color, grad_depth, grad_alpha, grad_extra)
         return (*g, None, None) + g_cam
 
 
@@ -622,33 +667,67 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations, raster_settings, aux=False,
-                viewmatrix=None, projmatrix=None, campos=None):
+                viewmatrix=None, projmatrix=None, campos=None, extra_colors=None):
         rs = raster_settings
         _camera_meta(ctx, (viewmatrix, projmatrix, campos), 9)         # (as _RasterizeGaussians.forward)
+        ctx.extra_needs = extra_colors is not None and ctx.needs_input_grad[12]
         n = ctx.needs_input_grad       # xyz, means2D, f_dc, f_rest, opacity, scales, rotations
         needs = (n[0], n[1], n[2], False, n[4], n[5], n[6], False, n[3])
         # features_rest None: features_dc is the whole interleaved table [P,M,3] (scene.GaussianModel's packed leaf)
         color, radii, frame = rasterize_forward(xyz, features_dc, None, opacity_logits, log_scales, raw_rotations, None, rs,
                                                 sh_rest=features_rest, raw=2 if features_rest is None else 1,
-                                                prepare_needs=None if rs.debug else needs, aux=aux)
+                                                prepare_needs=None if rs.debug else needs, aux=aux, extra=extra_colors)
         if rs.debug:
             torch.cuda.synchronize(xyz.device)
         prepare_backward(frame, needs, screen_prefix_only=True)
         return _finish_forward(ctx, frame, color, radii, aux, means2D, opacity_logits)
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None):
+    def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None, grad_extra=None):
         n = ctx.needs_input_grad       # xyz, means2D, f_dc, f_rest, opacity, scales, rotations
         needs = (n[0], n[1], n[2], False, n[4], n[5], n[6], False, n[3])
-        g, g_cam = _backward_core(ctx, _unstash_frame(ctx), needs, grad_out_color, grad_depth, grad_alpha)
+        g, g_cam = _backward_core(ctx, _unstash_frame(ctx), needs, grad_out_color, grad_depth, grad_alpha, grad_extra)
         g_xyz, g_means2D, g_dc, _, g_op, g_sc, g_rot, _, g_rest = g
         return (g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None, None) + g_cam
 
 
+def check_extra_colors(extra_colors, means3D, depth_alpha, absgrad=False, contributions=None, tile_rows=None, rs=None):
+    """The rules of `extra_colors` (module docstring), checked before anything runs: a ValueError with the reason."""
+    who = "extra_colors"
+    if absgrad:
+        raise ValueError(f"{who}: not with absgrad=True (the abs blend backward carries neither the depth / alpha nor the extra gradients)")
+    if contributions is not None:
+        raise ValueError(f"{who}: not with contributions (a statistics frame is the plain colour forward)")
+    if not depth_alpha:
+        raise ValueError(f"{who}: the extra channels ride on the depth / alpha blend kernels: construct the rasterizer with depth_alpha=True")
+    if tile_rows is not None:
+        raise ValueError(f"{who}: whole images only: no tile_rows (sharded slabs / ShardedRenderer)")
+    if not isinstance(extra_colors, torch.Tensor):
+        raise ValueError(f"{who}: a float32 tensor [P,3] is expected, got {type(extra_colors).__name__}")
+    P = int(means3D.shape[0])
+    if tuple(extra_colors.shape) != (P, 3):
+        raise ValueError(f"{who}: shape {tuple(extra_colors.shape)}, expected ({P}, 3): three values per Gaussian")
+    if extra_colors.dtype != torch.float32:
+        raise ValueError(f"{who}: dtype {extra_colors.dtype}, expected torch.float32")
+    if extra_colors.device != means3D.device:
+        raise ValueError(f"{who}: on {extra_colors.device}, the frame's inputs live on {means3D.device}")
+    if rs is not None and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (rs.viewmatrix, rs.projmatrix, rs.campos)):
+        raise ValueError(f"{who}: camera gradients are not computed for the extra channels: detach viewmatrix, projmatrix and campos")
+
+
+def _extra_args(extra_colors):
+    """The tail of an autograd call with extra colours: no camera inputs (refused), then the tensor.  None: nothing, the call as it was."""
+    return () if extra_colors is None else (None, None, None, extra_colors)
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, depth_alpha=False, absgrad=False):
+                        raster_settings, depth_alpha=False, absgrad=False, extra_colors=None):
     if absgrad and depth_alpha:
         raise ValueError(_ABSGRAD_NO_AUX)
+    if extra_colors is not None:
+        check_extra_colors(extra_colors, means3D, depth_alpha, absgrad, rs=raster_settings)
+        return _apply(_RasterizeGaussians, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                      cov3Ds_precomp, raster_settings, True, *_extra_args(extra_colors))
     return _apply(_RasterizeGaussians, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                   cov3Ds_precomp, raster_settings, bool(depth_alpha), *_camera_args(raster_settings),
                   absgrad_to=means2D if absgrad else None)
@@ -794,8 +873,12 @@ class GaussianRasterizer(nn.Module):
         return present.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None):
+                cov3D_precomp=None, extra_colors=None):
+        """extra_colors (extension; [P,3] float32, with depth_alpha=True): three more channels blended in this frame; the call then
+        returns (color, radii, depth, alpha, extra [3,H,W]) (module docstring)."""
         rs = self.raster_settings
+        if extra_colors is not None:             # (before anything runs: a refused call has launched nothing)
+            check_extra_colors(extra_colors, means3D, self.depth_alpha, self.absgrad, self.contributions, rs=rs)
         if self.contributions is not None:       # (before anything runs: a refused call has launched nothing)
             from .contrib import check_inputs
             check_inputs(self.contributions, (means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp,
@@ -827,18 +910,22 @@ class GaussianRasterizer(nn.Module):
             leaves = _match_getters(means3D, opacities, shs, scales, rotations)
             if leaves is not None:
                 xyz, dc, rest, op, sc, rot = leaves
+                if extra_colors is not None:
+                    return _apply(_RasterizeGaussiansRaw, xyz, means2D, dc, rest, op, sc, rot, rs, True, *_extra_args(extra_colors))
                 return _apply(_RasterizeGaussiansRaw, xyz, means2D, dc, rest, op, sc, rot, rs, self.depth_alpha, *_camera_args(rs),
                               absgrad_to=means2D if self.absgrad else None)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, rs, self.depth_alpha, self.absgrad)
+                                   cov3D_precomp, rs, self.depth_alpha, self.absgrad, extra_colors)
 
-    def forward_raw(self, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations):
+    def forward_raw(self, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations, extra_colors=None):
         """Extension (not in the reference API): render straight from the reference GaussianModel's raw parameters
         (`_xyz, _features_dc, _features_rest, _opacity, _scaling, _rotation`), activations fused into the kernels.
         Same pixels and radii as forward(get_xyz, ..., get_opacity, get_features, get_scaling, get_rotation) and the
         same gradients on the raw parameters as autograd through those getters, to fp32 rounding."""
         rs = self.raster_settings
         rs = rs._replace(sh_degree=int(rs.sh_degree), image_height=int(rs.image_height), image_width=int(rs.image_width))
+        if extra_colors is not None:             # (as forward: the same rules, the same fifth output)
+            check_extra_colors(extra_colors, xyz, self.depth_alpha, self.absgrad, self.contributions, rs=rs)
         if self.contributions is not None:
             from .contrib import check_inputs
             check_inputs(self.contributions, (xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations,
@@ -853,5 +940,8 @@ class GaussianRasterizer(nn.Module):
         if self.contributions is not None:
             return self._contrib_frame(error_map, xyz, features_dc, None, opacity_logits, log_scales, raw_rotations,
                                        None, rs, sh_rest=features_rest, raw=2 if features_rest is None else 1)
+        if extra_colors is not None:
+            return _apply(_RasterizeGaussiansRaw, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations, rs,
+                          True, *_extra_args(extra_colors))
         return _apply(_RasterizeGaussiansRaw, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations, rs,
                       self.depth_alpha, *_camera_args(rs), absgrad_to=means2D if self.absgrad else None)

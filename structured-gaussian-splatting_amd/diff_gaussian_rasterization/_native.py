@@ -255,7 +255,16 @@ NORMALS_SIGNATURES = {
     "gsr_normal_consistency_forward": (_int, _image + (_dev,) * 4 + (_size, _dev, _dev)),
     "gsr_normal_consistency_backward": (_int, _image + (_dev,) * 8),
 }
-_ALL_SIGNATURES = {**SIGNATURES, **NORMALS_SIGNATURES}
+# The extra-channel entry points, declared in include/gsrast_extra.h (which gsrast.h includes): a table of their own, held to that
+# header's prototypes by tests/test_extra_abi.py.  They take no struct of their own (the aux frame's gsr_aux_outputs and plain pointers).
+EXTRA_SIGNATURES = {
+    "gsr_extra_workspace_size": (_int, (_desc, _i64, _P(_size))),
+    "gsr_extra_rows_size": (_int, (_desc, _plan, _P(_size))),
+    "gsr_forward_render_extra": (_int, _forward_render + (_aux, _dev, _dev, _dev)),
+    "gsr_forward_extra": (_int, _forward + (_aux, _dev, _dev, _dev)),
+    "gsr_backward_render_extra": (_int, _backward_render + (_aux,) + (_dev,) * 10),
+}
+_ALL_SIGNATURES = {**SIGNATURES, **NORMALS_SIGNATURES, **EXTRA_SIGNATURES}
 
 _lib = None
 
@@ -371,9 +380,13 @@ def forward_preprocess(desc, cam: Camera, g: Gaussians, geom_ws, radii, device, 
     return plan
 
 
-def _variant(who: str, aux, contrib, err):
-    """(i, more) of a frame's variant: i picks among a wrapper's (plain, _aux, _contrib, _contrib_error) entry points, `more` are the
-    arguments that one takes in front of the stream."""
+def _variant(who: str, aux, contrib, err, extra=None):
+    """(i, more) of a frame's variant: i picks among a wrapper's (plain, _aux, _contrib, _contrib_error, _extra) entry points, `more` are
+    the arguments that one takes in front of the stream.  extra: (table [P,4], map [3,H,W]) of an extra frame, which is an aux frame."""
+    if extra is not None:
+        if aux is None or contrib is not None or err is not None:
+            raise ValueError(f"{who}: extra channels ride on the aux frame (aux required, no contrib / err)")
+        return 4, (aux, _ptr(extra[0]), _ptr(extra[1]))
     if aux is not None and contrib is not None:
         raise ValueError(f"{who}: aux and contrib together (that kernel is not built)")
     if err is not None and contrib is None:
@@ -385,16 +398,16 @@ def _variant(who: str, aux, contrib, err):
 
 def forward_both(desc, cam: Camera, g: Gaussians, geom_ws, image_ws, radii, binning_ws, binning_capacity, out_color, device,
                  early_fill: Optional[Grads] = None, aux: Optional[AuxOutputs] = None, contrib: Optional[ContribStats] = None,
-                 err: Optional[ContribError] = None):
-    """gsr_forward (gsr_forward_aux with `aux`, gsr_forward_contrib with `contrib`; not both; gsr_forward_contrib_error with `contrib`
+                 err: Optional[ContribError] = None, extra=None):
+    """gsr_forward (gsr_forward_extra with `aux` and `extra`; gsr_forward_aux with `aux`, gsr_forward_contrib with `contrib`; not both; gsr_forward_contrib_error with `contrib`
     and `err`): both stages in one call.  Returns
     (plan, done): done = False when the binning workspace was too small for the first chunk (nothing of stage 2 ran: allocate and
     call forward_render) - or, when the plan has more than one chunk, for a later one: a statistics frame has then already added
     its earlier chunks (include/gsrast.h), so its caller sizes the workspace for num_rendered."""
     plan = FramePlan()
     lib = load()                      # the plain functions: GSR_ERR_WORKSPACE is an answer here, not an error
-    i, more = _variant("forward_both", aux, contrib, err)
-    fn = (lib.gsr_forward, lib.gsr_forward_aux, lib.gsr_forward_contrib, lib.gsr_forward_contrib_error)[i]
+    i, more = _variant("forward_both", aux, contrib, err, extra)
+    fn = (lib.gsr_forward, lib.gsr_forward_aux, lib.gsr_forward_contrib, lib.gsr_forward_contrib_error, lib.gsr_forward_extra)[i]
     rc = fn(desc, cam, g, _ptr(geom_ws), _ptr(image_ws), _ptr(radii), plan, _ptr(binning_ws), int(binning_capacity), _ptr(out_color),
             early_fill, *more, _stream(device))
     if rc == ERR_WORKSPACE:           # the guessed workspace did not do (for the first chunk, or for a later one)
@@ -404,9 +417,11 @@ def forward_both(desc, cam: Camera, g: Gaussians, geom_ws, image_ws, radii, binn
 
 
 def forward_render(desc, cam: Camera, g: Gaussians, geom_ws, binning_ws, image_ws, plan: FramePlan, out_color, device,
-                   aux: Optional[AuxOutputs] = None, contrib: Optional[ContribStats] = None, err: Optional[ContribError] = None):
-    i, more = _variant("forward_render", aux, contrib, err)
-    fn = (_gsr.gsr_forward_render, _gsr.gsr_forward_render_aux, _gsr.gsr_forward_render_contrib, _gsr.gsr_forward_render_contrib_error)[i]
+                   aux: Optional[AuxOutputs] = None, contrib: Optional[ContribStats] = None, err: Optional[ContribError] = None,
+                   extra=None):
+    i, more = _variant("forward_render", aux, contrib, err, extra)
+    fn = (_gsr.gsr_forward_render, _gsr.gsr_forward_render_aux, _gsr.gsr_forward_render_contrib, _gsr.gsr_forward_render_contrib_error,
+          _gsr.gsr_forward_render_extra)[i]
     fn(desc, cam, g, _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws), plan, _ptr(out_color), *more, _stream(device))
 
 
@@ -418,6 +433,25 @@ def contrib_error_fold(error_frame_q32, error_sum_q32, error_max, device):
 def aux_workspace_size(desc: FrameDesc, binning_capacity: int) -> int:
     """gsr_aux_workspace_size: bytes of the depth checkpoints of an aux frame whose binning workspace holds that many instances."""
     return _size(_gsr.gsr_aux_workspace_size, desc, int(binning_capacity))
+
+
+def extra_workspace_size(desc: FrameDesc, binning_capacity: int) -> int:
+    """gsr_extra_workspace_size: bytes of the four-plane aux checkpoints of an extra frame (its gsr_aux_outputs.ckpt_ws)."""
+    return _size(_gsr.gsr_extra_workspace_size, desc, int(binning_capacity))
+
+
+def extra_rows_size(desc: FrameDesc, plan: FramePlan) -> int:
+    """gsr_extra_rows_size: bytes of the extra backward's second row plane."""
+    return _size(_gsr.gsr_extra_rows_size, desc, plan)
+
+
+def backward_render_extra(desc, cam: Camera, geom_ws, binning_ws, image_ws, rows_ws, plan: FramePlan, out_color, aux: AuxOutputs, extra,
+                          extra_map, dL_dcolor, dL_ddepth, dL_dalpha, dL_dextra_map, screen_grads, extra_rows_ws, dL_dextra, device):
+    """gsr_backward_render_extra: any of the four upstream gradients may be None (zero); screen_grads as backward_render_aux leaves
+    it, dL_dextra [P,3] receives the extra table's gradient."""
+    _gsr.gsr_backward_render_extra(desc, cam, _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws), _ptr(rows_ws), plan, _ptr(out_color), aux,
+                                   _ptr(extra), _ptr(extra_map), _ptr(dL_dcolor), _ptr(dL_ddepth), _ptr(dL_dalpha), _ptr(dL_dextra_map),
+                                   _ptr(screen_grads), _ptr(extra_rows_ws), _ptr(dL_dextra), _stream(device))
 
 
 def backward_rows_size(desc: FrameDesc, plan: FramePlan) -> int:

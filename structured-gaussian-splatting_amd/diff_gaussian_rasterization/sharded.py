@@ -469,10 +469,17 @@ class ShardedRenderer:
     def render_normals(self, viewpoint_camera, pc, pipe, scaling_modifier=1.0):
         raise ValueError(_NO_NORMALS)
 
-    def render(self, viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, contributions=None):
+    def render_with_normals(self, viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0):
+        raise ValueError(_NO_NORMALS)
+
+    def render(self, viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, contributions=None,
+               extra_colors=None):
         import math
         if contributions is not None:
             raise ValueError(_NO_CONTRIBUTIONS)
+        if extra_colors is not None:
+            raise ValueError("extra_colors is not supported by ShardedRenderer: the extra channels ride on the depth / alpha blend, "
+                             "which runs on whole images only (render unsharded)")
 
         from . import GaussianRasterizationSettings
         if getattr(pipe, "antialiasing", False):

@@ -34,6 +34,11 @@ Gaussian's error-weighted blend total into the ErrorStats and folds it (diff_gau
 render_normals() (extension) is a frame of its own for the normal-consistency term (diff_gaussian_rasterization.normals): the
 Gaussians' view-space normals as precomputed colours, with the depth and alpha maps and the normal map the depth implies.  render()
 neither gains nor loses anything by it.
+
+`extra_colors` (extension; with depth_alpha=True; [P,3] float32): three more per-Gaussian values blended inside the colour frame with
+the colour's own weights (diff_gaussian_rasterization, "extra_colors"): the dict also holds "extra" [3,H,W], differentiable, on both
+paths.  render_with_normals() is the one-frame form of render() + render_normals(): the colour frame carries the Gaussians' view-space
+normals as its extra colours, so the four maps of the normal-consistency term come from one frame instead of two.
 """
 import math
 
@@ -96,6 +101,32 @@ def render_normals(viewpoint_camera, pc, pipe, scaling_modifier=1.0):
             "viewspace_points": pkg["viewspace_points"], "radii": pkg["radii"], "visibility_filter": pkg["visibility_filter"]}
 
 
+def render_with_normals(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0):
+    """render() and the maps of render_normals() from ONE frame (extension): the colour frame, on whichever of the raw and getter
+    paths render() would take, with depth_alpha=True and the Gaussians' view-space normals as its extra colours.  The normals are
+    computed from the very scales and rotations that frame is rendered from (raw log-scales and quaternions on the raw path:
+    gaussian_normals takes either), a model's 3D filter included.
+    -> render()'s dict (with "depth", "alpha" and "extra") plus "normal" [3,H,W] (= "extra": alpha-weighted, not normalised) and
+    "depth_normal" [3,H,W] (depth_to_normal of the depth and alpha maps).  "render" is render()'s, bit for bit; on the getter path
+    "normal", "depth" and "alpha" are render_normals()'s, bit for bit.  pipe.absgrad and pipe.compute_cov3D_python raise ValueError."""
+    from diff_gaussian_rasterization.normals import depth_to_normal, gaussian_normals
+    if getattr(pipe, "absgrad", False):
+        raise ValueError("render_with_normals: the frame is rendered with depth_alpha=True, which pipe.absgrad is not supported with: "
+                         "turn pipe.absgrad off for this frame")
+    if pipe.compute_cov3D_python:
+        raise ValueError("render_with_normals: the normals are the shortest axes of the scales and rotations the frame is rendered "
+                         "from; pipe.compute_cov3D_python renders from precomputed covariances")
+
+    def normals(scales, rotations):
+        return gaussian_normals(scales, rotations, pc.get_xyz, viewpoint_camera.world_view_transform, viewpoint_camera.camera_center)
+
+    pkg = _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, None, True, None, None, extra_colors=normals)
+    pkg["normal"] = pkg["extra"]
+    pkg["depth_normal"] = depth_to_normal(pkg["depth"], pkg["alpha"], math.tan(viewpoint_camera.FoVx * 0.5),
+                                          math.tan(viewpoint_camera.FoVy * 0.5))
+    return pkg
+
+
 def _zero_points(like: torch.Tensor) -> torch.Tensor:
     """One block of zeros shaped like `like` per device (re-made when the model's size or dtype changes)."""
     key = (like.device.type, like.device.index)
@@ -106,19 +137,25 @@ def _zero_points(like: torch.Tensor) -> torch.Tensor:
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, depth_alpha=False,
-           contributions=None, pixel_error=None):
+           contributions=None, pixel_error=None, extra_colors=None):
     """Render the scene.  Background tensor (bg_color) must be on the GPU.
     depth_alpha=True (extension): the dict also holds "depth" and "alpha" [1,H,W], differentiable (diff_gaussian_rasterization).
     contributions (extension): a ContributionStats the frame's blend statistics are added into; rendered under torch.no_grad(),
     through the getters whatever pipe.fused_activations says (module docstring).
-    pixel_error (extension; with an ErrorStats as contributions): the error map of this view, passed to the rasterizer."""
+    pixel_error (extension; with an ErrorStats as contributions): the error map of this view, passed to the rasterizer.
+    extra_colors (extension; with depth_alpha=True): [P,3] float32 blended in the same frame; the dict also holds "extra" [3,H,W]."""
+    if extra_colors is not None:
+        return _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, depth_alpha, contributions, pixel_error,
+                       extra_colors=extra_colors)
     if contributions is not None:
         with torch.no_grad():
             return _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, depth_alpha, contributions, pixel_error)
     return _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, depth_alpha, None, pixel_error)
 
 
-def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, depth_alpha, contributions, pixel_error=None):
+def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, depth_alpha, contributions, pixel_error=None,
+            extra_colors=None):
+    # extra_colors: a tensor, or (render_with_normals) a function of the (scales, rotations) the frame is rendered from
     xyz = pc.get_xyz
     # (the reference builds this as zeros_like(...) + 0 and retain_grad()s the non-leaf result; a leaf with requires_grad keeps
     # its .grad by itself.  Its VALUES are never read, by the rasterizer or by the training loop, only its .grad: every frame
@@ -139,7 +176,15 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
         d = {"render": out[0], "viewspace_points": screenspace_points, "visibility_filter": out[1] > 0, "radii": out[1]}
         if depth_alpha:
             d["depth"], d["alpha"] = out[2], out[3]
+        if extra_colors is not None:
+            d["extra"] = out[4]
         return d
+
+    def extra_kw(scales, rotations):
+        """The rasterizer call's extra_colors keyword; nothing without one: the call as it was."""
+        if extra_colors is None:
+            return {}
+        return {"extra_colors": extra_colors(scales, rotations) if callable(extra_colors) else extra_colors}
 
     # the fused path hands the RAW parameters to the kernels and so bypasses the getters — and with them the reference's
     # freeze flags (scene/gaussian_model.py:104-125 detach() the getter's result): a model with any of them set takes the
@@ -167,9 +212,9 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
             opacity, scaling = apply_filter_3d(opacity, scaling, filter_3D, raw=True)
         if packed:               # exp / normalize / sigmoid inside the kernels, the SH table as it is: no getter runs at all
             return result(rasterizer.forward_raw(pc._xyz, screenspace_points, pc._features, None,
-                                                 opacity, scaling, pc._rotation))
+                                                 opacity, scaling, pc._rotation, **extra_kw(scaling, pc._rotation)))
         return result(rasterizer.forward_raw(pc._xyz, screenspace_points, pc._features_dc, pc._features_rest,
-                                             opacity, scaling, pc._rotation))
+                                             opacity, scaling, pc._rotation, **extra_kw(scaling, pc._rotation)))
 
     filtered = filter_3D is not None
     scales = rotations = cov3D_precomp = None
@@ -193,4 +238,4 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
 
     return result(rasterizer(means3D=xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp,
                              opacities=pc.get_opacity_with_3D_filter if filtered else pc.get_opacity, scales=scales, rotations=rotations,
-                             cov3D_precomp=cov3D_precomp))
+                             cov3D_precomp=cov3D_precomp, **extra_kw(scales, rotations)))

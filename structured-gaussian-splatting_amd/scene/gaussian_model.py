@@ -89,6 +89,7 @@ class OptimizationDefaults:
     densify_error_score: str = "max"              # "max": the largest single view's error (Revising Densification); "sum": over the views (Taming-3DGS)
     lambda_normal: float = 0.0                    # > 0: weight of the normal-consistency loss, one render_normals frame per iteration (train_loop.train); untuned
     normal_from_iter: int = 7000                  # the first iteration that adds it (2DGS's value, not tuned here)
+    normal_in_frame: bool = False                 # True: colour and the normal term's maps from ONE render_with_normals frame (train_loop.train)
 
 
 def expon_lr(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1_000_000):

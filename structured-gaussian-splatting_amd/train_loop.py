@@ -16,7 +16,10 @@ prune is unchanged.  0 (the default): the loop is as before.  The defaults of th
 opt.lambda_normal > 0 adds the normal-consistency loss from iteration opt.normal_from_iter on: one
 gaussian_renderer.render_normals frame of the same camera beside the colour frame, opt.lambda_normal * normal_consistency_loss(...)
 added to the loss in front of backward(); on_iteration still receives the image loss alone.  It composes with every strategy above (the
-normals frame is rendered without pipe.absgrad).  0 (the default): the loop is as before.  Neither number is tuned on captured scenes."""
+normals frame is rendered without pipe.absgrad).  0 (the default): the loop is as before.  Neither number is tuned on captured scenes.
+opt.normal_in_frame (with lambda_normal > 0) takes the colour image and the three maps from ONE gaussian_renderer.render_with_normals
+frame per iteration from normal_from_iter on instead of two frames; the densification statistics then see the normal
+term's means2D gradient too.  Not with opt.densify_absgrad (the frame carries depth and alpha).  False (the default): the loop is as before."""
 import math
 import random
 
@@ -65,6 +68,12 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
     if lambda_normal > 0:
         from diff_gaussian_rasterization.normals import normal_consistency_loss
         from gaussian_renderer import render_normals
+    normal_in_frame = lambda_normal > 0 and bool(getattr(opt, "normal_in_frame", False))
+    if normal_in_frame:
+        from gaussian_renderer import render_with_normals
+        if getattr(opt, "densify_absgrad", False):
+            raise ValueError("normal_in_frame with densify_absgrad: the one frame carries the depth and alpha maps, which the abs blend "
+                             "backward does not (use the two-frame path: normal_in_frame = False)")
     if filter_3d:
         gaussians.compute_3D_filter(cameras)
     for it in range(first_iter, iterations + 1):
@@ -77,14 +86,19 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
         bg = torch.rand(3, device=background.device) if opt.random_background else background
         if getattr(opt, "densify_absgrad", False):             # the abs blend backward costs a little: only while its statistics are read
             pipe.absgrad = it < opt.densify_until_iter
-        pkg = render(cameras[idx], gaussians, pipe, bg)
+        in_frame = normal_in_frame and it >= opt.normal_from_iter
+        pkg = render_with_normals(cameras[idx], gaussians, pipe, bg) if in_frame else render(cameras[idx], gaussians, pipe, bg)
         image, vsp, vis, radii = pkg["render"], pkg["viewspace_points"], pkg["visibility_filter"], pkg["radii"]
         if use_bilagrid:
             image = bilagrid(image, idx)
         loss = training_loss(image, targets[idx], opt.lambda_dssim)
         if use_bilagrid:
             loss = loss + opt.bilateral_grid_tv * total_variation_loss(bilagrid.grids)
-        if lambda_normal > 0 and it >= opt.normal_from_iter:
+        if in_frame:
+            cam = cameras[idx]
+            normal_loss = normal_consistency_loss(pkg["normal"], pkg["depth"], pkg["alpha"], math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5))
+            (loss + lambda_normal * normal_loss).backward()
+        elif lambda_normal > 0 and it >= opt.normal_from_iter:
             cam, absgrad = cameras[idx], getattr(pipe, "absgrad", False)
             if absgrad:                                            # the normals frame carries depth and alpha: rendered without it
                 pipe.absgrad = False
