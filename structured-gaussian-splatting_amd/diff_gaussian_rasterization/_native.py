@@ -264,7 +264,16 @@ EXTRA_SIGNATURES = {
     "gsr_forward_extra": (_int, _forward + (_aux, _dev, _dev, _dev)),
     "gsr_backward_render_extra": (_int, _backward_render + (_aux,) + (_dev,) * 10),
 }
-_ALL_SIGNATURES = {**SIGNATURES, **NORMALS_SIGNATURES, **EXTRA_SIGNATURES}
+# TSDF fusion and mesh extraction, declared in include/gsrast_tsdf.h (which gsrast.h includes): held to that header's prototypes by
+# tests/test_tsdf_ref.py.  No struct of their own; the two totals of gsr_tsdf_mesh_count are host out-parameters.
+_dims = (_i32, _i32, _i32)                                                                 # nx, ny, nz
+TSDF_SIGNATURES = {
+    "gsr_tsdf_integrate": (_int, _dims + (_f32,) * 5 + (_i32, _i32) + (_f32,) * 4 + (_dev,) * 8),
+    "gsr_tsdf_mesh_workspace_size": (_int, _dims + (_P(_size),)),
+    "gsr_tsdf_mesh_count": (_int, _dims + (_f32, _dev, _dev, _dev, _size, _P(_i64), _P(_i64), _dev)),
+    "gsr_tsdf_mesh_emit": (_int, _dims + (_f32,) * 5 + (_dev,) * 4 + (_size, _i64, _i64) + (_dev,) * 4),
+}
+_ALL_SIGNATURES = {**SIGNATURES, **NORMALS_SIGNATURES, **EXTRA_SIGNATURES, **TSDF_SIGNATURES}
 
 _lib = None
 
@@ -1133,3 +1142,30 @@ def normal_consistency_backward(normal_map, depth, alpha, tanfovx, tanfovy, alph
         _gsr.gsr_normal_consistency_backward(H, W, tanfovx, tanfovy, alpha_min, _ptr(normal_map), _ptr(depth), _ptr(alpha), _ptr(grad_loss),
                                              _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _stream(depth.device))
     return tuple(outs)
+
+
+def tsdf_integrate(dims, origin, voxel_size, sdf_trunc, viewmatrix, depth, alpha, color, tanfovx, tanfovy, alpha_min, depth_max, tsdf, weight,
+                   vol_color):
+    """gsr_tsdf_integrate on the volume's device and its current stream: depth, alpha [H,W], color [3,H,W], viewmatrix [4,4] and the three
+    volume arrays, contiguous fp32 on one device.  One launch, no synchronisation."""
+    H, W = int(depth.shape[-2]), int(depth.shape[-1])
+    with torch.cuda.device(tsdf.device):
+        _gsr.gsr_tsdf_integrate(*dims, *origin, voxel_size, sdf_trunc, H, W, tanfovx, tanfovy, alpha_min, depth_max, _ptr(viewmatrix), _ptr(depth),
+                                _ptr(alpha), _ptr(color), _ptr(tsdf), _ptr(weight), _ptr(vol_color), _stream(tsdf.device))
+
+
+def tsdf_extract_mesh(dims, origin, voxel_size, min_weight, tsdf, weight, vol_color):
+    """gsr_tsdf_mesh_count and gsr_tsdf_mesh_emit on the volume's device and its current stream -> (vertices [V,3] float32, faces [F,3]
+    int32, colors [V,3] float32).  One host readback: the two totals that size the outputs."""
+    dev = tsdf.device
+    nbytes = _size(_gsr.gsr_tsdf_mesh_workspace_size, *dims)
+    nv, nf = C.c_int64(0), C.c_int64(0)
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        _gsr.gsr_tsdf_mesh_count(*dims, min_weight, _ptr(tsdf), _ptr(weight), _ptr(ws), nbytes, nv, nf, _stream(dev))
+        vertices = torch.empty(nv.value, 3, dtype=torch.float32, device=dev)
+        faces = torch.empty(nf.value, 3, dtype=torch.int32, device=dev)
+        colors = torch.empty(nv.value, 3, dtype=torch.float32, device=dev)
+        _gsr.gsr_tsdf_mesh_emit(*dims, *origin, voxel_size, min_weight, _ptr(tsdf), _ptr(weight), _ptr(vol_color), _ptr(ws), nbytes, nv.value,
+                                nf.value, _ptr(vertices), _ptr(faces), _ptr(colors), _stream(dev))
+    return vertices, faces, colors

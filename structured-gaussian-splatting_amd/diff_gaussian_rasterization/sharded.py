@@ -377,6 +377,10 @@ _NO_NORMALS = ("lambda_normal / render_normals is not supported by ShardedRender
                "unsharded, or leave lambda_normal at 0)")
 
 
+_NO_MESH = ("extract_mesh / fuse_depth_maps is not supported by ShardedRenderer: the fusion reads whole depth and alpha maps, a rank "
+            "renders a slab of tile rows and no depth or alpha map (extract the mesh unsharded: scene.mesh.extract_mesh)")
+
+
 class ShardedRenderer:
     """render()-shaped front end for world_size > 1 (same arguments and returned dict as
     gaussian_renderer.render, reference gaussian_renderer/__init__.py:18-100)."""
@@ -471,6 +475,12 @@ class ShardedRenderer:
 
     def render_with_normals(self, viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0):
         raise ValueError(_NO_NORMALS)
+
+    def fuse_depth_maps(self, pc, cameras, pipe, background, volume, **kw):
+        raise ValueError(_NO_MESH)
+
+    def extract_mesh(self, pc, cameras, pipe, background, **kw):
+        raise ValueError(_NO_MESH)
 
     def render(self, viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, contributions=None,
                extra_colors=None):

@@ -681,6 +681,12 @@ class GaussianModel:
         self.xyz_gradient_accum, self.denom = accum, denom
         self._load_optimizer_state(opt_state)
 
+    def extract_mesh(self, cameras, pipe, background, **kw):
+        """The triangle mesh of the surface `cameras` see: depth maps fused into a TSDF volume, surface nets (scene/mesh.py extract_mesh,
+        which takes kw: voxel_size, sdf_trunc, bounds, depth_max, min_weight) -> (vertices [V,3], faces [F,3] int32, colors [V,3])."""
+        from . import mesh
+        return mesh.extract_mesh(self, cameras, pipe, background, **kw)
+
     def save_ply(self, path, fuse_filter=False):
         """Without a 3D filter: the reference's file.  With one: Mip-Splatting's layout, one more property `filter_3D` after rot_3;
         fuse_filter=True (its save_fused_ply): the filtered logits and log-scales in the opacity and scale columns and no filter
