@@ -753,6 +753,10 @@ int gsr_profile_read(int max_entries, char (*names)[GSR_PROFILE_NAME_LEN], float
  * in a header of their own that this one brings in. */
 #include "gsrast_tsdf.h"
 
+/* Mesh cleaning (connected components of a triangle mesh, removal of small pieces and of unused vertices): the entry points are part
+ * of this ABI and of libgsrast.so, declared in a header of their own that this one brings in. */
+#include "gsrast_mesh.h"
+
 #ifdef __cplusplus
 }
 #endif

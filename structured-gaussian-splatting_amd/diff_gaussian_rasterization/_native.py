@@ -273,7 +273,15 @@ TSDF_SIGNATURES = {
     "gsr_tsdf_mesh_count": (_int, _dims + (_f32, _dev, _dev, _dev, _size, _P(_i64), _P(_i64), _dev)),
     "gsr_tsdf_mesh_emit": (_int, _dims + (_f32,) * 5 + (_dev,) * 4 + (_size, _i64, _i64) + (_dev,) * 4),
 }
-_ALL_SIGNATURES = {**SIGNATURES, **NORMALS_SIGNATURES, **EXTRA_SIGNATURES, **TSDF_SIGNATURES}
+# Mesh cleaning, declared in include/gsrast_mesh.h (which gsrast.h includes): held to that header's prototypes by
+# tests/test_mesh_clean_ref.py.  No struct of their own; the two totals of gsr_mesh_clean_count are host out-parameters.
+MESH_SIGNATURES = {
+    "gsr_mesh_clean_workspace_size": (_int, (_i32, _i32, _P(_size))),
+    "gsr_mesh_components": (_int, (_i32, _i32, _dev, _dev, _dev, _dev, _size, _dev)),
+    "gsr_mesh_clean_count": (_int, (_i32, _i32) + (_dev,) * 5 + (_size, _P(_i64), _P(_i64), _dev)),
+    "gsr_mesh_clean_emit": (_int, (_i32, _i32, _dev, _dev, _size, _i64, _i64) + (_dev,) * 4),
+}
+_ALL_SIGNATURES = {**SIGNATURES, **NORMALS_SIGNATURES, **EXTRA_SIGNATURES, **TSDF_SIGNATURES, **MESH_SIGNATURES}
 
 _lib = None
 
@@ -1169,3 +1177,32 @@ def tsdf_extract_mesh(dims, origin, voxel_size, min_weight, tsdf, weight, vol_co
         _gsr.gsr_tsdf_mesh_emit(*dims, *origin, voxel_size, min_weight, _ptr(tsdf), _ptr(weight), _ptr(vol_color), _ptr(ws), nbytes, nv.value,
                                 nf.value, _ptr(vertices), _ptr(faces), _ptr(colors), _stream(dev))
     return vertices, faces, colors
+
+
+def mesh_components(faces, V):
+    """gsr_mesh_components on the faces' device and its current stream -> (labels [F] int32, sizes [V] int32, workspace, its bytes).  No
+    host synchronisation; the workspace carries the union-find's give-up word to mesh_clean."""
+    dev, F = faces.device, int(faces.shape[0])
+    nbytes = _size(_gsr.gsr_mesh_clean_workspace_size, V, F)
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        labels = torch.empty(F, dtype=torch.int32, device=dev)
+        sizes = torch.empty(V, dtype=torch.int32, device=dev)
+        _gsr.gsr_mesh_components(V, F, _ptr(faces), _ptr(labels), _ptr(sizes), _ptr(ws), nbytes, _stream(dev))
+    return labels, sizes, ws, nbytes
+
+
+def mesh_clean(faces, V, labels, sizes, threshold_dev, ws, nbytes):
+    """gsr_mesh_clean_count and gsr_mesh_clean_emit behind mesh_components (its labels, sizes and workspace), on the same stream ->
+    (vertex_src [V'] int32, face_src [F'] int32, faces_out [F',3] int32).  threshold_dev: a one-element int32 device tensor.  One host
+    readback: the two totals that size the outputs (and the give-up word: a set one raises GsrError)."""
+    dev, F = faces.device, int(faces.shape[0])
+    nv, nf = C.c_int64(0), C.c_int64(0)
+    with torch.cuda.device(dev):
+        _gsr.gsr_mesh_clean_count(V, F, _ptr(faces), _ptr(labels), _ptr(sizes), _ptr(threshold_dev), _ptr(ws), nbytes, nv, nf, _stream(dev))
+        vertex_src = torch.empty(nv.value, dtype=torch.int32, device=dev)
+        face_src = torch.empty(nf.value, dtype=torch.int32, device=dev)
+        faces_out = torch.empty(nf.value, 3, dtype=torch.int32, device=dev)
+        _gsr.gsr_mesh_clean_emit(V, F, _ptr(faces), _ptr(ws), nbytes, nv.value, nf.value, _ptr(vertex_src), _ptr(face_src), _ptr(faces_out),
+                                 _stream(dev))
+    return vertex_src, face_src, faces_out

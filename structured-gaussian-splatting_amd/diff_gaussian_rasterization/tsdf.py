@@ -14,7 +14,7 @@ pixel (x, y) has its centre at x + 0.5.  The volume is indexed [z, y, x]; voxel 
 origin + voxel_size * (ix, iy, iz).
 
 The fusion rule is KinectFusion's and Open3D's projective rule with free-space carving, restated from the literature.  Out of scope:
-median depth, unbounded (contracted) volumes, sparse voxel hashing, mesh cleaning and decimation.
+median depth, unbounded (contracted) volumes, sparse voxel hashing and decimation (mesh cleaning: meshops.py).
 """
 from __future__ import annotations
 

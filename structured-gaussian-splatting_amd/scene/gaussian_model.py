@@ -683,7 +683,7 @@ class GaussianModel:
 
     def extract_mesh(self, cameras, pipe, background, **kw):
         """The triangle mesh of the surface `cameras` see: depth maps fused into a TSDF volume, surface nets (scene/mesh.py extract_mesh,
-        which takes kw: voxel_size, sdf_trunc, bounds, depth_max, min_weight) -> (vertices [V,3], faces [F,3] int32, colors [V,3])."""
+        which takes kw: voxel_size, sdf_trunc, bounds, depth_max, min_weight, and min_component_faces, keep_largest to clean it) -> (vertices [V,3], faces [F,3] int32, colors [V,3])."""
         from . import mesh
         return mesh.extract_mesh(self, cameras, pipe, background, **kw)
 

@@ -3,8 +3,9 @@ extract the surface (diff_gaussian_rasterization/tsdf.py).  T
 all end in, without leaving the device.
 
 The functions work with any model render() accepts: a GaussianModel (with or without a 3D filter), a LatentGaussianModel.  Projective
-fusion of a few views leaves holes and silhouette artefacts by nature; mesh cleaning and decimation, median depth, unbounded
-(contracted) volumes and sparse voxel hashing are out of scope.
+fusion of a few views leaves holes and silhouette artefacts by nature: clean_mesh (diff_gaussian_rasterization/meshops.py, DESIGN
+section 27) drops the small detached pieces on the device.  Decimation, median depth, unbounded (contracted) volumes and sparse voxel
+hashing are out of scope.
 """
 import math
 import os
@@ -45,10 +46,19 @@ def camera_bounds(cameras):
     return (centroid - half).tolist(), 2.0 * half
 
 
-def extract_mesh(pc, cameras, pipe, background, voxel_size=None, sdf_trunc=None, bounds=None, depth_max=None, min_weight=1.0):
+def clean_mesh(vertices, faces, colors=None, **kw):
+    """diff_gaussian_rasterization.meshops.clean_mesh: drops the faces of components smaller than max(min_faces, the size of the
+    keep_largest-th largest component), invalid faces and unused vertices (kw: min_faces, keep_largest, return_index, native)."""
+    from diff_gaussian_rasterization.meshops import clean_mesh as clean
+    return clean(vertices, faces, colors, **kw)
+
+
+def extract_mesh(pc, cameras, pipe, background, voxel_size=None, sdf_trunc=None, bounds=None, depth_max=None, min_weight=1.0,
+                 min_component_faces=None, keep_largest=None):
     """-> (vertices [V,3] float32, faces [F,3] int32, colors [V,3] float32) of the surface the cameras see.
     bounds: (lo [3], hi [3]); default camera_bounds(cameras).  voxel_size: default the bounds' longest side / 512.  sdf_trunc: default
-    5 voxel_size.  depth_max: default the bounds' longest side."""
+    5 voxel_size.  depth_max: default the bounds' longest side.  min_component_faces, keep_largest: when either is given the mesh is
+    cleaned after the extraction (clean_mesh's min_faces and keep_largest); with both None it is returned as extracted."""
     from diff_gaussian_rasterization.tsdf import TSDFVolume
     cameras = list(cameras)
     if not cameras:
@@ -70,7 +80,10 @@ def extract_mesh(pc, cameras, pipe, background, voxel_size=None, sdf_trunc=None,
     dims = tuple(max(int(math.ceil((h - l) / voxel_size - 1e-6)), 1) for l, h in zip(lo, hi))
     volume = TSDFVolume([l + 0.5 * voxel_size for l in lo], voxel_size, dims, sdf_trunc, device=pc.get_xyz.device)
     fuse_depth_maps(pc, cameras, pipe, background, volume, depth_max=depth_max)
-    return volume.extract_mesh(min_weight=min_weight)
+    mesh = volume.extract_mesh(min_weight=min_weight)
+    if min_component_faces is None and keep_largest is None:
+        return mesh
+    return clean_mesh(*mesh, min_faces=1 if min_component_faces is None else min_component_faces, keep_largest=keep_largest)
 
 
 _PLY_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])

@@ -1,0 +1,306 @@
+"""CPU checks of mesh cleaning (diff_gaussian_rasterization/meshops.py, csrc/gsr_mesh.hip, scene/mesh.py): the C ABI is
+additive (four new symbols in include/gsrast_mesh.h, which gsrast.h includes; the version unchanged), its ctypes table agrees with the
+header's prototypes, and every refusal comes without touching a GPU; the torch twins give the integers of the independent reference
+(tests/mesh_ref.py, itself cross-checked once against scipy) on every shared case and threshold, and attribute rows bit for bit; the
+kernels' own union-find (csrc/gsr_mesh_math.h compiled by g++: tests/mesh_host.cpp, a stand-alone program run as a subprocess, once
+under AddressSanitizer + UBSan and once under ThreadSanitizer) gives the reference's labels from 8 threads, and sets its give-up word
+under a retry cap of 1 without touching anything out of bounds; scene.mesh.extract_mesh without the new keywords returns what it did.
+Every comparison is exact."""
+import ctypes as C
+import os
+import re
+import subprocess
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import mesh_ref as MR
+from test_abi import header_prototypes, signature_mismatches
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_FUNCTIONS = ("gsr_mesh_clean_workspace_size", "gsr_mesh_components", "gsr_mesh_clean_count", "gsr_mesh_clean_emit")
+CASE_THRESHOLDS = [(name, mf, kl) for name in MR.cases() for mf, kl in MR.thresholds(name)]
+
+
+@pytest.fixture(scope="module")
+def native():
+    from diff_gaussian_rasterization import _native
+    if not os.path.exists(_native.lib_path()):
+        _native.build()
+    return _native
+
+
+def case_tensors(name, device="cpu", seed=5):
+    """(vertices [V,3] float32 of random bits - NaN payloads and infinities among them -, faces, colors likewise) of a shared case."""
+    V, f = MR.cases()[name]
+    g = torch.Generator().manual_seed(seed)
+    bits = lambda: torch.randint(-2 ** 31, 2 ** 31 - 1, (V, 3), generator=g, dtype=torch.int64).to(torch.int32).view(torch.float32)
+    return bits().to(device), torch.as_tensor(f).to(device).contiguous(), bits().to(device)
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and bool(torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32)))
+
+
+def check_components(got, ref, what):
+    labels, sizes = (t.cpu().numpy() for t in got)
+    assert labels.dtype == np.int32 and sizes.dtype == np.int32, what
+    assert np.array_equal(labels, ref["labels"]), f"{what}: labels differ"
+    assert np.array_equal(sizes, ref["sizes"]), f"{what}: sizes differ"
+
+
+def check_clean(got, ref, vertices, colors, what):
+    """clean_mesh(..., return_index=True)'s five results against the reference: integers exactly, attribute rows bit for bit."""
+    v, f, c, vsrc, fsrc = got
+    assert f.dtype == torch.int32 and vsrc.dtype == torch.int32 and fsrc.dtype == torch.int32, what
+    assert np.array_equal(vsrc.cpu().numpy(), ref["vertex_src"]), f"{what}: vertex_src differs"
+    assert np.array_equal(fsrc.cpu().numpy(), ref["face_src"]), f"{what}: face_src differs"
+    assert f.shape == ref["faces_out"].shape and np.array_equal(f.cpu().numpy(), ref["faces_out"]), f"{what}: faces differ"
+    idx = torch.from_numpy(ref["vertex_src"].astype(np.int64))
+    assert same_bits(v.cpu(), vertices.cpu()[idx]) and same_bits(c.cpu(), colors.cpu()[idx]), f"{what}: an attribute row is not the source's bits"
+
+
+# ---- ABI ----------------------------------------------------------------------------------------------------------------------
+def _mesh_header():
+    with open(os.path.join(ROOT, "include", "gsrast_mesh.h")) as f:
+        return re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
+
+
+def test_functions_are_declared_and_exported_and_the_version_stays(native):
+    main = open(os.path.join(ROOT, "include", "gsrast.h")).read()
+    assert '#include "gsrast_mesh.h"' in main and "#define GSR_VERSION 12" in main
+    protos = header_prototypes(_mesh_header())
+    assert tuple(protos) == NEW_FUNCTIONS == tuple(native.MESH_SIGNATURES)
+    bad = signature_mismatches(protos, native.MESH_SIGNATURES, native.MIRRORS)
+    assert not bad, "\n".join(bad)
+    lib = native.load()
+    for name, (restype, argtypes) in native.MESH_SIGNATURES.items():
+        assert hasattr(lib, name), f"{name} not exported by libgsrast.so"
+        assert getattr(lib, name).restype is restype and tuple(getattr(lib, name).argtypes) == tuple(argtypes), name
+        assert not any(name in t for t in (native.SIGNATURES, native.NORMALS_SIGNATURES, native.EXTRA_SIGNATURES, native.TSDF_SIGNATURES))
+    assert lib.gsr_version() == 12
+    assert "typedef" not in _mesh_header()                           # no struct of its own: gsrast.h's mirrors stay the whole set
+    mk = open(os.path.join(ROOT, "structured-gaussian-splatting_amd", "csrc", "Makefile")).read()
+    assert "gsr_mesh.hip" in mk and "gsr_mesh_math.h" in mk and "gsrast_mesh.h" in mk
+
+
+def test_header_is_plain_c(tmp_path):
+    src = tmp_path / "t.c"
+    src.write_text('#include "gsrast.h"\nint main(void) { size_t b; return gsr_mesh_clean_workspace_size(0, 0, &b) != 0 ? 0 : 0; }\n')
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-c", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "t.o")])
+
+
+def test_argument_validation_without_gpu(native):
+    """Every refusal comes before anything touches the device: the pointers here are never dereferenced."""
+    lib = native.load()
+    p, odd = C.c_void_p(256), C.c_void_p(258)
+    b = C.c_size_t(7)
+    assert lib.gsr_mesh_clean_workspace_size(0, 9, b) == 0 and b.value == 0
+    assert lib.gsr_mesh_clean_workspace_size(1000, 3000, b) == 0
+    # per vertex: parent and remap (4 B each) and a used byte; per face a keep bit; per block of 256 two counts and two prefixes
+    assert 9 * 1000 + 3000 // 8 <= b.value <= 9 * 1000 + 3000 // 8 + 16 * 12 + 16 * 4 + 9 * 256
+    assert lib.gsr_mesh_clean_workspace_size(2 ** 31 - 1, 2 ** 31 - 1, b) == 0 and b.value > 9 * (2 ** 31 - 1)
+    assert lib.gsr_mesh_clean_workspace_size(-1, 0, b) == -1 and b"gsr_mesh_clean_workspace_size" in lib.gsr_last_error()
+    assert lib.gsr_mesh_clean_workspace_size(4, -1, b) == -1 and lib.gsr_mesh_clean_workspace_size(4, 4, None) == -1
+    nv, nf = C.c_int64(5), C.c_int64(5)
+
+    def components(V=8, F=8, f=p, l=p, s=p, ws=p, nb=1 << 20):
+        return lib.gsr_mesh_components(V, F, f, l, s, ws, nb, None), lib.gsr_last_error()
+
+    def count(V=8, F=8, f=p, l=p, s=p, t=p, ws=p, nb=1 << 20, v=nv, n=nf):
+        return lib.gsr_mesh_clean_count(V, F, f, l, s, t, ws, nb, v, n, None), lib.gsr_last_error()
+
+    def emit(V=8, F=8, f=p, ws=p, nb=1 << 20, v=4, n=2, ov=p, of=p, oo=p):
+        return lib.gsr_mesh_clean_emit(V, F, f, ws, nb, v, n, ov, of, oo, None), lib.gsr_last_error()
+
+    for call, names in ((components, dict(f=b"faces", l=b"labels", s=b"sizes", ws=b"workspace")),
+                        (count, dict(f=b"faces", l=b"labels", s=b"sizes", t=b"threshold_dev", ws=b"workspace")),
+                        (emit, dict(f=b"faces", ws=b"workspace", ov=b"vertex_src", of=b"face_src", oo=b"faces_out"))):
+        for kw in (dict(V=-1), dict(F=-1)):
+            rc, msg = call(**kw)
+            assert rc == -1 and call.__name__.encode() in msg, (call.__name__, kw, msg)
+        for arg, shown in names.items():
+            rc, msg = call(**{arg: None})
+            assert rc == -1 and shown + b" is NULL" in msg, (call.__name__, arg, msg)
+            rc, msg = call(**{arg: odd})
+            assert rc == -1 and shown in msg and b"aligned" in msg, (call.__name__, arg, msg)
+        rc, msg = call(ws=C.c_void_p(128))
+        assert rc == -1 and b"256-byte" in msg
+        rc, msg = call(nb=8)
+        assert rc == native.ERR_WORKSPACE and b"workspace_bytes" in msg
+    assert count(v=None)[0] == -1 and count(n=None)[0] == -1
+    for kw in (dict(v=-1), dict(n=-1), dict(v=9), dict(n=9)):
+        rc, msg = emit(**kw)
+        assert rc == -1 and b"num_vertices" in msg, kw
+    # an empty mesh: nothing is read, every total is 0
+    assert components(V=0, F=0, f=None, l=None, s=None, ws=None, nb=0)[0] == 0
+    for kw in (dict(V=0, F=0), dict(V=5, F=0), dict(V=0, F=3)):
+        nv.value = nf.value = 5
+        assert count(f=None, l=None, s=None, t=None, ws=None, nb=0, **kw)[0] == 0 and nv.value == 0 and nf.value == 0
+        assert emit(f=None, ws=None, nb=0, v=0, n=0, ov=None, of=None, oo=None, **kw)[0] == 0
+    assert emit(v=0, n=0, f=None, ws=None, ov=None, of=None, oo=None)[0] == 0     # nothing kept: nothing is read or written
+
+
+def test_python_refusals_are_value_errors_and_native_on_host_raises():
+    from diff_gaussian_rasterization import meshops as M
+    v, f, c = torch.zeros(4, 3), torch.tensor([[0, 1, 2]], dtype=torch.int32), torch.zeros(4, 3)
+    for bad in (dict(faces=f.long()), dict(faces=f.reshape(3)), dict(faces=torch.zeros(2, 4, dtype=torch.int32)),
+                dict(faces=torch.zeros(3, 2, dtype=torch.int32).t()), dict(faces=f.numpy()), dict(vertices=torch.zeros(4, 2)),
+                dict(vertices=torch.zeros(4)), dict(colors=torch.zeros(3, 3)), dict(colors=torch.zeros(4, 4)), dict(min_faces=0),
+                dict(min_faces=-3), dict(min_faces=1.5), dict(keep_largest=0), dict(keep_largest=-1), dict(vertices=v.to("meta")),
+                dict(colors=c.to("meta"))):
+        for fn in (M.clean_mesh, M.clean_mesh_torch):
+            with pytest.raises(ValueError):
+                fn(**{**dict(vertices=v, faces=f, colors=c), **bad})
+    for fn in (M.face_components, M.face_components_torch):
+        for bad in (dict(faces=f.long()), dict(faces=f, num_vertices=-1), dict(faces=f, num_vertices=2 ** 31)):
+            with pytest.raises(ValueError):
+                fn(**{**dict(faces=f, num_vertices=4), **bad})
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        M.face_components(f, 4, native=True)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        M.clean_mesh(v, f, c, native=True)
+    out = M.clean_mesh(v, f)                                                     # colours are optional
+    assert out[2] is None and out[0].shape == (3, 3) and len(M.clean_mesh(v, f, return_index=True)) == 5
+    from scene import mesh
+    assert all(torch.equal(a, b) for a, b in zip(mesh.clean_mesh(v, f, c, min_faces=1), M.clean_mesh(v, f, c)))
+
+
+# ---- the reference, and the twins against it ------------------------------------------------------------------------------------
+def test_reference_components_agree_with_scipy():
+    sp = pytest.importorskip("scipy.sparse")
+    from scipy.sparse.csgraph import connected_components
+    checked = 0
+    for name, (V, f) in MR.cases().items():
+        if V == 0:
+            continue
+        ref = MR.reference(name)
+        fv = f[MR.face_valid(f, V)].astype(np.int64)
+        rows, cols = np.concatenate([fv[:, 0], fv[:, 0]]), np.concatenate([fv[:, 1], fv[:, 2]])
+        n, comp = connected_components(sp.coo_matrix((np.ones(len(rows)), (rows, cols)), shape=(V, V)), directed=False)
+        smallest = np.full(n, V, np.int64)
+        np.minimum.at(smallest, comp, np.arange(V))
+        want = np.full(len(f), -1, np.int64)
+        want[MR.face_valid(f, V)] = smallest[comp[fv[:, 0]]]
+        assert np.array_equal(ref["labels"], want), name
+        assert np.array_equal(ref["sizes"], np.bincount(want[want >= 0], minlength=V)), name
+        checked += 1
+    assert checked >= 8
+
+
+def test_the_cases_hold_what_they_are_for():
+    c = MR.cases()
+    sizes = lambda name: sorted(MR.reference(name)["sizes"][MR.reference(name)["sizes"] > 0].tolist())
+    assert sizes("path") == [5000] and sizes("star") == [4096] and c["path"][1].shape[0] % 256 != 0
+    assert sizes("islands") == [1] * 1000 + [300] and c["islands"][1].shape[0] % 256 != 0
+    assert sizes("pinch_shared") == [36] and sizes("pinch_duplicated") == [18, 18]
+    assert sizes("mixed") == [1, 1, 1, 10, 18, 18]
+    V, f = c["mixed"]
+    ref = MR.reference("mixed")
+    assert int((ref["labels"] < 0).sum()) == 7 and len(np.unique(f[ref["labels"] >= 0], axis=0)) == int((ref["labels"] >= 0).sum()) - 2
+    unused = np.setdiff1d(np.arange(V), ref["vertex_src"])
+    assert unused[0] == 0 and unused[-1] == V - 1 and ((unused > 2) & (unused < V - 4)).any()
+    assert MR.reference("islands", 1, 2)["threshold"] == 1 and MR.reference("islands", 1, 5000)["threshold"] == 1
+    assert MR.reference("mixed", 1, 1)["threshold"] == 18 and len(MR.reference("mixed", 1, 1)["face_src"]) == 36
+
+
+@pytest.mark.parametrize("name", list(MR.cases()))
+def test_components_twin_against_the_reference(name):
+    from diff_gaussian_rasterization.meshops import face_components
+    V, f = MR.cases()[name]
+    check_components(face_components(torch.as_tensor(f), V), MR.reference(name), f"twin {name}")
+
+
+@pytest.mark.parametrize("name, min_faces, keep_largest", CASE_THRESHOLDS)
+def test_clean_twin_against_the_reference(name, min_faces, keep_largest):
+    from diff_gaussian_rasterization.meshops import clean_mesh
+    v, f, c = case_tensors(name)
+    ref = MR.reference(name, min_faces, keep_largest)
+    check_clean(clean_mesh(v, f, c, min_faces=min_faces, keep_largest=keep_largest, return_index=True), ref, v, c, f"twin {name}")
+    three = clean_mesh(v, f, c, min_faces=min_faces, keep_largest=keep_largest, native=False)
+    assert len(three) == 3 and np.array_equal(three[1].numpy(), ref["faces_out"])
+
+
+# ---- the kernels' union-find on the host, under sanitizers ----------------------------------------------------------------------
+@pytest.fixture(scope="module", params=["address,undefined", "thread"])
+def host(request, tmp_path_factory):
+    d = str(tmp_path_factory.mktemp("mesh"))
+    exe = os.path.join(d, "mesh_host")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-pthread", f"-fsanitize={request.param}", "-fno-sanitize-recover=all", "-o", exe,
+                           os.path.join(ROOT, "tests", "mesh_host.cpp")])
+    fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
+
+    def run(name, link_tries=0, threads=8):
+        V, f = MR.cases()[name]
+        with open(fin, "wb") as fh:
+            np.array([V, len(f), threads, link_tries], np.int32).tofile(fh)
+            f.tofile(fh)
+        subprocess.check_call([exe, fin, fout])                                  # a sanitizer report is a non-zero exit status
+        out = np.fromfile(fout, np.int32)
+        assert out.size == 1 + len(f) + V
+        return int(out[0]), out[1:1 + len(f)], out[1 + len(f):]
+    return run
+
+
+@pytest.mark.parametrize("name", ["path", "star", "islands", "mixed"])
+def test_union_find_from_eight_threads_under_sanitizers(host, name):
+    gave_up, labels, sizes = host(name)
+    ref = MR.reference(name)
+    assert gave_up == 0
+    assert np.array_equal(labels, ref["labels"]) and np.array_equal(sizes, ref["sizes"])
+
+
+def test_a_retry_cap_of_one_gives_up_under_the_stars_contention_in_bounds(host):
+    gave_up, labels, sizes = host("star", link_tries=1)
+    assert gave_up == 1                                                          # and the sanitizers saw nothing out of bounds
+    assert ((labels >= 0) & (labels < MR.cases()["star"][0])).all() and int(sizes.sum()) == 4096
+
+
+# ---- scene.mesh.extract_mesh ----------------------------------------------------------------------------------------------------
+def test_extract_mesh_without_the_new_keywords_returns_what_the_volume_returns(monkeypatch):
+    """A stub renderer and a stub volume on the host: with both keywords None extract_mesh makes the calls it made before and hands the
+    volume's own objects through; with one given the mesh goes through clean_mesh."""
+    import gaussian_renderer
+    from diff_gaussian_rasterization import tsdf
+    from scene import mesh
+    calls = []
+    V, f = MR.cases()["mixed"]
+    v, faces, c = case_tensors("mixed")
+    result = (v, faces, c)
+
+    class Volume:
+        def __init__(self, origin, voxel_size, dims, sdf_trunc, device="cuda", dtype=torch.float32):
+            calls.append(("volume", tuple(dims)))
+
+        def integrate(self, depth, alpha, color, viewmatrix, tx, ty, alpha_min=0.5, depth_max=None):
+            calls.append(("integrate", tuple(depth.shape)))
+
+        def extract_mesh(self, min_weight=1.0):
+            calls.append(("extract", min_weight))
+            return result
+
+    def render(cam, pc, pipe, bg, depth_alpha=False):
+        calls.append(("render", depth_alpha))
+        return dict(depth=torch.ones(1, 4, 5), alpha=torch.ones(1, 4, 5), render=torch.ones(3, 4, 5))
+
+    monkeypatch.setattr(tsdf, "TSDFVolume", Volume)
+    monkeypatch.setattr(gaussian_renderer, "render", render)
+    cams = [types.SimpleNamespace(camera_center=torch.tensor([float(i), 0.0, 0.0]), FoVx=0.8, FoVy=0.7, world_view_transform=torch.eye(4))
+            for i in range(2)]
+    pc = types.SimpleNamespace(get_xyz=torch.zeros(1, 3))
+    kw = dict(bounds=((0, 0, 0), (1, 1, 1)), voxel_size=0.25)
+    want_calls = [("volume", (4, 4, 4)), ("render", True), ("integrate", (1, 4, 5)), ("render", True), ("integrate", (1, 4, 5)), ("extract", 1.0)]
+    got = mesh.extract_mesh(pc, cams, None, None, **kw)
+    assert calls == want_calls and isinstance(got, tuple) and all(a is b for a, b in zip(got, result))
+    del calls[:]
+    got = mesh.extract_mesh(pc, cams, None, None, min_component_faces=None, keep_largest=None, **kw)
+    assert calls == want_calls and all(a is b for a, b in zip(got, result))
+    for kwc, (mf, kl) in ((dict(keep_largest=1), (1, 1)), (dict(min_component_faces=11), (11, None)), (dict(min_component_faces=12, keep_largest=3), (12, 3))):
+        got = mesh.extract_mesh(pc, cams, None, None, **kw, **kwc)
+        ref = MR.reference("mixed", mf, kl)
+        assert np.array_equal(got[1].numpy(), ref["faces_out"]) and same_bits(got[0], v[torch.from_numpy(ref["vertex_src"].astype(np.int64))])
+    from scene import GaussianModel
+    import inspect
+    assert "**kw" in str(inspect.signature(GaussianModel.extract_mesh))          # the model forwards every keyword
