@@ -749,6 +749,10 @@ int gsr_profile_read(int max_entries, char (*names)[GSR_PROFILE_NAME_LEN], float
  * entry points are part of this ABI and of libgsrast.so, declared in a header of their own that this one brings in. */
 #include "gsrast_extra.h"
 
+/* The median depth map of an aux frame (the depth of the splat at which a pixel's accumulated opacity crosses one half, differentiable
+ * in that splat's depth): the entry points are part of this ABI and of libgsrast.so, declared in a header of their own. */
+#include "gsrast_median.h"
+
 /* TSDF fusion of depth maps and mesh extraction by surface nets: the entry points are part of this ABI and of libgsrast.so, declared
  * in a header of their own that this one brings in. */
 #include "gsrast_tsdf.h"

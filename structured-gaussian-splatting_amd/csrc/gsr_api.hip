@@ -381,7 +381,24 @@ static AuxWS aux_workspace(const gsr_aux_outputs *aux_out, bool binned, int64_t 
 struct FwdArgs {
     const gsr_aux_outputs *aux = nullptr; const gsr_contrib_stats *stats = nullptr; const gsr_contrib_error *err = nullptr;
     bool ext = false; const float *extra = nullptr; float *extra_map = nullptr;
+    bool med = false; float *median = nullptr; int32_t *median_enc = nullptr;      // (gsr_forward_median: `med` set, with aux, without ext)
 };
+
+// A median frame's arguments (include/gsrast_median.h): refused with a message before anything is launched
+static int validate_median(const gsr_frame_desc *desc, const gsr_aux_outputs *aux, const void *median, const int32_t *median_enc, bool backward,
+                           const char *who)
+{
+    if (!desc) { set_error("%s: NULL frame description", who); return GSR_ERR_INVALID_ARGUMENT; }
+    if (!aux) { set_error("%s: aux is required (a median frame is an aux frame: depth, alpha and ckpt_ws)", who); return GSR_ERR_INVALID_ARGUMENT; }
+    if (!backward && !median) { set_error("%s: median is NULL ([H,W] float)", who); return GSR_ERR_INVALID_ARGUMENT; }
+    if (!median_enc) { set_error("%s: median_enc is NULL ([H,W] int32)", who); return GSR_ERR_INVALID_ARGUMENT; }
+    if ((((uintptr_t)median | (uintptr_t)median_enc) & 3u) != 0) { set_error("%s: median / median_enc are not 4-byte aligned", who); return GSR_ERR_INVALID_ARGUMENT; }
+    if (!median_frame_allowed(true, false, false, desc->tile_row_begin == 0 && desc->tile_row_end <= 0)) {
+        set_error("%s: whole images only (tile_row_begin = tile_row_end = 0)", who);
+        return GSR_ERR_INVALID_ARGUMENT;
+    }
+    return GSR_OK;
+}
 
 // An extra frame's arguments (include/gsrast_extra.h): refused with a message before anything is launched
 static int validate_extra(const gsr_frame_desc *desc, const gsr_aux_outputs *aux, const float *extra, const float *extra_map, const char *who)
@@ -407,6 +424,7 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
     int rc = validate_contrib(desc, v.stats, v.err, "gsr_forward_render_contrib");
     if (rc) return rc;
     if (v.ext && (rc = validate_extra(desc, v.aux, v.extra, v.extra_map, "gsr_forward_render_extra"))) return rc;
+    if (v.med && (rc = validate_median(desc, v.aux, v.median, v.median_enc, false, "gsr_forward_render_median"))) return rc;
     if ((rc = validate_inputs(desc, cam, g))) return rc;
     if (!cam || !cam->bg || !image_ws || !out_color || !plan || plan->num_rendered < 0 ||
         (desc->P > 0 && !geom_ws) || (plan->num_rendered > 0 && !binning_ws)) {
@@ -433,7 +451,10 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
         const ExtWS ex0{reinterpret_cast<const float4 *>(v.extra), v.extra_map, nullptr, nullptr, nullptr};
         // (err is not handed on: nothing is blended, every error total is zero, and with P == 0 the caller may have passed no map -
         // the error kernel would load it at tile start whatever the ranges hold)
-        if ((rc = launch_render_fwd(f, *cam, 0, true, 0, gw0, bw0, iw, out_color, dbg, s, false, {v.aux ? &ax0 : nullptr, v.stats, nullptr, v.ext ? &ex0 : nullptr}))) return rc;
+        const MedWS md0{v.median, v.median_enc, nullptr};
+        if ((rc = launch_render_fwd(f, *cam, 0, true, 0, gw0, bw0, iw, out_color, dbg, s, false,
+                                    {v.aux ? &ax0 : nullptr, v.stats, nullptr, v.ext ? &ex0 : nullptr, v.med ? &md0 : nullptr})))
+            return rc;
         plan->chunks_run = 1;
         return GSR_OK;
     }
@@ -446,7 +467,8 @@ static int forward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam
     BinningWS bw = carve_binning(binning_ws, capacity, f);
     const AuxWS ax = aux_workspace(v.aux, true, capacity, f, v.ext ? kExtCkptPlanes : 1);
     const ExtWS ex{reinterpret_cast<const float4 *>(v.extra), v.extra_map, nullptr, nullptr, nullptr};
-    const FwdVariant variant{v.aux ? &ax : nullptr, v.stats, v.err, v.ext ? &ex : nullptr};
+    const MedWS md{v.median, v.median_enc, nullptr};
+    const FwdVariant variant{v.aux ? &ax : nullptr, v.stats, v.err, v.ext ? &ex : nullptr, v.med ? &md : nullptr};
     if (!plan->binning_initialised && (rc = launch_binning_init(f, gw, iw, dbg, s))) return rc;
     plan->binning_initialised = 0;                  // a re-run of this stage must reset the tile ranges / open flags itself
     int sort_result = 0;
@@ -531,6 +553,7 @@ static int forward_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const
     int rc = validate_contrib(desc, v.stats, v.err, "gsr_forward_contrib");      // (before stage 1: a refused call launches nothing)
     if (rc) return rc;
     if (v.ext && (rc = validate_extra(desc, v.aux, v.extra, v.extra_map, "gsr_forward_extra"))) return rc;
+    if (v.med && (rc = validate_median(desc, v.aux, v.median, v.median_enc, false, "gsr_forward_median"))) return rc;
     if ((rc = gsr_forward_preprocess(desc, cam, g, geom_ws, image_ws, radii, plan, stream))) return rc;
     const int64_t need = first_chunk_capacity(*plan);
     if (plan->num_rendered > 0 && (!binning_ws || binning_capacity < need)) {
@@ -603,6 +626,24 @@ int gsr_forward_render_extra(const gsr_frame_desc *desc, const gsr_camera *cam, 
 {
     return forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, nullptr, nullptr,
                                {aux, nullptr, nullptr, true, extra, extra_map});
+}
+
+int gsr_forward_median(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *image_ws, int32_t *radii,
+                       gsr_frame_plan *plan, void *binning_ws, int64_t binning_capacity, float *out_color, gsr_grads *early_fill,
+                       const gsr_aux_outputs *aux, float *median, int32_t *median_enc, void *stream)
+{
+    FwdArgs v{aux};
+    v.med = true; v.median = median; v.median_enc = median_enc;
+    return forward_impl(desc, cam, g, geom_ws, image_ws, radii, plan, binning_ws, binning_capacity, out_color, early_fill, stream, v);
+}
+
+int gsr_forward_render_median(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, void *geom_ws, void *binning_ws,
+                              void *image_ws, gsr_frame_plan *plan, float *out_color, const gsr_aux_outputs *aux, float *median,
+                              int32_t *median_enc, void *stream)
+{
+    FwdArgs v{aux};
+    v.med = true; v.median = median; v.median_enc = median_enc;
+    return forward_render_impl(desc, cam, g, geom_ws, binning_ws, image_ws, plan, out_color, stream, nullptr, nullptr, v);
 }
 
 int gsr_extra_workspace_size(const gsr_frame_desc *desc, int64_t binning_capacity, size_t *bytes)
@@ -702,10 +743,11 @@ int gsr_bwd_segment_entries(void) { return kSeg; }
 static int backward_render_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const void *geom_ws, void *binning_ws,
                                 const void *image_ws, void *rows_ws, const gsr_frame_plan *plan, const float *out_color,
                                 const gsr_aux_outputs *aux_out, const float *dL_dcolor, const float *dL_ddepth, const float *dL_dalpha,
-                                float *screen_grads, void *stream, BwdKind kind, const ExtWS *ext = nullptr)
+                                float *screen_grads, void *stream, BwdKind kind, const ExtWS *ext = nullptr, const MedWS *med = nullptr)
 {
     int rc = validate(desc);
     if (rc) return rc;
+    if (kind == BwdKind::kMed && (rc = validate_median(desc, aux_out, nullptr, med->median_enc, true, "gsr_backward_render_median"))) return rc;
     if (kind == BwdKind::kExt) {
         if ((rc = validate_extra(desc, aux_out, (const float *)ext->table, ext->map, "gsr_backward_render_extra"))) return rc;
         if (desc->P > 0 && !ext->dL_dtable) { set_error("gsr_backward_render_extra: dL_dextra is NULL ([P,3])"); return GSR_ERR_INVALID_ARGUMENT; }
@@ -741,8 +783,12 @@ static int backward_render_impl(const gsr_frame_desc *desc, const gsr_camera *ca
         const long long rows_n = plan->instances_emitted >= 0 ? (long long)plan->instances_emitted : rows_upper;
         const AuxWS ax = aux_workspace(aux_out, true, plan_capacity(plan), f, kind == BwdKind::kExt ? kExtCkptPlanes : 1);
         if ((rc = launch_render_bwd(f, plan->chunks_run, plan->sort_result, rows_n, gw, bw, iw, out_color, dL_dcolor, dbg, s,
-                                    {kind, &ax, dL_ddepth, dL_dalpha, ext})))
+                                    {kind, &ax, dL_ddepth, dL_dalpha, ext, med})))
             return rc;
+    }
+    if (kind == BwdKind::kMed) {      // (kMedianReducesAsAux: the rows are the aux backward's)
+        static_assert(kMedianReducesAsAux, "a median frame's rows are reduced by the aux instantiation");
+        return launch_reduce_rows(f, *plan, gw, bw, screen_grads, plan->screen_prezeroed, dbg, s, BwdKind::kAux);
     }
     // only the depth ranks of chunks that ran can own gradient rows
     if (kind == BwdKind::kExt && plan->num_rendered <= 0) return launch_reduce_rows(f, *plan, gw, bw, screen_grads, plan->screen_prezeroed, dbg, s, BwdKind::kAux);
@@ -801,6 +847,16 @@ int gsr_backward_render_extra(const gsr_frame_desc *desc, const gsr_camera *cam,
                     reinterpret_cast<float4 *>(extra_rows_ws), dL_dextra};
     return backward_render_impl(desc, cam, geom_ws, binning_ws, image_ws, rows_ws, plan, out_color, aux, dL_dcolor, dL_ddepth, dL_dalpha,
                                 screen_grads, stream, BwdKind::kExt, &ext);
+}
+
+int gsr_backward_render_median(const gsr_frame_desc *desc, const gsr_camera *cam, const void *geom_ws, void *binning_ws,
+                               const void *image_ws, void *rows_ws, const gsr_frame_plan *plan, const float *out_color,
+                               const gsr_aux_outputs *aux, const float *dL_dcolor, const float *dL_ddepth, const float *dL_dalpha,
+                               const int32_t *median_enc, const float *dL_dmedian, float *screen_grads, void *stream)
+{
+    const MedWS med{nullptr, const_cast<int32_t *>(median_enc), dL_dmedian};
+    return backward_render_impl(desc, cam, geom_ws, binning_ws, image_ws, rows_ws, plan, out_color, aux, dL_dcolor, dL_ddepth, dL_dalpha,
+                                screen_grads, stream, BwdKind::kMed, nullptr, &med);
 }
 
 static int backward_geom_impl(const gsr_frame_desc *desc, const gsr_camera *cam, const gsr_gaussians *g, const int32_t *radii,

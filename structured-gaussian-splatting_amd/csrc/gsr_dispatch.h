@@ -198,6 +198,13 @@ inline bool colors_in_index_order(int r0, int r1, int num_visible, int P)
 // of their bound) take one 16-lane group per quadrant
 inline bool small_splats(uint64_t n, uint64_t n_max, bool filtered) { return !filtered && n > 0 && n_max * 2 < n * 9; }
 
+// ---- a median frame (include/gsrast_median.h) is an aux frame at every step: its chunks take the mapping small_splats() chooses, in
+// the median instantiation of the aux blend forward; its blend backward is ONE more instantiation of the aux one (row slot 9 carries the
+// median's share of dL/dz), so the row reduction and the depth chain that follow are the aux frame's own kernels, and no launch is added.
+// With extra colours the ext kernels would be needed too: ext x median is not built, such a frame is refused.
+constexpr bool kMedianReducesAsAux = true;      // launch_reduce_rows / k_geom_bwd_depth of a median frame: the aux frame's
+inline bool median_frame_allowed(bool aux, bool ext, bool stats, bool whole_image) { return aux && !ext && !stats && whole_image; }
+
 // ---- the chunk's row reduction (launch_reduce_rows): a whole wave per Gaussian where the chunk's Gaussians own many rows each (the
 // nearest, screen-filling splats: a few thousand rows), eight lanes otherwise — and always eight for a chunk that went through the live
 // filter, whose instance bound says nothing about what it emitted (a training frame's last chunk is most of the scene with a bound of

@@ -224,6 +224,12 @@ struct ExtWS {
     float4 *rows;               // [instances emitted] (sum w g_e0, .. g_e1, .. g_e2, 0) by slot (backward)
     float *dL_dtable;           // [P, 3] (backward)
 };
+// The median depth of a median frame (include/gsrast_median.h): the caller's two maps and the upstream gradient.  No checkpoint of its own.
+struct MedWS {
+    float *median;              // [H, W]
+    int32_t *median_enc;        // [H, W] the median's list entry, encoded as last_enc
+    const float *dL_dmedian;    // [H, W] or NULL (backward)
+};
 constexpr int kLastShift = 26;  // last_enc = (chunk + 1) << kLastShift | position
 constexpr int kQuadMaskShift = 28;                // BinningWS::gids = quadrant mask << 28 | Gaussian (P < 2^28)
 constexpr uint32_t kGidMask = (1u << kQuadMaskShift) - 1u;
@@ -286,7 +292,8 @@ ZeroSegs zero_segments(const FrameK &f, const gsr_gaussians &g, float *screen, c
 // whatever `groups` says): the chunk's per-Gaussian blend statistics, added to the caller's accumulators.  err (with stats): its
 // error-weighted totals, added to err->error_frame_q32
 // ext (with aux): its three extra channels
-struct FwdVariant { const AuxWS *aux; const gsr_contrib_stats *stats; const gsr_contrib_error *err; const ExtWS *ext = nullptr; };
+// med (with aux, without ext): its median depth
+struct FwdVariant { const AuxWS *aux; const gsr_contrib_stats *stats; const gsr_contrib_error *err; const ExtWS *ext = nullptr; const MedWS *med = nullptr; };
 // groups: the chunk's splats are small (fewer than 4.5 tiles per Gaussian): the quadrant-group mapping (gsr_render.hip)
 int launch_render_fwd(const FrameK &f, const gsr_camera &cam, int c, bool last_chunk, int sort_result, const GeomWS &gw, const BinningWS &bw,
                       ImageWS &iw, float *out_color, bool debug, hipStream_t s, bool groups, const FwdVariant &v);
@@ -295,8 +302,10 @@ int launch_contrib_error_fold(long long P, uint64_t *frame_q32, uint64_t *sum_q3
 // The blend backward's kind.  kAux: dL_dcolor, dL_ddepth, dL_dalpha may each be NULL (zero); rows get slot 9 = dL/dz of the splat (the sum
 // of w dL/ddepth).  kAbs: rows get slots 10, 11 = the per-pixel absolute sums of d/dmean2D.  launch_reduce_rows sums the kind's slots too
 // kExt: kAux plus the extra channels - three more sums per entry, into ExtWS::rows; launch_reduce_rows sums them into ExtWS::dL_dtable
-enum class BwdKind { kPlain, kAux, kAbs, kExt };
-struct BwdVariant { BwdKind kind; const AuxWS *aux; const float *dL_ddepth, *dL_dalpha; const ExtWS *ext = nullptr; };      // the pointers: kAux, kExt only
+// kMed: kAux of a median frame - slot 9 also gains MedWS::dL_dmedian at each pixel's median splat; launch_reduce_rows takes kAux for it
+// (gsr_dispatch.h kMedianReducesAsAux)
+enum class BwdKind { kPlain, kAux, kAbs, kExt, kMed };
+struct BwdVariant { BwdKind kind; const AuxWS *aux; const float *dL_ddepth, *dL_dalpha; const ExtWS *ext = nullptr; const MedWS *med = nullptr; };      // the pointers: kAux, kExt, kMed only
 // rows_upper: bound of the instances the chunks that ran emitted (sizes the launch: the unit count lives on the device)
 int launch_render_bwd(const FrameK &f, int chunks_run, int sort_result, long long rows_upper, const GeomWS &gw, BinningWS &bw,
                       const ImageWS &iw, const float *out_color, const float *dL_dcolor, bool debug, hipStream_t s, const BwdVariant &v);

@@ -387,6 +387,7 @@ __device__ __forceinline__ void fwd_tile_epilogue(int t, int tile, int c, int la
 // out_color); in front of every checkpoint it goes into the aux checkpoint plane of the same slot (AuxFwdK).
 struct AuxFwdK {
     static constexpr int kPlanes = 1;  // planes of kAuxCkptFloats per aux checkpoint
+    static constexpr bool kMedian = false;      // MedFwdK: the blend also selects the median depth
     float *depth, *alpha;              // [H, W]
     float *ckpt;                       // [R / kSeg + 2][kAuxCkptFloats]: Z in front of the checkpoint of the same slot (BinningWS::ckpt)
     float *ckpt_start_c;               // [Tn][kAuxCkptFloats]: Z when this chunk (>= 1) starts on a tile (ImageWS::ckpt_start)
@@ -400,6 +401,17 @@ struct ExtFwdK : AuxFwdK {
     static constexpr int kPlanes = kExtCkptPlanes;
     const float4 *table;               // [P] (e0, e1, e2, unused)
     float *map;                        // [3, H, W]
+};
+// kMed (gsr_forward_render_median; the aux kernels handed a MedFwdK): the same blend also selects the pixel's median depth - the view
+// depth of the last composited splat whose front transmittance is above one half.  Per pair: T in front of the
+// splat is taken before fwd_pair, w behind it, and M = (T > 0.5 && w > 0) ? z : M, likewise the entry's last_enc encoding - two compares
+// and two selects per pixel, no arithmetic, so every other value of the frame is the aux frame's.  A done pixel has T < 0 and a pixel whose T
+// has fallen to one half or below never passes the test again, so a later chunk cannot move it.  Between chunks the two values live in
+// their maps, as Z lives in the depth map; the backward does not re-derive the median, so no checkpoint plane holds it.
+struct MedFwdK : AuxFwdK {
+    static constexpr bool kMedian = true;
+    float *median;                     // [H, W]
+    int32_t *median_enc;               // [H, W] the median's list entry, encoded as last_enc (0: none)
 };
 // kStats (gsr_forward_render_contrib; lock step only): the same blend also takes, per blended splat, three totals over the wave's 256
 // pixels of the weights w that fwd_pair returns - n = the pixels with w > 0 (ballots: scalar), s = their sum (the lane's four in a
@@ -439,6 +451,8 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
                                            const AX &ax, const ContribK &cs = ContribK{}, const ErrK &er = ErrK{})
 {
     constexpr bool kExt = AX::kPlanes > 1;
+    constexpr bool kMed = AX::kMedian;
+    static_assert(!kMed || (kAux && !kExt), "the median rides on the aux kernels; ext x median is not built");
     constexpr int kAuxStride = AX::kPlanes * kAuxCkptFloats;      // floats per aux checkpoint
     static_assert(!kExt || kAux, "the extra channels ride on the aux kernels");
     static_assert(!kStats || (Map::kLockStep && !kAux), "the statistics are built for the lock-step colour kernel");
@@ -502,6 +516,18 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
         };
         Z0 = v2f{load_z(0), load_z(1)}; Z1 = v2f{load_z(2), load_z(3)};
     }
+    v2f M0 = {0.f, 0.f}, M1 = {0.f, 0.f};                  // kMed: the median depth so far of the two pairs, and its list entry
+    int me00 = 0, me01 = 0, me10 = 0, me11 = 0;
+    if constexpr (kMed) {
+        auto load_m = [&](int e, float &m_, int &enc) {
+            const int px = px0 + map.ex(e), py = py0 + map.ey(e);
+            m_ = 0.f; enc = 0;
+            if (c > 0 && px < f.W && py < f.H) { m_ = ax.median[(size_t)py * f.W + px]; enc = ax.median_enc[(size_t)py * f.W + px]; }
+        };
+        float m0, m1;
+        load_m(0, m0, me00); load_m(1, m1, me01); M0 = v2f{m0, m1};
+        load_m(2, m0, me10); load_m(3, m1, me11); M1 = v2f{m0, m1};
+    }
     v2f X0[3] = {}, X1[3] = {};                            // kExt: the three extra channels so far of the two pairs
     if constexpr (kExt) {
         auto load_x = [&](int e, int k) {
@@ -543,7 +569,15 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
         const LpTerms lt = lp_terms(a.z, a.w, b.y, dx);
         if (m & 3u) {
             const float dy = a.y - fy0;
+            v2f Tf = {0.f, 0.f};                                  // kMed: T in front of the splat
+            if constexpr (kMed) Tf = P0.T;
             const v2f w = fwd_pair(active, lp_at(lt, b.x, dy), b.y, b.z, b.w, cbl, contributor, P0);
+            if constexpr (kMed) {
+                const float z = sh_rec[3u * j + 2u].y;
+                const bool s0 = Tf[0] > 0.5f && w[0] > 0.f, s1 = Tf[1] > 0.5f && w[1] > 0.f;
+                M0 = v2f{s0 ? z : M0[0], s1 ? z : M0[1]};
+                me00 = s0 ? contributor : me00; me01 = s1 ? contributor : me01;
+            }
             if constexpr (kAux) { const float z = sh_rec[3u * j + 2u].y; Z0 = __builtin_elementwise_fma(v2f{z, z}, w, Z0); }
             if constexpr (kExt) {
                 const float4 x = sh_ext[j];
@@ -555,7 +589,15 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
         }
         if (m & 12u) {
             const float dy = a.y - fy1;
+            v2f Tf = {0.f, 0.f};
+            if constexpr (kMed) Tf = P1.T;
             const v2f w = fwd_pair(active, lp_at(lt, b.x, dy), b.y, b.z, b.w, cbl, contributor, P1);
+            if constexpr (kMed) {
+                const float z = sh_rec[3u * j + 2u].y;
+                const bool s0 = Tf[0] > 0.5f && w[0] > 0.f, s1 = Tf[1] > 0.5f && w[1] > 0.f;
+                M1 = v2f{s0 ? z : M1[0], s1 ? z : M1[1]};
+                me10 = s0 ? contributor : me10; me11 = s1 ? contributor : me11;
+            }
             if constexpr (kAux) { const float z = sh_rec[3u * j + 2u].y; Z1 = __builtin_elementwise_fma(v2f{z, z}, w, Z1); }
             if constexpr (kExt) {
                 const float4 x = sh_ext[j];
@@ -666,6 +708,13 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
         };
         store_aux(0, P0.T[0], Z0[0]); store_aux(1, P0.T[1], Z0[1]); store_aux(2, P1.T[0], Z1[0]); store_aux(3, P1.T[1], Z1[1]);
     }
+    if constexpr (kMed) {
+        auto store_m = [&](int e, float m_, int enc) {
+            const int px = px0 + map.ex(e), py = py0 + map.ey(e);
+            if (px < f.W && py < f.H) { ax.median[(size_t)py * f.W + px] = m_; ax.median_enc[(size_t)py * f.W + px] = enc; }
+        };
+        store_m(0, M0[0], me00); store_m(1, M0[1], me01); store_m(2, M1[0], me10); store_m(3, M1[1], me11);
+    }
     if constexpr (kExt) {
         auto store_x = [&](int e, int k, float x_) {
             const int px = px0 + map.ex(e), py = py0 + map.ey(e);
@@ -686,7 +735,7 @@ __device__ __forceinline__ void render_fwd(FrameK f, int c, int finalize_all, co
 
 // Every variant of the blend forward is an instantiation of this one kernel.  X: the variant's own kernel arguments - AuxFwdK for the aux
 // instantiations of both pixel mappings (colour, radii and every array as the plain kernels, plus depth and alpha), ExtFwdK in its
-// place for the ext instantiations (every array as the aux kernels, plus the extra map); ContribK, then
+// place for the ext instantiations (every array as the aux kernels, plus the extra map), MedFwdK for the median ones (plus the median maps); ContribK, then
 // ErrK, for the statistics instantiations (lock step, whatever the chunk's splats are like: both mappings render the same bits)
 template <class Map, bool kAux, bool kStats, bool kErr, int kMinWaves, class... X>
 __global__ __launch_bounds__(kWave, kMinWaves) void k_render_fwd(FrameK f, int n_tiles, int c, int finalize_all,
@@ -756,6 +805,14 @@ int launch_render_fwd(const FrameK &f, const gsr_camera &cam, int c, bool last_c
         return launch(groups ? k_render_fwd<GroupLanes, true, false, false, kFwdExtWaves, ExtFwdK> : k_render_fwd<QuadrantLanes, true, false, false, kFwdExtWaves, ExtFwdK>,
                       "render_fwd_ext", ex);
     }
+    if (v.aux && v.med) {
+        MedFwdK mx;
+        mx.depth = v.aux->depth; mx.alpha = v.aux->alpha; mx.ckpt = v.aux->ckpt;
+        mx.ckpt_start_c = c > 0 ? v.aux->ckpt_start + (size_t)(c - 1) * Tn * kAuxCkptFloats : nullptr;
+        mx.median = v.med->median; mx.median_enc = v.med->median_enc;
+        return launch(groups ? k_render_fwd<GroupLanes, true, false, false, 4, MedFwdK> : k_render_fwd<QuadrantLanes, true, false, false, 4, MedFwdK>,
+                      "render_fwd_median", mx);
+    }
     if (v.aux) {
         const AuxFwdK ax{v.aux->depth, v.aux->alpha, v.aux->ckpt, c > 0 ? v.aux->ckpt_start + (size_t)(c - 1) * Tn * kAuxCkptFloats : nullptr};
         return launch(groups ? k_render_fwd<GroupLanes, true, false, false, 4, AuxFwdK> : k_render_fwd<QuadrantLanes, true, false, false, 4, AuxFwdK>,
@@ -812,6 +869,18 @@ struct BwdPairExt {
     v2f dpe0, dpe1, dpe2;
 };
 struct BwdAccExt { v2f S10, S11, S12; };      // ext: the lane's sums of w dL/dextra
+struct BwdPairMed {          // median: the same pair's dL/dmedian, and each pixel's median as a position + 1 in this unit's chunk (0: none here)
+    v2f gm;
+    int mpos0, mpos1;
+};
+// The median's share of the tenth sum: g_m where this entry is the pixel's median, and -0.0 - the one value whose addition changes no
+// float, -0.0 and +0.0 included - elsewhere.  An add of its own, never contracted into the product in front of it: with a zero (or
+// NULL) dL/dmedian the sum keeps the aux backward's roundings, and at most a zero's sign differs (which the row's first add absorbs).
+__device__ __forceinline__ v2f add_median_share(v2f s9, int mabs, const BwdPairMed &PM)
+{
+#pragma clang fp contract(off)
+    return s9 + v2f{mabs == PM.mpos0 ? PM.gm[0] : -0.f, mabs == PM.mpos1 ? PM.gm[1] : -0.f};
+}
 // the lane's partial sums of one splat, per pair element: X = sum tA dx, Y = sum tA dy (dL/dmean2D = ln2 (2 qA X + qB Y, 2 qC Y + qB X):
 // formed once per splat by the lane that stores the row), S2..S4 the conic's, S5 the opacity's, S6..S8 the colour's, S9 (aux) the depth's
 struct BwdAcc { v2f X, Y, S2, S3, S4, S5, S6, S7, S8; };
@@ -826,11 +895,12 @@ __device__ __forceinline__ float add_halves(v2f v)
     return r;
 }
 
-template <bool INIT, bool kAux = false, bool kAbs = false, bool kExt = false>         // INIT: the splat's first pair, the sums start here (A comes in undefined)
+// kMed (with kAux): mabs = the entry's position + 1 in the chunk's list (-1 for an idle group's pass), PM the pair's median
+template <bool INIT, bool kAux = false, bool kAbs = false, bool kExt = false, bool kMed = false>         // INIT: the splat's first pair, the sums start here (A comes in undefined)
 __device__ __forceinline__ void bwd_pair(const BwdSplat sp, v2f lp, v2f dx, float dy, int pos, BwdPair &P, BwdAcc &A,
                                          const BwdPairAux &PA = BwdPairAux{}, v2f *S9 = nullptr, const BwdAbsQ &Q = BwdAbsQ{},
                                          BwdAbs *AB = nullptr, const BwdExt *se = nullptr, const BwdPairExt *PE = nullptr,
-                                         BwdAccExt *AE = nullptr)
+                                         BwdAccExt *AE = nullptr, int mabs = -1, const BwdPairMed *PM = nullptr)
 {
     const bool valid0 = (pos < P.limit0) && !(lp[0] > sp.lop) && !(lp[0] < kLog2AlphaMin);      // power > 0 <=> lp > lop
     const bool valid1 = (pos < P.limit1) && !(lp[1] > sp.lop) && !(lp[1] < kLog2AlphaMin);
@@ -880,6 +950,7 @@ __device__ __forceinline__ void bwd_pair(const BwdSplat sp, v2f lp, v2f dx, floa
             AB->AY += __builtin_elementwise_abs(Q.qC2 * ty + Q.qB * tx);
         }
     }
+    if constexpr (kMed) *S9 = add_median_share(*S9, mabs, *PM);
 }
 
 // The kernel: one wave per work unit, front to back from the forward's checkpoint, with the wave split into four GROUPS of 16 lanes,
@@ -903,6 +974,15 @@ struct AuxBwdK {
     const float *dL_ddepth, *dL_dalpha;      // [H, W] each, NULL = zero
     const float *ckpt, *ckpt_start;    // the aux checkpoints (AuxWS)
 };
+// kMed (k_render_bwd<true, false, kBwdWaves, MedBwdK>; gsr_backward_render_median): the aux backward of a median frame.  The selection
+// is piecewise constant, so the median map's upstream gradient g_m goes to dL/dz of the pixel's median splat and nowhere else: per pixel
+// g_m and the median's position in this unit's chunk (decoded from median_enc as `limit` is from last_enc; 0 when it lies in another
+// chunk), and in bwd_pair S9 += (position == the pixel's ? g_m : 0) behind the aux backward's own add.  Every other value is the aux
+// backward's; the sum leaves in row slot 9 and the aux row reduction and depth chain follow unchanged.
+struct MedBwdK {
+    const int32_t *median_enc;         // [H, W] the forward's
+    const float *dL_dmedian;           // [H, W], NULL = zero
+};
 struct ExtBwdK {
     const float4 *table;               // [P] (e0, e1, e2, unused)
     const float *map;                  // [3, H, W] the forward's extra map (final)
@@ -910,7 +990,8 @@ struct ExtBwdK {
     float4 *rows;                      // [instances emitted] by slot
 };
 constexpr int kBwdExtWaves = 3;        // minimum waves per SIMD of the ext instantiation: at kBwdWaves = 4 (128 VGPRs) it spills three registers
-// X: nothing, or ExtBwdK (the ext instantiation: kAux, and an aux checkpoint of kExtCkptPlanes planes)
+template <class K, class... X> struct HasArg { static constexpr bool value = (... || __is_same(K, X)); };
+// X: nothing, ExtBwdK (the ext instantiation: kAux, and an aux checkpoint of kExtCkptPlanes planes) or MedBwdK (the median one: kAux)
 template <bool kAux, bool kAbs, int kMinWaves, class... X>
 __global__ __launch_bounds__(kWave, kMinWaves) void k_render_bwd(FrameK f, const uint2 *__restrict__ ranges,
                                                       const uint32_t *__restrict__ tile_walk,
@@ -923,8 +1004,8 @@ __global__ __launch_bounds__(kWave, kMinWaves) void k_render_bwd(FrameK f, const
                                                       const uint32_t *__restrict__ unit_count, AuxBwdK ax, X... x)
 {
     static_assert(!(kAux && kAbs), "the aux x abs blend backward is not built");
-    constexpr bool kExt = sizeof...(X) == 1;
-    static_assert(sizeof...(X) <= 1 && (!kExt || kAux), "the extra channels ride on the aux backward");
+    constexpr bool kExt = HasArg<ExtBwdK, X...>::value, kMed = HasArg<MedBwdK, X...>::value;
+    static_assert(sizeof...(X) <= 1 && ((!kExt && !kMed) || kAux), "the extra channels and the median ride on the aux backward");
     constexpr int kSums = kExt ? 13 : kAux ? 10 : kAbs ? 11 : 9;         // per-entry sums
     constexpr int kAccStride = kExt ? 13 : (kAux || kAbs) ? 11 : 9;
     constexpr int kAuxStride = (kExt ? kExtCkptPlanes : 1) * kAuxCkptFloats;      // floats per aux checkpoint
@@ -936,6 +1017,8 @@ __global__ __launch_bounds__(kWave, kMinWaves) void k_render_bwd(FrameK f, const
         sh_ext = sh_ext_rows;
         ex = ExtBwdK{x...};
     }
+    MedBwdK md{};
+    if constexpr (kMed) md = MedBwdK{x...};
     __shared__ float sh_acc[kWave * kAccStride];      // the batch's sums, [entry][value]: stride 9 (11) words, conflict-free by lane
 #ifdef GSR_BWD_TRACE
     TraceEnd trace_end{(unsigned long long)wall_clock64(), (int)blockIdx.x};
@@ -1030,6 +1113,20 @@ __global__ __launch_bounds__(kWave, kMinWaves) void k_render_bwd(FrameK f, const
             P0.E = v2f{E0, E1}; PA0.dpz = v2f{z0, z1}; PA0.GA = v2f{a0, a1};
             P1.E = v2f{E2, E3}; PA1.dpz = v2f{z2, z3}; PA1.GA = v2f{a2, a3};
         }
+        BwdPairMed PM0{}, PM1{};
+        if constexpr (kMed) {
+            auto load_med = [&](int e, float &gm, int &mpos) {
+                const int px = px0 + map.ex(e), py = py0 + map.ey(e);
+                const bool inside = px < f.W && py < f.H;
+                const size_t pix = inside ? (size_t)py * f.W + px : 0;
+                gm = inside && md.dL_dmedian ? md.dL_dmedian[pix] : 0.f;
+                const int enc = inside ? md.median_enc[pix] : 0;
+                mpos = (enc >> kLastShift) - 1 == c ? (enc & ((1 << kLastShift) - 1)) : 0;
+            };
+            float g0, g1, g2, g3;
+            load_med(0, g0, PM0.mpos0); load_med(1, g1, PM0.mpos1); load_med(2, g2, PM1.mpos0); load_med(3, g3, PM1.mpos1);
+            PM0.gm = v2f{g0, g1}; PM1.gm = v2f{g2, g3};
+        }
         BwdPairExt PE0{}, PE1{};
         if constexpr (kExt) {
             // E gains <extra_final - extra in front of the segment, g_e>
@@ -1090,6 +1187,8 @@ __global__ __launch_bounds__(kWave, kMinWaves) void k_render_bwd(FrameK f, const
                 BwdAbs AB;                               // abs: the lane's sums of |u|
                 const BwdAbsQ Q{2.f * a.z, a.w, 2.f * b.x};
                 BwdAccExt AE;                            // ext: the lane's sums of w dL/dextra
+                // median: the entry's position + 1 in the chunk's list, as median_enc counts it (an idle group's pass: never a median)
+                const int mabs = kMed && j < (unsigned)kWave ? base + (int)j + 1 : -1;
                 if constexpr (kExt) {
                     const float4 xe = sh_ext[jj];        // the splat's extra triple
                     float xe1 = xe.y;
@@ -1104,12 +1203,14 @@ __global__ __launch_bounds__(kWave, kMinWaves) void k_render_bwd(FrameK f, const
                     {
                         const float dy = a.y - fy0;
                         if constexpr (kAbs) bwd_pair<true, false, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P0, A, PA0, nullptr, Q, &AB);
+                        else if constexpr (kMed) bwd_pair<true, true, false, false, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P0, A, PA0, &S9, Q, nullptr, nullptr, nullptr, nullptr, mabs, &PM0);
                         else if constexpr (kAux) bwd_pair<true, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P0, A, PA0, &S9);
                         else bwd_pair<true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P0, A);
                     }
                     {
                         const float dy = a.y - fy1;
                         if constexpr (kAbs) bwd_pair<false, false, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P1, A, PA1, nullptr, Q, &AB);
+                        else if constexpr (kMed) bwd_pair<false, true, false, false, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P1, A, PA1, &S9, Q, nullptr, nullptr, nullptr, nullptr, mabs, &PM1);
                         else if constexpr (kAux) bwd_pair<false, true>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P1, A, PA1, &S9);
                         else bwd_pair<false>(sp, lp_at(lt, b.x, dy), dx, dy, (int)j, P1, A);
                     }
@@ -1178,9 +1279,9 @@ int launch_render_bwd(const FrameK &f, int chunks_run, int sort_result, long lon
     // by BwdKind: the instantiations take the same arguments; only the aux one reads the aux block
     static const decltype(&k_render_bwd<false, false, kBwdWaves>) kernels[] = {k_render_bwd<false, false, kBwdWaves>, k_render_bwd<true, false, kBwdWaves>,
                                                                                k_render_bwd<false, true, kBwdWaves>};
-    static const char *const names[] = {"render_bwd", "render_bwd_aux", "render_bwd_abs", "render_bwd_ext"};
+    static const char *const names[] = {"render_bwd", "render_bwd_aux", "render_bwd_abs", "render_bwd_ext", "render_bwd_median"};
     const char *name = names[(int)v.kind];
-    const bool with_aux = v.kind == BwdKind::kAux || v.kind == BwdKind::kExt;
+    const bool with_aux = v.kind == BwdKind::kAux || v.kind == BwdKind::kExt || v.kind == BwdKind::kMed;
     const AuxBwdK ax = with_aux ? AuxBwdK{v.aux->depth, v.dL_ddepth, v.dL_dalpha, v.aux->ckpt, v.aux->ckpt_start} : AuxBwdK{};
     ProfileScope prof(name, s);
     if (v.kind == BwdKind::kExt) {
@@ -1188,6 +1289,14 @@ int launch_render_bwd(const FrameK &f, int chunks_run, int sort_result, long lon
         hipLaunchKernelGGL((k_render_bwd<true, false, kBwdExtWaves, ExtBwdK>), dim3((unsigned)(per_shard * kUnitShards)), dim3(kWave), 0, s, f,
                            iw.ranges, iw.tile_walk, bw.gids[1], bw.vals[sort_result], gw.records, out_color, iw.T_state, iw.last_enc, dL_dcolor,
                            bw.ckpt, iw.ckpt_start, reinterpret_cast<float4 *>(bw.grad_rows), bw.row_valid, bw.units, iw.unit_count, ax, ex);
+        GSR_LAUNCH_CHECK(name, debug, s);
+        return GSR_OK;
+    }
+    if (v.kind == BwdKind::kMed) {
+        const MedBwdK md{v.med->median_enc, v.med->dL_dmedian};
+        hipLaunchKernelGGL((k_render_bwd<true, false, kBwdWaves, MedBwdK>), dim3((unsigned)(per_shard * kUnitShards)), dim3(kWave), 0, s, f,
+                           iw.ranges, iw.tile_walk, bw.gids[1], bw.vals[sort_result], gw.records, out_color, iw.T_state, iw.last_enc, dL_dcolor,
+                           bw.ckpt, iw.ckpt_start, reinterpret_cast<float4 *>(bw.grad_rows), bw.row_valid, bw.units, iw.unit_count, ax, md);
         GSR_LAUNCH_CHECK(name, debug, s);
         return GSR_OK;
     }

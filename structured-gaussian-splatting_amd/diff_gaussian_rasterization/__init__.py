@@ -55,6 +55,18 @@ FUSE_GETTERS) alike, with debug, antialiasing and a model's 3D filter.  Refused 
 depth_alpha=True, another shape, dtype or device, absgrad, contributions, tile_rows / ShardedRenderer, and a viewmatrix / projmatrix /
 campos that requires grad.  extra_colors=None (the default): the calls made without it, the same launches, the same bits.
 
+Extension: GaussianRasterizer(raster_settings, depth_alpha=True, median_depth=True) returns (color, radii, depth, alpha, median):
+median [1,H,W] is, per pixel, the view depth z_m of the LAST composited splat whose front transmittance T_m (the blend's own float32
+T, the value that multiplies alpha_m into w_m) is above one half - the depth at which the accumulated opacity crosses one half, 2DGS's
+rule - selected inside the same blend by one more instantiation of the aux kernels.  A pixel with a composited splat
+always has one (where the opacity never reaches one half: the farthest composited splat); a pixel nothing composited gets +0.0; not
+normalised, no background term: mask by alpha.  The selection is piecewise constant: dL/dmedian of a pixel goes to the depth of that
+pixel's median splat, and through it to means3D (and to a viewmatrix that requires grad), and to nothing else.  color, radii, depth,
+alpha and their gradients are the bits of the call without the flag.  forward, forward_raw and FUSE_GETTERS alike, with debug,
+antialiasing, a model's 3D filter and camera tensors that require grad.  Refused with a ValueError: median_depth without
+depth_alpha=True, absgrad, contributions, tile_rows / ShardedRenderer and extra_colors (the ext x median kernels are not built).
+Off (the default): the calls made without it, the same launches, the same bits.
+
 Autograd contract (train.py:106, scene/gaussian_model.py:415-417): gradients for
 (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, None) in that order;
 `means2D.grad[:, :2]` is dL/d(NDC position) with the W/2, H/2 pixel scale folded in, `[:, 2] = 0`.
@@ -123,7 +135,7 @@ _binning_guess = {}        # (P, W, H, slab, device) -> instances the binning wo
 class _Frame:
     """Native handles of one forward pass, kept alive by autograd's ctx for the backward."""
     __slots__ = ("desc", "cam", "keep", "plan", "geom_ws", "binning_ws", "image_ws", "radii", "color", "gauss", "M", "device", "raw", "pre",
-                 "depth", "alpha", "aux_ws", "aux", "extra_table", "extra_map")
+                 "depth", "alpha", "aux_ws", "aux", "extra_table", "extra_map", "median", "median_enc")
 
     @property
     def R(self):
@@ -190,11 +202,13 @@ def _aux_outputs(fr: "_Frame", capacity: int):
 
 def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                       rs: GaussianRasterizationSettings, tile_rows=None, out_color=None, sh_rest=None, raw=False,
-                      prepare_needs=None, aux=False, contrib=None, pixel_error=None, pixel_error_checked=False, extra=None):
+                      prepare_needs=None, aux=False, contrib=None, pixel_error=None, pixel_error_checked=False, extra=None, median=False):
     """Stage 1 + stage 2 of the native forward.  Returns (color, radii, frame).
     aux=True: the same blend also renders frame.depth and frame.alpha ([1,H,W] each; whole images only).
     extra (with aux=True; [P,3] float32 on the inputs' device, whole images, no contrib): the same blend also renders frame.extra_map
     [3,H,W] from it (check_extra_colors' rules).
+    median (with aux=True; whole images, no contrib, no extra): the same blend also selects frame.median [1,H,W] and frame.median_enc
+    (int32 [H,W], the backward's; check_median_depth's rules).
     contrib (a contrib.ContributionStats of this P and device; whole images, no aux): the blend also adds the frame's per-Gaussian
     statistics into it.  Such a frame runs the two stages as two calls: a stage 2 that stops for want of room in a later chunk has
     already added its earlier chunks, so a frame that can stop that way (several chunks planned, a workspace for fewer than all
@@ -210,6 +224,8 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
     backward's output tensors are then allocated up front, while the host waits for the plan anyway."""
     if extra is not None:
         check_extra_colors(extra, means3D, aux, tile_rows=tile_rows, contributions=contrib, rs=rs)
+    if median:
+        check_median_depth(aux, tile_rows=tile_rows, contributions=contrib, extra_colors=extra)
     if aux and tile_rows is not None:
         raise ValueError("depth / alpha maps are rendered for whole images only: no tile_rows (sharded slabs) with aux=True")
     if contrib is not None and (aux or tile_rows is not None):
@@ -254,7 +270,11 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
     fr.keep = (cam_keep, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, sh_rest)
     fr.raw = raw
     fr.pre = None
-    fr.depth = fr.alpha = fr.aux_ws = fr.aux = fr.extra_table = fr.extra_map = None
+    fr.depth = fr.alpha = fr.aux_ws = fr.aux = fr.extra_table = fr.extra_map = fr.median = fr.median_enc = None
+    if median:             # every pixel is written by the first chunk's blend
+        fr.median = torch.empty(1, H, W, dtype=torch.float32, device=device)
+        fr.median_enc = torch.empty(H, W, dtype=torch.int32, device=device)
+    med = (fr.median, fr.median_enc) if median else None
     if extra is not None:  # the kernels gather 16-byte rows (e0, e1, e2, unused)
         fr.extra_table = torch.nn.functional.pad(extra.detach().contiguous(), (0, 1))
         fr.extra_map = torch.empty(3, H, W, dtype=torch.float32, device=device)
@@ -289,7 +309,7 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
             plan, done = N.forward_both(fr.desc, fr.cam, fr.gauss, fr.geom_ws, fr.image_ws, fr.radii, binning, guess, color, device,
                                         early_fill=early[2] if early is not None else None,
                                         aux=_aux_outputs(fr, guess) if aux else None,
-                                        extra=None if extra is None else (fr.extra_table, fr.extra_map))
+                                        extra=None if extra is None else (fr.extra_table, fr.extra_map), median=med)
         else:
             plan = N.forward_preprocess(fr.desc, fr.cam, fr.gauss, fr.geom_ws, fr.radii, device, image_ws=fr.image_ws)
         fr.plan = plan
@@ -323,7 +343,7 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
             try:
                 N.forward_render(fr.desc, fr.cam, fr.gauss, fr.geom_ws, binning, fr.image_ws, plan, color, device,
                                  aux=_aux_outputs(fr, capacity) if aux else None,
-                                 extra=None if extra is None else (fr.extra_table, fr.extra_map),
+                                 extra=None if extra is None else (fr.extra_table, fr.extra_map), median=med,
                                  contrib=contrib.native() if contrib is not None else None,
                                  err=contrib.native_error(pixel_error) if pixel_error is not None else None)
                 if pixel_error is not None:
@@ -348,12 +368,14 @@ def rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations,
 
 
 def rasterize_backward_screen(fr: "_Frame", grad_color: torch.Tensor, only_for_own_geom: bool = False, grad_depth=None,
-                              grad_alpha=None, absgrad: bool = False, grad_extra=None, extra_out=None) -> torch.Tensor:
+                              grad_alpha=None, absgrad: bool = False, grad_extra=None, extra_out=None, grad_median=None) -> torch.Tensor:
     """K7 + deterministic per-Gaussian reduction -> screen-space gradients [P, 12].
     grad_depth / grad_alpha ([1,H,W] or [H,W], an aux frame only; None = zero): when either is given the aux backward runs and slot 9
     holds dL/dz; otherwise the colour-only kernels (the plain frame's bits).
     grad_extra ([3,H,W], an extra frame only; None = zero) / extra_out ([P,3], required for an extra frame): an extra frame always
     runs the ext backward - slot 9 as the aux backward leaves it - which also writes the extra table's gradient into extra_out.
+    grad_median ([1,H,W] or [H,W], a median frame only; None = zero): when given the median backward runs - the aux backward whose
+    slot 9 also gains the median's share of dL/dz; without it a median frame takes the aux frame's calls.
     absgrad: the abs instantiation of the colour-only kernels - slots 10, 11 also hold the per-pixel absolute sums of d/dmean2D
     (rasterize_screen_absgrad extracts them); whole images, no aux gradients.
     only_for_own_geom: the tensor goes straight into this frame's geometry backward and nowhere else (the autograd path): rows it
@@ -368,6 +390,8 @@ def rasterize_backward_screen(fr: "_Frame", grad_color: torch.Tensor, only_for_o
     if with_ext and extra_out is None:
         raise ValueError("rasterize_backward_screen: an extra frame's backward needs extra_out [P,3]")
     with_aux = with_aux or (with_ext and grad_extra is not None)
+    grad_median = _f32c(grad_median, fr.device) if fr.median_enc is not None else None
+    with_aux = with_aux or grad_median is not None
     if absgrad and (fr.aux is not None or fr.desc.tile_row_end > 0 or fr.desc.tile_row_begin != 0):
         raise ValueError("absgrad: the abs blend backward is built for whole colour-only frames: no depth / alpha maps, no tile_rows")
     screen = fr.pre.pop("screen", None) if fr.pre is not None else None        # allocated (and, on sparse frames, zero-filled) by the forward
@@ -386,6 +410,9 @@ def rasterize_backward_screen(fr: "_Frame", grad_color: torch.Tensor, only_for_o
             ext_rows = _workspace(N.extra_rows_size(fr.desc, fr.plan), fr.device)
             N.backward_render_extra(fr.desc, fr.cam, fr.geom_ws, fr.binning_ws, fr.image_ws, rows, fr.plan, fr.color, fr.aux, fr.extra_table,
                                     fr.extra_map, grad_color, grad_depth, grad_alpha, grad_extra, screen, ext_rows, extra_out, fr.device)
+        elif grad_median is not None:
+            N.backward_render_median(fr.desc, fr.cam, fr.geom_ws, fr.binning_ws, fr.image_ws, rows, fr.plan, fr.color, fr.aux, grad_color,
+                                     grad_depth, grad_alpha, fr.median_enc, grad_median, screen, fr.device)
         elif with_aux:
             N.backward_render_aux(fr.desc, fr.cam, fr.geom_ws, fr.binning_ws, fr.image_ws, rows, fr.plan, fr.color, fr.aux, grad_color,
                                   grad_depth, grad_alpha, screen, fr.device)
@@ -545,14 +572,16 @@ def _stash_frame(ctx, frame):
     keep = [t for t in frame.keep[1:] if t is not None]
     aux = (frame.depth, frame.aux_ws) if frame.aux is not None else ()          # an aux frame: its depth map and checkpoints, last
     ext = (frame.extra_table, frame.extra_map) if frame.extra_table is not None else ()      # an extra frame: its table and map, in front
-    ctx.save_for_backward(*(getattr(frame, n) for n in _FRAME_TENSORS), *frame.keep[0], *keep, *ext, *aux)
+    med = (frame.median_enc,) if frame.median_enc is not None else ()           # a median frame: which entry each pixel's median is
+    ctx.save_for_backward(*(getattr(frame, n) for n in _FRAME_TENSORS), *frame.keep[0], *keep, *ext, *med, *aux)
     ctx.frame_keep_mask = tuple(t is not None for t in frame.keep[1:])
     ctx.frame_aux = bool(aux)
     ctx.frame_ext = bool(ext)
+    ctx.frame_med = bool(med)
     for n in _FRAME_TENSORS:
         setattr(frame, n, None)
     frame.keep = None
-    frame.depth = frame.alpha = frame.aux_ws = frame.extra_table = frame.extra_map = None
+    frame.depth = frame.alpha = frame.aux_ws = frame.extra_table = frame.extra_map = frame.median = frame.median_enc = None
     ctx.frame = frame
 
 
@@ -565,6 +594,8 @@ def _unstash_frame(ctx):
     fr.keep = (tuple(saved[5:9]),) + tuple(next(it) if m else None for m in ctx.frame_keep_mask)
     if ctx.frame_ext:
         fr.extra_table, fr.extra_map = next(it), next(it)
+    if ctx.frame_med:
+        fr.median_enc = next(it)
     if ctx.frame_aux:
         fr.depth, fr.aux_ws = saved[-2], saved[-1]
         fr.aux = N.AuxOutputs(N._ptr(fr.depth), None, N._ptr(fr.aux_ws))      # (the backward does not read alpha)
@@ -575,13 +606,14 @@ def _restash_frame(fr):
     for n in _FRAME_TENSORS:
         setattr(fr, n, None)
     fr.keep = None
-    fr.depth = fr.aux_ws = fr.extra_table = fr.extra_map = None
+    fr.depth = fr.aux_ws = fr.extra_table = fr.extra_map = fr.median_enc = None
     fr.plan.screen_prezeroed = 0
 
 
 def _finish_forward(ctx, frame, color, radii, aux, means2D, opacities):
     """The tail of both Functions' forward(): the frame into autograd's slots, what backward() needs on ctx, the return tuple."""
     maps = (frame.depth, frame.alpha) + ((frame.extra_map,) if frame.extra_map is not None else ())
+    maps += (frame.median,) if frame.median is not None else ()
     _stash_frame(ctx, frame)
     ctx.absgrad_to = getattr(_tls, "absgrad_to", None)
     ctx.shapes = (means2D.shape, opacities.shape)
@@ -590,18 +622,21 @@ def _finish_forward(ctx, frame, color, radii, aux, means2D, opacities):
     return (color, radii) + (maps if aux else ())
 
 
-def _backward_core(ctx, fr, needs, grad_out_color, grad_depth, grad_alpha, grad_extra=None):
+def _backward_core(ctx, fr, needs, grad_out_color, grad_depth, grad_alpha, grad_fifth=None):
     """The core of both Functions' backward(): (rasterize_backward_geom's gradients for `needs`, means2D's and the opacities' in
     their inputs' shapes; the camera gradients - for an extra frame (no camera gradients) the tail of the inputs' gradients instead:
-    three Nones and the extra colours').  The frame goes back to its stashed state."""
+    three Nones and the extra colours').  grad_fifth: the gradient of the call's fifth output - the extra map's, or a median frame's
+    median map's.  The frame goes back to its stashed state."""
+    grad_median = grad_fifth if fr.median_enc is not None else None
+    grad_extra = grad_fifth if fr.extra_table is not None else None
     # no depth / alpha gradient: the colour-only kernels, bit for bit the plain frame's gradients
-    with_aux = grad_depth is not None or grad_alpha is not None
+    with_aux = grad_depth is not None or grad_alpha is not None or grad_median is not None
     g_extra = None
     if fr.extra_table is not None:            # an extra frame: the ext backward, which leaves slot 9 as the aux backward does
         with_aux = True
         g_extra = torch.empty(fr.desc.P, 3, dtype=torch.float32, device=fr.device)
     screen = rasterize_backward_screen(fr, grad_out_color, only_for_own_geom=True, grad_depth=grad_depth, grad_alpha=grad_alpha,
-                                       absgrad=ctx.absgrad_to is not None, grad_extra=grad_extra, extra_out=g_extra)
+                                       absgrad=ctx.absgrad_to is not None, grad_extra=grad_extra, extra_out=g_extra, grad_median=grad_median)
     g = list(rasterize_backward_geom(fr, screen, needs, depth_chain=with_aux))
     g_cam = _camera_backward(ctx, fr, screen, with_aux)
     if g_extra is not None:
@@ -628,27 +663,28 @@ class _RasterizeGaussians(torch.autograd.Function):
         if rs.debug:
             cpu_args = tuple(a.detach().cpu().clone() for a in args)      # README.md:147-150 semantics
             try:
-                color, radii, frame = rasterize_forward(*args, rs, aux=aux, extra=extra_colors)
+                color, radii, frame = rasterize_forward(*args, rs, aux=bool(aux), extra=extra_colors, median=aux == _AUX_MEDIAN)
                 torch.cuda.synchronize(means3D.device)
             except Exception:
                 _dump("snapshot_fw.dump", (cpu_args, tuple(rs)))
                 print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
                 raise
         else:
-            color, radii, frame = rasterize_forward(*args, rs, prepare_needs=tuple(ctx.needs_input_grad[:8]), aux=aux, extra=extra_colors)
+            color, radii, frame = rasterize_forward(*args, rs, prepare_needs=tuple(ctx.needs_input_grad[:8]), aux=bool(aux), extra=extra_colors,
+                                                    median=aux == _AUX_MEDIAN)
             prepare_backward(frame, tuple(ctx.needs_input_grad[:8]), screen_prefix_only=True)
         ctx.raster_settings = rs
         return _finish_forward(ctx, frame, color, radii, aux, means2D, opacities)
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None, grad_extra=None):
+    def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None, grad_fifth=None):
         fr, rs = _unstash_frame(ctx), ctx.raster_settings
         # input order: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp
         needs = tuple(ctx.needs_input_grad[:8])
         if rs.debug:
             kept = fr.keep[1:]                 # (the frame lets go of them once its gradients are enqueued)
             try:
-                g, g_cam = _backward_core(ctx, fr, needs, grad_out_color, grad_depth, grad_alpha, grad_extra)
+                g, g_cam = _backward_core(ctx, fr, needs, grad_out_color, grad_depth, grad_alpha, grad_fifth)
                 torch.cuda.synchronize(fr.device)
             except Exception:
                 _dump("snapshot_bw.dump", (tuple(None if k is None else k.detach().cpu() for k in kept),
@@ -656,7 +692,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
                 raise
         else:
-            g, g_cam = _backward_core(ctx, fr, needs, grad_out_color, grad_depth, grad_alpha, grad_extra)
+            g, g_cam = _backward_core(ctx, fr, needs, grad_out_color, grad_depth, grad_alpha, grad_fifth)
         return (*g, None, None) + g_cam
 
 
@@ -676,19 +712,39 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         # features_rest None: features_dc is the whole interleaved table [P,M,3] (scene.GaussianModel's packed leaf)
         color, radii, frame = rasterize_forward(xyz, features_dc, None, opacity_logits, log_scales, raw_rotations, None, rs,
                                                 sh_rest=features_rest, raw=2 if features_rest is None else 1,
-                                                prepare_needs=None if rs.debug else needs, aux=aux, extra=extra_colors)
+                                                prepare_needs=None if rs.debug else needs, aux=bool(aux), extra=extra_colors,
+                                                median=aux == _AUX_MEDIAN)
         if rs.debug:
             torch.cuda.synchronize(xyz.device)
         prepare_backward(frame, needs, screen_prefix_only=True)
         return _finish_forward(ctx, frame, color, radii, aux, means2D, opacity_logits)
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None, grad_extra=None):
+    def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None, grad_fifth=None):
         n = ctx.needs_input_grad       # xyz, means2D, f_dc, f_rest, opacity, scales, rotations
         needs = (n[0], n[1], n[2], False, n[4], n[5], n[6], False, n[3])
-        g, g_cam = _backward_core(ctx, _unstash_frame(ctx), needs, grad_out_color, grad_depth, grad_alpha, grad_extra)
+        g, g_cam = _backward_core(ctx, _unstash_frame(ctx), needs, grad_out_color, grad_depth, grad_alpha, grad_fifth)
         g_xyz, g_means2D, g_dc, _, g_op, g_sc, g_rot, _, g_rest = g
         return (g_xyz, g_means2D, g_dc, g_rest, g_op, g_sc, g_rot, None, None) + g_cam
+
+
+_AUX_MEDIAN = 2            # the autograd functions' `aux` argument of a median frame (False / True: none / the depth and alpha maps)
+
+
+def check_median_depth(depth_alpha, absgrad=False, contributions=None, tile_rows=None, extra_colors=None):
+    """The rules of `median_depth` (module docstring), checked before anything runs: a ValueError with the reason."""
+    who = "median_depth"
+    if absgrad:
+        raise ValueError(f"{who}: not with absgrad=True (the abs blend backward carries no depth gradients)")
+    if contributions is not None:
+        raise ValueError(f"{who}: not with contributions (a statistics frame is the plain colour forward)")
+    if not depth_alpha:
+        raise ValueError(f"{who}: the median rides on the depth / alpha blend kernels: construct the rasterizer with depth_alpha=True")
+    if tile_rows is not None:
+        raise ValueError(f"{who}: whole images only: no tile_rows (sharded slabs / ShardedRenderer)")
+    if extra_colors is not None:
+        raise ValueError(f"{who}: not with extra_colors (the ext x median blend kernels are not built): render the median in a frame "
+                         "of its own")
 
 
 def check_extra_colors(extra_colors, means3D, depth_alpha, absgrad=False, contributions=None, tile_rows=None, rs=None):
@@ -721,7 +777,9 @@ def _extra_args(extra_colors):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, depth_alpha=False, absgrad=False, extra_colors=None):
+                        raster_settings, depth_alpha=False, absgrad=False, extra_colors=None, median_depth=False):
+    if median_depth:
+        check_median_depth(depth_alpha, absgrad, extra_colors=extra_colors)
     if absgrad and depth_alpha:
         raise ValueError(_ABSGRAD_NO_AUX)
     if extra_colors is not None:
@@ -729,7 +787,7 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
         return _apply(_RasterizeGaussians, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                       cov3Ds_precomp, raster_settings, True, *_extra_args(extra_colors))
     return _apply(_RasterizeGaussians, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                  cov3Ds_precomp, raster_settings, bool(depth_alpha), *_camera_args(raster_settings),
+                  cov3Ds_precomp, raster_settings, _AUX_MEDIAN if median_depth else bool(depth_alpha), *_camera_args(raster_settings),
                   absgrad_to=means2D if absgrad else None)
 
 
@@ -817,8 +875,10 @@ def _match_getters(means3D, opacities, shs, scales, rotations):
 
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings: GaussianRasterizationSettings, depth_alpha: bool = False, antialiasing: bool = False,
-                 absgrad: bool = False, contributions=None, pixel_error=None):
-        """contributions (a contrib.ContributionStats, extension): every frame is also added into it (module docstring); the frame has
+                 absgrad: bool = False, contributions=None, pixel_error=None, median_depth: bool = False):
+        """median_depth=True (extension; with depth_alpha=True): forward / forward_raw also return the median depth map [1,H,W] as a fifth
+        output (module docstring); not with absgrad, contributions, tile_rows or extra_colors.
+        contributions (a contrib.ContributionStats, extension): every frame is also added into it (module docstring); the frame has
         no backward; not with depth_alpha or absgrad.
         pixel_error (float32 [H,W] or [1,H,W], extension; with a contrib.ErrorStats as contributions): every frame also adds its
         error-weighted totals and folds them into the running sum and maximum (module docstring).
@@ -830,6 +890,9 @@ class GaussianRasterizer(nn.Module):
         self.depth_alpha = bool(depth_alpha)
         self.antialiasing = bool(antialiasing)
         self.absgrad = bool(absgrad)
+        self.median_depth = bool(median_depth)
+        if self.median_depth:
+            check_median_depth(self.depth_alpha, self.absgrad, contributions)
         if self.absgrad and self.depth_alpha:
             raise ValueError(_ABSGRAD_NO_AUX)
         self.contributions = contributions
@@ -860,6 +923,10 @@ class GaussianRasterizer(nn.Module):
                 torch.cuda.synchronize(radii.device)
         return color, radii
 
+    def _aux_arg(self):
+        """The autograd functions' `aux` argument of this rasterizer's frames."""
+        return _AUX_MEDIAN if self.median_depth else self.depth_alpha
+
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         """Frustum test per point (the reference's `_C.mark_visible`; unused in-tree, kept for API parity)."""
         rs = self.raster_settings
@@ -877,6 +944,8 @@ class GaussianRasterizer(nn.Module):
         """extra_colors (extension; [P,3] float32, with depth_alpha=True): three more channels blended in this frame; the call then
         returns (color, radii, depth, alpha, extra [3,H,W]) (module docstring)."""
         rs = self.raster_settings
+        if self.median_depth:                    # (before anything runs: a refused call has launched nothing)
+            check_median_depth(self.depth_alpha, self.absgrad, self.contributions, extra_colors=extra_colors)
         if extra_colors is not None:             # (before anything runs: a refused call has launched nothing)
             check_extra_colors(extra_colors, means3D, self.depth_alpha, self.absgrad, self.contributions, rs=rs)
         if self.contributions is not None:       # (before anything runs: a refused call has launched nothing)
@@ -912,10 +981,10 @@ class GaussianRasterizer(nn.Module):
                 xyz, dc, rest, op, sc, rot = leaves
                 if extra_colors is not None:
                     return _apply(_RasterizeGaussiansRaw, xyz, means2D, dc, rest, op, sc, rot, rs, True, *_extra_args(extra_colors))
-                return _apply(_RasterizeGaussiansRaw, xyz, means2D, dc, rest, op, sc, rot, rs, self.depth_alpha, *_camera_args(rs),
+                return _apply(_RasterizeGaussiansRaw, xyz, means2D, dc, rest, op, sc, rot, rs, self._aux_arg(), *_camera_args(rs),
                               absgrad_to=means2D if self.absgrad else None)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, rs, self.depth_alpha, self.absgrad, extra_colors)
+                                   cov3D_precomp, rs, self.depth_alpha, self.absgrad, extra_colors, self.median_depth)
 
     def forward_raw(self, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations, extra_colors=None):
         """Extension (not in the reference API): render straight from the reference GaussianModel's raw parameters
@@ -924,6 +993,8 @@ class GaussianRasterizer(nn.Module):
         same gradients on the raw parameters as autograd through those getters, to fp32 rounding."""
         rs = self.raster_settings
         rs = rs._replace(sh_degree=int(rs.sh_degree), image_height=int(rs.image_height), image_width=int(rs.image_width))
+        if self.median_depth:
+            check_median_depth(self.depth_alpha, self.absgrad, self.contributions, extra_colors=extra_colors)
         if extra_colors is not None:             # (as forward: the same rules, the same fifth output)
             check_extra_colors(extra_colors, xyz, self.depth_alpha, self.absgrad, self.contributions, rs=rs)
         if self.contributions is not None:
@@ -944,4 +1015,4 @@ class GaussianRasterizer(nn.Module):
             return _apply(_RasterizeGaussiansRaw, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations, rs,
                           True, *_extra_args(extra_colors))
         return _apply(_RasterizeGaussiansRaw, xyz, means2D, features_dc, features_rest, opacity_logits, log_scales, raw_rotations, rs,
-                      self.depth_alpha, *_camera_args(rs), absgrad_to=means2D if self.absgrad else None)
+                      self._aux_arg(), *_camera_args(rs), absgrad_to=means2D if self.absgrad else None)

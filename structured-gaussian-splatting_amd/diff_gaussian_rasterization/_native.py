@@ -264,6 +264,13 @@ EXTRA_SIGNATURES = {
     "gsr_forward_extra": (_int, _forward + (_aux, _dev, _dev, _dev)),
     "gsr_backward_render_extra": (_int, _backward_render + (_aux,) + (_dev,) * 10),
 }
+# The median-depth entry points, declared in include/gsrast_median.h (which gsrast.h includes): a table of their own, held to that
+# header's prototypes by tests/test_median_abi.py.  The aux frame's gsr_aux_outputs and plain pointers.
+MEDIAN_SIGNATURES = {
+    "gsr_forward_render_median": (_int, _forward_render + (_aux, _dev, _dev, _dev)),
+    "gsr_forward_median": (_int, _forward + (_aux, _dev, _dev, _dev)),
+    "gsr_backward_render_median": (_int, _backward_render + (_aux,) + (_dev,) * 7),
+}
 # TSDF fusion and mesh extraction, declared in include/gsrast_tsdf.h (which gsrast.h includes): held to that header's prototypes by
 # tests/test_tsdf_ref.py.  No struct of their own; the two totals of gsr_tsdf_mesh_count are host out-parameters.
 _dims = (_i32, _i32, _i32)                                                                 # nx, ny, nz
@@ -281,7 +288,7 @@ MESH_SIGNATURES = {
     "gsr_mesh_clean_count": (_int, (_i32, _i32) + (_dev,) * 5 + (_size, _P(_i64), _P(_i64), _dev)),
     "gsr_mesh_clean_emit": (_int, (_i32, _i32, _dev, _dev, _size, _i64, _i64) + (_dev,) * 4),
 }
-_ALL_SIGNATURES = {**SIGNATURES, **NORMALS_SIGNATURES, **EXTRA_SIGNATURES, **TSDF_SIGNATURES, **MESH_SIGNATURES}
+_ALL_SIGNATURES = {**SIGNATURES, **NORMALS_SIGNATURES, **EXTRA_SIGNATURES, **MEDIAN_SIGNATURES, **TSDF_SIGNATURES, **MESH_SIGNATURES}
 
 _lib = None
 
@@ -397,9 +404,14 @@ def forward_preprocess(desc, cam: Camera, g: Gaussians, geom_ws, radii, device, 
     return plan
 
 
-def _variant(who: str, aux, contrib, err, extra=None):
-    """(i, more) of a frame's variant: i picks among a wrapper's (plain, _aux, _contrib, _contrib_error, _extra) entry points, `more` are
-    the arguments that one takes in front of the stream.  extra: (table [P,4], map [3,H,W]) of an extra frame, which is an aux frame."""
+def _variant(who: str, aux, contrib, err, extra=None, median=None):
+    """(i, more) of a frame's variant: i picks among a wrapper's (plain, _aux, _contrib, _contrib_error, _extra, _median) entry points,
+    `more` are the arguments that one takes in front of the stream.  extra: (table [P,4], map [3,H,W]) of an extra frame, which is an
+    aux frame.  median: (median [H,W] float32, median_enc [H,W] int32) of a median frame, which is an aux frame without extra."""
+    if median is not None:
+        if aux is None or contrib is not None or err is not None or extra is not None:
+            raise ValueError(f"{who}: the median depth rides on the aux frame (aux required, no extra / contrib / err)")
+        return 5, (aux, _ptr(median[0]), _ptr(median[1]))
     if extra is not None:
         if aux is None or contrib is not None or err is not None:
             raise ValueError(f"{who}: extra channels ride on the aux frame (aux required, no contrib / err)")
@@ -415,16 +427,17 @@ def _variant(who: str, aux, contrib, err, extra=None):
 
 def forward_both(desc, cam: Camera, g: Gaussians, geom_ws, image_ws, radii, binning_ws, binning_capacity, out_color, device,
                  early_fill: Optional[Grads] = None, aux: Optional[AuxOutputs] = None, contrib: Optional[ContribStats] = None,
-                 err: Optional[ContribError] = None, extra=None):
-    """gsr_forward (gsr_forward_extra with `aux` and `extra`; gsr_forward_aux with `aux`, gsr_forward_contrib with `contrib`; not both; gsr_forward_contrib_error with `contrib`
+                 err: Optional[ContribError] = None, extra=None, median=None):
+    """gsr_forward (gsr_forward_median with `aux` and `median`; gsr_forward_extra with `aux` and `extra`; gsr_forward_aux with `aux`, gsr_forward_contrib with `contrib`; not both; gsr_forward_contrib_error with `contrib`
     and `err`): both stages in one call.  Returns
     (plan, done): done = False when the binning workspace was too small for the first chunk (nothing of stage 2 ran: allocate and
     call forward_render) - or, when the plan has more than one chunk, for a later one: a statistics frame has then already added
     its earlier chunks (include/gsrast.h), so its caller sizes the workspace for num_rendered."""
     plan = FramePlan()
     lib = load()                      # the plain functions: GSR_ERR_WORKSPACE is an answer here, not an error
-    i, more = _variant("forward_both", aux, contrib, err, extra)
-    fn = (lib.gsr_forward, lib.gsr_forward_aux, lib.gsr_forward_contrib, lib.gsr_forward_contrib_error, lib.gsr_forward_extra)[i]
+    i, more = _variant("forward_both", aux, contrib, err, extra, median)
+    fn = (lib.gsr_forward, lib.gsr_forward_aux, lib.gsr_forward_contrib, lib.gsr_forward_contrib_error, lib.gsr_forward_extra,
+          lib.gsr_forward_median)[i]
     rc = fn(desc, cam, g, _ptr(geom_ws), _ptr(image_ws), _ptr(radii), plan, _ptr(binning_ws), int(binning_capacity), _ptr(out_color),
             early_fill, *more, _stream(device))
     if rc == ERR_WORKSPACE:           # the guessed workspace did not do (for the first chunk, or for a later one)
@@ -435,10 +448,10 @@ def forward_both(desc, cam: Camera, g: Gaussians, geom_ws, image_ws, radii, binn
 
 def forward_render(desc, cam: Camera, g: Gaussians, geom_ws, binning_ws, image_ws, plan: FramePlan, out_color, device,
                    aux: Optional[AuxOutputs] = None, contrib: Optional[ContribStats] = None, err: Optional[ContribError] = None,
-                   extra=None):
-    i, more = _variant("forward_render", aux, contrib, err, extra)
+                   extra=None, median=None):
+    i, more = _variant("forward_render", aux, contrib, err, extra, median)
     fn = (_gsr.gsr_forward_render, _gsr.gsr_forward_render_aux, _gsr.gsr_forward_render_contrib, _gsr.gsr_forward_render_contrib_error,
-          _gsr.gsr_forward_render_extra)[i]
+          _gsr.gsr_forward_render_extra, _gsr.gsr_forward_render_median)[i]
     fn(desc, cam, g, _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws), plan, _ptr(out_color), *more, _stream(device))
 
 
@@ -469,6 +482,15 @@ def backward_render_extra(desc, cam: Camera, geom_ws, binning_ws, image_ws, rows
     _gsr.gsr_backward_render_extra(desc, cam, _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws), _ptr(rows_ws), plan, _ptr(out_color), aux,
                                    _ptr(extra), _ptr(extra_map), _ptr(dL_dcolor), _ptr(dL_ddepth), _ptr(dL_dalpha), _ptr(dL_dextra_map),
                                    _ptr(screen_grads), _ptr(extra_rows_ws), _ptr(dL_dextra), _stream(device))
+
+
+def backward_render_median(desc, cam: Camera, geom_ws, binning_ws, image_ws, rows_ws, plan: FramePlan, out_color, aux: AuxOutputs,
+                           dL_dcolor, dL_ddepth, dL_dalpha, median_enc, dL_dmedian, screen_grads, device):
+    """gsr_backward_render_median: any of the four upstream gradients may be None (zero); screen_grads slot 9 receives dL/dz, the
+    median map's share at each pixel's median splat included."""
+    _gsr.gsr_backward_render_median(desc, cam, _ptr(geom_ws), _ptr(binning_ws), _ptr(image_ws), _ptr(rows_ws), plan, _ptr(out_color), aux,
+                                    _ptr(dL_dcolor), _ptr(dL_ddepth), _ptr(dL_dalpha), _ptr(median_enc), _ptr(dL_dmedian),
+                                    _ptr(screen_grads), _stream(device))
 
 
 def backward_rows_size(desc: FrameDesc, plan: FramePlan) -> int:

@@ -241,3 +241,20 @@ def normal_consistency_loss(normal_map, depth, alpha, tanfovx, tanfovy, alpha_mi
     if _use_native(native, depth, "normal_consistency_loss"):
         return _NormalConsistency.apply(normal_map, depth, alpha, float(tanfovx), float(tanfovy), float(alpha_min))
     return normal_consistency_loss_torch(normal_map, depth, alpha, tanfovx, tanfovy, alpha_min)
+
+
+def surface_depth(depth, alpha, median, depth_ratio):
+    """2DGS's depth_ratio mix as a depth map of the kind `depth` is: (1 - r) depth + r alpha median, UNNORMALISED (depth = sum w z, median
+    = the rasterizer's median_depth map, a plain depth), so that depth_to_normal, normal_consistency_loss and TSDFVolume.integrate take
+    it beside the same alpha unchanged: their z = D / alpha is (1 - r) mean + r median.  Plain torch ops, differentiable in all three
+    maps.  r = 0 returns `depth` itself; r outside [0, 1] is a ValueError.  2DGS uses r = 1 for bounded scenes, 0 for unbounded ones."""
+    r = float(depth_ratio)
+    if not 0.0 <= r <= 1.0:
+        raise ValueError(f"surface_depth: depth_ratio {r} outside [0, 1]")
+    if r == 0.0:
+        return depth
+    if depth.shape != alpha.shape or depth.shape != median.shape:
+        raise ValueError(f"surface_depth: depth {tuple(depth.shape)}, alpha {tuple(alpha.shape)}, median {tuple(median.shape)}: one shape expected")
+    if r == 1.0:
+        return alpha * median
+    return (1.0 - r) * depth + r * (alpha * median)

@@ -483,10 +483,13 @@ class ShardedRenderer:
         raise ValueError(_NO_MESH)
 
     def render(self, viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, contributions=None,
-               extra_colors=None):
+               extra_colors=None, median_depth=False):
         import math
         if contributions is not None:
             raise ValueError(_NO_CONTRIBUTIONS)
+        if median_depth:
+            raise ValueError("median_depth is not supported by ShardedRenderer: the median rides on the depth / alpha blend, which runs "
+                             "on whole images only (render unsharded)")
         if extra_colors is not None:
             raise ValueError("extra_colors is not supported by ShardedRenderer: the extra channels ride on the depth / alpha blend, "
                              "which runs on whole images only (render unsharded)")

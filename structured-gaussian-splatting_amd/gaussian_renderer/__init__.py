@@ -39,6 +39,12 @@ neither gains nor loses anything by it.
 the colour's own weights (diff_gaussian_rasterization, "extra_colors"): the dict also holds "extra" [3,H,W], differentiable, on both
 paths.  render_with_normals() is the one-frame form of render() + render_normals(): the colour frame carries the Gaussians' view-space
 normals as its extra colours, so the four maps of the normal-consistency term come from one frame instead of two.
+
+`median_depth=True` (extension; with depth_alpha=True): the dict also holds "median_depth" [1,H,W], per pixel the depth of the splat at
+which the accumulated opacity crosses one half (diff_gaussian_rasterization, "median_depth"), differentiable in that splat's depth, on
+both paths.  render_normals(depth_ratio=r) mixes it into the depth the normals are taken from (normals.surface_depth; 2DGS uses r = 1
+for bounded scenes, 0 - the default, the expected depth alone - for unbounded ones); not with extra_colors, so render_with_normals()
+refuses a non-zero depth_ratio.
 """
 import math
 
@@ -77,13 +83,19 @@ _ZERO_POINTS = {}
 _ZERO_BG = {}
 
 
-def render_normals(viewpoint_camera, pc, pipe, scaling_modifier=1.0):
+def render_normals(viewpoint_camera, pc, pipe, scaling_modifier=1.0, depth_ratio=0.0):
     """The maps of the normal-consistency term (extension; diff_gaussian_rasterization.normals), one frame: the Gaussians' view-space
     normals (the shortest axis, turned to the camera) rendered as precomputed colours over a zero background with depth_alpha=True.
     -> {"normal" [3,H,W] (alpha-weighted, not normalised), "depth", "alpha" [1,H,W], "depth_normal" [3,H,W] (depth_to_normal of the two),
     "viewspace_points", "radii", "visibility_filter"}.  The model's getters are used; a model with a 3D filter renders its filtered
-    scales, as render() does, and the same scales choose the axis.  pipe.absgrad raises (depth_alpha=True refuses it)."""
-    from diff_gaussian_rasterization.normals import depth_to_normal, gaussian_normals
+    scales, as render() does, and the same scales choose the axis.  pipe.absgrad raises (depth_alpha=True refuses it).
+    depth_ratio (2DGS's; in [0, 1]; 0: the calls made without it): above 0 the frame also renders the median depth, "depth_normal" is
+    taken from surface_depth(depth, alpha, median, depth_ratio) - whose z = D / alpha is (1 - r) mean + r median - and the dict also
+    holds "median_depth" and "surf_depth" [1,H,W]."""
+    from diff_gaussian_rasterization.normals import depth_to_normal, gaussian_normals, surface_depth
+    depth_ratio = float(depth_ratio)
+    if not 0.0 <= depth_ratio <= 1.0:
+        raise ValueError(f"render_normals: depth_ratio {depth_ratio} outside [0, 1]")
     if getattr(pipe, "absgrad", False):
         raise ValueError("render_normals: the frame is rendered with depth_alpha=True, which pipe.absgrad is not supported with (the abs "
                          "blend backward does not carry the depth and alpha gradients): turn pipe.absgrad off for this frame")
@@ -95,21 +107,34 @@ def render_normals(viewpoint_camera, pc, pipe, scaling_modifier=1.0):
     bg = _ZERO_BG.get(key)
     if bg is None:
         bg = _ZERO_BG[key] = torch.zeros(3, dtype=torch.float32, device=xyz.device)
+    if depth_ratio > 0.0:
+        pkg = render(viewpoint_camera, pc, pipe, bg, scaling_modifier, override_color=normals, depth_alpha=True, median_depth=True)
+        surf = surface_depth(pkg["depth"], pkg["alpha"], pkg["median_depth"], depth_ratio)
+        depth_normal = depth_to_normal(surf, pkg["alpha"], math.tan(viewpoint_camera.FoVx * 0.5), math.tan(viewpoint_camera.FoVy * 0.5))
+        return {"normal": pkg["render"], "depth": pkg["depth"], "alpha": pkg["alpha"], "depth_normal": depth_normal,
+                "median_depth": pkg["median_depth"], "surf_depth": surf,
+                "viewspace_points": pkg["viewspace_points"], "radii": pkg["radii"], "visibility_filter": pkg["visibility_filter"]}
     pkg = render(viewpoint_camera, pc, pipe, bg, scaling_modifier, override_color=normals, depth_alpha=True)
     depth_normal = depth_to_normal(pkg["depth"], pkg["alpha"], math.tan(viewpoint_camera.FoVx * 0.5), math.tan(viewpoint_camera.FoVy * 0.5))
     return {"normal": pkg["render"], "depth": pkg["depth"], "alpha": pkg["alpha"], "depth_normal": depth_normal,
             "viewspace_points": pkg["viewspace_points"], "radii": pkg["radii"], "visibility_filter": pkg["visibility_filter"]}
 
 
-def render_with_normals(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0):
+def render_with_normals(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, depth_ratio=0.0):
     """render() and the maps of render_normals() from ONE frame (extension): the colour frame, on whichever of the raw and getter
     paths render() would take, with depth_alpha=True and the Gaussians' view-space normals as its extra colours.  The normals are
     computed from the very scales and rotations that frame is rendered from (raw log-scales and quaternions on the raw path:
     gaussian_normals takes either), a model's 3D filter included.
     -> render()'s dict (with "depth", "alpha" and "extra") plus "normal" [3,H,W] (= "extra": alpha-weighted, not normalised) and
     "depth_normal" [3,H,W] (depth_to_normal of the depth and alpha maps).  "render" is render()'s, bit for bit; on the getter path
-    "normal", "depth" and "alpha" are render_normals()'s, bit for bit.  pipe.absgrad and pipe.compute_cov3D_python raise ValueError."""
+    "normal", "depth" and "alpha" are render_normals()'s, bit for bit.  pipe.absgrad and pipe.compute_cov3D_python raise ValueError,
+    and so does a non-zero depth_ratio: the frame carries extra colours, and the ext x median blend kernels are not built (use
+    render() + render_normals(depth_ratio=...))."""
     from diff_gaussian_rasterization.normals import depth_to_normal, gaussian_normals
+    if float(depth_ratio) != 0.0:
+        raise ValueError("render_with_normals: depth_ratio must be 0: the one-frame form carries the normals as extra colours, and the "
+                         "median depth is not rendered together with extra colours (the ext x median blend kernels are not built); "
+                         "use render() and render_normals(depth_ratio=...)")
     if getattr(pipe, "absgrad", False):
         raise ValueError("render_with_normals: the frame is rendered with depth_alpha=True, which pipe.absgrad is not supported with: "
                          "turn pipe.absgrad off for this frame")
@@ -137,13 +162,20 @@ def _zero_points(like: torch.Tensor) -> torch.Tensor:
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, depth_alpha=False,
-           contributions=None, pixel_error=None, extra_colors=None):
+           contributions=None, pixel_error=None, extra_colors=None, median_depth=False):
     """Render the scene.  Background tensor (bg_color) must be on the GPU.
     depth_alpha=True (extension): the dict also holds "depth" and "alpha" [1,H,W], differentiable (diff_gaussian_rasterization).
     contributions (extension): a ContributionStats the frame's blend statistics are added into; rendered under torch.no_grad(),
     through the getters whatever pipe.fused_activations says (module docstring).
     pixel_error (extension; with an ErrorStats as contributions): the error map of this view, passed to the rasterizer.
-    extra_colors (extension; with depth_alpha=True): [P,3] float32 blended in the same frame; the dict also holds "extra" [3,H,W]."""
+    extra_colors (extension; with depth_alpha=True): [P,3] float32 blended in the same frame; the dict also holds "extra" [3,H,W].
+    median_depth=True (extension; with depth_alpha=True; not with extra_colors, contributions or pipe.absgrad): the dict also holds
+    "median_depth" [1,H,W], differentiable in the median splat's depth."""
+    if median_depth:
+        from diff_gaussian_rasterization import check_median_depth
+        check_median_depth(depth_alpha, getattr(pipe, "absgrad", False), contributions, extra_colors=extra_colors)
+        return _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, depth_alpha, None, pixel_error,
+                       median_depth=True)
     if extra_colors is not None:
         return _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, depth_alpha, contributions, pixel_error,
                        extra_colors=extra_colors)
@@ -154,7 +186,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
 
 
 def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, depth_alpha, contributions, pixel_error=None,
-            extra_colors=None):
+            extra_colors=None, median_depth=False):
     # extra_colors: a tensor, or (render_with_normals) a function of the (scales, rotations) the frame is rendered from
     xyz = pc.get_xyz
     # (the reference builds this as zeros_like(...) + 0 and retain_grad()s the non-leaf result; a leaf with requires_grad keeps
@@ -170,7 +202,7 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
         campos=viewpoint_camera.camera_center, prefiltered=False, debug=pipe.debug)
     rasterizer = GaussianRasterizer(raster_settings=raster_settings, depth_alpha=depth_alpha,
                                     antialiasing=getattr(pipe, "antialiasing", False), absgrad=getattr(pipe, "absgrad", False),
-                                    contributions=contributions, pixel_error=pixel_error)
+                                    contributions=contributions, pixel_error=pixel_error, median_depth=median_depth)
 
     def result(out):
         d = {"render": out[0], "viewspace_points": screenspace_points, "visibility_filter": out[1] > 0, "radii": out[1]}
@@ -178,6 +210,8 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
             d["depth"], d["alpha"] = out[2], out[3]
         if extra_colors is not None:
             d["extra"] = out[4]
+        if median_depth:
+            d["median_depth"] = out[4]
         return d
 
     def extra_kw(scales, rotations):

@@ -89,6 +89,7 @@ class OptimizationDefaults:
     densify_error_score: str = "max"              # "max": the largest single view's error (Revising Densification); "sum": over the views (Taming-3DGS)
     lambda_normal: float = 0.0                    # > 0: weight of the normal-consistency loss, one render_normals frame per iteration (train_loop.train); untuned
     normal_from_iter: int = 7000                  # the first iteration that adds it (2DGS's value, not tuned here)
+    depth_ratio: float = 0.0                      # in [0, 1], with lambda_normal > 0: the normal term's depth is (1 - r) mean + r median (render_normals; 2DGS: 1 for bounded scenes); untuned
     normal_in_frame: bool = False                 # True: colour and the normal term's maps from ONE render_with_normals frame (train_loop.train)
 
 
@@ -683,7 +684,8 @@ class GaussianModel:
 
     def extract_mesh(self, cameras, pipe, background, **kw):
         """The triangle mesh of the surface `cameras` see: depth maps fused into a TSDF volume, surface nets (scene/mesh.py extract_mesh,
-        which takes kw: voxel_size, sdf_trunc, bounds, depth_max, min_weight, and min_component_faces, keep_largest to clean it) -> (vertices [V,3], faces [F,3] int32, colors [V,3])."""
+        which takes kw: voxel_size, sdf_trunc, bounds, depth_max, min_weight, depth_ratio (0: the expected depth is fused; 1: the median depth),
+        and min_component_faces, keep_largest to clean it) -> (vertices [V,3], faces [F,3] int32, colors [V,3])."""
         from . import mesh
         return mesh.extract_mesh(self, cameras, pipe, background, **kw)
 

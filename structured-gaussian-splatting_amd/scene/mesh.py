@@ -4,8 +4,10 @@ all end in, without leaving the device.
 
 The functions work with any model render() accepts: a GaussianModel (with or without a 3D filter), a LatentGaussianModel.  Projective
 fusion of a few views leaves holes and silhouette artefacts by nature: clean_mesh (diff_gaussian_rasterization/meshops.py, DESIGN
-section 27) drops the small detached pieces on the device.  Decimation, median depth, unbounded (contracted) volumes and sparse voxel
-hashing are out of scope.
+section 27) drops the small detached pieces on the device.  depth_ratio (2DGS's; 0, the default: the expected depth; 2DGS uses 1, the
+median depth, for bounded scenes) chooses the depth that is fused (diff_gaussian_rasterization.normals.surface_depth, DESIGN section
+28): at a silhouette or behind a thin layer the expected depth is a blend at which nothing exists, the median is a splat's own.
+Decimation, unbounded (contracted) volumes and sparse voxel hashing are out of scope.
 """
 import math
 import os
@@ -21,14 +23,24 @@ def _tanfov(cam):
     return math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5)
 
 
-def fuse_depth_maps(pc, cameras, pipe, background, volume, alpha_min=0.5, depth_max=None):
+def fuse_depth_maps(pc, cameras, pipe, background, volume, alpha_min=0.5, depth_max=None, depth_ratio=0.0):
     """Per camera, under torch.no_grad(): render(..., depth_alpha=True), then volume.integrate of its depth, alpha and colour maps.
-    depth_max None: nothing is cut.  Returns the volume."""
+    depth_max None: nothing is cut.  depth_ratio in [0, 1] (0: the calls made without it): above 0 the frame also renders the median
+    depth and surface_depth(depth, alpha, median, depth_ratio) is integrated in the depth map's place, beside the same alpha.
+    Returns the volume."""
     from gaussian_renderer import render
+    from diff_gaussian_rasterization.normals import surface_depth
     depth_max = math.inf if depth_max is None else float(depth_max)
+    depth_ratio = float(depth_ratio)
+    if not 0.0 <= depth_ratio <= 1.0:
+        raise ValueError(f"fuse_depth_maps: depth_ratio {depth_ratio} outside [0, 1]")
     with torch.no_grad():
         for cam in cameras:
-            pkg = render(cam, pc, pipe, background, depth_alpha=True)
+            if depth_ratio > 0.0:
+                pkg = render(cam, pc, pipe, background, depth_alpha=True, median_depth=True)
+                pkg["depth"] = surface_depth(pkg["depth"], pkg["alpha"], pkg["median_depth"], depth_ratio)
+            else:
+                pkg = render(cam, pc, pipe, background, depth_alpha=True)
             tx, ty = _tanfov(cam)
             volume.integrate(pkg["depth"].contiguous(), pkg["alpha"].contiguous(), pkg["render"].contiguous(),
                              cam.world_view_transform.contiguous(), tx, ty, alpha_min=alpha_min, depth_max=depth_max)
@@ -54,11 +66,12 @@ def clean_mesh(vertices, faces, colors=None, **kw):
 
 
 def extract_mesh(pc, cameras, pipe, background, voxel_size=None, sdf_trunc=None, bounds=None, depth_max=None, min_weight=1.0,
-                 min_component_faces=None, keep_largest=None):
+                 min_component_faces=None, keep_largest=None, depth_ratio=0.0):
     """-> (vertices [V,3] float32, faces [F,3] int32, colors [V,3] float32) of the surface the cameras see.
     bounds: (lo [3], hi [3]); default camera_bounds(cameras).  voxel_size: default the bounds' longest side / 512.  sdf_trunc: default
     5 voxel_size.  depth_max: default the bounds' longest side.  min_component_faces, keep_largest: when either is given the mesh is
-    cleaned after the extraction (clean_mesh's min_faces and keep_largest); with both None it is returned as extracted."""
+    cleaned after the extraction (clean_mesh's min_faces and keep_largest); with both None it is returned as extracted.
+    depth_ratio: fuse_depth_maps' (0: the expected depth; 1: the median depth, 2DGS's choice for bounded scenes)."""
     from diff_gaussian_rasterization.tsdf import TSDFVolume
     cameras = list(cameras)
     if not cameras:
@@ -79,7 +92,7 @@ def extract_mesh(pc, cameras, pipe, background, voxel_size=None, sdf_trunc=None,
     # the bounds cut into voxels, a voxel's centre in the middle of its cut: side / voxel_size voxels along the longest side
     dims = tuple(max(int(math.ceil((h - l) / voxel_size - 1e-6)), 1) for l, h in zip(lo, hi))
     volume = TSDFVolume([l + 0.5 * voxel_size for l in lo], voxel_size, dims, sdf_trunc, device=pc.get_xyz.device)
-    fuse_depth_maps(pc, cameras, pipe, background, volume, depth_max=depth_max)
+    fuse_depth_maps(pc, cameras, pipe, background, volume, depth_max=depth_max, depth_ratio=depth_ratio)
     mesh = volume.extract_mesh(min_weight=min_weight)
     if min_component_faces is None and keep_largest is None:
         return mesh

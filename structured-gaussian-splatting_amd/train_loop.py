@@ -19,7 +19,10 @@ added to the loss in front of backward(); on_iteration still receives the image 
 normals frame is rendered without pipe.absgrad).  0 (the default): the loop is as before.  Neither number is tuned on captured scenes.
 opt.normal_in_frame (with lambda_normal > 0) takes the colour image and the three maps from ONE gaussian_renderer.render_with_normals
 frame per iteration from normal_from_iter on instead of two frames; the densification statistics then see the normal
-term's means2D gradient too.  Not with opt.densify_absgrad (the frame carries depth and alpha).  False (the default): the loop is as before."""
+term's means2D gradient too.  Not with opt.densify_absgrad (the frame carries depth and alpha).  False (the default): the loop is as before.
+opt.depth_ratio (2DGS's, in [0, 1]; with lambda_normal > 0) is handed to render_normals: above 0 the normal term's depth normals are
+taken from the mix (1 - r) mean + r median depth (2DGS uses 1 for bounded scenes), and the loss is formed on that
+depth.  Not with normal_in_frame (the one frame carries extra colours).  0 (the default): the loop is as before.  Untuned."""
 import math
 import random
 
@@ -69,6 +72,12 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
         from diff_gaussian_rasterization.normals import normal_consistency_loss
         from gaussian_renderer import render_normals
     normal_in_frame = lambda_normal > 0 and bool(getattr(opt, "normal_in_frame", False))
+    depth_ratio = float(getattr(opt, "depth_ratio", 0.0)) if lambda_normal > 0 else 0.0
+    if not 0.0 <= depth_ratio <= 1.0:
+        raise ValueError(f"depth_ratio = {depth_ratio}: a value in [0, 1] expected")
+    if normal_in_frame and depth_ratio > 0:
+        raise ValueError("normal_in_frame with depth_ratio > 0: the one frame carries the normals as extra colours, and the median depth "
+                         "is not rendered together with extra colours (use the two-frame path: normal_in_frame = False)")
     if normal_in_frame:
         from gaussian_renderer import render_with_normals
         if getattr(opt, "densify_absgrad", False):
@@ -102,10 +111,10 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
             cam, absgrad = cameras[idx], getattr(pipe, "absgrad", False)
             if absgrad:                                            # the normals frame carries depth and alpha: rendered without it
                 pipe.absgrad = False
-            maps = render_normals(cam, gaussians, pipe)
+            maps = render_normals(cam, gaussians, pipe, depth_ratio=depth_ratio) if depth_ratio > 0 else render_normals(cam, gaussians, pipe)
             if absgrad:
                 pipe.absgrad = absgrad
-            normal_loss = normal_consistency_loss(maps["normal"], maps["depth"], maps["alpha"], math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5))
+            normal_loss = normal_consistency_loss(maps["normal"], maps["surf_depth" if depth_ratio > 0 else "depth"], maps["alpha"], math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5))
             (loss + lambda_normal * normal_loss).backward()
         else:
             loss.backward()
