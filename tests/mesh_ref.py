@@ -171,12 +171,122 @@ def _components(name):
     return components_ref(f, V)
 
 
-@functools.lru_cache(maxsize=None)
-def reference(name, min_faces=1, keep_largest=None):
-    """clean_ref of a case, computed once and shared; the arrays are read-only."""
-    V, f = cases()[name]
-    ref = clean_ref(f, V, min_faces, keep_largest, _components(name))
+def _read_only(ref):
     for a in ref.values():
         if isinstance(a, np.ndarray):
             a.setflags(write=False)
     return ref
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name, min_faces=1, keep_largest=None):
+    """clean_ref of a case, computed once and shared; the arrays are read-only."""
+    V, f = cases()[name]
+    return _read_only(clean_ref(f, V, min_faces, keep_largest, _components(name)))
+
+
+# ---- the large mesh: past the first round of the kernels' scans, its reference known by construction --------------------------------
+# k_mesh_scan walks the blocks' counts (256 faces or vertices each) in rounds of 8 192 blocks = 2 097 152 elements.  At scale 1 the mesh
+# below has F = 4 505 500 and V = 4 751 825: three rounds of the face scan and three of the vertex scan.  The sequential references
+# above take minutes at that size, so this one comes from how the mesh is built, in vectorised numpy, and is held to the sequential
+# ones at a small scale and to scipy at the full one (tests/test_mesh_clean_ref.py).
+BIG_SHEETS = ((900, 900), (700, 600), (500, 500), (500, 500), (120, 100))      # quads; the two equal sheets tie as third largest
+BIG_TRIANGLES = 1_000_000                                   # isolated: one face and three vertices each
+BIG_INVALID = 3000                                          # of each of _mixed's seven kinds
+BIG_DUPLICATES = 500                                        # faces of the smallest sheet that come twice
+BIG_UNUSED = (1000, 2000, 1500)                             # unreferenced vertices at the front, in the middle, at the end
+BIG_TIE = 3                                                 # keep_largest = 3: the threshold is the equal sheets' size, and both stay
+BIG_THRESHOLDS = [(1, None), (2, None), (1, 1), (1, 2), (1, BIG_TIE)]
+SMALL_SCALE = 0.001                                         # a few thousand faces: the sequential references' size
+
+
+def sheet_faces(nx, ny, base=0):
+    """sheet() without its loop -> (faces [2 nx ny, 3] int64 in sheet()'s order, the number of vertices)."""
+    j, i = np.mgrid[0:ny, 0:nx]
+    v = base + j * (nx + 1) + i
+    return np.stack([v, v + 1, v + nx + 2, v, v + nx + 2, v + nx + 1], -1).reshape(-1, 3).astype(np.int64), (nx + 1) * (ny + 1)
+
+
+@functools.lru_cache(maxsize=None)
+def _big(scale):
+    rng = np.random.default_rng(14)
+    k = float(scale) ** 0.5
+    dims = [(max(2, round(nx * k)), max(2, round(ny * k))) for nx, ny in BIG_SHEETS]
+    n_tri, n_inv, n_dup = max(8, round(BIG_TRIANGLES * scale)), max(2, round(BIG_INVALID * scale)), max(2, round(BIG_DUPLICATES * scale))
+    unused = [max(2, round(u * scale)) for u in BIG_UNUSED]
+    # the valid faces over local vertex indices: sheet after sheet, then the triangles; `comp` numbers the components in that order
+    faces, comp, starts, base = [], [], [], 0
+    for c, (nx, ny) in enumerate(dims):
+        f, n = sheet_faces(nx, ny, base)
+        faces.append(f)
+        comp.append(np.full(len(f), c, np.int64))
+        starts.append(base)
+        base += n
+    faces.append(faces[-1][rng.choice(len(faces[-1]), n_dup, replace=False)])               # the duplicates
+    comp.append(np.full(n_dup, len(dims) - 1, np.int64))
+    tri0 = base + 3 * np.arange(n_tri, dtype=np.int64)
+    faces.append(tri0[:, None] + np.arange(3)[None])
+    comp.append(len(dims) + np.arange(n_tri, dtype=np.int64))
+    starts = np.concatenate([np.asarray(starts, np.int64), tri0])
+    R = base + 3 * n_tri                                                                    # referenced vertices
+    V = R + sum(unused)
+    # where the referenced vertices go: a random permutation over every place that is not kept free
+    free = np.zeros(V, bool)
+    free[:unused[0]] = True
+    free[V // 2:V // 2 + unused[1]] = True
+    free[V - unused[2]:] = True
+    place = np.nonzero(~free)[0][rng.permutation(R)]
+    valid = place[np.concatenate(faces)]
+    la = rng.integers(R, size=(7, n_inv))
+    a, b = place[la], place[(la + 1 + rng.integers(R - 1, size=(7, n_inv))) % R]              # two different vertices
+    kinds = [(np.full(n_inv, -1), a[0], b[0]), (a[1], np.full(n_inv, V), b[1]), (a[2], a[2], b[2]), (a[3], b[3], a[3]), (b[4], a[4], a[4]),
+             (a[5], b[5], np.full(n_inv, 2 ** 31 - 1)), (np.full(n_inv, -2 ** 31), a[6], b[6])]
+    invalid = np.concatenate([np.stack(kd, 1) for kd in kinds]).astype(np.int64)
+    allf = np.concatenate([valid, invalid])
+    comp = np.concatenate(comp + [np.full(len(invalid), -1, np.int64)])
+    order = rng.permutation(len(allf))
+    allf, comp = allf[order], comp[order]
+    # by construction: a component's label is the smallest place of its vertices
+    smallest = np.minimum.reduceat(place, starts)
+    labels = np.where(comp >= 0, smallest[np.maximum(comp, 0)], -1).astype(np.int32)
+    sizes = np.bincount(labels[labels >= 0], minlength=V).astype(np.int32)
+    faces32 = np.ascontiguousarray(allf.astype(np.int32))
+    assert np.array_equal(faces32.astype(np.int64), allf)
+    out = dict(V=V, faces=faces32, labels=labels, sizes=sizes, free=free, sheet_faces=[2 * nx * ny for nx, ny in dims], triangles=n_tri,
+               invalid=len(invalid), duplicates=n_dup)
+    return _read_only(out)
+
+
+def big_mesh(scale=1.0):
+    """(V, faces [F,3] int32): BIG_SHEETS with their sides scaled by sqrt(scale) (two of them equal), BIG_TRIANGLES x scale isolated
+    triangles, duplicates of faces of the smallest sheet, every kind of invalid face of _mixed, unreferenced vertices at the front, in
+    the middle and at the end; the vertex indices randomly permuted, the faces shuffled.  Fixed seed; computed once; read-only."""
+    b = _big(scale)
+    return b["V"], b["faces"]
+
+
+def big_info(scale=1.0):
+    """What big_mesh(scale) was built from: dict(V, faces, labels, sizes, free (the vertices kept unreferenced), sheet_faces, triangles,
+    invalid, duplicates)."""
+    return _big(scale)
+
+
+def clean_vectorised(faces, V, labels, sizes, min_faces=1, keep_largest=None):
+    """clean_ref's rule without its loops, from given components."""
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    thr = threshold_ref(sizes, min_faces, keep_largest)
+    keep = (labels >= 0) & (sizes[np.maximum(labels, 0)] >= thr) if V else np.zeros(len(f), bool)
+    face_src = np.nonzero(keep)[0]
+    used = np.zeros(V, bool)
+    used[f[face_src].reshape(-1)] = True
+    vertex_src = np.nonzero(used)[0]
+    new = np.cumsum(used) - 1
+    return dict(labels=labels, sizes=sizes, threshold=thr, vertex_src=vertex_src.astype(np.int32), face_src=face_src.astype(np.int32),
+                faces_out=new[f[face_src]].reshape(-1, 3).astype(np.int32))
+
+
+@functools.lru_cache(maxsize=None)
+def big_reference(scale=1.0, min_faces=1, keep_largest=None):
+    """The reference of big_mesh(scale): labels and sizes by construction, the rest by the rule; computed once and shared; read-only."""
+    b = _big(scale)
+    return _read_only(clean_vectorised(b["faces"], b["V"], b["labels"], b["sizes"], min_faces, keep_largest))

@@ -4,7 +4,8 @@ it, holes in alpha, a depth_max that cuts pixels) into volumes of 17 x 9 x 21, 1
 and 96 x 96 pixels; skipped voxels keep every bit of a volume of random bits; the same frames give the same bits twice, and on a side
 stream.  Extraction: on the GPU's own fused volume, the faces integer for integer and the vertices and colours within the replayed
 bound, for one cell, an odd volume, a volume with block edges along every axis, a volume without an active cell and the analytic
-sphere with its topological checks.  End to end: Gaussians on a sphere shell, eight cameras, a 48^3 volume, a PLY file.  The references
+sphere with its topological checks; and past the first round of k_sn_scan (every volume above stays inside it: 1 024 blocks at most), an
+analytic volume of 131 x 127 x 300 voxels, three rounds, at two min_weight values.  End to end: Gaussians on a sphere shell, eight cameras, a 48^3 volume, a PLY file.  The references
 are computed once (tests/test_tsdf_ref.py's caches) and shared.  Every test prints the figures it judged."""
 import math
 
@@ -15,8 +16,8 @@ import torch
 import scene_synth as S
 import streams as ST
 import tsdf_ref as TR
-from test_tsdf_ref import (FUSION_CASES, check_mesh, fusion_reference, integrate_frames, make_volume, sphere_checks, sphere_reference, volume_arrays,
-                           volume_of)
+from test_tsdf_ref import (FUSION_CASES, check_mesh, fusion_reference, integrate_frames, make_volume, sphere_checks, sphere_reference,
+                           three_round_conditions, volume_arrays, volume_of)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -138,6 +139,27 @@ def test_extraction_of_the_analytic_sphere(half):
         obs = weight >= 1
         for dx, dy, dz in TR.CORNER:
             assert obs[used[:, 2] + dz, used[:, 1] + dy, used[:, 0] + dx].all(), "a face references a cell with an unobserved corner"
+
+
+@pytest.fixture(scope="module")
+def three_round_device_volume():
+    """TR.three_round_volume() on the device, uploaded once (100 MB)."""
+    return volume_of(*TR.three_round_volume(), DEV)
+
+
+@pytest.mark.parametrize("min_weight", [1.0, 2.0])
+def test_extraction_past_the_first_round_of_the_voxel_scan(three_round_device_volume, min_weight):
+    """131 x 127 x 300 voxels are 19 497 blocks, three rounds of k_sn_scan: the vertices and quads that voxels of rounds 1 and 2 own
+    are placed by the carry between rounds, and every face that names one of their vertices reads a prefix of those rounds."""
+    grid, ref = three_round_conditions(min_weight, "kernel")
+    vol = three_round_device_volume
+    got = vol.extract_mesh(min_weight=min_weight, native=True)
+    print(f"three rounds min_weight {min_weight}: V = {got[0].shape[0]}, F = {got[1].shape[0]}; vertices per round "
+          f"{TR.scan_rounds(ref['vertex_owners'], grid.n).tolist()}, quads per round {TR.scan_rounds(ref['quad_owners'], grid.n).tolist()}")
+    assert got[0].dtype == torch.float32 and got[1].dtype == torch.int32 and got[2].dtype == torch.float32
+    check_mesh(got, ref, f"kernel three rounds min_weight {min_weight}")
+    again = vol.extract_mesh(min_weight=min_weight, native=True)
+    assert all(ST.same_bits(a.cpu(), b.cpu()) for a, b in zip(got, again)), "two extractions of one volume differ"
 
 
 # ---- end to end ---------------------------------------------------------------------------------------------------------------

@@ -4,8 +4,9 @@ header's prototypes, and every refusal comes without touching a GPU; the torch t
 (tests/mesh_ref.py, itself cross-checked once against scipy) on every shared case and threshold, and attribute rows bit for bit; the
 kernels' own union-find (csrc/gsr_mesh_math.h compiled by g++: tests/mesh_host.cpp, a stand-alone program run as a subprocess, once
 under AddressSanitizer + UBSan and once under ThreadSanitizer) gives the reference's labels from 8 threads, and sets its give-up word
-under a retry cap of 1 without touching anything out of bounds; scene.mesh.extract_mesh without the new keywords returns what it did.
-Every comparison is exact."""
+under a retry cap of 1 without touching anything out of bounds; scene.mesh.extract_mesh without the new keywords returns what it did;
+the large mesh of three scan rounds has a reference by construction that equals the sequential one at a small scale and scipy's
+components at the full one, and tells a scan with a wrong carry between rounds from the right one.  Every comparison is exact."""
 import ctypes as C
 import os
 import re
@@ -221,6 +222,118 @@ def test_clean_twin_against_the_reference(name, min_faces, keep_largest):
     check_clean(clean_mesh(v, f, c, min_faces=min_faces, keep_largest=keep_largest, return_index=True), ref, v, c, f"twin {name}")
     three = clean_mesh(v, f, c, min_faces=min_faces, keep_largest=keep_largest, native=False)
     assert len(three) == 3 and np.array_equal(three[1].numpy(), ref["faces_out"])
+
+
+# ---- the large mesh: past the first round of k_mesh_scan ------------------------------------------------------------------------
+def big_tensors(scale, device="cpu", seed=6):
+    """case_tensors for MR.big_mesh(scale)."""
+    V, f = MR.big_mesh(scale)
+    g = torch.Generator().manual_seed(seed)
+    bits = lambda: torch.randint(-2 ** 31, 2 ** 31 - 1, (V, 3), generator=g, dtype=torch.int64).to(torch.int32).view(torch.float32)
+    return bits().to(device), torch.from_numpy(f.copy()).to(device).contiguous(), bits().to(device)
+
+
+def big_conditions(scale, min_faces, keep_largest, what):
+    """What the issue asks of the large mesh at one threshold, asserted wherever it is used: three rounds of the face scan and of the
+    vertex scan; in every round at least 1 000 faces kept and 1 000 vertices used and, past (1, None), as many dropped and unused.
+    Prints the counts per round.  -> the reference"""
+    import tsdf_ref as TR
+    V, f = MR.big_mesh(scale)
+    ref = MR.big_reference(scale, min_faces, keep_largest)
+    F = len(f)
+    assert 2 * TR.SCAN_ROUND < F < 5_500_000 and 2 * TR.SCAN_ROUND < V < 5_500_000
+    tag = f"{what} min_faces {min_faces} keep_largest {keep_largest}"
+    kept = TR.assert_rounds(ref["face_src"], F, f"{tag}: threshold {ref['threshold']}, kept faces")
+    used = TR.assert_rounds(ref["vertex_src"], V, f"{tag}: used vertices")
+    all_f, all_v = TR.scan_rounds(np.arange(F), F), TR.scan_rounds(np.arange(V), V)
+    least = 1000 if (min_faces, keep_largest) != (1, None) else 1
+    assert len(kept) == len(used) == 3
+    assert (all_f - kept >= least).all() and (all_v - used >= least).all(), f"{tag}: dropped per round {(all_f - kept).tolist()}, unused {(all_v - used).tolist()}"
+    return ref
+
+
+def test_the_big_mesh_at_a_small_scale_against_the_sequential_reference_and_the_twins():
+    from diff_gaussian_rasterization.meshops import clean_mesh_torch, face_components_torch
+    info = MR.big_info(MR.SMALL_SCALE)
+    V, f = MR.big_mesh(MR.SMALL_SCALE)
+    print(f"scale {MR.SMALL_SCALE}: V = {V}, F = {len(f)}: sheets of {info['sheet_faces']} faces, {info['triangles']} triangles, "
+          f"{info['duplicates']} duplicates, {info['invalid']} invalid faces")
+    assert 2000 <= len(f) <= 9000
+    for nx, ny, base in ((3, 2, 0), (5, 7, 11)):                                  # the generator's sheets are sheet()'s
+        assert np.array_equal(MR.sheet_faces(nx, ny, base)[0], np.asarray(MR.sheet(nx, ny, base)[0])) and MR.sheet_faces(nx, ny)[1] == MR.sheet(nx, ny)[1]
+    labels, sizes = MR.components_ref(f, V)
+    assert np.array_equal(info["labels"], labels) and np.array_equal(info["sizes"], sizes)
+    v, faces, c = big_tensors(MR.SMALL_SCALE)
+    check_components(face_components_torch(faces, V), info, "twin big mesh, small scale")
+    for mf, kl in MR.BIG_THRESHOLDS:
+        ref, want = MR.big_reference(MR.SMALL_SCALE, mf, kl), MR.clean_ref(f, V, mf, kl, (labels, sizes))
+        assert ref["threshold"] == want["threshold"]
+        for key in ("vertex_src", "face_src", "faces_out"):
+            assert ref[key].dtype == want[key].dtype and np.array_equal(ref[key], want[key]), (mf, kl, key)
+        check_clean(clean_mesh_torch(v, faces, c, min_faces=mf, keep_largest=kl, return_index=True), ref, v, c, f"twin big mesh {mf} {kl}")
+
+
+@pytest.mark.parametrize("scale", [MR.SMALL_SCALE, 1.0])
+def test_the_big_mesh_holds_what_it_is_for(scale):
+    info = MR.big_info(scale)
+    V, f = MR.big_mesh(scale)
+    sheets, T = info["sheet_faces"], info["triangles"]
+    assert f.dtype == np.int32 and f.flags.c_contiguous and not f.flags.writeable
+    comp = np.sort(info["sizes"][info["sizes"] > 0])[::-1]
+    want = sorted(sheets[:-1] + [sheets[-1] + info["duplicates"]], reverse=True)
+    assert comp[:len(sheets)].tolist() == want and (comp[len(sheets):] == 1).all() and len(comp) == len(sheets) + T
+    assert want[0] > want[1] > want[2] == want[3] > want[4] > 1                   # the tie is at keep_largest = 3, and nowhere else
+    assert int((info["labels"] < 0).sum()) == info["invalid"] and info["invalid"] % 7 == 0
+    assert np.array_equal(info["labels"] >= 0, MR.face_valid(f, V))
+    bad = f[info["labels"] < 0].astype(np.int64)
+    assert (bad == -1).any() and (bad == V).any() and (bad == 2 ** 31 - 1).any() and (bad == -2 ** 31).any()
+    assert (bad[:, 0] == bad[:, 1]).any() and (bad[:, 0] == bad[:, 2]).any() and (bad[:, 1] == bad[:, 2]).any()
+    where_bad = np.nonzero(info["labels"] < 0)[0]                                 # spread over the whole face list (two dozen at the small scale)
+    assert (np.bincount(where_bad * 8 // len(f), minlength=8) >= 1000).all() if scale == 1.0 else where_bad[0] < len(f) // 4 < 3 * len(f) // 4 < where_bad[-1]
+    ref = MR.big_reference(scale)
+    unused = np.setdiff1d(np.arange(V), ref["vertex_src"])
+    assert np.array_equal(unused, np.nonzero(info["free"])[0])
+    assert unused[0] == 0 and unused[-1] == V - 1 and (unused == V // 2).any()   # at the front, at the end, in the middle
+    if scale < 1:                                                                 # the duplicates (a sort of all rows: at the small scale)
+        assert len(np.unique(f[info["labels"] >= 0], axis=0)) == int((info["labels"] >= 0).sum()) - info["duplicates"]
+    thr = {(mf, kl): MR.big_reference(scale, mf, kl)["threshold"] for mf, kl in MR.BIG_THRESHOLDS}
+    assert thr == {(1, None): 1, (2, None): 2, (1, 1): want[0], (1, 2): want[1], (1, MR.BIG_TIE): want[2]}
+    kept = {k: len(MR.big_reference(scale, *k)["face_src"]) for k in thr}
+    assert kept[(1, None)] == sum(want) + T and kept[(2, None)] == sum(want) and kept[(1, 1)] == want[0] and kept[(1, 2)] == want[0] + want[1]
+    assert kept[(1, MR.BIG_TIE)] == sum(want[:4])                                 # both equal sheets stay
+    print(f"scale {scale}: V = {V}, F = {len(f)}; components {want} and {T} triangles; thresholds {thr}; kept faces {kept}")
+
+
+def test_the_big_mesh_labels_agree_with_scipy():
+    sp = pytest.importorskip("scipy.sparse")
+    from scipy.sparse.csgraph import connected_components
+    info = MR.big_info(1.0)
+    V, f = MR.big_mesh(1.0)
+    valid = info["labels"] >= 0
+    fv = f[valid].astype(np.int64)
+    rows, cols = np.concatenate([fv[:, 0], fv[:, 0]]), np.concatenate([fv[:, 1], fv[:, 2]])
+    n, comp = connected_components(sp.coo_matrix((np.ones(len(rows), np.int8), (rows, cols)), shape=(V, V)), directed=False)
+    smallest = np.full(n, V, np.int64)
+    np.minimum.at(smallest, comp, np.arange(V))
+    want = np.full(len(f), -1, np.int64)
+    want[valid] = smallest[comp[fv[:, 0]]]
+    assert np.array_equal(info["labels"], want)
+    assert np.array_equal(info["sizes"], np.bincount(want[want >= 0], minlength=V))
+
+
+@pytest.mark.parametrize("min_faces, keep_largest", MR.BIG_THRESHOLDS)
+def test_the_big_mesh_reaches_three_rounds_of_both_scans_and_tells_the_carry_rules_apart(min_faces, keep_largest):
+    """numpy on the reference, no kernel: the per-block counts of kept faces and of used vertices, scanned with the carry dropped
+    between rounds or with the last round's total alone, give other prefixes than the right rule in rounds 1 and 2, or in round 2."""
+    import tsdf_ref as TR
+    ref = big_conditions(1.0, min_faces, keep_largest, "reference")
+    V, f = MR.big_mesh(1.0)
+    TR.assert_rules_differ(TR.block_counts(ref["face_src"], len(f)), "face_prefix")
+    TR.assert_rules_differ(TR.block_counts(ref["vertex_src"], V), "vertex_prefix")
+    if (min_faces, keep_largest) != (1, None):                                    # no prefix equals the plain index
+        for src, n in ((ref["face_src"], len(f)), (ref["vertex_src"], V)):
+            prefix = TR.block_prefixes(TR.block_counts(src, n))
+            assert (prefix[1:] != TR.SCAN_BLOCK * np.arange(1, len(prefix))).all()
 
 
 # ---- the kernels' union-find on the host, under sanitizers ----------------------------------------------------------------------

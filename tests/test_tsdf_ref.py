@@ -5,7 +5,9 @@ own per-element functions (csrc/gsr_tsdf_math.h compiled by g++ under AddressSan
 program run as a subprocess) agree with the binary64 restatement (tests/tsdf_ref.py) under its error rule, fragile voxels by their
 reachable states; on every fixture the fragile (voxel, frame) pairs are at most 1 % of the updates; surface nets on an analytic sphere
 is a closed, consistently oriented surface of genus 0 whose vertices lie on the sphere as closely as the reference's own; no face
-touches a cell with an unobserved corner; the PLY file reads back.  Every test prints the figures it judged."""
+touches a cell with an unobserved corner; a volume of three rounds of the extraction's block scan holds what the kernel test needs of
+it, and its reference tells a scan with a wrong carry between rounds from the right one; the PLY file reads back.  Every test prints
+the figures it judged."""
 import ctypes as C
 import functools
 import os
@@ -317,8 +319,35 @@ def sphere_reference(half=False):
 def volume_of(grid, tsdf, weight, color, device="cpu", dtype=F32):
     vol = make_volume(grid, device, dtype)
     for dst, src in ((vol.tsdf, tsdf), (vol.weight, weight), (vol.color, color)):
-        dst.copy_(torch.as_tensor(np.asarray(src)).reshape(dst.shape))
+        src = np.asarray(src)
+        dst.copy_(torch.as_tensor(src if src.flags.writeable else src.copy()).reshape(dst.shape))      # (a shared fixture is read-only)
     return vol
+
+
+@functools.lru_cache(maxsize=None)
+def three_round_reference(min_weight=1.0):
+    """surface_nets_ref of TR.three_round_volume() at one min_weight plus `vertex_owners`, the voxel index of every vertex's cell:
+    computed once and shared, here and in tests/test_gpu_tsdf.py; the arrays are read-only."""
+    grid, tsdf, weight, color = TR.three_round_volume()
+    ref = TR.surface_nets_ref(grid, tsdf, weight, color, min_weight)
+    nx, ny, _ = grid.dims
+    ref["vertex_owners"] = (ref["cells"][:, 2] * ny + ref["cells"][:, 1]) * nx + ref["cells"][:, 0]
+    for a in ref.values():
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    return ref
+
+
+def three_round_conditions(min_weight, what):
+    """What the issue asks of the fixture, asserted wherever it is used: three rounds of the voxel scan, voxels of every round own at
+    least 1 000 vertices and 1 000 quads, the first blocks of rounds 1 and 2 have non-zero prefixes.  -> (grid, ref)"""
+    grid, ref = TR.three_round_volume()[0], three_round_reference(min_weight)
+    assert grid.n > 2 * TR.SCAN_ROUND and grid.dims[0] % 64 != 0
+    assert np.array_equal(np.sort(ref["vertex_owners"]), ref["vertex_owners"]) and np.array_equal(np.sort(ref["quad_owners"]), ref["quad_owners"])
+    assert 2 * len(ref["quad_owners"]) == len(ref["faces"]) and len(ref["vertex_owners"]) == ref["vertices"].v.shape[0]
+    TR.assert_rounds(ref["vertex_owners"], grid.n, f"{what} min_weight {min_weight}: vertices")
+    TR.assert_rounds(ref["quad_owners"], grid.n, f"{what} min_weight {min_weight}: quads")
+    return grid, ref
 
 
 def test_surface_nets_on_an_analytic_sphere(host):
@@ -382,6 +411,50 @@ def test_degenerate_volumes_give_an_empty_mesh(host):
     assert ref["vertices"].v.shape == (1, 3) and ref["faces"].shape == (0, 3)
     check_mesh(host.mesh(grid, tsdf, np.ones(8, np.float32), color), ref, "host 2x2x2")
     check_mesh(volume_of(grid, tsdf, np.ones(8, np.float32), color).extract_mesh(), ref, "twin 2x2x2")
+
+
+# ---- past the first round of k_sn_scan ----------------------------------------------------------------------------------------
+def test_the_three_round_fixture_holds_what_it_is_for():
+    import mesh_ref as MR
+    grid, tsdf, weight, color = TR.three_round_volume()
+    refs = {mw: three_round_conditions(mw, "reference")[1] for mw in (1.0, 2.0)}
+    assert 4_194_304 < grid.n < 5_500_000
+    assert sorted(np.unique(weight).tolist()) == [0.0, 1.0, 2.0]
+    v1, v2 = refs[1.0]["vertices"].v.shape[0], refs[2.0]["vertices"].v.shape[0]
+    assert 0 < v2 < v1 and 0 < len(refs[2.0]["faces"]) < len(refs[1.0]["faces"])              # the two cuts give different meshes
+    # the hole cuts the surface: a volume observed everywhere has more faces, and no face names a cell with an unobserved corner
+    full = TR.surface_nets_ref(grid, tsdf, np.ones_like(weight), color)
+    assert len(full["faces"]) > len(refs[1.0]["faces"])
+    used = refs[1.0]["cells"][np.unique(refs[1.0]["faces"])]
+    for dx, dy, dz in TR.CORNER:
+        assert (weight[used[:, 2] + dz, used[:, 1] + dy, used[:, 0] + dx] >= 1).all()
+    # two disjoint surfaces, the plane in one piece around its hole and the larger; without the small one only the plane is left
+    faces = refs[1.0]["faces"]
+    labels, sizes = MR.components_ref(faces, v1)
+    pieces = sorted(sizes[sizes > 0].tolist())
+    alone = TR.surface_nets_ref(*TR.three_round_volume(small=False))
+    print(f"min_weight 1: V = {v1}, F = {len(faces)} in components of {pieces} faces; min_weight 2: V = {v2}, F = {len(refs[2.0]['faces'])}; "
+          f"observed everywhere F = {len(full['faces'])}; the plane alone F = {len(alone['faces'])}")
+    assert len(pieces) == 2 and pieces[0] < pieces[1] == len(alone["faces"])
+    assert TR.mesh_topology(faces[labels == np.argmax(sizes == pieces[0])])["undirected_ok"], "the small surface is not closed"
+
+
+@pytest.mark.parametrize("min_weight", [1.0, 2.0])
+def test_the_three_round_fixture_tells_the_carry_rules_apart(min_weight):
+    """numpy on the reference's owners, no kernel: a scan that drops the carry between rounds, or keeps only the last round's total,
+    gives other prefixes than the right one in rounds 1 and 2, or in round 2, for the vertices and for the quads."""
+    grid, ref = three_round_conditions(min_weight, "reference")
+    for name in ("vertex_owners", "quad_owners"):
+        TR.assert_rules_differ(TR.block_counts(ref[name], grid.n), f"min_weight {min_weight} {name}")
+
+
+@pytest.mark.parametrize("min_weight", [1.0, 2.0])
+def test_the_twin_on_the_three_round_fixture(min_weight):
+    """The float32 torch twin takes a fraction of the reference's time on this volume (measured: 0.1 s against 2.5 s), so it is held to
+    the reference here too."""
+    grid, tsdf, weight, color = TR.three_round_volume()
+    check_mesh(volume_of(grid, tsdf, weight, color).extract_mesh(min_weight=min_weight, native=False), three_round_reference(min_weight),
+               f"twin three rounds min_weight {min_weight}")
 
 
 # ---- PLY ----------------------------------------------------------------------------------------------------------------------

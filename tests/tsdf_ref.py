@@ -18,6 +18,7 @@ depth > 0) is decided on the binary32 inputs themselves and is never fragile.  `
 every state a binary32 evaluation can reach (`alternatives`): the frame's update taken or not and, where u or v is within its bound of
 an integer, the update through the pixel on either side of it.  A fragile voxel must equal one of them within that one's bound.
 """
+import functools
 import itertools
 
 import numpy as np
@@ -279,10 +280,11 @@ CORNER = np.array([[k & 1, (k >> 1) & 1, k >> 2] for k in range(8)], np.int64)
 
 def surface_nets_ref(grid: Grid, tsdf32, weight32, color32, min_weight=1.0):
     """tsdf32, weight32 [nz,ny,nx], color32 [3,nz,ny,nx]: binary32 arrays -> dict(vertices: Tracked [V,3], colors: Tracked [V,3], faces:
-    int64 [F,3], cells: int64 [V,3] (the cells' lowest corners)).  The values are the world-space means; the bounds the replay's."""
+    int64 [F,3], cells: int64 [V,3] (the cells' lowest corners), quad_owners: int64 [F/2] (the voxel index, x fastest, that owns each
+    quad, in the faces' order)).  The values are the world-space means; the bounds the replay's."""
     nx, ny, nz = grid.dims
     empty = dict(vertices=Tracked(torch.zeros(0, 3, dtype=F64)), colors=Tracked(torch.zeros(0, 3, dtype=F64)), faces=np.zeros((0, 3), np.int64),
-                 cells=np.zeros((0, 3), np.int64))
+                 cells=np.zeros((0, 3), np.int64), quad_owners=np.zeros(0, np.int64))
     if min(nx, ny, nz) < 2:
         return empty
     tsdf32, weight32 = np.asarray(tsdf32, np.float32).reshape(nz, ny, nx), np.asarray(weight32, np.float32).reshape(nz, ny, nx)
@@ -353,7 +355,67 @@ def surface_nets_ref(grid: Grid, tsdf32, weight32, color32, min_weight=1.0):
     for lin, a, v0, v1, v2, v3, voxel_inside in rows.tolist():
         faces += [(v0, v1, v2), (v0, v2, v3)] if voxel_inside else [(v0, v2, v1), (v0, v3, v2)]
     faces = np.asarray(faces, np.int64).reshape(-1, 3)
-    return dict(vertices=vertices, colors=colors, faces=faces, cells=cells, replay=replay)
+    return dict(vertices=vertices, colors=colors, faces=faces, cells=cells, replay=replay, quad_owners=rows[:, 0].copy())
+
+
+# ---- the kernels' one-block scans: rounds, and the rules a scan could follow between them ----------------------------------------------
+
+SCAN_BLOCK = 256                                            # voxels, faces or vertices per block (kSnBlock, kMeshBlock)
+SCAN_ROUND = 8192 * SCAN_BLOCK                              # per round of k_sn_scan and of mesh_scan_counts: 1 024 threads x 8 blocks each
+CARRY_RULES = ("right", "reset", "last")
+
+
+def scan_rounds(owners, n):
+    """The number of `owners` (element indices in [0, n)) per scan round of SCAN_ROUND elements -> int64 [ceil(n / SCAN_ROUND)]."""
+    owners = np.asarray(owners, np.int64).reshape(-1)
+    return np.bincount(owners // SCAN_ROUND, minlength=max(1, -(-int(n) // SCAN_ROUND))).astype(np.int64)
+
+
+def block_counts(owners, n):
+    """The number of `owners` per block of SCAN_BLOCK elements -> int64 [ceil(n / SCAN_BLOCK)]."""
+    return np.bincount(np.asarray(owners, np.int64).reshape(-1) // SCAN_BLOCK, minlength=-(-int(n) // SCAN_BLOCK)).astype(np.int64)
+
+
+def block_prefixes(counts, rule="right"):
+    """The exclusive prefix of every block's count as a scan in rounds of 8 192 blocks gives it under `rule`: "right" (the carry is the
+    sum of all rounds before), "reset" (the carry is 0 in every round), "last" (the carry is the previous round's total alone)."""
+    counts = np.asarray(counts, np.int64)
+    per = SCAN_ROUND // SCAN_BLOCK
+    rounds = -(-len(counts) // per)
+    padded = np.zeros(rounds * per, np.int64)
+    padded[:len(counts)] = counts
+    padded = padded.reshape(rounds, per)
+    within = np.cumsum(padded, 1) - padded
+    totals = padded.sum(1)
+    carry = {"right": np.cumsum(totals) - totals, "reset": np.zeros(rounds, np.int64), "last": np.concatenate([[0], totals[:-1]])}[rule]
+    return (within + carry[:, None]).reshape(-1)[:len(counts)]
+
+
+def assert_rules_differ(counts, what):
+    """A fixture of three rounds or more tells the two wrong carry rules from the right one: "reset" is wrong at every block of rounds
+    1 and 2, "last" at every block of round 2, and both are right wherever else the first three rounds go."""
+    per = SCAN_ROUND // SCAN_BLOCK
+    assert len(counts) > 2 * per, f"{what}: {len(counts)} blocks are fewer than three rounds"
+    right, reset, last = (block_prefixes(counts, r) for r in CARRY_RULES)
+    assert np.array_equal(right, np.cumsum(counts) - counts)
+    rnd = np.arange(len(counts)) // per
+    assert np.array_equal(reset[rnd == 0], right[rnd == 0]) and (reset[rnd == 1] != right[rnd == 1]).all() and (reset[rnd == 2] != right[rnd == 2]).all()
+    assert np.array_equal(last[rnd <= 1], right[rnd <= 1]) and (last[rnd == 2] != right[rnd == 2]).all()
+    print(f"{what}: the prefixes of blocks {per} and {2 * per} are {right[per]} and {right[2 * per]}; with the carry reset {reset[per]} and "
+          f"{reset[2 * per]}; with the last round's total alone {last[per]} and {last[2 * per]}")
+
+
+def assert_rounds(owners, n, what, at_least=1000):
+    """The condition on a fixture of the scans: three rounds or more, `at_least` owners in every round, and a non-zero prefix at the
+    first block of rounds 1 and 2.  Prints and returns the counts per round."""
+    rounds = scan_rounds(owners, n)
+    print(f"{what}: {n} elements in {-(-n // SCAN_BLOCK)} blocks, {len(rounds)} rounds; per round {rounds.tolist()}")
+    assert len(rounds) >= 3, f"{what}: {len(rounds)} rounds"
+    assert int(rounds.min()) >= at_least, f"{what}: a round holds fewer than {at_least}"
+    prefix = block_prefixes(block_counts(owners, n))
+    per = SCAN_ROUND // SCAN_BLOCK
+    assert prefix[per] > 0 and prefix[2 * per] > prefix[per], f"{what}: the first block of round 1 or 2 has a zero prefix"
+    return rounds
 
 
 def mesh_topology(faces):
@@ -453,6 +515,38 @@ def analytic_sphere(n=24, radius=SPHERE_R):
     tsdf = np.clip(sdf, -1, 1).astype(np.float32).reshape(n, n, n)
     color = np.clip(0.5 + 0.5 * p.T / radius, 0, 1).astype(np.float32).reshape(3, n, n, n)
     return grid, tsdf, np.ones((n, n, n), np.float32), color
+
+
+THREE_ROUND_DIMS = (131, 127, 300)                          # 4 991 100 voxels = 19 497 blocks of 256: three rounds of k_sn_scan; x no multiple of 64
+THREE_ROUND_PLANE = ((1.0, 0.21, 0.13), 90.0)               # n . p = d, p in voxels: x runs from 24.7 to 90, so every z slab is crossed
+THREE_ROUND_SPHERE = ((108.0, 50.0, 200.0), 14.0)           # wholly inside the volume, 35 voxels and more away from the plane
+THREE_ROUND_HOLE = ((40, 80), (30, 60), (100, 140))         # [lo, hi) per axis: weight 0, a hole inside the plane (it does not split it)
+THREE_ROUND_SEEN_TWICE = 40                                 # y >= this: weight 2 (it cuts the plane, the hole and the sphere)
+
+
+@functools.lru_cache(maxsize=None)
+def three_round_volume(small=True):
+    """(grid, tsdf, weight, color), read-only and computed once: an analytic volume of THREE_ROUND_DIMS voxels (voxel size 1, trunc 3)
+    that holds a tilted plane (inside: below it) and, with `small`, a sphere on its outer side; weight 0 in a box that the plane crosses,
+    2 where y >= THREE_ROUND_SEEN_TWICE and 1 elsewhere; the colour is a function of the place.  Without `small` every value the plane's
+    cells read is the same: the sphere's distance is past the truncation there."""
+    nx, ny, nz = THREE_ROUND_DIMS
+    grid = Grid(THREE_ROUND_DIMS, (0.0, 0.0, 0.0), 1.0, 3.0)
+    x, y, z = np.arange(nx, dtype=np.float64)[None, None, :], np.arange(ny, dtype=np.float64)[None, :, None], np.arange(nz, dtype=np.float64)[:, None, None]
+    (a, b, c), d = THREE_ROUND_PLANE
+    sdf = (a * x + b * y + c * z - d) / np.sqrt(a * a + b * b + c * c)
+    if small:
+        (cx, cy, cz), r = THREE_ROUND_SPHERE
+        sdf = np.minimum(sdf, np.sqrt((x - cx) ** 2 + (y - cy) ** 2 + (z - cz) ** 2) - r)
+    tsdf = np.clip(sdf / 3.0, -1, 1).astype(np.float32)
+    weight = np.ones((nz, ny, nx), np.float32)
+    weight[:, THREE_ROUND_SEEN_TWICE:, :] = 2.0
+    (x0, x1), (y0, y1), (z0, z1) = THREE_ROUND_HOLE
+    weight[z0:z1, y0:y1, x0:x1] = 0.0
+    color = np.stack([np.broadcast_to(v / n, (nz, ny, nx)) for v, n in ((x, nx), (y, ny), (z, nz))]).astype(np.float32)
+    for arr in (tsdf, weight, color):
+        arr.setflags(write=False)
+    return grid, tsdf, weight, color
 
 
 def sphere_deviation(grid: Grid, vertices, radius=SPHERE_R):
