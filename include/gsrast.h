@@ -761,6 +761,10 @@ int gsr_profile_read(int max_entries, char (*names)[GSR_PROFILE_NAME_LEN], float
  * of this ABI and of libgsrast.so, declared in a header of their own that this one brings in. */
 #include "gsrast_mesh.h"
 
+/* The depth-distortion loss (per-Gaussian depth moments, the distortion map of a rendered moments map, its mean as a fused loss): the
+ * entry points are part of this ABI and of libgsrast.so, declared in a header of their own that this one brings in. */
+#include "gsrast_distortion.h"
+
 #ifdef __cplusplus
 }
 #endif

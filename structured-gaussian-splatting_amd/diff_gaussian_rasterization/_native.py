@@ -288,7 +288,21 @@ MESH_SIGNATURES = {
     "gsr_mesh_clean_count": (_int, (_i32, _i32) + (_dev,) * 5 + (_size, _P(_i64), _P(_i64), _dev)),
     "gsr_mesh_clean_emit": (_int, (_i32, _i32, _dev, _dev, _size, _i64, _i64) + (_dev,) * 4),
 }
-_ALL_SIGNATURES = {**SIGNATURES, **NORMALS_SIGNATURES, **EXTRA_SIGNATURES, **MEDIAN_SIGNATURES, **TSDF_SIGNATURES, **MESH_SIGNATURES}
+# The depth-distortion loss, declared in include/gsrast_distortion.h (which gsrast.h includes): held to that header's prototypes by
+# tests/test_distortion_ref.py.  No struct of their own.
+_moments = (_i64, _dev, _dev, _i32, _f32, _f32)                                            # P, means3D, viewmatrix, mapping, near, far
+DISTORTION_MAPPINGS = {"ndc": 0, "linear": 1}                                              # GSR_DISTORTION_NDC, GSR_DISTORTION_LINEAR
+DISTORTION_SIGNATURES = {
+    "gsr_depth_moments_forward": (_int, _moments + (_dev, _dev)),
+    "gsr_depth_moments_backward": (_int, _moments + (_dev, _dev, _dev)),
+    "gsr_distortion_map_forward": (_int, (_i32, _i32) + (_dev,) * 4),
+    "gsr_distortion_map_backward": (_int, (_i32, _i32) + (_dev,) * 6),
+    "gsr_distortion_loss_workspace_size": (_int, (_i32, _i32, _P(_size))),
+    "gsr_distortion_loss_forward": (_int, (_i32, _i32, _dev, _dev, _dev, _size, _dev, _dev)),
+    "gsr_distortion_loss_backward": (_int, (_i32, _i32) + (_dev,) * 6),
+}
+_ALL_SIGNATURES = {**SIGNATURES, **NORMALS_SIGNATURES, **EXTRA_SIGNATURES, **MEDIAN_SIGNATURES, **TSDF_SIGNATURES, **MESH_SIGNATURES,
+                   **DISTORTION_SIGNATURES}
 
 _lib = None
 
@@ -1172,6 +1186,66 @@ def normal_consistency_backward(normal_map, depth, alpha, tanfovx, tanfovy, alph
         _gsr.gsr_normal_consistency_backward(H, W, tanfovx, tanfovy, alpha_min, _ptr(normal_map), _ptr(depth), _ptr(alpha), _ptr(grad_loss),
                                              _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _stream(depth.device))
     return tuple(outs)
+
+
+def depth_moments_forward(means3D, viewmatrix, mapping: int, near: float, far: float):
+    """gsr_depth_moments_forward: means3D [P,3], viewmatrix [4,4], contiguous fp32 on one device -> the depth moments [P,3]."""
+    P = int(means3D.shape[0])
+    out = torch.empty(P, 3, dtype=torch.float32, device=means3D.device)
+    with torch.cuda.device(means3D.device):
+        _gsr.gsr_depth_moments_forward(P, _ptr(means3D), _ptr(viewmatrix), mapping, near, far, _ptr(out), _stream(means3D.device))
+    return out
+
+
+def depth_moments_backward(means3D, viewmatrix, mapping: int, near: float, far: float, grad_out):
+    """gsr_depth_moments_backward: grad_out [P,3] contiguous -> dL/dmeans3D [P,3]."""
+    P = int(means3D.shape[0])
+    out = torch.empty(P, 3, dtype=torch.float32, device=means3D.device)
+    with torch.cuda.device(means3D.device):
+        _gsr.gsr_depth_moments_backward(P, _ptr(means3D), _ptr(viewmatrix), mapping, near, far, _ptr(grad_out), _ptr(out),
+                                        _stream(means3D.device))
+    return out
+
+
+def distortion_map_forward(moments_map, alpha):
+    """gsr_distortion_map_forward: moments_map [3,H,W], alpha [1,H,W] or [H,W], contiguous fp32 on one device -> the map [1,H,W]."""
+    H, W = int(moments_map.shape[-2]), int(moments_map.shape[-1])
+    out = torch.empty(1, H, W, dtype=torch.float32, device=alpha.device)
+    with torch.cuda.device(alpha.device):
+        _gsr.gsr_distortion_map_forward(H, W, _ptr(moments_map), _ptr(alpha), _ptr(out), _stream(alpha.device))
+    return out
+
+
+def _distortion_backward(fn, moments_map, alpha, grad, want):
+    H, W = int(moments_map.shape[-2]), int(moments_map.shape[-1])
+    outs = [torch.empty_like(t) if w else None for t, w in zip((moments_map, alpha), want)]
+    if H * W == 0 or not any(want):
+        return tuple(outs)
+    with torch.cuda.device(alpha.device):
+        fn(H, W, _ptr(moments_map), _ptr(alpha), _ptr(grad), _ptr(outs[0]), _ptr(outs[1]), _stream(alpha.device))
+    return tuple(outs)
+
+
+def distortion_map_backward(moments_map, alpha, grad_out, want):
+    """gsr_distortion_map_backward.  grad_out [H W] contiguous; want: two booleans for (moments_map, alpha).  Returns the two gradients,
+    shaped like the inputs, None where not wanted."""
+    return _distortion_backward(_gsr.gsr_distortion_map_backward, moments_map, alpha, grad_out, want)
+
+
+def distortion_loss_forward(moments_map, alpha):
+    """gsr_distortion_loss_forward -> the loss, a 0-dim tensor.  The blocks' sums live in a workspace of the call's own (the caching
+    allocator hands it out on the current stream), so calls on two streams share nothing."""
+    H, W = int(moments_map.shape[-2]), int(moments_map.shape[-1])
+    out = torch.empty(1, dtype=torch.float32, device=alpha.device)
+    with torch.cuda.device(alpha.device):
+        ws = torch.empty(_size(_gsr.gsr_distortion_loss_workspace_size, H, W), dtype=torch.uint8, device=alpha.device)
+        _gsr.gsr_distortion_loss_forward(H, W, _ptr(moments_map), _ptr(alpha), _ptr(ws), ws.numel(), _ptr(out), _stream(alpha.device))
+    return out.reshape(())
+
+
+def distortion_loss_backward(moments_map, alpha, grad_loss, want):
+    """gsr_distortion_loss_backward.  grad_loss: a one-element fp32 device tensor; want as for distortion_map_backward."""
+    return _distortion_backward(_gsr.gsr_distortion_loss_backward, moments_map, alpha, grad_loss, want)
 
 
 def tsdf_integrate(dims, origin, voxel_size, sdf_trunc, viewmatrix, depth, alpha, color, tanfovx, tanfovy, alpha_min, depth_max, tsdf, weight,

@@ -377,6 +377,11 @@ _NO_NORMALS = ("lambda_normal / render_normals is not supported by ShardedRender
                "unsharded, or leave lambda_normal at 0)")
 
 
+_NO_DISTORTION = ("lambda_dist / render_with_distortion is not supported by ShardedRenderer: the depth moments ride on the depth / alpha "
+                  "blend as extra colours, which runs on whole images only, and the loss is a mean over the whole image (train unsharded, "
+                  "or leave lambda_dist at 0)")
+
+
 _NO_MESH = ("extract_mesh / fuse_depth_maps is not supported by ShardedRenderer: the fusion reads whole depth and alpha maps, a rank "
             "renders a slab of tile rows and no depth or alpha map (extract the mesh unsharded: scene.mesh.extract_mesh)")
 
@@ -387,7 +392,7 @@ class ShardedRenderer:
 
     def __init__(self, dist, world: int, rank: int, backend=None, group=None, row_weights=None,
                  backward_mode: str = "allreduce_screen", balance_every: int = 0, async_gather: bool = True,
-                 bilateral_grid: bool = False, lambda_normal: float = 0.0):
+                 bilateral_grid: bool = False, lambda_normal: float = 0.0, lambda_dist: float = 0.0):
         """row_weights: fixed per-tile-row weights for the slab boundaries (None = equal rows).  balance_every = k > 0:
         SURVEY 7 "slab load balance" — every k-th frame the ranks' measured per-tile-row work (instances binned) rides
         on the all-gather and the next frames' slabs are cut at equal cumulative work.  async_gather=False: the slabs'
@@ -400,6 +405,8 @@ class ShardedRenderer:
                              "over all of an image's pixels, a rank holds a slab of rows (train unsharded, or turn it off)")
         if lambda_normal:
             raise ValueError(_NO_NORMALS)
+        if lambda_dist:
+            raise ValueError(_NO_DISTORTION)
         self.balance_every, self._frames, self._pending = int(balance_every), 0, None
         self.comm = _Comm(dist, world, rank, group, async_gather=async_gather)
         self.backend = NativeBackend() if backend is None else backend
@@ -475,6 +482,9 @@ class ShardedRenderer:
 
     def render_with_normals(self, viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0):
         raise ValueError(_NO_NORMALS)
+
+    def render_with_distortion(self, viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, near=0.2, far=100.0, mapping="ndc"):
+        raise ValueError(_NO_DISTORTION)
 
     def fuse_depth_maps(self, pc, cameras, pipe, background, volume, **kw):
         raise ValueError(_NO_MESH)

@@ -45,6 +45,9 @@ which the accumulated opacity crosses one half (diff_gaussian_rasterization, "me
 both paths.  render_normals(depth_ratio=r) mixes it into the depth the normals are taken from (normals.surface_depth; 2DGS uses r = 1
 for bounded scenes, 0 - the default, the expected depth alone - for unbounded ones); not with extra_colors, so render_with_normals()
 refuses a non-zero depth_ratio.
+
+render_with_distortion() (extension) is the colour frame with the depth moments (m, m^2, 0) of its own means3D as extra colours, for
+the depth-distortion term (diff_gaussian_rasterization.distortion): render()'s dict plus "depth", "alpha", "extra" and "distortion".
 """
 import math
 
@@ -149,6 +152,30 @@ def render_with_normals(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scal
     pkg["normal"] = pkg["extra"]
     pkg["depth_normal"] = depth_to_normal(pkg["depth"], pkg["alpha"], math.tan(viewpoint_camera.FoVx * 0.5),
                                           math.tan(viewpoint_camera.FoVy * 0.5))
+    return pkg
+
+
+def render_with_distortion(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, near=0.2, far=100.0, mapping="ndc",
+                           with_map=True):
+    """render() and the maps of the depth-distortion term from ONE frame (extension; diff_gaussian_rasterization.distortion, DESIGN
+    section 29): the colour frame, on whichever of the raw and getter paths render() would take, with depth_alpha=True and
+    depth_moments(means3D, world_view_transform, near, far, mapping) - of the very means3D the frame renders - as its extra colours.
+    -> render()'s dict (with "depth", "alpha" and "extra" = the moments map (M1, M2, 0)) plus "distortion" [1,H,W], distortion_map of
+    the two.  "render" and "radii" are render()'s, bit for bit.  A model's 3D filter, pipe.antialiasing and a LatentGaussianModel
+    compose as they do with render().  pipe.absgrad raises ValueError (the frame carries depth and alpha, which the abs blend backward
+    does not).  A training loop takes distortion_loss(pkg["extra"], pkg["alpha"]) instead of the map's mean, which never stores the map;
+    with_map=False leaves "distortion" out of the dict and its launch out of the frame."""
+    from diff_gaussian_rasterization.distortion import depth_moments, distortion_map
+    if getattr(pipe, "absgrad", False):
+        raise ValueError("render_with_distortion: the frame is rendered with depth_alpha=True, which pipe.absgrad is not supported with "
+                         "(the abs blend backward does not carry the depth and alpha gradients): turn pipe.absgrad off for this frame")
+
+    def moments(scales, rotations):
+        return depth_moments(pc.get_xyz, viewpoint_camera.world_view_transform, near, far, mapping)
+
+    pkg = _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, None, True, None, None, extra_colors=moments)
+    if with_map:
+        pkg["distortion"] = distortion_map(pkg["extra"], pkg["alpha"])
     return pkg
 
 

@@ -91,6 +91,8 @@ class OptimizationDefaults:
     normal_from_iter: int = 7000                  # the first iteration that adds it (2DGS's value, not tuned here)
     depth_ratio: float = 0.0                      # in [0, 1], with lambda_normal > 0: the normal term's depth is (1 - r) mean + r median (render_normals; 2DGS: 1 for bounded scenes); untuned
     normal_in_frame: bool = False                 # True: colour and the normal term's maps from ONE render_with_normals frame (train_loop.train)
+    lambda_dist: float = 0.0                      # > 0: weight of the depth-distortion loss, taken from the colour frame itself (render_with_distortion; train_loop.train); untuned
+    dist_from_iter: int = 3000                    # the first iteration that adds it (2DGS's value, not tuned here)
 
 
 def expon_lr(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1_000_000):

@@ -22,7 +22,14 @@ frame per iteration from normal_from_iter on instead of two 
 term's means2D gradient too.  Not with opt.densify_absgrad (the frame carries depth and alpha).  False (the default): the loop is as before.
 opt.depth_ratio (2DGS's, in [0, 1]; with lambda_normal > 0) is handed to render_normals: above 0 the normal term's depth normals are
 taken from the mix (1 - r) mean + r median depth (2DGS uses 1 for bounded scenes), and the loss is formed on that
-depth.  Not with normal_in_frame (the one frame carries extra colours).  0 (the default): the loop is as before.  Untuned."""
+depth.  Not with normal_in_frame (the one frame carries extra colours).  0 (the default): the loop is as before.  Untuned.
+opt.lambda_dist > 0 adds the depth-distortion loss from iteration opt.dist_from_iter on: the colour frame itself
+comes from gaussian_renderer.render_with_distortion (one frame, no second render), and opt.lambda_dist * distortion_loss(pkg["extra"],
+pkg["alpha"]) joins the loss in front of backward(); on_iteration still receives the image loss alone.  The densification statistics
+then see the distortion term's means2D gradient too, as 2DGS's do.  It composes with the two-frame normal term and every strategy
+above.  Not with normal_in_frame (the frame's one extra triple is taken by the normals, and a fourth extra channel is not built), not
+with opt.densify_absgrad (the frame carries depth and alpha), not with a ShardedRenderer.  0 (the default): the loop is as before.
+Neither number is tuned on captured scenes."""
 import math
 import random
 
@@ -83,6 +90,18 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
         if getattr(opt, "densify_absgrad", False):
             raise ValueError("normal_in_frame with densify_absgrad: the one frame carries the depth and alpha maps, which the abs blend "
                              "backward does not (use the two-frame path: normal_in_frame = False)")
+    lambda_dist = float(getattr(opt, "lambda_dist", 0.0))
+    if lambda_dist < 0:
+        raise ValueError(f"lambda_dist = {lambda_dist}: a weight of at least 0 expected")
+    if lambda_dist > 0:
+        from diff_gaussian_rasterization.distortion import distortion_loss
+        from gaussian_renderer import render_with_distortion
+        if normal_in_frame:
+            raise ValueError("lambda_dist with normal_in_frame: the colour frame carries one extra triple, which the normals take, and a "
+                             "blend with a fourth extra channel is not built (use the two-frame normal term: normal_in_frame = False)")
+        if getattr(opt, "densify_absgrad", False):
+            raise ValueError("lambda_dist with densify_absgrad: the distortion term's frame carries the depth and alpha maps, which the "
+                             "abs blend backward does not")
     if filter_3d:
         gaussians.compute_3D_filter(cameras)
     for it in range(first_iter, iterations + 1):
@@ -96,13 +115,20 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
         if getattr(opt, "densify_absgrad", False):             # the abs blend backward costs a little: only while its statistics are read
             pipe.absgrad = it < opt.densify_until_iter
         in_frame = normal_in_frame and it >= opt.normal_from_iter
-        pkg = render_with_normals(cameras[idx], gaussians, pipe, bg) if in_frame else render(cameras[idx], gaussians, pipe, bg)
+        with_dist = lambda_dist > 0 and it >= opt.dist_from_iter
+        if with_dist:
+            pkg = render_with_distortion(cameras[idx], gaussians, pipe, bg, with_map=False)
+        else:
+            pkg = render_with_normals(cameras[idx], gaussians, pipe, bg) if in_frame else render(cameras[idx], gaussians, pipe, bg)
         image, vsp, vis, radii = pkg["render"], pkg["viewspace_points"], pkg["visibility_filter"], pkg["radii"]
         if use_bilagrid:
             image = bilagrid(image, idx)
         loss = training_loss(image, targets[idx], opt.lambda_dssim)
         if use_bilagrid:
             loss = loss + opt.bilateral_grid_tv * total_variation_loss(bilagrid.grids)
+        image_loss = loss                                          # what on_iteration receives
+        if with_dist:
+            loss = loss + lambda_dist * distortion_loss(pkg["extra"], pkg["alpha"])
         if in_frame:
             cam = cameras[idx]
             normal_loss = normal_consistency_loss(pkg["normal"], pkg["depth"], pkg["alpha"], math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5))
@@ -165,5 +191,5 @@ def train(gaussians, cameras, targets, opt, pipe, background, iterations, first_
             if filter_3d and it % 100 == 0 and opt.densify_until_iter < it < iterations - 100:
                 gaussians.compute_3D_filter(cameras)
         if on_iteration is not None:
-            on_iteration(it, loss, gaussians)
+            on_iteration(it, image_loss, gaussians)
     return gaussians
