@@ -765,6 +765,10 @@ int gsr_profile_read(int max_entries, char (*names)[GSR_PROFILE_NAME_LEN], float
  * entry points are part of this ABI and of libgsrast.so, declared in a header of their own that this one brings in. */
 #include "gsrast_distortion.h"
 
+/* The sparse (brick-allocated) TSDF volume: allocation from depth maps, fusion and mesh extraction over the allocated bricks alone.
+ * The entry points are part of this ABI and of libgsrast.so, declared in a header of their own that this one brings in. */
+#include "gsrast_tsdf_sparse.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -301,8 +301,21 @@ DISTORTION_SIGNATURES = {
     "gsr_distortion_loss_forward": (_int, (_i32, _i32, _dev, _dev, _dev, _size, _dev, _dev)),
     "gsr_distortion_loss_backward": (_int, (_i32, _i32) + (_dev,) * 6),
 }
+# The sparse TSDF volume, declared in include/gsrast_tsdf_sparse.h (which gsrast.h includes): held to that header's prototypes by
+# tests/test_tsdf_sparse_ref.py.  No struct of their own; the counts of the two count calls are host out-parameters.
+_bricks = (_dev,) * 4                                                                      # brick_table, brick_coords, brick_order, brick_rank
+TSDF_SPARSE_SIGNATURES = {
+    "gsr_tsdf_sparse_allocate": (_int, _dims + (_f32,) * 6 + (_i32, _i32) + (_f32,) * 4 + (_dev,) * 5),
+    "gsr_tsdf_sparse_commit_workspace_size": (_int, _dims + (_P(_size),)),
+    "gsr_tsdf_sparse_commit_count": (_int, _dims + (_dev, _dev, _dev, _size, _P(_i64), _dev)),
+    "gsr_tsdf_sparse_commit_assign": (_int, _dims + (_i64, _i64, _dev, _dev, _dev, _size, _dev, _dev, _dev, _dev)),
+    "gsr_tsdf_sparse_integrate": (_int, _dims + (_f32,) * 5 + (_i32, _i32) + (_f32,) * 4 + (_i64,) + (_dev,) * 9),
+    "gsr_tsdf_sparse_mesh_workspace_size": (_int, (_i64, _P(_size))),
+    "gsr_tsdf_sparse_mesh_count": (_int, _dims + (_i64, _f32, _dev, _dev) + _bricks + (_dev, _size, _P(_i64), _P(_i64), _dev)),
+    "gsr_tsdf_sparse_mesh_emit": (_int, _dims + (_f32,) * 4 + (_i64, _f32, _dev, _dev, _dev) + _bricks + (_dev, _size, _i64, _i64) + (_dev,) * 5),
+}
 _ALL_SIGNATURES = {**SIGNATURES, **NORMALS_SIGNATURES, **EXTRA_SIGNATURES, **MEDIAN_SIGNATURES, **TSDF_SIGNATURES, **MESH_SIGNATURES,
-                   **DISTORTION_SIGNATURES}
+                   **DISTORTION_SIGNATURES, **TSDF_SPARSE_SIGNATURES}
 
 _lib = None
 
@@ -1273,6 +1286,64 @@ def tsdf_extract_mesh(dims, origin, voxel_size, min_weight, tsdf, weight, vol_co
         _gsr.gsr_tsdf_mesh_emit(*dims, *origin, voxel_size, min_weight, _ptr(tsdf), _ptr(weight), _ptr(vol_color), _ptr(ws), nbytes, nv.value,
                                 nf.value, _ptr(vertices), _ptr(faces), _ptr(colors), _stream(dev))
     return vertices, faces, colors
+
+
+def tsdf_sparse_allocate(dims, origin, voxel_size, sdf_trunc, pad, viewmatrix_inverse, depth, alpha, tanfovx, tanfovy, alpha_min, depth_max, marks):
+    """gsr_tsdf_sparse_allocate on the marks' device and its current stream.  One launch, no synchronisation."""
+    H, W = int(depth.shape[-2]), int(depth.shape[-1])
+    with torch.cuda.device(marks.device):
+        _gsr.gsr_tsdf_sparse_allocate(*dims, *origin, voxel_size, sdf_trunc, pad, H, W, tanfovx, tanfovy, alpha_min, depth_max,
+                                      _ptr(viewmatrix_inverse), _ptr(depth), _ptr(alpha), _ptr(marks), _stream(marks.device))
+
+
+def tsdf_sparse_commit_count(dims, marks, table):
+    """gsr_tsdf_sparse_commit_count on the table's device and its current stream -> (new bricks, workspace, its bytes).  The one host
+    readback of a commit; the workspace carries the prefixes to tsdf_sparse_commit_assign."""
+    dev = table.device
+    nbytes = _size(_gsr.gsr_tsdf_sparse_commit_workspace_size, *dims)
+    new = C.c_int64(0)
+    with torch.cuda.device(dev):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _gsr.gsr_tsdf_sparse_commit_count(*dims, _ptr(marks), _ptr(table), _ptr(ws), nbytes, new, _stream(dev))
+    return new.value, ws, nbytes
+
+
+def tsdf_sparse_commit_assign(dims, num_bricks, marks, table, ws, nbytes, coords, order, rank):
+    """gsr_tsdf_sparse_commit_assign: coords [capacity,3], order and rank [capacity] int32 with room for the new bricks."""
+    dev = table.device
+    with torch.cuda.device(dev):
+        _gsr.gsr_tsdf_sparse_commit_assign(*dims, num_bricks, int(coords.shape[0]), _ptr(marks), _ptr(table), _ptr(ws), nbytes, _ptr(coords),
+                                           _ptr(order), _ptr(rank), _stream(dev))
+
+
+def tsdf_sparse_integrate(dims, origin, voxel_size, sdf_trunc, viewmatrix, depth, alpha, color, tanfovx, tanfovy, alpha_min, depth_max, num_bricks,
+                          coords, tsdf, weight, vol_color):
+    """gsr_tsdf_sparse_integrate on the pool's device and its current stream.  One launch, no synchronisation."""
+    H, W = int(depth.shape[-2]), int(depth.shape[-1])
+    with torch.cuda.device(tsdf.device):
+        _gsr.gsr_tsdf_sparse_integrate(*dims, *origin, voxel_size, sdf_trunc, H, W, tanfovx, tanfovy, alpha_min, depth_max, num_bricks,
+                                       _ptr(viewmatrix), _ptr(depth), _ptr(alpha), _ptr(color), _ptr(coords), _ptr(tsdf), _ptr(weight),
+                                       _ptr(vol_color), _stream(tsdf.device))
+
+
+def tsdf_sparse_extract_mesh(dims, origin, voxel_size, min_weight, num_bricks, tsdf, weight, vol_color, table, coords, order, rank, return_cells):
+    """gsr_tsdf_sparse_mesh_count and gsr_tsdf_sparse_mesh_emit on the pool's device and its current stream -> (vertices [V,3] float32,
+    faces [F,3] int32, colors [V,3] float32, cells [V,3] int32 or None).  One host readback: the two totals that size the outputs."""
+    dev = table.device
+    nbytes = _size(_gsr.gsr_tsdf_sparse_mesh_workspace_size, num_bricks)
+    nv, nf = C.c_int64(0), C.c_int64(0)
+    bricks = (_ptr(table), _ptr(coords), _ptr(order), _ptr(rank))
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        _gsr.gsr_tsdf_sparse_mesh_count(*dims, num_bricks, min_weight, _ptr(tsdf), _ptr(weight), *bricks, _ptr(ws), nbytes, nv, nf, _stream(dev))
+        vertices = torch.empty(nv.value, 3, dtype=torch.float32, device=dev)
+        faces = torch.empty(nf.value, 3, dtype=torch.int32, device=dev)
+        colors = torch.empty(nv.value, 3, dtype=torch.float32, device=dev)
+        cells = torch.empty(nv.value, 3, dtype=torch.int32, device=dev) if return_cells else None
+        _gsr.gsr_tsdf_sparse_mesh_emit(*dims, *origin, voxel_size, num_bricks, min_weight, _ptr(tsdf), _ptr(weight), _ptr(vol_color), *bricks,
+                                       _ptr(ws), nbytes, nv.value, nf.value, _ptr(vertices), _ptr(faces), _ptr(colors),
+                                       _ptr(cells) if return_cells else None, _stream(dev))
+    return vertices, faces, colors, cells
 
 
 def mesh_components(faces, V):

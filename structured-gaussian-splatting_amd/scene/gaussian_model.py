@@ -687,6 +687,7 @@ class GaussianModel:
     def extract_mesh(self, cameras, pipe, background, **kw):
         """The triangle mesh of the surface `cameras` see: depth maps fused into a TSDF volume, surface nets (scene/mesh.py extract_mesh,
         which takes kw: voxel_size, sdf_trunc, bounds, depth_max, min_weight, depth_ratio (0: the expected depth is fused; 1: the median depth),
+        sparse (False; True: a brick-allocated volume), resolution (voxels along the longest side: 512, and 1024 when sparse), two_pass,
         and min_component_faces, keep_largest to clean it) -> (vertices [V,3], faces [F,3] int32, colors [V,3])."""
         from . import mesh
         return mesh.extract_mesh(self, cameras, pipe, background, **kw)

@@ -7,7 +7,9 @@ fusion of a few views leaves holes and silhouette artefacts by nature: clean_mes
 section 27) drops the small detached pieces on the device.  depth_ratio (2DGS's; 0, the default: the expected depth; 2DGS uses 1, the
 median depth, for bounded scenes) chooses the depth that is fused (diff_gaussian_rasterization.normals.surface_depth, DESIGN section
 28): at a silhouette or behind a thin layer the expected depth is a blend at which nothing exists, the median is a splat's own.
-Decimation, unbounded (contracted) volumes and sparse voxel hashing are out of scope.
+sparse=True fuses into a SparseTSDFVolume (bricks of 8 x 8 x 8 voxels allocated where the depth maps put a surface):
+the same mesh at a fraction of the memory, and the resolutions the dense volume cannot hold.  Decimation, unbounded (contracted)
+volumes, hashing in place of the dense brick table and brick deallocation are out of scope.
 """
 import math
 import os
@@ -16,6 +18,7 @@ import numpy as np
 import torch
 
 VOLUME_RESOLUTION = 512          # voxels along the default cube's side
+SPARSE_RESOLUTION = 1024         # the same of a sparse volume (2DGS's mesh_res)
 TRUNC_VOXELS = 5.0               # the default sdf_trunc, in voxels
 
 
@@ -23,27 +26,36 @@ def _tanfov(cam):
     return math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5)
 
 
-def fuse_depth_maps(pc, cameras, pipe, background, volume, alpha_min=0.5, depth_max=None, depth_ratio=0.0):
+def fuse_depth_maps(pc, cameras, pipe, background, volume, alpha_min=0.5, depth_max=None, depth_ratio=0.0, two_pass=True):
     """Per camera, under torch.no_grad(): render(..., depth_alpha=True), then volume.integrate of its depth, alpha and colour maps.
     depth_max None: nothing is cut.  depth_ratio in [0, 1] (0: the calls made without it): above 0 the frame also renders the median
     depth and surface_depth(depth, alpha, median, depth_ratio) is integrated in the depth map's place, beside the same alpha.
-    Returns the volume."""
+    two_pass applies to a SparseTSDFVolume alone (a dense volume takes the calls above, whatever it says).  True: the frames are
+    rendered twice, first for volume.allocate and then for volume.integrate, and the maps are not kept: every allocated brick holds
+    what the dense volume holds.  False: one render per frame, volume.allocate and volume.integrate on it (streaming: a brick holds
+    the frames from the one that allocated it on).  Returns the volume."""
     from gaussian_renderer import render
     from diff_gaussian_rasterization.normals import surface_depth
     depth_max = math.inf if depth_max is None else float(depth_max)
     depth_ratio = float(depth_ratio)
     if not 0.0 <= depth_ratio <= 1.0:
         raise ValueError(f"fuse_depth_maps: depth_ratio {depth_ratio} outside [0, 1]")
-    with torch.no_grad():
-        for cam in cameras:
-            if depth_ratio > 0.0:
-                pkg = render(cam, pc, pipe, background, depth_alpha=True, median_depth=True)
-                pkg["depth"] = surface_depth(pkg["depth"], pkg["alpha"], pkg["median_depth"], depth_ratio)
-            else:
-                pkg = render(cam, pc, pipe, background, depth_alpha=True)
-            tx, ty = _tanfov(cam)
-            volume.integrate(pkg["depth"].contiguous(), pkg["alpha"].contiguous(), pkg["render"].contiguous(),
-                             cam.world_view_transform.contiguous(), tx, ty, alpha_min=alpha_min, depth_max=depth_max)
+    sparse = hasattr(volume, "allocate")
+    for step in (("allocate", "integrate") if sparse and two_pass else ("both",) if sparse else ("integrate",)):
+        with torch.no_grad():
+            for cam in cameras:
+                if depth_ratio > 0.0:
+                    pkg = render(cam, pc, pipe, background, depth_alpha=True, median_depth=True)
+                    pkg["depth"] = surface_depth(pkg["depth"], pkg["alpha"], pkg["median_depth"], depth_ratio)
+                else:
+                    pkg = render(cam, pc, pipe, background, depth_alpha=True)
+                tx, ty = _tanfov(cam)
+                if step != "integrate":
+                    volume.allocate(pkg["depth"].contiguous(), pkg["alpha"].contiguous(), cam.world_view_transform.contiguous(), tx, ty,
+                                    alpha_min=alpha_min, depth_max=depth_max)
+                if step != "allocate":
+                    volume.integrate(pkg["depth"].contiguous(), pkg["alpha"].contiguous(), pkg["render"].contiguous(),
+                                     cam.world_view_transform.contiguous(), tx, ty, alpha_min=alpha_min, depth_max=depth_max)
     return volume
 
 
@@ -66,13 +78,16 @@ def clean_mesh(vertices, faces, colors=None, **kw):
 
 
 def extract_mesh(pc, cameras, pipe, background, voxel_size=None, sdf_trunc=None, bounds=None, depth_max=None, min_weight=1.0,
-                 min_component_faces=None, keep_largest=None, depth_ratio=0.0):
+                 min_component_faces=None, keep_largest=None, depth_ratio=0.0, sparse=False, resolution=None, two_pass=True):
     """-> (vertices [V,3] float32, faces [F,3] int32, colors [V,3] float32) of the surface the cameras see.
-    bounds: (lo [3], hi [3]); default camera_bounds(cameras).  voxel_size: default the bounds' longest side / 512.  sdf_trunc: default
+    bounds: (lo [3], hi [3]); default camera_bounds(cameras).  voxel_size: default the bounds' longest side / resolution; resolution
+    (voxels along the longest side; giving both is a ValueError): default 512, and 1024 with sparse=True.  sparse: fuse into a
+    SparseTSDFVolume (two_pass: fuse_depth_maps'); the mesh is the dense volume's at the same voxel size, its vertices and faces in
+    the sparse volume's order.  sdf_trunc: default
     5 voxel_size.  depth_max: default the bounds' longest side.  min_component_faces, keep_largest: when either is given the mesh is
     cleaned after the extraction (clean_mesh's min_faces and keep_largest); with both None it is returned as extracted.
     depth_ratio: fuse_depth_maps' (0: the expected depth; 1: the median depth, 2DGS's choice for bounded scenes)."""
-    from diff_gaussian_rasterization.tsdf import TSDFVolume
+    from diff_gaussian_rasterization.tsdf import SparseTSDFVolume, TSDFVolume
     cameras = list(cameras)
     if not cameras:
         raise ValueError("extract_mesh: no cameras")
@@ -84,15 +99,19 @@ def extract_mesh(pc, cameras, pipe, background, voxel_size=None, sdf_trunc=None,
         if len(lo) != 3 or len(hi) != 3 or not all(h > l for l, h in zip(lo, hi)):
             raise ValueError(f"extract_mesh: bounds = {bounds}: (lo [3], hi [3]) with hi > lo expected")
         side = max(h - l for l, h in zip(lo, hi))
-    voxel_size = side / VOLUME_RESOLUTION if voxel_size is None else float(voxel_size)
+    if resolution is not None and (voxel_size is not None or not resolution >= 1):
+        raise ValueError(f"extract_mesh: resolution = {resolution}, voxel_size = {voxel_size}: one of them, the resolution at least 1 voxel")
+    if resolution is None:
+        resolution = SPARSE_RESOLUTION if sparse else VOLUME_RESOLUTION
+    voxel_size = side / resolution if voxel_size is None else float(voxel_size)
     sdf_trunc = TRUNC_VOXELS * voxel_size if sdf_trunc is None else float(sdf_trunc)
     depth_max = side if depth_max is None else float(depth_max)
     if not voxel_size > 0:
         raise ValueError(f"extract_mesh: voxel_size = {voxel_size}: positive expected")
     # the bounds cut into voxels, a voxel's centre in the middle of its cut: side / voxel_size voxels along the longest side
     dims = tuple(max(int(math.ceil((h - l) / voxel_size - 1e-6)), 1) for l, h in zip(lo, hi))
-    volume = TSDFVolume([l + 0.5 * voxel_size for l in lo], voxel_size, dims, sdf_trunc, device=pc.get_xyz.device)
-    fuse_depth_maps(pc, cameras, pipe, background, volume, depth_max=depth_max, depth_ratio=depth_ratio)
+    volume = (SparseTSDFVolume if sparse else TSDFVolume)([l + 0.5 * voxel_size for l in lo], voxel_size, dims, sdf_trunc, device=pc.get_xyz.device)
+    fuse_depth_maps(pc, cameras, pipe, background, volume, depth_max=depth_max, depth_ratio=depth_ratio, two_pass=two_pass)
     mesh = volume.extract_mesh(min_weight=min_weight)
     if min_component_faces is None and keep_largest is None:
         return mesh
